@@ -26,6 +26,9 @@ when N > 1 or --strong is given, the `kem` block (second half of the BASELINE me
 block (FK23 openings at d = 2^21, the kernel family that dominates config 5; rank 0's GPU) and a `laconic` block (BASELINE config 5: the
 three phases of the reference's Laconic OT test at 2^20 bits, sharded over ALL ranks of the job: laconic_ot.run_flow). Exit code 1 if any
 parity check fails.
+
+--dump-outputs DIR writes the result of the last timed step (the affine MSM point) to DIR/msm_g1_affine.npy. The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -173,6 +176,9 @@ def main():
     ap.add_argument("--fk-log2d", type=int, default=21, help="log2 of the FK23 domain of the `fk` block (BASELINE config 5: 2^21); 0 disables")
     ap.add_argument("--g2-log2n", type=int, default=20, help="log2 of the points of the `msm_g2` block; 0 disables")
     ap.add_argument("--laconic-log2n", type=int, default=20, help="log2 of the receiver bits of the `laconic` block (BASELINE config 5: 2^20); 0 disables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the MSM result a caller receives) to DIR/<name>.npy "
+                         "(rank 0): msm_g1_affine.npy = affine x, y as eight little-endian 32-bit words each, float64 (exact)")
     args = ap.parse_args()
     if args.gpus > 1 and not under_launcher():
         # `python3 bench.py --gpus N` typed as it stands (the driver's N = 1 line has that shape): this process -- which has not imported
@@ -293,6 +299,11 @@ def main():
     # The K timed steps are enqueued back to back: nothing reads an event or synchronises with the host between them (for N > 1 step
     # k + 1 is enqueued while the all-gather of step k runs).
     elapsed = inst.timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result, read before anything else runs on the instance; 32-bit words are exact in float64
+        last = inst.last_result_affine()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_g1_affine.npy"), last.view(np.uint32).reshape(2, 8).astype(np.float64))
     # HIP-event time of the dominant kernel, on the stream it is launched on, from a SEPARATE untimed pass over the same steps (reading
     # an event is a host round trip, which does not belong in the timed region): one value per launch.
     hip.set_timing(True)

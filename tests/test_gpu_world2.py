@@ -141,28 +141,48 @@ def test_rccl_executes_on_hardware_with_one_rank(multirank_runs):
     assert j["strong"]["full_size_check"] is True and j["strong"]["ranks_seen"] == 1
 
 
-def test_eight_ranks_config4_and_config5_at_full_size(multirank_runs):
-    """BASELINE configs 4 and 5 at their stated sizes through the driver's 8-rank launch lines, all eight ranks on the one GPU of the box
-    (gloo instead of RCCL: the transport is the only thing that differs from an 8-GPU node).
-      config 4: 2^26-point G1 MSM, 2^23 points per rank with the window tables of the chunk, all-gather of eight 96-byte partials + EC sum,
+def test_four_ranks_config4_and_config5_at_full_size(multirank_runs):
+    """BASELINE configs 4 and 5 at their stated sizes through the driver's multi-rank launch lines, four ranks on the one GPU of the box
+    (gloo instead of RCCL: the transport is the only thing that differs from a multi-GPU node; a shared GPU takes at most six processes).
+      config 4: 2^26-point G1 MSM, 2^24 points per rank with the window tables of the chunk, all-gather of four 96-byte partials + EC sum,
                 checked at full size by the O(n) identity over all ranks (every rank contributes its sum of s_i k_i);
-      config 5: Laconic OT at 2^20 receiver bits: FK23 openings sharded 8 ways at d = 2^21 (three rank bits in every layout switch), commit
+      config 5: Laconic OT at 2^20 receiver bits: FK23 openings sharded 4 ways at d = 2^21 (two rank bits in every layout switch), commit
                 by point range, 2^21 encapsulations / 2^20 decapsulations by item range; rank 0 re-runs the un-sharded calls with the same
                 seeds and compares commitment, all 2^21 proofs and its ciphertexts byte for byte (those un-sharded calls are what
-                tests/test_gpu_config5.py checks against the oracle)."""
-    run = multirank_runs["bench8"]
+                tests/test_gpu_config5.py checks against the oracle). Eight-way sharding: tests/test_gpu_fk_shard.py."""
+    world = 4
+    run = multirank_runs["bench4_full"]
     assert run["rc"] == 0, run["log"][-3000:]
     j = _json_line(run["log"])
-    assert j["n_gpus"] == 8 and j["config"]["ranks_seen"] == 8 and j["scaling"] == "weak" and j["value"] > 0
+    assert j["n_gpus"] == world and j["config"]["ranks_seen"] == world and j["scaling"] == "weak" and j["value"] > 0
     assert j["checks"]["full_size_check"] is True and j["checks"]["sample_bit_exact"] is True
     st = j["strong"]
-    assert st["total_points"] == 1 << 26 and st["points_per_gpu"] == 1 << 23 and st["ranks_seen"] == 8 and st["full_size_check"] is True
-    lo = j["laconic"]                                      # the bench line's own Laconic OT block, sharded over the eight ranks (small here; full size below)
-    assert lo["n_gpus"] == 8 and lo["ranks_seen"] == 8 and lo["fk_sharded"] is True and lo["all_messages_recovered"] is True and lo["n_choices"] == 1 << 10
-    run = multirank_runs["laconic8"]
+    assert st["total_points"] == 1 << 26 and st["points_per_gpu"] == 1 << 24 and st["ranks_seen"] == world and st["full_size_check"] is True
+    lo = j["laconic"]                                      # the bench line's own Laconic OT block, sharded over the four ranks (small here; full size below)
+    assert lo["n_gpus"] == world and lo["ranks_seen"] == world and lo["fk_sharded"] is True and lo["all_messages_recovered"] is True and lo["n_choices"] == 1 << 10
+    run = multirank_runs["laconic4_full"]
     assert run["rc"] == 0, run["log"][-3000:]
     j = _json_line(run["log"])
-    assert j["n_gpus"] == 8 and j["ranks_seen"] == 8 and j["n_choices"] == 1 << 20
+    assert j["n_gpus"] == world and j["ranks_seen"] == world and j["n_choices"] == 1 << 20
     assert j["all_messages_recovered"] is True and j["sharded_equals_single_process"] is True and j["fk_sharded"] is True
     d = 1 << 21
-    assert j["fk_exchange_bytes_sent_per_rank"] == 7 * (2 * (d // 64 * 96) + d // 8 * 64) + 7 * (2 * d // 64 * 96)
+    assert j["fk_exchange_bytes_sent_per_rank"] == (world - 1) * (2 * (d // world ** 2 * 96) + d // world * 64) + (world - 1) * (2 * d // world ** 2 * 96)
+
+
+def test_bench_dump_outputs_hold_the_last_timed_step(multirank_runs, oc):
+    """bench.py --dump-outputs (the world-1 job above: 2^18 points, one warm-up and two timed steps): msm_g1_affine.npy is the result of
+    the LAST timed step (steps alternate between two scalar vectors: warm-up 0, timed 1 then 0) as float64 32-bit words, equal to
+    (sum s_i k_i) G from the oracle for vector 0 and not for vector 1"""
+    run = multirank_runs["bench1"]
+    assert run["rc"] == 0, run["log"][-3000:]
+    from bench import random_fr_limbs, SEED
+    a = np.load(os.path.join(run["dump"], "msm_g1_affine.npy"))
+    assert a.dtype == np.float64 and a.shape == (2, 8) and np.all(a == np.floor(a)) and np.all((a >= 0) & (a < 2.0 ** 32))
+    got = a.astype(np.uint32).view(np.uint64).reshape(8)
+    n = 1 << 18
+    k = random_fr_limbs(n, SEED + 1)
+    s0 = random_fr_limbs(n, SEED + 104729)
+    s1 = np.ascontiguousarray(np.roll(s0, 1, axis=0)[:, ::-1] >> np.uint64(3))           # bench.py's second vector
+    g1, _ = oc.generators()
+    assert np.array_equal(got, oc.g1_mul_batch(g1, oc.fr_dot(s0, k).reshape(1, 4))[0])
+    assert not np.array_equal(got, oc.g1_mul_batch(g1, oc.fr_dot(s1, k).reshape(1, 4))[0])
