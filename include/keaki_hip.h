@@ -93,7 +93,9 @@ int32_t keaki_hip_ctx_device(const keaki_hip_ctx* ctx);
 const char* keaki_hip_version(void);
 /* keaki_hip_last_error: the returned string is a copy private to the calling thread (valid until its next call of this function). */
 /* Tuning / A-B switches of a context (profiling and tests; defaults are what ships). Initial values come from the environment variable
- * KEAKI_<NAME> at keaki_hip_ctx_create; afterwards only this call changes them. Names: "msm_c", "msm_c_shared" (window bits, 0 = automatic),
+ * KEAKI_<NAME> at keaki_hip_ctx_create; afterwards only this call changes them. Names: "msm_c", "msm_c_shared" (window bits of the MSM without / with
+ * window tables: 3 .. 19 / 3 .. 23; 0 or any value outside 3 .. 24 = automatic; 20 .. 24 / 24 name plans with more buckets than the bucket sort
+ * addresses and are refused with KEAKI_ERR_BAD_ARG, in the environment ignored),
  * "reduce_l", "part_shift", "acc_u29", "acc_u29_g2", "acc_nt", "acc_prefetch", "acc_idxq" (the G1 bucket kernel reads its index stream by aligned
  * 64-byte groups through a lane-private LDS slot; 0 = one 4-byte load per entry as until round 5), "cs_masked", "fk_uniform", "fk_gtab", "fk_addsub29", "fk_radix4", "fb_occ1", "gt_wb_b" (window bits of the table of
  * e(g1, g2), 0 = automatic; a change rebuilds the table on the next use), "encap_gt" (batch size from which encap_batch takes the GT

@@ -416,8 +416,8 @@ namespace {
 void tune_from_env(Tuning& t) {
   auto geti = [](const char* name, long long& out) { const char* e = getenv(name); if (!e || !*e) return false; out = atoll(e); return true; };
   long long v;
-  if (geti("KEAKI_MSM_C", v)) t.msm_c = (int)v;
-  if (geti("KEAKI_MSM_C_SHARED", v)) t.msm_c_shared = (int)v;
+  if (geti("KEAKI_MSM_C", v) && !msm_c_too_wide(v, MSM_C_MAX)) t.msm_c = (int)v;                      // a width no plan can run stays automatic
+  if (geti("KEAKI_MSM_C_SHARED", v) && !msm_c_too_wide(v, MSM_C_SHARED_MAX)) t.msm_c_shared = (int)v;
   if (geti("KEAKI_REDUCE_L", v)) t.reduce_l = (int)v;
   if (geti("KEAKI_PART_SHIFT", v)) t.part_shift = (int)v;
   if (geti("KEAKI_ACC_U29", v)) t.acc_u29 = v != 0;
@@ -526,8 +526,14 @@ keaki_status keaki_hip_ctx_set_option(keaki_hip_ctx* ctx, const char* name, int6
   if (!name) return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: name is null");
   Tuning& t = ctx->tune;
   const std::string k(name);
-  if (k == "msm_c") t.msm_c = (int)value;
-  else if (k == "msm_c_shared") t.msm_c_shared = (int)value;
+  if (k == "msm_c" || k == "msm_c_shared") {
+    const bool sh = k == "msm_c_shared";
+    const int mx = sh ? MSM_C_SHARED_MAX : MSM_C_MAX;
+    if (msm_c_too_wide(value, mx))
+      return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: %s = %lld exceeds %d, the widest window whose buckets the bucket sort can address (3 .. %d; 0 = automatic)",
+                  name, (long long)value, mx, mx);
+    (sh ? t.msm_c_shared : t.msm_c) = (int)value;
+  }
   else if (k == "reduce_l") t.reduce_l = (int)value;
   else if (k == "part_shift") t.part_shift = (int)value;
   else if (k == "acc_u29") t.acc_u29 = value != 0;

@@ -25,18 +25,25 @@ struct DevBuf {
 }  // namespace keaki_internal
 
 namespace keaki_internal {
+// Widest forced windows. A plan with more than 2^22 buckets to sort (generic: the buckets of all windows; window tables: those of the largest
+// window) is beyond the two-pass bucket sort (msm.hip.h: part_make_shape, 2^11 bins of 2^11 buckets): generic 20 .. 24 and shared 24 bits
+// could never run. msm_g2.hip checks both limits against the plans. keaki_hip_ctx_set_option refuses the widths between a limit and 24,
+// tune_from_env ignores them; any other value outside 3 .. 24 means automatic, as it always did.
+constexpr int MSM_C_MAX = 19, MSM_C_SHARED_MAX = 23;
+inline bool msm_c_too_wide(long long v, int max) { return v > max && v <= 24; }
 // Tuning / diagnostic switches of a context. The environment is read ONCE, in keaki_hip_ctx_create (tune_from_env); afterwards only
 // keaki_hip_ctx_set_option changes them (under the context lock). No other code in the library calls getenv.
 struct Tuning {
-  int msm_c = 0;                 // KEAKI_MSM_C / "msm_c": window bits of the generic MSM, 0 = choose_window
-  int msm_c_shared = 0;          // KEAKI_MSM_C_SHARED / "msm_c_shared": window target of the SRS window tables, 0 = choose_window_shared
+  int msm_c = 0;                 // KEAKI_MSM_C / "msm_c": window bits of the generic MSM, 3 .. MSM_C_MAX; 0 (or any value outside 3 .. 24) = choose_window
+  int msm_c_shared = 0;          // KEAKI_MSM_C_SHARED / "msm_c_shared": window target of the SRS window tables, 3 .. MSM_C_SHARED_MAX; 0 (or outside 3 .. 24) = choose_window_shared
   int msm_short_tables = -1;     // KEAKI_MSM_SHORT_TABLES / "msm_short_tables": an MSM over less than half of an SRS with window tables uses them (1, and automatic = -1) or the generic path (0)
   int reduce_l = 0;              // KEAKI_REDUCE_L / "reduce_l": chunk length of the bucket reduction, 0 = automatic
   int part_shift = -1;           // KEAKI_PART_SHIFT / "part_shift": log2 of the bucket sort's bin count, -1 = automatic
   bool acc_u29 = true;           // KEAKI_ACC_U29 / "acc_u29": G1 bucket kernel in the 29-bit lazy limbs (A/B switch for profiling)
   bool acc_u29_g2 = true;        // KEAKI_ACC_U29_G2 / "acc_u29_g2"
   bool acc_prefetch = true;      // KEAKI_ACC_PREFETCH / "acc_prefetch": the G1 bucket kernel requests the next pair's table row an iteration ahead (A/B switch)
-  bool acc_idxq = true;          // KEAKI_ACC_IDXQ / "acc_idxq": the G1 bucket kernel reads its index stream by aligned 16-byte quads through a lane-private LDS slot (0: one 4-byte load per entry, as until round 5; A/B switch)
+  bool acc_idxq = true;          // KEAKI_ACC_IDXQ / "acc_idxq": the G1 bucket kernel reads its index stream by aligned 64-byte groups through a lane-private LDS slot (0: one 4-byte load per entry, as until round 5; A/B switch)
+                                 // acc_nt, acc_prefetch and acc_idxq choose among the WHOLE-MSM kernels only: the passes of a chunked call always run the default kernel
   bool cs_masked = true;         // KEAKI_CS_MASKED / "cs_masked": pass 2 of the bucket sort skips empty gather slots under the exec mask (0: every empty slot counts into a dummy word per lane, as in round 4; A/B switch: 0.84 -> 0.70 ms at 2^24)
   bool acc_nt = false;           // KEAKI_ACC_NT / "acc_nt": non-temporal loads of the table rows in the G1 bucket kernel
   bool fk_uniform = true;        // KEAKI_FK_UNIFORM / "fk_uniform": sliding-window ladder in the wave-uniform FK23 stages

@@ -1,0 +1,177 @@
+"""CPU suite: the variant model of tests/variant_cases.py against the sources. Every instantiation the host code can launch must be reached
+by a case of tests/test_gpu_variants.py (or be listed as unreachable, with the model's reason); the digit-edge scalars must drive every
+window of every plan through each branch of the digit walk; the model must reproduce the operating points the repository records."""
+import os
+import re
+
+import structured_inputs as S
+import variant_cases as V
+
+R = S.R
+
+
+def _src(name):
+    return V._src(name)
+
+
+def launchable():
+    """the instantiations the host code launches, parsed from the launch sites"""
+    out = set()
+    host = _src("msm_host.hip.h")
+    out |= {"k_tile_sort<%s>" % w for w in re.findall(r"KEAKI_TILE_SORT\((\d+)\);", host)}
+    m = re.search(r"#define KEAKI_CHUNK_SORT\(L, R, Q\).*", host).group(0)
+    masks = re.findall(r"KEAKI_CHUNK_SORT1\(L, R, Q, (true|false)\)", m)
+    assert sorted(masks) == ["false", "true"], m
+    for geom in re.findall(r"KEAKI_CHUNK_SORT\((\d+, \d+, \d+)\);", host):
+        for mk in masks:
+            out.add("k_chunk_sort<%s,%s>" % (geom.replace(" ", ""), mk))
+    for nt, mode in re.findall(r"KEAKI_ACC\((\d), (ACC_\w+)\);", host):
+        out.add(V.acc_g1_name(int(nt), mode))
+    for nt, mode, pf in re.findall(r"k_msm_accumulate_g1_u29<(\d), (ACC_\w+), (\d)>", host):
+        out.add(V.acc_g1_name(int(nt), mode, int(pf)))
+    assert "k_msm_accumulate<F>" in host
+    out.add("k_msm_accumulate<Fq>")
+    fft = _src("fft_g1.hip")
+    body = re.search(r"static void launch_stage3\(.*?\n}\n", fft, re.S).group(0)
+    as29 = re.findall(r"k_g1_fft_stage_map<DIT, UNI, GT, (true|false)>", body)
+    assert sorted(as29) == ["false", "true"]
+    for dit, uni, gt in re.findall(r"launch_stage3<(true|false), (true|false), (true|false)>", fft):
+        for a in as29:
+            out.add("k_g1_fft_stage_map<%s,%s,%s,%s>" % (dit, uni, gt, a))
+    for dit, a in re.findall(r"k_g1_fft_stage4<(true|false), (true|false)>\)", fft):
+        out.add("k_g1_fft_stage4<%s,%s>" % (dit, a))
+    for occ in re.findall(r"k_encap_fixed<Fq2, (\d)>", _src("ec_batch_g2.hip")):
+        out.add("k_encap_fixed<Fq2,%s>" % occ)
+    return out
+
+
+def test_the_launch_sites_parse_into_the_expected_families():
+    ls = launchable()
+    fam = lambda p: {k for k in ls if k.startswith(p)}
+    assert len(fam("k_tile_sort<")) == 7
+    assert len(fam("k_chunk_sort<")) == 8
+    assert len(fam("k_msm_accumulate_g1_u29<")) == 7
+    assert len(fam("k_g1_fft_stage_map<")) == 12
+    assert len(fam("k_g1_fft_stage4<")) == 4
+    assert fam("k_encap_fixed<") == {"k_encap_fixed<Fq2,1>", "k_encap_fixed<Fq2,2>"}
+
+
+def test_the_case_table_reaches_every_launchable_instantiation():
+    reached = set()
+    for _, ks in V.cases():
+        reached |= set(ks)
+    ls = launchable()
+    assert set(V.UNREACHABLE) <= ls
+    assert not (set(V.UNREACHABLE) & reached)
+    missing = ls - reached - set(V.UNREACHABLE)
+    assert not missing, "instantiations no case of tests/test_gpu_variants.py reaches: %s" % sorted(missing)
+
+
+def test_unreachable_instantiations_are_unreachable_for_every_accepted_width():
+    """k_tile_sort<11>: the plan of 11 windows is c = 24 only, which neither path accepts"""
+    for c in range(3, 25):
+        W = V.plan(c)["W"]
+        if W == 11:
+            assert V.width_refused(c, False) and V.width_refused(c, True), c
+    for n in [1 << k for k in range(0, 31)]:
+        assert V.plan(V.choose_window(n))["W"] != 11 and V.plan(V.choose_window_shared(n))["W"] != 11
+
+
+def test_refused_widths_are_exactly_the_plans_the_sort_cannot_take():
+    """set_option's limits (internal.h) against the sort model: a width is refused iff part_make_shape refuses its plan at any n and
+    bin count (generic: all buckets; window tables: the largest window)"""
+    for c in range(3, 25):
+        p = V.plan(c)
+        for shared in (False, True):
+            nb = p["max_b"] if shared else p["nb"]
+            for n in (1, V.N_SMALL, V.N_LARGE, 1 << 24):
+                for lb in (-1, 0, 11):
+                    assert (V.part_make_shape(n, p["W"], nb, lb) is None) == V.width_refused(c, shared), (c, shared, n, lb)
+    assert [c for c in range(3, 25) if V.width_refused(c, False)] == [20, 21, 22, 23, 24]
+    assert [c for c in range(3, 25) if V.width_refused(c, True)] == [24]
+    # the C side states the same rule once, checked by the compiler
+    assert "static_assert(msm_c_limit_is(MSM_C_MAX, false) && msm_c_limit_is(MSM_C_SHARED_MAX, true)" in _src("msm_g2.hip")
+    api = _src("api.hip")
+    assert 'geti("KEAKI_MSM_C", v) && !msm_c_too_wide(v, MSM_C_MAX)' in api
+    assert 'geti("KEAKI_MSM_C_SHARED", v) && !msm_c_too_wide(v, MSM_C_SHARED_MAX)' in api
+
+
+def test_digit_edge_scalars_reach_every_branch_of_every_plan():
+    need = {"zero", "one", "half", "neg_first", "neg", "full"}
+    for c in range(3, 25):
+        p = V.plan(c)
+        sc = V.digit_edge_scalars(c)
+        assert all(0 <= s < R for s in sc), c
+        seen = set()
+        for s in sc:
+            seen |= V.digit_branches(s, c)
+            # the digits restate the scalar: sum of +-(bucket + 1) 2^offset(w)
+            tot = sum((-(b + 1) if neg else (b + 1)) << p["offs"][w] for w, b, neg in S.msm_digits(s, c))
+            assert tot == s, (c, s)
+        for w in range(p["W"] - 1):
+            want = need - ({"full"} if w == 0 else set())        # no carry enters window 0
+            got = {b for ww, b in seen if ww == w}
+            assert want <= got, (c, w, want - got)
+        assert (p["W"] - 1, "top_max") in seen, c
+        assert all(1 << p["offs"][w] in sc for w in range(p["W"]))
+
+
+def test_switch_matrix_covers_every_geometry_masked_and_unmasked():
+    lbs = V.switch_lbs()
+    p = V.plan(V.choose_window(V.N_LARGE))
+    geoms = {V.part_make_shape(V.N_LARGE, p["W"], p["nb"], lb)["geom"] for lb in lbs}
+    assert geoms == {0, 1, 2, 3}
+    Ls = {V.reduce_len(p["max_b"], False, l) for l in V.REDUCE_L}
+    assert any(p["max_b"] % L for L in Ls), "no ragged last chunk"
+    assert V.reduce_len(p["max_b"], False, 4096) == V.reduce_len(p["max_b"]) or 4096 <= p["max_b"]
+    runs = V.switch_runs()
+    for sw in V.SWITCHES:
+        for ss in V.SCALAR_SETS:
+            mine = [r for r in runs if r[1] == ss and {k: v for k, v in r[0].items() if k not in ("part_shift", "reduce_l")} == sw]
+            assert {r[0].get("part_shift") for r in mine if not r[2]} == set(lbs)
+            assert {r[0].get("reduce_l") for r in mine if not r[2]} == set(V.REDUCE_L)
+            assert any(r[2] for r in mine)
+
+
+def test_operating_points_the_repository_records():
+    # 2^24 points with tables: c = 22 (README; tests/test_gpu_baseline_sizes.py: test_headline_msm_2p24_with_tables), lb 10, geometry 1
+    assert V.auto_shape(1 << 24, True) == (True, 22, 10, 1)
+    # generic MSMs of 2^22 points or more: c = 19, 2048 bins, geometry 0
+    for k in range(22, 27):
+        assert V.auto_shape(1 << k, False) == (False, 19, 11, 0)
+    # 2^22 points over tables: the shared path at >= 20 bits (tests/test_gpu_group.py: test_two_contexts_share_one_table_allocation)
+    assert V.auto_shape(1 << 22, True)[1] >= 20
+    # forced widths the GPU tests assert as window_bits: test_gpu_group.py (5, 9, 13), test_gpu_structured_srs.py (8, 10, 13, 16)
+    for c in (5, 9, 13, 8, 10, 16):
+        assert V.msm(3000, {"msm_c": c})["c"] == c
+        assert V.msm(1000, {}, table_c=c)["c"] == c
+    # a forced target is a plan target: 18 bits give the 15-window plan of 17, 21 / 23 those of 20 / 22
+    assert V.plan(18)["c"] == 17 and V.plan(21)["c"] == 20 and V.plan(23)["c"] == 22
+
+
+def test_every_automatic_shape_is_reached_by_a_test():
+    """automatic (path, geometry) over 2^5 .. 2^26 points: the small cases reach geometry 3; the large ones are reached by existing tests,
+    whose functions must still exist"""
+    auto = {(s[0], s[3]) for k in range(5, 27) for s in (V.auto_shape(1 << k, False), V.auto_shape(1 << k, True))}
+    reached = {(s[0], s[3]) for s in (V.auto_shape(V.N_LARGE, False), V.auto_shape(V.N_SMALL, False), V.auto_shape(V.N_LARGE, True))}
+    for test, n, tables, passes in V.AUTO_LARGE:
+        f, name = test.split("::")
+        with open(os.path.join(V.ROOT, f)) as fh:
+            assert re.search(r"def %s\(" % name, fh.read()), test
+        reached.add((lambda s: (s[0], s[3]))(V.auto_shape(n, tables, passes)))
+    assert auto <= reached, sorted(auto - reached)
+    # geometries 0, 1, 2 are automatic only at 2^19 points or more
+    assert {g for _, g in auto} == {0, 1, 2, 3}
+
+
+def test_fk_and_encap_models_follow_the_switches():
+    # fk_radix4 only acts under fk_uniform; fk_gtab only on the per-lane ladders
+    for log2d in V.FK_LOG2D:
+        base = V.fk_stage_kernels(log2d, {"fk_uniform": 0})
+        assert base == V.fk_stage_kernels(log2d, {"fk_uniform": 0, "fk_radix4": 0})
+        assert not any("stage4" in k for k in base)
+    big = V.fk_stage_kernels(12, {})
+    assert "k_g1_fft_stage4<true,true>" in big and "k_g1_fft_stage4<false,true>" in big
+    assert V.encap_g2_fixed_name(V.ENCAP_N, True, 0) == V.encap_g2_fixed_name(V.ENCAP_N, False, 0) == "k_encap_fixed<Fq2,2>"
+    assert V.encap_g2_fixed_name(V.ENCAP_N, True, 1) == "k_encap_fixed<Fq2,1>"
+    assert 65536 < V.ENCAP_N < 2 * 65536                 # one launch: above 2^16 items, below the two-chunk pipeline
