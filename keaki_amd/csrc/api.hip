@@ -4,7 +4,9 @@
 #include "internal.h"
 
 #include <algorithm>
+#include <cctype>
 #include <set>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -88,7 +90,7 @@ void mem_sub(std::atomic<size_t>& m, size_t v) {
   size_t cur = m.load();
   while (!m.compare_exchange_weak(cur, cur - std::min(cur, v))) {}
 }
-constexpr size_t G1_AFF_BYTES = 64, G2_AFF_BYTES = 128;
+constexpr size_t G1_AFF_BYTES = 64, G2_AFF_BYTES = 128, G1_JAC_BYTES = 96, G2_JAC_BYTES = 192;
 }  // namespace
 
 namespace keaki_internal {
@@ -191,7 +193,7 @@ H* new_srs(keaki_hip_ctx* ctx, const void* d, size_t n, bool owned) {
 // a handle may be used by any context of the device it lives on
 #define SRS_CHECK(ctx, srs, what)                                                                                                     \
   if ((srs)->device != (ctx)->device)                                                                                                 \
-    return fail(ctx, KEAKI_ERR_BAD_ARG, what ": the SRS handle lives on device %d, this context on device %d", (srs)->device, (ctx)->device)
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: the SRS handle lives on device %d, this context on device %d", what, (srs)->device, (ctx)->device)
 
 // The caller's OUTPUT buffer is usually fresh memory (calloc / vec![0; n] / numpy.zeros): its pages do not exist until first touched, and a
 // device-to-host copy into such pages crawls (160 MB of ciphertexts: 30 ms instead of 3). Touch one byte per page from the host WHILE the
@@ -309,6 +311,49 @@ static keaki_status pipelined(keaki_hip_ctx* ctx, size_t n, size_t ch, size_t ou
   HIP_TRY(ctx, hipStreamSynchronize(cs));
   return KEAKI_OK;
 }
+// One per-item region of a pipelined host batch, `bytes` per item: `in` is uploaded into it, `out` downloaded from it (both: in place --
+// messages in, bodies out), neither: device scratch.
+struct Region { const void* in; void* out; size_t bytes; };
+// A host batch through pipelined(): io_a = [head | half 0 | half 1], each half the chunk's regions one after the other (rounded to 256 B).
+// The head -- constants of the whole batch, laid out like the regions of a single item -- goes up on ctx->stream before the chunks.
+// `run(lo, m, d_head, d)` enqueues the kernels of items [lo, lo + m): d_head[i] = head region i, d[i] = region i of the chunk's half.
+template <class Run>
+static keaki_status pipelined_regions(keaki_hip_ctx* ctx, size_t n, size_t ch, std::initializer_list<Region> head,
+                                      std::initializer_list<Region> regions, Run run) {
+  const std::vector<Region> rg(regions);
+  size_t head_bytes = 0, half = 0, out_bytes = 0;
+  for (const Region& x : head) head_bytes += x.bytes;
+  for (const Region& x : rg) { half += ch * x.bytes; if (x.out) out_bytes += x.bytes; }
+  head_bytes = (head_bytes + 255) & ~(size_t)255;
+  half = (half + 255) & ~(size_t)255;
+  ST_TRY(reserve(ctx, ctx->io_a, head_bytes + 2 * half));
+  std::vector<char*> d_head, d[2];
+  char* p = (char*)ctx->io_a.p;
+  for (const Region& x : head) {
+    d_head.push_back(p);
+    HIP_TRY(ctx, hipMemcpyAsync(p, x.in, x.bytes, hipMemcpyHostToDevice, ctx->stream));
+    p += x.bytes;
+  }
+  for (int h = 0; h < 2; h++) {
+    p = (char*)ctx->io_a.p + head_bytes + h * half;
+    for (const Region& x : rg) { d[h].push_back(p); p += ch * x.bytes; }
+  }
+  return pipelined(ctx, n, ch, out_bytes,
+    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
+      for (size_t i = 0; i < rg.size(); i++)
+        if (rg[i].in) HIP_TRY(ctx, hipMemcpyAsync(d[h][i], (const char*)rg[i].in + lo * rg[i].bytes, m * rg[i].bytes, hipMemcpyHostToDevice, cs));
+      return KEAKI_OK;
+    },
+    [&](size_t lo, size_t m, int h) -> keaki_status { return run(lo, m, d_head.data(), d[h].data()); },
+    [&](size_t lo, size_t m) {
+      for (const Region& x : rg) if (x.out) prefault_out(ctx, (char*)x.out + lo * x.bytes, m * x.bytes);
+    },
+    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
+      for (size_t i = 0; i < rg.size(); i++)
+        if (rg[i].out) HIP_TRY(ctx, hipMemcpyAsync((char*)rg[i].out + lo * rg[i].bytes, d[h][i], m * rg[i].bytes, hipMemcpyDeviceToHost, cs));
+      return KEAKI_OK;
+    });
+}
 
 
 // ---- MSM of a scalar vector in HOST memory -----------------------------------------------------------------------------------------
@@ -395,6 +440,59 @@ static keaki_status msm_from_host(keaki_hip_ctx* ctx, const uint64_t* scalars, s
   keaki_internal::DeviceScope dev_((ctx)->device);              \
   if (!dev_.ok) return fail(ctx, KEAKI_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
 
+// What tells the G1 and G2 forms of the MSM and mul_batch entries apart: the point sizes, the launchers and the names in messages and traces.
+struct GroupEntries {
+  size_t aff, jac;
+  const char *msm, *msm_trace, *mul, *mul_trace;
+  decltype(&msm_g1_run) msm_run;
+  decltype(&g1_mul_batch_run) mul_run;
+};
+constexpr GroupEntries G1E = {G1_AFF_BYTES, G1_JAC_BYTES, "msm_g1", "keaki.msm_g1", "g1_mul_batch", "keaki.g1_mul_batch", msm_g1_run, g1_mul_batch_run};
+constexpr GroupEntries G2E = {G2_AFF_BYTES, G2_JAC_BYTES, "msm_g2", "keaki.msm_g2", "g2_mul_batch", "keaki.g2_mul_batch", msm_g2_run, g2_mul_batch_run};
+template <class Srs>
+keaki_status msm_dev(const GroupEntries& g, keaki_hip_ctx* ctx, const Srs* srs, const void* d_scalars, size_t n, void* d_out_jac) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE(g.msm_trace);
+  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: srs is null", g.msm);
+  SRS_CHECK(ctx, srs, g.msm);
+  const auto tb = srs_tables(srs);
+  return g.msm_run(ctx, srs->d, srs->n, d_scalars, n, d_out_jac, tb.first, tb.second, nullptr);
+}
+template <class Srs>
+keaki_status msm_host(const GroupEntries& g, keaki_hip_ctx* ctx, const Srs* srs, const uint64_t* scalars, size_t n, uint64_t* out_jac) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE(g.msm_trace);
+  if (!srs || !out_jac || (n && !scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", g.msm);
+  SRS_CHECK(ctx, srs, g.msm);
+  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
+  ST_TRY(reserve(ctx, ctx->io_b, g.jac));
+  const auto tb = srs_tables(srs);
+  ST_TRY(msm_from_host(ctx, scalars, n, [&](const MsmPipe* pipe) {
+    return g.msm_run(ctx, srs->d, srs->n, ctx->io_a.p, n, ctx->io_b.p, tb.first, tb.second, pipe);
+  }));
+  ST_TRY(download(ctx, out_jac, ctx->io_b.p, g.jac));
+  resolve_timing(ctx);
+  return KEAKI_OK;
+}
+keaki_status mul_batch_dev(const GroupEntries& g, keaki_hip_ctx* ctx, const void* d_points_aff, int32_t point_stride, const void* d_scalars, size_t n, void* d_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE(g.mul_trace);
+  if (n == 0) return KEAKI_OK;
+  if (!d_points_aff || !d_scalars || !d_out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", g.mul);
+  return g.mul_run(ctx, d_points_aff, (int)point_stride, d_scalars, n, d_out_aff);
+}
+keaki_status mul_batch_host(const GroupEntries& g, keaki_hip_ctx* ctx, const uint64_t* points_aff, int32_t point_stride, const uint64_t* scalars, size_t n, uint64_t* out_aff) {
+  CTX_GUARD(ctx);                 // held across stage -> kernel -> download: io_a/io_b/io_c belong to this call until it returns
+  if (n == 0) return KEAKI_OK;
+  if (!points_aff || !scalars || !out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", g.mul);
+  ST_TRY(upload(ctx, ctx->io_a, points_aff, (point_stride ? n : 1) * g.aff));
+  ST_TRY(upload(ctx, ctx->io_b, scalars, n * 32));
+  ST_TRY(reserve(ctx, ctx->io_c, n * g.aff));
+  ST_TRY(mul_batch_dev(g, ctx, ctx->io_a.p, point_stride, ctx->io_b.p, n, ctx->io_c.p));
+  prefault_out(ctx, out_aff, n * g.aff);
+  return download(ctx, out_aff, ctx->io_c.p, n * g.aff);
+}
+
 }  // namespace
 
 extern "C" {
@@ -412,35 +510,61 @@ const char* keaki_hip_version(void) { return "keaki-hip 0.3 (gfx950) src=" KEAKI
 
 extern "C++" {
 namespace {
-// The ONE place the library reads the environment: initial values of a context's tuning switches.
+// The tuning options (Tuning, internal.h), each declared ONCE: keaki_hip_ctx_set_option and the environment (tune_from_env) both go through
+// this table. An option is named after its member, its variable is KEAKI_<NAME>, and its value converts as the member's type does ((int)v,
+// v != 0, long long). `refuses(ctx, name, v)`: the values set_option fails (KEAKI_ERR_BAD_ARG, the message recorded on ctx); the environment
+// asks with ctx = nullptr and ignores what is refused. `on_change`: what a set_option that changes the value invalidates.
+struct TuneOption {
+  const char* name;
+  bool (*assign)(Tuning& t, long long v);                               // true: the value changed
+  bool (*refuses)(keaki_hip_ctx* ctx, const char* name, long long v) = nullptr;
+  void (*on_change)(keaki_hip_ctx* ctx) = nullptr;
+  bool from_env = true;
+};
+template <auto M>
+bool assign_member(Tuning& t, long long v) {
+  auto& f = t.*M;
+  const auto old = f;
+  f = (std::remove_reference_t<decltype(f)>)v;
+  return f != old;
+}
+template <int MX>
+bool msm_c_refuses(keaki_hip_ctx* ctx, const char* name, long long v) {           // a width no plan can run (the environment: stays automatic)
+  if (!msm_c_too_wide(v, MX)) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: %s = %lld exceeds %d, the widest window whose buckets the bucket sort can address (3 .. %d; 0 = automatic)",
+                name, v, MX, MX);
+  return true;
+}
+bool gt_wb_b_refuses(keaki_hip_ctx* ctx, const char*, long long v) {          // the environment's width is taken as it is: encap_impl refuses it on use
+  if (!ctx || v == 0 || (v >= 8 && v <= 22 && gt_table_powers((uint32_t)v) <= 320)) return false;
+  fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: gt_wb_b = %lld out of range", v);
+  return true;
+}
+#define TUNE_OPTION(member, ...) TuneOption{#member, assign_member<&Tuning::member>, __VA_ARGS__}
+const TuneOption TUNE_OPTIONS[] = {
+    TUNE_OPTION(msm_c, msm_c_refuses<MSM_C_MAX>), TUNE_OPTION(msm_c_shared, msm_c_refuses<MSM_C_SHARED_MAX>), TUNE_OPTION(msm_short_tables),
+    TUNE_OPTION(reduce_l), TUNE_OPTION(part_shift), TUNE_OPTION(acc_u29), TUNE_OPTION(acc_u29_g2), TUNE_OPTION(acc_prefetch), TUNE_OPTION(acc_idxq),
+    TUNE_OPTION(cs_masked), TUNE_OPTION(acc_nt), TUNE_OPTION(fk_uniform), TUNE_OPTION(fk_gtab), TUNE_OPTION(fk_radix4), TUNE_OPTION(fk_addsub29),
+    TUNE_OPTION(fb_occ1), TUNE_OPTION(pair_wide_max), TUNE_OPTION(pair_two_waves),
+    TUNE_OPTION(gt_wb_b, gt_wb_b_refuses, [](keaki_hip_ctx* ctx) { ctx->gt_b_ready = ctx->gt_b_fallback = false; }),   // B's table: rebuilt at the new width on next use
+    TUNE_OPTION(encap_gt), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
+    TUNE_OPTION(msm_pipe_growth),
+#ifdef KEAKI_DIAG
+    TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
+#endif
+};
+#undef TUNE_OPTION
+// The ONE place the library reads the environment: initial values of a context's tuning switches (an unset or empty variable is ignored).
 void tune_from_env(Tuning& t) {
-  auto geti = [](const char* name, long long& out) { const char* e = getenv(name); if (!e || !*e) return false; out = atoll(e); return true; };
-  long long v;
-  if (geti("KEAKI_MSM_C", v) && !msm_c_too_wide(v, MSM_C_MAX)) t.msm_c = (int)v;                      // a width no plan can run stays automatic
-  if (geti("KEAKI_MSM_C_SHARED", v) && !msm_c_too_wide(v, MSM_C_SHARED_MAX)) t.msm_c_shared = (int)v;
-  if (geti("KEAKI_REDUCE_L", v)) t.reduce_l = (int)v;
-  if (geti("KEAKI_PART_SHIFT", v)) t.part_shift = (int)v;
-  if (geti("KEAKI_ACC_U29", v)) t.acc_u29 = v != 0;
-  if (geti("KEAKI_ACC_U29_G2", v)) t.acc_u29_g2 = v != 0;
-  if (geti("KEAKI_ACC_NT", v)) t.acc_nt = v != 0;
-  if (geti("KEAKI_ACC_PREFETCH", v)) t.acc_prefetch = v != 0;
-  if (geti("KEAKI_ACC_IDXQ", v)) t.acc_idxq = v != 0;
-  if (geti("KEAKI_CS_MASKED", v)) t.cs_masked = v != 0;
-  if (geti("KEAKI_FK_UNIFORM", v)) t.fk_uniform = v != 0;
-  if (geti("KEAKI_FK_GTAB", v)) t.fk_gtab = v != 0;
-  if (geti("KEAKI_FK_ADDSUB29", v)) t.fk_addsub29 = v != 0;
-  if (geti("KEAKI_FK_RADIX4", v)) t.fk_radix4 = v != 0;
-  if (geti("KEAKI_FB_OCC1", v)) t.fb_occ1 = v != 0;
-  if (geti("KEAKI_MSM_SHORT_TABLES", v)) t.msm_short_tables = (int)v;
-  if (geti("KEAKI_PAIR_WIDE_MAX", v)) t.pair_wide_max = (int)v;
-  if (geti("KEAKI_PAIR_TWO_WAVES", v)) t.pair_two_waves = v != 0;
-  if (geti("KEAKI_GT_WB_B", v)) t.gt_wb_b = (int)v;
-  if (geti("KEAKI_ENCAP_GT", v)) t.encap_gt = v;
-  if (geti("KEAKI_HOST_PREFAULT", v)) t.host_prefault = v != 0;
-  if (geti("KEAKI_PIPE_CHUNKS", v)) t.pipe_chunks = v != 0;
-  if (geti("KEAKI_MSM_PIPE_CHUNKS", v)) t.msm_pipe_chunks = (int)v;
-  if (geti("KEAKI_MSM_PIPE_MIN", v)) t.msm_pipe_min = v;
-  if (geti("KEAKI_MSM_PIPE_GROWTH", v)) t.msm_pipe_growth = (int)v;
+  for (const TuneOption& o : TUNE_OPTIONS) {
+    if (!o.from_env) continue;
+    std::string var = "KEAKI_";
+    for (const char* c = o.name; *c; c++) var += (char)toupper((unsigned char)*c);
+    const char* e = getenv(var.c_str());
+    if (!e || !*e) continue;
+    const long long v = atoll(e);
+    if (!o.refuses || !o.refuses(nullptr, o.name, v)) o.assign(t, v);
+  }
 }
 struct BufClass { DevBuf* b; int cls; };   // cls: 1 = workspace, 2 = GT / fixed-base tables of encapsulate
 std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
@@ -524,47 +648,13 @@ keaki_status keaki_hip_ctx_set_option(keaki_hip_ctx* ctx, const char* name, int6
   if (!ctx) return KEAKI_ERR_BAD_ARG;
   std::lock_guard<std::recursive_mutex> lock_(ctx->mu);
   if (!name) return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: name is null");
-  Tuning& t = ctx->tune;
-  const std::string k(name);
-  if (k == "msm_c" || k == "msm_c_shared") {
-    const bool sh = k == "msm_c_shared";
-    const int mx = sh ? MSM_C_SHARED_MAX : MSM_C_MAX;
-    if (msm_c_too_wide(value, mx))
-      return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: %s = %lld exceeds %d, the widest window whose buckets the bucket sort can address (3 .. %d; 0 = automatic)",
-                  name, (long long)value, mx, mx);
-    (sh ? t.msm_c_shared : t.msm_c) = (int)value;
+  for (const TuneOption& o : TUNE_OPTIONS) {
+    if (strcmp(o.name, name) != 0) continue;
+    if (o.refuses && o.refuses(ctx, name, value)) return KEAKI_ERR_BAD_ARG;
+    if (o.assign(ctx->tune, value) && o.on_change) o.on_change(ctx);
+    return KEAKI_OK;
   }
-  else if (k == "reduce_l") t.reduce_l = (int)value;
-  else if (k == "part_shift") t.part_shift = (int)value;
-  else if (k == "acc_u29") t.acc_u29 = value != 0;
-  else if (k == "acc_u29_g2") t.acc_u29_g2 = value != 0;
-  else if (k == "acc_nt") t.acc_nt = value != 0;
-  else if (k == "acc_prefetch") t.acc_prefetch = value != 0;
-  else if (k == "acc_idxq") t.acc_idxq = value != 0;
-  else if (k == "cs_masked") t.cs_masked = value != 0;
-  else if (k == "fk_uniform") t.fk_uniform = value != 0;
-  else if (k == "fk_gtab") t.fk_gtab = value != 0;
-  else if (k == "fk_addsub29") t.fk_addsub29 = value != 0;
-  else if (k == "fk_radix4") t.fk_radix4 = value != 0;
-  else if (k == "fb_occ1") t.fb_occ1 = value != 0;
-  else if (k == "msm_short_tables") t.msm_short_tables = (int)value;
-  else if (k == "pair_wide_max") t.pair_wide_max = (int)value;
-  else if (k == "pair_two_waves") t.pair_two_waves = value != 0;
-  else if (k == "gt_wb_b") {
-    if (value != 0 && (value < 8 || value > 22 || gt_table_powers((uint32_t)value) > 320)) return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: gt_wb_b = %lld out of range", (long long)value);
-    if ((int)value != t.gt_wb_b) { ctx->gt_b_ready = false; ctx->gt_b_fallback = false; }      // the table of B is rebuilt at the new width on the next use
-    t.gt_wb_b = (int)value;
-  } else if (k == "encap_gt") t.encap_gt = value;
-  else if (k == "host_prefault") t.host_prefault = value != 0;
-  else if (k == "pipe_chunks") t.pipe_chunks = value != 0;
-#ifdef KEAKI_DIAG
-  else if (k == "diag_row_mask") t.diag_row_mask = (unsigned)value;
-#endif
-  else if (k == "msm_pipe_chunks") t.msm_pipe_chunks = (int)value;
-  else if (k == "msm_pipe_min") t.msm_pipe_min = value;
-  else if (k == "msm_pipe_growth") t.msm_pipe_growth = (int)value;
-  else return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: unknown option '%s'", name);
-  return KEAKI_OK;
+  return fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: unknown option '%s'", name);
 }
 keaki_status keaki_hip_debug_set_alloc_limit(keaki_hip_ctx* ctx, size_t bytes) {
   if (!ctx) return KEAKI_ERR_BAD_ARG;
@@ -737,50 +827,16 @@ keaki_status keaki_hip_srs_g2_precompute(keaki_hip_ctx* ctx, keaki_hip_srs_g2* s
 
 // ---- MSM -----------------------------------------------------------------------------------------
 keaki_status keaki_hip_msm_g1_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_scalars, size_t n, void* d_out_jac) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.msm_g1");
-  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g1: srs is null");
-  SRS_CHECK(ctx, srs, "msm_g1");
-  const auto tb = srs_tables(srs);
-  return msm_g1_run(ctx, srs->d, srs->n, d_scalars, n, d_out_jac, tb.first, tb.second);
+  return msm_dev(G1E, ctx, srs, d_scalars, n, d_out_jac);
 }
 keaki_status keaki_hip_msm_g1(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* scalars, size_t n, uint64_t* out_jac) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.msm_g1");
-  if (!srs || !out_jac || (n && !scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g1: null pointer");
-  SRS_CHECK(ctx, srs, "msm_g1");
-  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
-  ST_TRY(reserve(ctx, ctx->io_b, 96));
-  const auto tb = srs_tables(srs);
-  ST_TRY(msm_from_host(ctx, scalars, n, [&](const MsmPipe* pipe) {
-    return msm_g1_run(ctx, srs->d, srs->n, ctx->io_a.p, n, ctx->io_b.p, tb.first, tb.second, pipe);
-  }));
-  ST_TRY(download(ctx, out_jac, ctx->io_b.p, 96));
-  resolve_timing(ctx);
-  return KEAKI_OK;
+  return msm_host(G1E, ctx, srs, scalars, n, out_jac);
 }
 keaki_status keaki_hip_msm_g2_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g2* srs, const void* d_scalars, size_t n, void* d_out_jac) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.msm_g2");
-  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g2: srs is null");
-  SRS_CHECK(ctx, srs, "msm_g2");
-  const auto tb = srs_tables(srs);
-  return msm_g2_run(ctx, srs->d, srs->n, d_scalars, n, d_out_jac, tb.first, tb.second);
+  return msm_dev(G2E, ctx, srs, d_scalars, n, d_out_jac);
 }
 keaki_status keaki_hip_msm_g2(keaki_hip_ctx* ctx, const keaki_hip_srs_g2* srs, const uint64_t* scalars, size_t n, uint64_t* out_jac) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.msm_g2");
-  if (!srs || !out_jac || (n && !scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g2: null pointer");
-  SRS_CHECK(ctx, srs, "msm_g2");
-  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
-  ST_TRY(reserve(ctx, ctx->io_b, 192));
-  const auto tb = srs_tables(srs);
-  ST_TRY(msm_from_host(ctx, scalars, n, [&](const MsmPipe* pipe) {
-    return msm_g2_run(ctx, srs->d, srs->n, ctx->io_a.p, n, ctx->io_b.p, tb.first, tb.second, pipe);
-  }));
-  ST_TRY(download(ctx, out_jac, ctx->io_b.p, 192));
-  resolve_timing(ctx);
-  return KEAKI_OK;
+  return msm_host(G2E, ctx, srs, scalars, n, out_jac);
 }
 keaki_status keaki_hip_g1_sum_dev(keaki_hip_ctx* ctx, const void* d_points_jac, size_t k, void* d_out_jac) {
   CTX_GUARD(ctx);
@@ -798,45 +854,17 @@ keaki_status keaki_hip_g1_sum(keaki_hip_ctx* ctx, const uint64_t* points_jac, si
 }
 
 // ---- batched scalar multiplication -------------------------------------------------------------------
-keaki_status keaki_hip_g1_mul_batch_dev(keaki_hip_ctx* ctx, const void* d_points_aff, int32_t point_stride, const void* d_scalars, size_t n,
-                                        void* d_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.g1_mul_batch");
-  if (n == 0) return KEAKI_OK;
-  if (!d_points_aff || !d_scalars || !d_out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g1_mul_batch: bad argument");
-  return g1_mul_batch_run(ctx, d_points_aff, (int)point_stride, d_scalars, n, d_out_aff);
+keaki_status keaki_hip_g1_mul_batch_dev(keaki_hip_ctx* ctx, const void* d_points_aff, int32_t point_stride, const void* d_scalars, size_t n, void* d_out_aff) {
+  return mul_batch_dev(G1E, ctx, d_points_aff, point_stride, d_scalars, n, d_out_aff);
 }
-keaki_status keaki_hip_g2_mul_batch_dev(keaki_hip_ctx* ctx, const void* d_points_aff, int32_t point_stride, const void* d_scalars, size_t n,
-                                        void* d_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.g2_mul_batch");
-  if (n == 0) return KEAKI_OK;
-  if (!d_points_aff || !d_scalars || !d_out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_mul_batch: bad argument");
-  return g2_mul_batch_run(ctx, d_points_aff, (int)point_stride, d_scalars, n, d_out_aff);
+keaki_status keaki_hip_g2_mul_batch_dev(keaki_hip_ctx* ctx, const void* d_points_aff, int32_t point_stride, const void* d_scalars, size_t n, void* d_out_aff) {
+  return mul_batch_dev(G2E, ctx, d_points_aff, point_stride, d_scalars, n, d_out_aff);
 }
-keaki_status keaki_hip_g1_mul_batch(keaki_hip_ctx* ctx, const uint64_t* points_aff, int32_t point_stride, const uint64_t* scalars, size_t n,
-                                    uint64_t* out_aff) {
-  CTX_GUARD(ctx);                 // held across stage -> kernel -> download: io_a/io_b/io_c belong to this call until it returns
-  if (n == 0) return KEAKI_OK;
-  if (!points_aff || !scalars || !out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g1_mul_batch: bad argument");
-  ST_TRY(upload(ctx, ctx->io_a, points_aff, (point_stride ? n : 1) * 64));
-  ST_TRY(upload(ctx, ctx->io_b, scalars, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_c, n * 64));
-  ST_TRY(keaki_hip_g1_mul_batch_dev(ctx, ctx->io_a.p, point_stride, ctx->io_b.p, n, ctx->io_c.p));
-  prefault_out(ctx, out_aff, n * 64);
-  return download(ctx, out_aff, ctx->io_c.p, n * 64);
+keaki_status keaki_hip_g1_mul_batch(keaki_hip_ctx* ctx, const uint64_t* points_aff, int32_t point_stride, const uint64_t* scalars, size_t n, uint64_t* out_aff) {
+  return mul_batch_host(G1E, ctx, points_aff, point_stride, scalars, n, out_aff);
 }
-keaki_status keaki_hip_g2_mul_batch(keaki_hip_ctx* ctx, const uint64_t* points_aff, int32_t point_stride, const uint64_t* scalars, size_t n,
-                                    uint64_t* out_aff) {
-  CTX_GUARD(ctx);                 // held across stage -> kernel -> download: io_a/io_b/io_c belong to this call until it returns
-  if (n == 0) return KEAKI_OK;
-  if (!points_aff || !scalars || !out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_mul_batch: bad argument");
-  ST_TRY(upload(ctx, ctx->io_a, points_aff, (point_stride ? n : 1) * 128));
-  ST_TRY(upload(ctx, ctx->io_b, scalars, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_c, n * 128));
-  ST_TRY(keaki_hip_g2_mul_batch_dev(ctx, ctx->io_a.p, point_stride, ctx->io_b.p, n, ctx->io_c.p));
-  prefault_out(ctx, out_aff, n * 128);
-  return download(ctx, out_aff, ctx->io_c.p, n * 128);
+keaki_status keaki_hip_g2_mul_batch(keaki_hip_ctx* ctx, const uint64_t* points_aff, int32_t point_stride, const uint64_t* scalars, size_t n, uint64_t* out_aff) {
+  return mul_batch_host(G2E, ctx, points_aff, point_stride, scalars, n, out_aff);
 }
 
 // ---- pairing ---------------------------------------------------------------------------------------------
@@ -1146,39 +1174,13 @@ keaki_status keaki_hip_encap_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff, 
   if (n == 0) return KEAKI_OK;
   if (!com_aff || !tau_g2_aff || !points || !values || !r || !ct_out_aff || (!gt_out && !key_out) || msg_len > 65536)
     return fail(ctx, KEAKI_ERR_BAD_ARG, "encap_batch: bad argument");
-  const size_t ch = pipe_chunk_items(ctx, n);
-  const size_t off_pts = 0, off_val = off_pts + ch * 32, off_r = off_val + ch * 32, off_ct = off_r + ch * 32, off_gt = off_ct + ch * 128,
-               off_key = off_gt + ch * 384, half = (off_key + ch * msg_len + 255) & ~(size_t)255;
-  ST_TRY(reserve(ctx, ctx->io_a, 256 + 2 * half));
-  char* base = (char*)ctx->io_a.p;
-  HIP_TRY(ctx, hipMemcpyAsync(base, com_aff, 64, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(base + 64, tau_g2_aff, 128, hipMemcpyHostToDevice, ctx->stream));
   const bool want_key = key_out && msg_len;
-  return pipelined(ctx, n, ch, 128 + (gt_out ? 384 : 0) + (want_key ? msg_len : 0),
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + 256 + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_pts, points + 4 * lo, m * 32, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_val, values + 4 * lo, m * 32, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_r, r + 4 * lo, m * 32, hipMemcpyHostToDevice, cs));
-      return KEAKI_OK;
-    },
-    [&](size_t lo, size_t m, int h) -> keaki_status {
-      char* b = base + 256 + h * half;
+  return pipelined_regions(ctx, n, pipe_chunk_items(ctx, n), {{com_aff, nullptr, G1_AFF_BYTES}, {tau_g2_aff, nullptr, G2_AFF_BYTES}},
+    {{points, nullptr, 32}, {values, nullptr, 32}, {r, nullptr, 32}, {nullptr, ct_out_aff, G2_AFF_BYTES}, {nullptr, gt_out, 384},
+     {nullptr, want_key ? key_out : nullptr, msg_len}},
+    [&](size_t lo, size_t m, char* const* hd, char* const* d) {
       const EncapHost eh = {com_aff, tau_g2_aff, n, lo == 0};
-      return encap_impl(ctx, false, base, base + 64, b + off_pts, b + off_val, b + off_r, m, b + off_ct, b + off_gt, want_key ? b + off_key : nullptr,
-                        msg_len, false, &eh);
-    },
-    [&](size_t lo, size_t m) {
-      prefault_out(ctx, ct_out_aff + 16 * lo, m * 128);
-      if (gt_out) prefault_out(ctx, gt_out + 384 * lo, m * 384);
-      if (want_key) prefault_out(ctx, key_out + msg_len * lo, m * msg_len);
-    },
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + 256 + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(ct_out_aff + 16 * lo, b + off_ct, m * 128, hipMemcpyDeviceToHost, cs));
-      if (gt_out) HIP_TRY(ctx, hipMemcpyAsync(gt_out + 384 * lo, b + off_gt, m * 384, hipMemcpyDeviceToHost, cs));
-      if (want_key) HIP_TRY(ctx, hipMemcpyAsync(key_out + msg_len * lo, b + off_key, m * msg_len, hipMemcpyDeviceToHost, cs));
-      return KEAKI_OK;
+      return encap_impl(ctx, false, hd[0], hd[1], d[0], d[1], d[2], m, d[3], d[4], want_key ? d[5] : nullptr, msg_len, false, &eh);
     });
 }
 keaki_status keaki_hip_decap_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_aff, const uint64_t* cts_aff, size_t n, uint8_t* gt_out,
@@ -1187,32 +1189,12 @@ keaki_status keaki_hip_decap_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_af
   TRACE_SCOPE("keaki.decap");
   if (n == 0) return KEAKI_OK;
   if (!proofs_aff || !cts_aff || (!gt_out && !key_out) || msg_len > 65536) return fail(ctx, KEAKI_ERR_BAD_ARG, "decap_batch: bad argument");
-  const size_t ch = pipe_chunk_items(ctx, n, pairing_launch_items());
-  const size_t off_ct = ch * 64, off_gt = off_ct + ch * 128, off_key = off_gt + ch * 384, half = (off_key + ch * msg_len + 255) & ~(size_t)255;
-  ST_TRY(reserve(ctx, ctx->io_a, 2 * half));
-  char* base = (char*)ctx->io_a.p;
   const bool want_key = key_out && msg_len;
-  return pipelined(ctx, n, ch, (gt_out ? 384 : 0) + (want_key ? msg_len : 0),
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(b, proofs_aff + 8 * lo, m * 64, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_ct, cts_aff + 16 * lo, m * 128, hipMemcpyHostToDevice, cs));
-      return KEAKI_OK;
-    },
-    [&](size_t, size_t m, int h) -> keaki_status {
-      char* b = base + h * half;
-      ST_TRY(pairing_run(ctx, b, b + off_ct, 1, m, b + off_gt));
-      if (want_key) ST_TRY(blake3_gt_run(ctx, b + off_gt, m, b + off_key, msg_len));
-      return KEAKI_OK;
-    },
-    [&](size_t lo, size_t m) {
-      if (gt_out) prefault_out(ctx, gt_out + 384 * lo, m * 384);
-      if (want_key) prefault_out(ctx, key_out + msg_len * lo, m * msg_len);
-    },
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + h * half;
-      if (gt_out) HIP_TRY(ctx, hipMemcpyAsync(gt_out + 384 * lo, b + off_gt, m * 384, hipMemcpyDeviceToHost, cs));
-      if (want_key) HIP_TRY(ctx, hipMemcpyAsync(key_out + msg_len * lo, b + off_key, m * msg_len, hipMemcpyDeviceToHost, cs));
+  return pipelined_regions(ctx, n, pipe_chunk_items(ctx, n, pairing_launch_items()), {},
+    {{proofs_aff, nullptr, G1_AFF_BYTES}, {cts_aff, nullptr, G2_AFF_BYTES}, {nullptr, gt_out, 384}, {nullptr, want_key ? key_out : nullptr, msg_len}},
+    [&](size_t, size_t m, char* const*, char* const* d) -> keaki_status {
+      ST_TRY(pairing_run(ctx, d[0], d[1], 1, m, d[2]));
+      if (want_key) ST_TRY(blake3_gt_run(ctx, d[2], m, d[3], msg_len));
       return KEAKI_OK;
     });
 }
@@ -1246,36 +1228,11 @@ keaki_status keaki_hip_encrypt_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff
   if (n == 0) return KEAKI_OK;
   if (!com_aff || !tau_g2_aff || !points || !values || !r || !msgs || !ct_out_aff || !body_out || msg_len == 0 || msg_len > 65536)
     return fail(ctx, KEAKI_ERR_BAD_ARG, "encrypt_batch: bad argument");
-  const size_t ch = pipe_chunk_items(ctx, n);
-  const size_t off_pts = 0, off_val = off_pts + ch * 32, off_r = off_val + ch * 32, off_ct = off_r + ch * 32, off_body = off_ct + ch * 128,
-               half = (off_body + ch * msg_len + 255) & ~(size_t)255;
-  ST_TRY(reserve(ctx, ctx->io_a, 256 + 2 * half));
-  char* base = (char*)ctx->io_a.p;
-  HIP_TRY(ctx, hipMemcpyAsync(base, com_aff, 64, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(base + 64, tau_g2_aff, 128, hipMemcpyHostToDevice, ctx->stream));
-  return pipelined(ctx, n, ch, 128 + msg_len,
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + 256 + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_pts, points + 4 * lo, m * 32, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_val, values + 4 * lo, m * 32, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_r, r + 4 * lo, m * 32, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_body, msgs + msg_len * lo, m * msg_len, hipMemcpyHostToDevice, cs));
-      return KEAKI_OK;
-    },
-    [&](size_t lo, size_t m, int h) -> keaki_status {
-      char* b = base + 256 + h * half;
+  return pipelined_regions(ctx, n, pipe_chunk_items(ctx, n), {{com_aff, nullptr, G1_AFF_BYTES}, {tau_g2_aff, nullptr, G2_AFF_BYTES}},
+    {{points, nullptr, 32}, {values, nullptr, 32}, {r, nullptr, 32}, {nullptr, ct_out_aff, G2_AFF_BYTES}, {msgs, body_out, msg_len}},
+    [&](size_t lo, size_t m, char* const* hd, char* const* d) {
       const EncapHost eh = {com_aff, tau_g2_aff, n, lo == 0};
-      return encap_impl(ctx, false, base, base + 64, b + off_pts, b + off_val, b + off_r, m, b + off_ct, nullptr, b + off_body, msg_len, true, &eh);
-    },
-    [&](size_t lo, size_t m) {
-      prefault_out(ctx, ct_out_aff + 16 * lo, m * 128);
-      prefault_out(ctx, body_out + msg_len * lo, m * msg_len);
-    },
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + 256 + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(ct_out_aff + 16 * lo, b + off_ct, m * 128, hipMemcpyDeviceToHost, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(body_out + msg_len * lo, b + off_body, m * msg_len, hipMemcpyDeviceToHost, cs));
-      return KEAKI_OK;
+      return encap_impl(ctx, false, hd[0], hd[1], d[0], d[1], d[2], m, d[3], nullptr, d[4], msg_len, true, &eh);
     });
 }
 keaki_status keaki_hip_decrypt_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_aff, const uint64_t* cts_aff, const uint8_t* bodies, size_t n,
@@ -1285,28 +1242,11 @@ keaki_status keaki_hip_decrypt_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_
   if (n == 0) return KEAKI_OK;
   if (!proofs_aff || !cts_aff || !bodies || !msgs_out || msg_len == 0 || msg_len > 65536) return fail(ctx, KEAKI_ERR_BAD_ARG, "decrypt_batch: bad argument");
   const size_t ch = pipe_chunk_items(ctx, n, pairing_launch_items());
-  const size_t off_ct = ch * 64, off_body = off_ct + ch * 128, half = (off_body + ch * msg_len + 255) & ~(size_t)255;
-  ST_TRY(reserve(ctx, ctx->io_a, 2 * half));
-  ST_TRY(reserve(ctx, ctx->tmp_b, ch * 384));
-  char* base = (char*)ctx->io_a.p;
-  return pipelined(ctx, n, ch, msg_len,
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(b, proofs_aff + 8 * lo, m * 64, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_ct, cts_aff + 16 * lo, m * 128, hipMemcpyHostToDevice, cs));
-      HIP_TRY(ctx, hipMemcpyAsync(b + off_body, bodies + msg_len * lo, m * msg_len, hipMemcpyHostToDevice, cs));
-      return KEAKI_OK;
-    },
-    [&](size_t, size_t m, int h) -> keaki_status {
-      char* b = base + h * half;
-      ST_TRY(pairing_run(ctx, b, b + off_ct, 1, m, ctx->tmp_b.p));
-      return blake3_gt_run(ctx, ctx->tmp_b.p, m, b + off_body, msg_len, true);
-    },
-    [&](size_t lo, size_t m) { prefault_out(ctx, msgs_out + msg_len * lo, m * msg_len); },
-    [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
-      char* b = base + h * half;
-      HIP_TRY(ctx, hipMemcpyAsync(msgs_out + msg_len * lo, b + off_body, m * msg_len, hipMemcpyDeviceToHost, cs));
-      return KEAKI_OK;
+  ST_TRY(reserve(ctx, ctx->tmp_b, ch * 384));            // the GT values stay on the device
+  return pipelined_regions(ctx, n, ch, {}, {{proofs_aff, nullptr, G1_AFF_BYTES}, {cts_aff, nullptr, G2_AFF_BYTES}, {bodies, msgs_out, msg_len}},
+    [&](size_t, size_t m, char* const*, char* const* d) -> keaki_status {
+      ST_TRY(pairing_run(ctx, d[0], d[1], 1, m, ctx->tmp_b.p));
+      return blake3_gt_run(ctx, ctx->tmp_b.p, m, d[2], msg_len, true);
     });
 }
 

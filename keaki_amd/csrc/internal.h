@@ -31,7 +31,8 @@ namespace keaki_internal {
 // tune_from_env ignores them; any other value outside 3 .. 24 means automatic, as it always did.
 constexpr int MSM_C_MAX = 19, MSM_C_SHARED_MAX = 23;
 inline bool msm_c_too_wide(long long v, int max) { return v > max && v <= 24; }
-// Tuning / diagnostic switches of a context. The environment is read ONCE, in keaki_hip_ctx_create (tune_from_env); afterwards only
+// Tuning / diagnostic switches of a context: every member but alloc_limit is an option of keaki_hip_ctx_set_option by its own name, with an
+// entry in TUNE_OPTIONS (api.hip). The environment is read ONCE, in keaki_hip_ctx_create (tune_from_env); afterwards only
 // keaki_hip_ctx_set_option changes them (under the context lock). No other code in the library calls getenv.
 struct Tuning {
   int msm_c = 0;                 // KEAKI_MSM_C / "msm_c": window bits of the generic MSM, 3 .. MSM_C_MAX; 0 (or any value outside 3 .. 24) = choose_window

@@ -299,3 +299,38 @@ def test_encap_g2_fixed_base_occupancy_variants(oc, vh):
         assert np.array_equal(cts[0][idx], g2_of(oc, [rs[i] * (tau - zs[i]) for i in idx]))
     finally:
         apply(vh)
+
+
+# ---- the environment: initial values of the options (TUNE_OPTIONS, api.hip), read once when a context is created -------------------
+def test_environment_goes_through_the_option_table(oc, vh, monkeypatch):
+    """KEAKI_MSM_C=12 makes a new context run a 2^16-point MSM on 12-bit windows; KEAKI_MSM_C=20, a width the bucket sort cannot address
+    and set_option refuses, leaves it on the automatic width, as no variable does. Every option of the shipped table is accepted by
+    set_option at its default."""
+    from conftest import rand_fr_ints
+    from keaki_amd.hip import KeakiHip
+    n = 1 << 16
+    dl = dlogs(n, 9300)
+    sc = rand_fr_ints(n, 9301)
+    exp = g1_of(oc, [S.msm_dlog(dl, sc)])[0]
+    srs = vh.srs_g1_upload(vh.g1_mul_batch(oc.generators()[0], mont(oc, dl)))      # a handle serves every context of its device
+    for k in [k for k in os.environ if k.startswith("KEAKI_")]:
+        monkeypatch.delenv(k)
+    widths = {}
+    try:
+        for env in (None, "12", "20"):
+            if env is not None:
+                monkeypatch.setenv("KEAKI_MSM_C", env)
+            h = KeakiHip(0)
+            try:
+                assert np.array_equal(jac_to_aff(h.msm_g1(srs, mont(oc, sc))), exp), env
+                widths[env] = h.last_msm_stats()["window_bits"]
+                if env is None:
+                    expect_refused(h, "msm_c", 20)
+                    for name, default in V.shipped_options().items():
+                        h.set_option(name, default)
+            finally:
+                h.close()
+    finally:
+        srs.free()
+    assert widths["12"] == 12
+    assert widths["20"] == widths[None] == V.msm(n)["c"] != 12, widths

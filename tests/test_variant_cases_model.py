@@ -77,7 +77,7 @@ def test_unreachable_instantiations_are_unreachable_for_every_accepted_width():
         assert V.plan(V.choose_window(n))["W"] != 11 and V.plan(V.choose_window_shared(n))["W"] != 11
 
 
-def test_refused_widths_are_exactly_the_plans_the_sort_cannot_take():
+def test_refused_widths_match_the_plans_the_sort_cannot_take():
     """set_option's limits (internal.h) against the sort model: a width is refused iff part_make_shape refuses its plan at any n and
     bin count (generic: all buckets; window tables: the largest window)"""
     for c in range(3, 25):
@@ -91,9 +91,18 @@ def test_refused_widths_are_exactly_the_plans_the_sort_cannot_take():
     assert [c for c in range(3, 25) if V.width_refused(c, True)] == [24]
     # the C side states the same rule once, checked by the compiler
     assert "static_assert(msm_c_limit_is(MSM_C_MAX, false) && msm_c_limit_is(MSM_C_SHARED_MAX, true)" in _src("msm_g2.hip")
+
+
+def test_set_option_and_environment_apply_the_same_width_limits():
+    """the option table (api.hip: TUNE_OPTIONS) states the limits once for both paths: set_option refuses and the environment
+    (KEAKI_MSM_C, KEAKI_MSM_C_SHARED) ignores the widths msm_c_too_wide names, with MSM_C_MAX / MSM_C_SHARED_MAX"""
     api = _src("api.hip")
-    assert 'geti("KEAKI_MSM_C", v) && !msm_c_too_wide(v, MSM_C_MAX)' in api
-    assert 'geti("KEAKI_MSM_C_SHARED", v) && !msm_c_too_wide(v, MSM_C_SHARED_MAX)' in api
+    assert "TUNE_OPTION(msm_c, msm_c_refuses<MSM_C_MAX>)" in api
+    assert "TUNE_OPTION(msm_c_shared, msm_c_refuses<MSM_C_SHARED_MAX>)" in api
+    check = re.search(r"template <int MX>\nbool msm_c_refuses\(keaki_hip_ctx\* ctx, const char\* name, long long v\) \{.*?\n\}\n", api, re.S).group(0)
+    assert "if (!msm_c_too_wide(v, MX)) return false;" in check and "return true;" in check
+    env = re.search(r"void tune_from_env\(Tuning& t\) \{\n.*?\n\}\n", api, re.S).group(0)
+    assert "if (!o.refuses || !o.refuses(nullptr, o.name, v)) o.assign(t, v);" in env
 
 
 def test_digit_edge_scalars_reach_every_branch_of_every_plan():

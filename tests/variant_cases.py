@@ -38,6 +38,50 @@ def header_consts():
 K = header_consts()
 
 
+# ---- the tuning options: Tuning (internal.h) and its table TUNE_OPTIONS (api.hip) ------------------------------------------------------
+def _diag_lines(body):
+    """(line, under #ifdef KEAKI_DIAG) for each line of a source excerpt"""
+    diag = False
+    for line in body.splitlines():
+        if line.strip().startswith("#ifdef KEAKI_DIAG"):
+            diag = True
+        elif line.strip().startswith("#endif"):
+            diag = False
+        else:
+            yield line, diag
+
+
+def _c_value(expr):
+    expr = expr.strip()
+    if expr in ("true", "false"):
+        return int(expr == "true")
+    m = re.fullmatch(r"(-?\d+) << (\d+)", expr)
+    return int(m.group(1)) << int(m.group(2)) if m else int(expr)
+
+
+def tuning_members():
+    """the members of struct Tuning as internal.h declares them: name -> (default as an int, diagnostic build only)"""
+    body = re.search(r"struct Tuning \{\n(.*?)\n\};", _src("internal.h"), re.S).group(1)
+    out = {}
+    for line, diag in _diag_lines(body):
+        m = re.match(r"\s+(?:int|bool|long long|unsigned|size_t) (\w+) = ([^;]+);", line)
+        if m:
+            out[m.group(1)] = (_c_value(m.group(2)), diag)
+    return out
+
+
+def table_options():
+    """the entries of TUNE_OPTIONS (api.hip) in table order: [(name, diagnostic build only)]"""
+    body = re.search(r"const TuneOption TUNE_OPTIONS\[\] = \{\n(.*?)\n\};", _src("api.hip"), re.S).group(1)
+    return [(name, diag) for line, diag in _diag_lines(body) for name in re.findall(r"TUNE_OPTION\((\w+)", line)]
+
+
+def shipped_options():
+    """option name -> default for the options of the shipped library (what keaki_hip_ctx_set_option accepts outside KEAKI_DIAG)"""
+    members = tuning_members()
+    return {name: members[name][0] for name, diag in table_options() if not diag}
+
+
 # ---- MSM: plan, window choice, bucket sort shape, reduction, kernels ---------------------------------------------------------------------
 def plan(c_target):
     """msm_make_plan -> dict(c, W, k, offs, widths, nb, max_b)"""
