@@ -248,6 +248,36 @@ keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, 
 keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, const uint64_t* tau_g2_aff, const uint64_t* point,
                                   const uint64_t* value, const uint64_t* proof_aff, int32_t* ok_out);
 
+/* ---- KZG batch verification: n openings in one call ------------------------------------------------------------------
+ * Generalises `verify` (reference src/kzg.rs:127-148) to n openings (C_i, z_i, y_i, proof_i) by a linear combination with the caller's
+ * coefficients gamma_i:
+ *     L = sum gamma_i C_i - (sum gamma_i y_i) g1 + sum (gamma_i z_i) proof_i        R = sum gamma_i proof_i
+ *     *ok_out = 1  <=>  e(L, g2) == e(R, [tau]_2)
+ * which is sum gamma_i x (the predicate of src/kzg.rs:135-148 with z_i proof_i moved across the pairing). Cost: one pass over the scalars, two
+ * MSMs over the proofs (three with com_stride = 1), two pairings in one launch -- not 2n pairings.
+ * The call evaluates EXACTLY this equation for the gammas it is given; that is a deterministic contract. If all n openings are valid it
+ * always accepts. If one is invalid it rejects except with probability <= 1/r -- PROVIDED the gamma_i are independent, uniform in Fr and
+ * unknown to whoever produced the proofs. Badly chosen gammas void the bound: with all gamma_i equal, two errors can cancel (y_0 + d and
+ * y_1 - d are accepted together), and gamma = 0 accepts anything. gammas are drawn by the caller, one Fr::rand per item in index order (the
+ * rule encap_batch follows for r), so the randomness stream stays the caller's and every result is reproducible.
+ *   com_aff      com_stride = 0: ONE affine G1 point u64[8], the commitment of all items; 1: n points, com_aff[i] belongs to item i
+ *   tau_g2_aff   u64[16]
+ *   points       point_mode = 0: n Fr, z_i; 1: ONE Fr omega, item i is opened at omega^i (the powers are derived on the device)
+ *   values, gammas   n Fr each;   proofs_aff   n affine G1 points
+ *   sums_out_aff u64[16] = L then R, affine ((0,0) = identity), or NULL: what the two pairings were evaluated on
+ * Identity commitments and proofs, zero values / points / gammas are ordinary inputs (L = R = identity is accepted: both sides are GT one).
+ * n = 0: *ok_out = 1, the sums are the identity. com_stride or point_mode outside {0, 1}, a null pointer: KEAKI_ERR_BAD_ARG.
+ * Host form: from 65,536 items on the arrays (160 B per item) go up on the context's copy stream in the order the kernels read them (gammas and
+ * proofs first); the call returns when the results are in place and no copy reads caller memory any more, also on failure.
+ * _dev: every array is a device pointer (the commitment, [tau]_2 and omega too); ok_out and sums_out_aff stay HOST pointers, so this form
+ * synchronises as well. Workspace: 32 B per item + 67 KB, grow-only, besides the MSM's own. */
+keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff, int32_t com_stride, const uint64_t* tau_g2_aff,
+                                        const uint64_t* points, int32_t point_mode, const uint64_t* values, const uint64_t* proofs_aff,
+                                        const uint64_t* gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff);
+keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff,
+                                            const void* d_points, int32_t point_mode, const void* d_values, const void* d_proofs_aff,
+                                            const void* d_gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff);
+
 /* ---- SRS ingest (scope row f-3) -----------------------------------------------------------------------------------------
  * The reference reads .ptau points with `deserialize_uncompressed_unchecked` (src/kzg/ptau.rs:266,314): no curve check at all.
  * A snarkjs .ptau stores coordinates as Montgomery limbs, which is this ABI's point layout, so sections 2 and 3 are uploaded

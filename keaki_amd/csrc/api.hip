@@ -571,7 +571,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v;
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums, &ctx->bsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->verify_io, &ctx->g2gen_lines, &ctx->fk_tab, &ctx->g2pow_lines, &ctx->g2pow_pts})
+                    &ctx->pair_ws, &ctx->verify_io, &ctx->vb_io, &ctx->vb_s, &ctx->g2gen_lines, &ctx->fk_tab, &ctx->g2pow_lines, &ctx->g2pow_pts})
     v.push_back({b, 1});
   for (DevBuf* b : {&ctx->fb_bases, &ctx->fb_g1_gen, &ctx->fb_g2_gen, &ctx->fb_com, &ctx->fb_tau, &ctx->gt_tab_a, &ctx->gt_tab_b, &ctx->gt_base,
                     &ctx->fbs_g2_gen, &ctx->fbs_tau, &ctx->fbs_g1_gen})
@@ -1643,6 +1643,136 @@ keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, c
   ST_TRY(download(ctx, gt, io + O_GT, 768));                                       // synchronises: `in` stays alive until here
   *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
   return KEAKI_OK;
+}
+
+// ---- KZG batch verification: n openings, one random linear combination, two pairings ------------------------------------------------------
+// L = sum gamma_i C_i - (sum gamma_i y_i) g1 + sum (gamma_i z_i) proof_i, R = sum gamma_i proof_i, accept <=> e(L, g2) == e(R, [tau]_2):
+// sum gamma_i x (the predicate of src/kzg.rs:135-148 with z_i proof_i moved across the pairing). Kernel sequence, all on ctx->stream:
+//   MSM R (gammas over the proofs as an ad-hoc base vector, no tables) | k_vb_prepare + k_vb_finish (s_i = gamma_i z_i, g, -t) | MSM M (s over the
+//   proofs) | K: MSM (gammas over the commitments) or g C | (-t) g1 (the same scalar-mult launch as g C) | g1_sum of K, M, (-t) g1 | the two
+//   pairings in ONE launch | 768 GT bytes + the two sums back.
+// vb_io block: [gt: g 32 | -t 32] [pts: C 64 | g1 64] [mul: g C 64 | (-t) g1 64] [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64]
+//              [qs: g2 128 | tau 128] [omega 32] [gt 768] [partials]
+extern "C++" {
+namespace {
+struct VbLayout {
+  static constexpr size_t O_SC = 0, O_PTS = 64, O_MUL = 192, O_SUM = 320, O_L = 608, O_R = 704, O_PS = 800, O_QS = 928, O_OMEGA = 1184, O_GT = 1216,
+                          O_PART = 1984;
+};
+// `stage(phase)`: the host form uploads what the phase reads and makes ctx->stream wait for it (0: gammas and proofs, in front of the first MSM;
+// 1: commitments, points, values). The commitment (com_stride 0), [tau]_2 and omega (point_mode 1) are already in their vb_io slots.
+keaki_status verify_batch_core(keaki_hip_ctx* ctx, const void* d_coms, int32_t com_stride, const void* d_points, int32_t point_mode, const void* d_values,
+                               const void* d_proofs, const void* d_gammas, size_t n, const std::function<keaki_status(int)>& stage, int32_t* ok_out,
+                               uint64_t* sums_out_aff) {
+  using V = VbLayout;
+  char* io = (char*)ctx->vb_io.p;
+  ST_TRY(g1_generator_to(ctx, io + V::O_PTS + 64));
+  ST_TRY(g2_generator_to(ctx, io + V::O_QS));
+  if (stage) ST_TRY(stage(0));
+  ST_TRY(msm_g1_run(ctx, d_proofs, n, d_gammas, n, io + V::O_R));
+  if (stage) ST_TRY(stage(1));
+  ST_TRY(verify_batch_scalars_run(ctx, d_gammas, point_mode ? (const void*)(io + V::O_OMEGA) : d_points, point_mode, d_values, n, ctx->vb_s.p, io + V::O_PART,
+                                  io + V::O_SC));
+  ST_TRY(msm_g1_run(ctx, d_proofs, n, ctx->vb_s.p, n, io + V::O_SUM + 96));
+  if (com_stride) {
+    ST_TRY(msm_g1_run(ctx, d_coms, n, d_gammas, n, io + V::O_SUM));
+    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS + 64, 1, io + V::O_SC + 32, 1, io + V::O_MUL + 64));           // (-t) g1
+    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL + 64, 1, io + V::O_SUM + 192));
+  } else {
+    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, io + V::O_SC, 2, io + V::O_MUL));                          // g C and (-t) g1, one launch
+    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
+    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL + 64, 1, io + V::O_SUM + 192));
+  }
+  ST_TRY(g1_sum_run(ctx, io + V::O_SUM, 3, io + V::O_L));
+  ST_TRY(verify_batch_jac_to_aff_run(ctx, io + V::O_L, io + V::O_R, io + V::O_PS));
+  ST_TRY(pairing_run(ctx, io + V::O_PS, io + V::O_QS, 1, 2, io + V::O_GT));
+  uint8_t gt[768];
+  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, io + V::O_PS, 128, hipMemcpyDeviceToHost, ctx->stream));
+  ST_TRY(download(ctx, gt, io + V::O_GT, 768));
+  *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
+  return KEAKI_OK;
+}
+keaki_status verify_batch_args(keaki_hip_ctx* ctx, const void* com, int32_t com_stride, const void* tau, const void* points, int32_t point_mode,
+                               const void* values, const void* proofs, const void* gammas, size_t n, const int32_t* ok_out) {
+  if ((com_stride != 0 && com_stride != 1) || (point_mode != 0 && point_mode != 1))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: com_stride = %d, point_mode = %d: both must be 0 or 1", (int)com_stride, (int)point_mode);
+  if (!ok_out) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: ok_out is null");
+  if (n && (!com || !tau || !points || !values || !proofs || !gammas)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: null pointer");
+  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: n must be < 2^31 per device");
+  return KEAKI_OK;
+}
+// the empty combination: both sums are the identity, which pairs to GT one on both sides
+void verify_batch_empty(int32_t* ok_out, uint64_t* sums_out_aff) {
+  *ok_out = 1;
+  if (sums_out_aff) memset(sums_out_aff, 0, 128);
+}
+keaki_status verify_batch_reserve(keaki_hip_ctx* ctx, size_t n) {
+  ST_TRY(reserve(ctx, ctx->vb_io, VbLayout::O_PART + verify_batch_partials_bytes()));
+  return reserve(ctx, ctx->vb_s, n * 32);
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff, const void* d_points,
+                                            int32_t point_mode, const void* d_values, const void* d_proofs_aff, const void* d_gammas, size_t n,
+                                            int32_t* ok_out, uint64_t* sums_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_batch");
+  ST_TRY(verify_batch_args(ctx, d_com_aff, com_stride, d_tau_g2_aff, d_points, point_mode, d_values, d_proofs_aff, d_gammas, n, ok_out));
+  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
+  ST_TRY(verify_batch_reserve(ctx, n));
+  char* io = (char*)ctx->vb_io.p;
+  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_PTS, d_com_aff, 64, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_QS + 128, d_tau_g2_aff, 128, hipMemcpyDeviceToDevice, ctx->stream));
+  if (point_mode) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_OMEGA, d_points, 32, hipMemcpyDeviceToDevice, ctx->stream));
+  return verify_batch_core(ctx, d_com_aff, com_stride, d_points, point_mode, d_values, d_proofs_aff, d_gammas, n, nullptr, ok_out, sums_out_aff);
+}
+
+keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff, int32_t com_stride, const uint64_t* tau_g2_aff, const uint64_t* points,
+                                        int32_t point_mode, const uint64_t* values, const uint64_t* proofs_aff, const uint64_t* gammas, size_t n,
+                                        int32_t* ok_out, uint64_t* sums_out_aff) {
+  CTX_GUARD(ctx);                 // held across stage -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_verify_batch");
+  ST_TRY(verify_batch_args(ctx, com_aff, com_stride, tau_g2_aff, points, point_mode, values, proofs_aff, gammas, n, ok_out));
+  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
+  // every buffer is reserved before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only
+  ST_TRY(verify_batch_reserve(ctx, n));
+  ST_TRY(reserve(ctx, ctx->io_a, n * 32));
+  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
+  ST_TRY(reserve(ctx, ctx->io_d, n * 32));
+  if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
+  if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
+  char* io = (char*)ctx->vb_io.p;
+  // a failing call, too, returns only when no copy reads the caller's arrays any more (the successful path synchronises in its download)
+  struct UploadFence { hipStream_t s; bool armed; ~UploadFence() { if (armed) (void)hipStreamSynchronize(s); } } fence{ctx->stream, true};
+  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_PTS, com_aff, 64, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_QS + 128, tau_g2_aff, 128, hipMemcpyHostToDevice, ctx->stream));
+  if (point_mode) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_OMEGA, points, 32, hipMemcpyHostToDevice, ctx->stream));
+  // Large batches (160 B per item) go up on the context's copy stream in the order the kernels ask for them: gammas and proofs, then -- under
+  // the first MSM -- commitments, points and values. Small ones, and a context told to use no other stream (pipe_chunks = 0), copy in front.
+  ChunkUploader up(ctx);
+  const bool on_copy_stream = ctx->tune.pipe_chunks && n >= PIPE_CHUNK;
+  if (on_copy_stream) ST_TRY(up.begin());
+  size_t piece = 0;
+  auto put = [&](void* dst, const void* src, size_t bytes) -> keaki_status {
+    if (on_copy_stream) return up.chunk(piece++, dst, src, bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return KEAKI_OK;
+  };
+  const std::function<keaki_status(int)> stage = [&](int phase) -> keaki_status {
+    if (phase == 0) {
+      ST_TRY(put(ctx->io_a.p, gammas, n * 32));
+      return put(ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES);
+    }
+    if (!point_mode) ST_TRY(put(ctx->io_c.p, points, n * 32));
+    ST_TRY(put(ctx->io_d.p, values, n * 32));
+    if (com_stride) ST_TRY(put(ctx->io_e.p, com_aff, n * G1_AFF_BYTES));
+    return KEAKI_OK;
+  };
+  const keaki_status st = verify_batch_core(ctx, ctx->io_e.p, com_stride, ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, ctx->io_a.p, n, stage, ok_out,
+                                            sums_out_aff);
+  if (st == KEAKI_OK) fence.armed = false;
+  return st;
 }
 
 // ---- SRS ingest: on-curve check (row f-3) ------------------------------------------------------------------------

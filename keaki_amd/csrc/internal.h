@@ -97,6 +97,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf pair_ws;                   // per-item slots of the final exponentiation (pairing.hip.h)
   keaki_internal::DevBuf fk_tab;                    // window tables of the per-lane-scalar ladders of FK23: 1 KB per lane of a launch (64 x 16 B), at most 2 GB (fft_g1.hip)
   keaki_internal::DevBuf verify_io;                 // kzg verify: small in/out block
+  keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
   bool verify_ready = false;
   bool verify_tables_ready = false;       // 8-bit window tables of g1 (fbs_g1_gen) and g2 (fbs_g2_gen) for the reference-form verify              // set only after every init step of kzg verify succeeded
   bool fb_tau_valid = false;          // window table of [tau]_2 (encap ciphertext side) is for this point
@@ -245,6 +246,15 @@ struct FkShard {
 };
 keaki_status fk_shard_setup_run(keaki_hip_ctx* ctx, FkShard& fk, const void* d_srs, int step, void* d_send, void* d_recv);
 keaki_status fk_shard_open_run(keaki_hip_ctx* ctx, FkShard& fk, int step, void* d_send, void* d_recv, void* d_out_aff);
+// kzg verify_batch (kzg_batch.hip): d_s_out[i] = gamma_i z_i (point_mode 0: z_i = d_points[i]; 1: z_i = d_points[0]^i) and d_gt_out = (g, -t) =
+// (sum gamma_i, -sum gamma_i y_i), through d_partials (verify_batch_partials_bytes()); 1 <= n < 2^31
+constexpr uint32_t VB_MAX_BLOCKS = 1024;
+size_t verify_batch_partials_bytes();
+keaki_status verify_batch_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const void* d_values, size_t n,
+                                      void* d_s_out, void* d_partials, void* d_gt_out);
+// layout moves around the final sum (no arithmetic): n <= 64 affine points -> normalised Jacobian | the normalised Jacobian sums L, R -> d_out_lr_aff[0], [1] affine
+keaki_status verify_batch_aff_to_jac_run(keaki_hip_ctx* ctx, const void* d_in_aff, uint32_t n, void* d_out_jac);
+keaki_status verify_batch_jac_to_aff_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_r_jac, void* d_out_lr_aff);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 

@@ -25,7 +25,7 @@ EXPORTS = [
     "keaki_hip_encap_batch", "keaki_hip_encap_batch_dev", "keaki_hip_decap_batch", "keaki_hip_decap_batch_dev",
     "keaki_hip_encrypt_batch", "keaki_hip_encrypt_batch_dev", "keaki_hip_decrypt_batch", "keaki_hip_decrypt_batch_dev",
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
-    "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
+    "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
@@ -128,6 +128,8 @@ def load_library():
         lib.keaki_hip_kzg_open.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
         lib.keaki_hip_g2_check.argtypes = [vp, vp, C.c_size_t, vp, vp]
         lib.keaki_hip_kzg_verify.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+        lib.keaki_hip_kzg_verify_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_kzg_verify_batch_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_final_exp_batch.argtypes = [vp, vp, sz, vp]
         lib.keaki_hip_miller_loop_batch.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_set_timing.argtypes = [vp, i32]
@@ -442,6 +444,27 @@ class KeakiHip:
         self._ck(self.lib.keaki_hip_kzg_verify(self.ctx, _ptr(_np(com_aff)), _ptr(_np(tau_g2_aff)), _ptr(_np(point)), _ptr(_np(value)),
                                                _ptr(_np(proof_aff)), C.byref(ok)))
         return bool(ok.value)
+
+    def kzg_verify_batch(self, com_aff, tau_g2_aff, points, values, proofs_aff, gammas, point_mode: int = 0):
+        """n openings in one call (keaki_hip_kzg_verify_batch) -> (ok, L u64[8], R u64[8]). com_aff: one affine point (u64[8]: the commitment of
+        every item) or n of them; points: n Fr, or with point_mode = 1 the ONE Fr omega (item i is opened at omega^i); gammas: n Fr the CALLER drew"""
+        v = _np(values, 4); n = v.shape[0]
+        pr, g, c, z = _np(proofs_aff, 8), _np(gammas, 4), _np(com_aff, 8), _np(points, 4)
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if pr.shape[0] != n or g.shape[0] != n or (com_stride and c.shape[0] != n) or z.shape[0] != (1 if point_mode else n):
+            raise ValueError("kzg_verify_batch: array lengths disagree")
+        ok = C.c_int32(0); sums = np.zeros(16, np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_batch(self.ctx, _ptr(c), com_stride, _ptr(_np(tau_g2_aff)), _ptr(z), int(point_mode), _ptr(v), _ptr(pr), _ptr(g),
+                                                     n, C.byref(ok), _ptr(sums)))
+        return bool(ok.value), sums[:8].copy(), sums[8:].copy()
+
+    def kzg_verify_batch_dev(self, d_com, com_stride: int, d_tau_g2, d_points, point_mode: int, d_values, d_proofs, d_gammas, n: int):
+        """the same with every array resident: device pointers (ints) or torch tensors -> (ok, L, R) on the host (the call synchronises)"""
+        dp = lambda x: C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+        ok = C.c_int32(0); sums = np.zeros(16, np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_batch_dev(self.ctx, dp(d_com), int(com_stride), dp(d_tau_g2), dp(d_points), int(point_mode), dp(d_values),
+                                                         dp(d_proofs), dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
+        return bool(ok.value), sums[:8].copy(), sums[8:].copy()
 
     def srs_g1_check(self, srs: "SrsG1"):
         """-> (number of off-curve points, index of the first or None)"""

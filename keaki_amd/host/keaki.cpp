@@ -258,6 +258,39 @@ Result<bool> verify(const KZGSetup& setup, const G1& commitment, const Fr& point
   return Result<bool>::Ok(ok != 0);
 }
 
+bool verify_batch_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values,
+                       const uint64_t* proofs, size_t n) {
+  if (n_coms != 1 && n_coms != n) throw std::invalid_argument("verify_batch: one commitment, or one per item");
+  std::vector<Fr> gammas(n);
+  for (size_t i = 0; i < n; i++) gammas[i] = fr_rand(rng);       // one draw per item in index order, whichever path follows
+  const Device& dev = *setup.device();
+  if (n < VERIFY_BATCH_MIN) {
+    // a batch call costs two MSM tails and a scalar-mult whatever n is; a few single checks are cheaper (profiles/verify_batch.txt)
+    Fr z = Fr::one();
+    for (size_t i = 0; i < n; i++) {
+      int32_t ok = 0;
+      dev.check(keaki_hip_kzg_verify(dev.ctx(), coms + (n_coms == 1 ? 0 : 8 * i), setup.tau_g2().w.data(), roots_of_unity ? z.l : points[i].l, values[i].l,
+                                     proofs + 8 * i, &ok));
+      if (!ok) return false;
+      if (roots_of_unity) z = z * points[0];
+    }
+    return true;
+  }
+  int32_t ok = 0;
+  dev.check(keaki_hip_kzg_verify_batch(dev.ctx(), coms, n_coms == 1 ? 0 : 1, setup.tau_g2().w.data(), points[0].l, roots_of_unity ? 1 : 0, values[0].l, proofs,
+                                       gammas[0].l, n, &ok, nullptr));
+  return ok != 0;
+}
+Result<bool> verify_batch(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& points,
+                          const std::vector<Fr>& values, const std::vector<G1>& proofs) {
+  static_assert(sizeof(G1) == 64 && sizeof(Fr) == 32, "G1 is eight u64 words, Fr four");
+  const size_t n = values.size();
+  if (points.size() != n || proofs.size() != n || (commitments.size() != 1 && commitments.size() != n))
+    throw std::invalid_argument("verify_batch: points, values and proofs must have one entry per item, commitments one or n");
+  return Result<bool>::Ok(verify_batch_flat(rng, setup, commitments.empty() ? nullptr : commitments[0].w.data(), commitments.size(), points.data(), false, values.data(),
+                                            n ? proofs[0].w.data() : nullptr, n));
+}
+
 void precompute_open_fk(const KZGSetup& setup, size_t d) {
   if (d < 1 || (d & (d - 1)) != 0 || d > setup.g1_pow().size()) return;   // open_fk falls back to per-point openings for such shapes
   unsigned log2d = 0;
@@ -472,6 +505,15 @@ std::pair<G1, std::vector<G1>> vec_commit(Rng& rng, const kzg::KZGSetup& setup, 
   std::vector<G1> proofs(Radix2Domain::create(v.size() + PADDING_LEN).size);
   G1 com = vec_commit_flat(rng, setup, v.data(), v.size(), proofs.empty() ? nullptr : proofs[0].w.data());
   return {com, std::move(proofs)};
+}
+
+bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs) {
+  const Radix2Domain domain = Radix2Domain::create(n + PADDING_LEN);      // the domain vec_commit interpolated over (src/vec.rs:36)
+  return kzg::verify_batch_flat(rng, setup, com.w.data(), 1, &domain.group_gen, true, v, proofs, n);
+}
+bool vec_verify(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs) {
+  if (proofs.size() < v.size()) throw std::invalid_argument("vec_verify: fewer proofs than values");
+  return vec_verify_flat(rng, setup, com, v.data(), v.size(), v.empty() ? nullptr : proofs[0].w.data());
 }
 
 std::vector<enc::Ciphertext> vec_encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points,

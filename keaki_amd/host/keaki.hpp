@@ -155,6 +155,18 @@ class KZGSetup {
 Result<G1> commit(const KZGSetup& setup, const DensePolynomial& p);                          // src/kzg.rs:89-101
 Result<G1> open(const KZGSetup& setup, const DensePolynomial& p, const Fr& point);           // src/kzg.rs:104-124
 Result<bool> verify(const KZGSetup& setup, const G1& commitment, const Fr& point, const Fr& value, const G1& proof);  // :127-151
+// n openings at once (no counterpart in the reference; generalises :127-148): draws one gamma_i = Fr::rand per item from `rng` in index order
+// and checks e(L, g2) == e(R, [tau]_2) for L = sum gamma_i C_i - (sum gamma_i y_i) g1 + sum (gamma_i z_i) proof_i, R = sum gamma_i proof_i
+// in ONE device call (keaki_hip_kzg_verify_batch: two or three MSMs and two pairings whatever n is). All openings valid: always true. One
+// invalid: false except with probability <= 1/r over the draws -- `rng` must be unpredictable to whoever produced the proofs.
+// commitments: one (shared by all items) or one per item. Below VERIFY_BATCH_MIN items the draws still happen (the stream of `rng` does not
+// depend on the path) and the items are checked one by one with `verify`, which is faster there. On a group device: member 0.
+constexpr size_t VERIFY_BATCH_MIN = 5;      // measured: a batch call costs 6.9 ms at n <= 16, a single verify 1.68 ms (profiles/verify_batch.txt)
+Result<bool> verify_batch(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& points,
+                          const std::vector<Fr>& values, const std::vector<G1>& proofs);
+// the same on contiguous buffers. n_coms: 1 or n. roots_of_unity: `points` is ONE Fr omega and item i is opened at omega^i.
+bool verify_batch_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values,
+                       const uint64_t* proofs, size_t n);
 // all openings at the roots of unity of a size-d domain (src/kzg.rs:157-203): FK23 -- three G1 FFTs + 2d scalar-mults on
 // the GPU (keaki_hip_open_fk) when p.size() == domain_size is a power of two; per-point `open` otherwise.
 Result<std::vector<G1>> open_fk(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size);
@@ -199,6 +211,11 @@ G1 vec_commit_flat(Rng& rng, const kzg::KZGSetup& setup, const Fr* v, size_t n, 
 std::vector<Fr> vec_commit_coeffs(Rng& rng, const kzg::KZGSetup& setup, const std::vector<Fr>& v);
 // lines :27-44 of it (padding draw, iFFT, open_fk): the dense coefficient vector and the proofs, without the final commit
 std::pair<DensePolynomial, std::vector<G1>> vec_commit_openings(Rng& rng, const kzg::KZGSetup& setup, const std::vector<Fr>& v);
+// The sibling src/vec.rs lacks: are the first v.size() proofs of a vec_commit openings of `com` to v? Item i is the opening at omega^i of the
+// domain Radix2Domain::create(v.size() + PADDING_LEN) to the value v[i]; the padding slot is the committer's secret and is not checked.
+// One kzg::verify_batch over the powers of the domain's generator (they are derived on the device): n draws from `rng`, one device call.
+bool vec_verify(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs);
+bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs);
 // src/vec.rs:52-69: one Fr::rand per item in index order, then ONE batched GPU call for all items
 std::vector<enc::Ciphertext> vec_encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points,
                                          const std::vector<Fr>& values, const std::vector<std::vector<uint8_t>>& messages);

@@ -217,6 +217,22 @@ int keaki_host_verify(void* s, const uint64_t* com, const uint64_t* point, const
     *out_ok = r.value ? 1 : 0; return 0;
   });
 }
+// n_coms: 1 or n; point_mode 1: `points` is ONE Fr omega, item i is opened at omega^i
+int keaki_host_verify_batch(void* rng, void* s, const uint64_t* coms, size_t n_coms, const uint64_t* points, int point_mode, const uint64_t* values,
+                            const uint64_t* proofs, size_t n, int* out_ok) {
+  return guard([&] {
+    static_assert(sizeof(Fr) == 32, "Fr is four u64 limbs");
+    *out_ok = kzg::verify_batch_flat(*(Rng*)rng, ((Setup*)s)->s, coms, n_coms, reinterpret_cast<const Fr*>(points), point_mode != 0,
+                                     reinterpret_cast<const Fr*>(values), proofs, n) ? 1 : 0;
+    return 0;
+  });
+}
+int keaki_host_vec_verify(void* rng, void* s, const uint64_t* com, const uint64_t* v, size_t n, const uint64_t* proofs, int* out_ok) {
+  return guard([&] {
+    *out_ok = vec::vec_verify_flat(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), reinterpret_cast<const Fr*>(v), n, proofs) ? 1 : 0;
+    return 0;
+  });
+}
 int keaki_host_precompute_open_fk(void* s, size_t domain_size) {
   return guard([&] { kzg::precompute_open_fk(((Setup*)s)->s, domain_size); return 0; });
 }

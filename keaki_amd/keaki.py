@@ -318,6 +318,30 @@ def verify(setup: KZGSetup, commitment, point, value, proof) -> bool:
     return bool(ok.value)
 
 
+def verify_batch(rng: "Rng", setup: "KZGSetup", commitments, points, values, proofs, roots_of_unity: bool = False) -> bool:
+    """kzg::verify_batch: n openings in one device call. One gamma per item is drawn from `rng` in index order. commitments: one G1 (shared) or n;
+    points: n Fr -- or, with roots_of_unity, the ONE Fr omega (item i is opened at omega^i)."""
+    vals = np.ascontiguousarray(_u64(values, 4)); n = vals.shape[0]
+    coms = np.ascontiguousarray(_u64(commitments, 8)); pts = np.ascontiguousarray(_u64(points, 4)); pr = np.ascontiguousarray(_u64(proofs, 8)[:n])
+    if coms.shape[0] not in (1, n) or pts.shape[0] != (1 if roots_of_unity else n) or pr.shape[0] != n:
+        raise ValueError("verify_batch: array lengths disagree")
+    ok = C.c_int(0)
+    _ck(_lib().keaki_host_verify_batch(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(pts), C.c_int(1 if roots_of_unity else 0), _p(vals), _p(pr),
+                                       C.c_size_t(n), C.byref(ok)))
+    return bool(ok.value)
+
+
+def vec_verify(rng: "Rng", setup: "KZGSetup", com, v, proofs) -> bool:
+    """vec::vec_verify: the first len(v) proofs of a vec_commit open `com` to v over the domain of len(v) + PADDING_LEN evaluations"""
+    vals = np.ascontiguousarray(_u64(v, 4)); n = vals.shape[0]
+    pr = np.ascontiguousarray(_u64(proofs, 8)[:n])
+    if pr.shape[0] != n:
+        raise ValueError("vec_verify: fewer proofs than values")
+    ok = C.c_int(0)
+    _ck(_lib().keaki_host_vec_verify(rng.h, setup.h, _p(_u64(com)), _p(vals), C.c_size_t(n), _p(pr), C.byref(ok)))
+    return bool(ok.value)
+
+
 def precompute_open_fk(setup: "KZGSetup", domain_size: int) -> None:
     """setup-time: the SRS-only transform of FK23 (hat_s) for this domain size"""
     _ck(_lib().keaki_host_precompute_open_fk(setup.h, C.c_size_t(domain_size)))

@@ -37,7 +37,7 @@ sys.path.insert(0, ROOT)
 from keaki_amd.launch import self_launch, under_launcher  # noqa: E402  (standard library only: no torch, no HIP)
 
 
-def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_single=False, backend=None):
+def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_single=False, backend=None, verify_proofs=False):
     """The whole flow on the ranks of `shard` (one rank: the un-sharded calls). Every rank calls this; returns the report (a dict; the same on
     every rank except for `sharded_equals_single_process`, which only rank 0 computes) whose `all_messages_recovered` is the AND over all
     ranks. bench.py's `laconic` block is this function on the bench's own process group."""
@@ -73,6 +73,14 @@ def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_s
     t0 = time.time()
     commitment, proofs = sharded_vec_commit(K, rng, s, choices, shard, fk)  # Receiver::new
     t_receiver_new = phase_max(time.time() - t0)
+
+    verified, t_verify = None, None
+    if verify_proofs:
+        # opt-in, outside the three timed phases: are the n proofs openings of the digest to the receiver's bits? One batch check (vec::vec_verify:
+        # n coefficients from a stream of its OWN -- the flow's stream of draws stays what it is without the check --, two MSMs, two pairings)
+        t0 = time.time()
+        verified = bool(K.vec_verify(K.Rng(0x5EED), s, commitment, choices, proofs))
+        t_verify = phase_max(time.time() - t0)
 
     sets = [np_rng.integers(0, 256, size=(n, vb), dtype=np.uint8) for _ in range(2)]
     elements = K.domain_elements(n + K.PADDING_LEN)
@@ -118,6 +126,10 @@ def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_s
                                                      if fk is not None else "replicated on every rank"),
               "note": "wall-clock through the C++ host mirror (contiguous arrays in, arrays out), max over ranks per phase; "
                       "GPU work: FK23 + MSM / 2n encaps / n decaps"}
+    if verify_proofs:
+        report["proofs_verified"] = verified
+        report["verify_proofs_s"] = round(t_verify, 4)
+        report["all_messages_recovered"] = bool(report["all_messages_recovered"] and verified)
     if fk is not None:
         fk.close()
     s.close()
@@ -133,6 +145,8 @@ def main():
     ap.add_argument("--fk", default="sharded", choices=["sharded", "replicated"], help="FK23 openings of Receiver::new on N > 1 ranks")
     ap.add_argument("--check-single", action="store_true",
                     help="rank 0 also runs the un-sharded calls with the same seeds and compares commitment and ciphertexts bit for bit")
+    ap.add_argument("--verify-proofs", action="store_true",
+                    help="after Receiver::new, check all n proofs against the digest in one batch (vec_verify); its time is reported on its own")
     args = ap.parse_args()
     if args.gpus > 1 and not under_launcher():
         # typed without torch.distributed.run: this process -- which has not imported torch or touched the GPU -- starts the N ranks as a
@@ -162,7 +176,7 @@ def main():
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)
     shard = Shard(rank, world, dist)
-    report = run_flow(K, shard, device, args.log2n, args.value_bytes, args.fk, args.check_single, args.backend)
+    report = run_flow(K, shard, device, args.log2n, args.value_bytes, args.fk, args.check_single, args.backend, args.verify_proofs)
     if rank == 0:
         print(json.dumps(report), flush=True)
     if world > 1:

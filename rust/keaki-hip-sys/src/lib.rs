@@ -117,6 +117,13 @@ extern "C" {
                                   value_out: *mut u64) -> keaki_status;
     pub fn keaki_hip_kzg_verify(ctx: *mut keaki_hip_ctx, com_aff: *const u64, tau_g2_aff: *const u64, point: *const u64, value: *const u64,
                                 proof_aff: *const u64, ok_out: *mut i32) -> keaki_status;
+    // n openings in one call (generalises src/kzg.rs:127-148): e(L, g2) == e(R, [tau]_2) for the caller's gammas; sums_out_aff: u64[16] = L, R or null
+    pub fn keaki_hip_kzg_verify_batch(ctx: *mut keaki_hip_ctx, com_aff: *const u64, com_stride: i32, tau_g2_aff: *const u64, points: *const u64,
+                                      point_mode: i32, values: *const u64, proofs_aff: *const u64, gammas: *const u64, n: usize, ok_out: *mut i32,
+                                      sums_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_batch_dev(ctx: *mut keaki_hip_ctx, d_com_aff: *const c_void, com_stride: i32, d_tau_g2_aff: *const c_void,
+                                          d_points: *const c_void, point_mode: i32, d_values: *const c_void, d_proofs_aff: *const c_void,
+                                          d_gammas: *const c_void, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
 
     // ---- SRS ingest checks (src/kzg/ptau.rs:266,314 read unchecked)
     pub fn keaki_hip_srs_g1_check(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, n_off_curve: *mut u64, first_off_curve: *mut u64) -> keaki_status;

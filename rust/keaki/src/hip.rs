@@ -412,6 +412,28 @@ pub fn verify(commitment: &G1Projective, tau_g2: &G2Projective, point: &Fr, valu
     ok != 0
 }
 
+/// n openings in one call (`keaki_hip_kzg_verify_batch`): `e(L, g2) == e(R, [tau]_2)` with L = sum gamma_i C_i - (sum gamma_i y_i) g1 +
+/// sum (gamma_i z_i) proof_i and R = sum gamma_i proof_i. `commitments`: one for all items or one per item. `points`: one per item, or -- with
+/// `roots_of_unity` -- the single generator omega (item i is opened at omega^i). `gammas`: drawn by the CALLER, one `Fr::rand` per item in
+/// index order; the soundness bound 1/r needs them independent, uniform and unknown to whoever made the proofs.
+pub fn verify_batch(commitments: &[G1Projective], tau_g2: &G2Projective, points: &[Fr], roots_of_unity: bool, values: &[Fr], proofs: &[G1Projective],
+                    gammas: &[Fr]) -> bool {
+    let dev = Device::global();
+    let n = values.len();
+    assert!(proofs.len() == n && gammas.len() == n && (commitments.len() == 1 || commitments.len() == n));
+    assert!(points.len() == if roots_of_unity { 1 } else { n });
+    let flat = |v: &[G1Projective]| -> Vec<u64> { G1Projective::normalize_batch(v).iter().flat_map(|p| g1_words(p)).collect() };
+    let (c, p, t) = (flat(commitments), flat(proofs), g2_words(&tau_g2.into_affine()));
+    let mut ok = 0i32;
+    dev.check(
+        unsafe {
+            sys::keaki_hip_kzg_verify_batch(dev.ctx, c.as_ptr(), if commitments.len() == 1 { 0 } else { 1 }, t.as_ptr(), fr_ptr(points), if roots_of_unity { 1 } else { 0 }, fr_ptr(values), p.as_ptr(), fr_ptr(gammas), n, &mut ok, core::ptr::null_mut())
+        },
+        "kzg_verify_batch",
+    );
+    ok != 0
+}
+
 /// FK23: all `d = coeffs.len()` openings at the d-th roots of unity (d a power of two, d <= srs.len()). `omega_2d`, `omega_2d_inv`,
 /// `inv_2d` = `group_gen`, `group_gen_inv`, `size_inv` of `Radix2EvaluationDomain::new(2 d)`.
 pub fn open_fk(srs: &HipSrs, coeffs: &[Fr], omega_2d: &Fr, omega_2d_inv: &Fr, inv_2d: &Fr) -> Vec<G1Projective> {
