@@ -286,6 +286,46 @@ keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_co
 keaki_status keaki_hip_srs_g1_check(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, uint64_t* n_off_curve, uint64_t* first_off_curve);
 keaki_status keaki_hip_g2_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint64_t* n_off_curve, uint64_t* first_off_curve);
 
+/* ---- compressed point wire format: what crosses a trust boundary -----------------------------------------------------------
+ * The byte format of ark-serialize 0.4.2 `serialize_compressed` for short-Weierstrass affine points (restated from memory, not pinned
+ * against a Rust build: DESIGN section 2), half the size of the limb layout:
+ *   G1, 32 bytes   x as a canonical (non-Montgomery) little-endian integer; p has 254 bits, so bits 6 and 7 of byte 31 are free
+ *   G2, 64 bytes   x.c0 then x.c1, 32 B little-endian each; the flags sit in byte 63
+ *   flags          bit 7 = YIsNegative, set iff y > -y (Fq: on canonical integers; Fq2: c1 is compared first, c0 when the c1 are equal);
+ *                  bit 6 = PointAtInfinity; the identity encodes as x = 0 with bit 6 set
+ * compress: n affine points in this ABI's Montgomery limb layout ((0,0) = identity) -> n x 32 B / n x 64 B. The points are taken as they
+ * are: an input that is not on the curve produces bytes that decompress rejects or decodes to another point.
+ * decompress -- the decoding rule of this library. An item is REJECTED when
+ *   status 1 (malformed)   both flag bits are set, x (or a coordinate of x) is >= p, or the identity flag comes with x != 0
+ *   status 2               x^3 + b is not a square (b = 3 on G1, 3/(9+u) on the twist): no point of the curve has this x
+ *   status 3               G2 with check_subgroup = 1: the point lies on the twist but outside the subgroup of order r. BN254's twist has a
+ *                          cofactor 2p - r of about 2^254, so a G2 point from another party MUST be checked before it is paired
+ *                          (arkworks' `deserialize_compressed` validates by default). G1 has cofactor 1: on the curve is in the group.
+ * otherwise (status 0) y is the root the sign flag names. out_aff: n affine points in the limb layout, a rejected item all zero.
+ * status: uint8_t[n] or NULL. n_bad: the number of rejected items (required); first_bad: the index of the first one, UINT64_MAX if none
+ * (may be NULL) -- shaped like keaki_hip_g2_check. One bad item does not fail the call: the return value stays KEAKI_OK.
+ * check_subgroup outside {0, 1}, a null bytes / out_aff / n_bad pointer with n > 0: KEAKI_ERR_BAD_ARG. n = 0: *n_bad = 0.
+ * keaki_hip_g2_subgroup_check: the same membership test for callers that already hold uncompressed points (it complements keaki_hip_g2_check,
+ * which tests the curve equation only; the points are assumed to be on the twist). n_outside / first_outside as above; the identity passes.
+ * The test is psi(Q) = [6 z^2]Q (psi: untwist-Frobenius-twist), which holds exactly on the subgroup.
+ * Host forms go through the stager of the KEM host batches; from 65,536 items on they run as its chunk pipeline (two halves, then chunks
+ * of 65,536: upload, kernels and download overlap; option "pipe_chunks" = 0: one chunk) and return when the results are in place. _dev: bytes, points and status are device pointers; the counters stay HOST pointers,
+ * so these forms synchronise as well. Device buffers must be 16-byte aligned. n < 2^31 per call. */
+keaki_status keaki_hip_g1_compress(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint8_t* bytes_out);
+keaki_status keaki_hip_g2_compress(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint8_t* bytes_out);
+keaki_status keaki_hip_g1_compress_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, void* d_bytes_out);
+keaki_status keaki_hip_g2_compress_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, void* d_bytes_out);
+keaki_status keaki_hip_g1_decompress(keaki_hip_ctx* ctx, const uint8_t* bytes, size_t n, uint64_t* out_aff, uint8_t* status, uint64_t* n_bad,
+                                     uint64_t* first_bad);
+keaki_status keaki_hip_g2_decompress(keaki_hip_ctx* ctx, const uint8_t* bytes, size_t n, int32_t check_subgroup, uint64_t* out_aff, uint8_t* status,
+                                     uint64_t* n_bad, uint64_t* first_bad);
+keaki_status keaki_hip_g1_decompress_dev(keaki_hip_ctx* ctx, const void* d_bytes, size_t n, void* d_out_aff, void* d_status, uint64_t* n_bad,
+                                         uint64_t* first_bad);
+keaki_status keaki_hip_g2_decompress_dev(keaki_hip_ctx* ctx, const void* d_bytes, size_t n, int32_t check_subgroup, void* d_out_aff, void* d_status,
+                                         uint64_t* n_bad, uint64_t* first_bad);
+keaki_status keaki_hip_g2_subgroup_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint64_t* n_outside, uint64_t* first_outside);
+keaki_status keaki_hip_g2_subgroup_check_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, uint64_t* n_outside, uint64_t* first_outside);
+
 /* ---- batched scalar multiplication: replaces `.mul(scalar)` (src/kem.rs:22,30,36,37; src/kzg.rs:57,60,135,144)
  * out[i] = scalars[i] * points[i]   (point_stride = 1) or scalars[i] * points[0] (point_stride = 0).
  * points affine in, affine out. */

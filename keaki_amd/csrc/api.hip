@@ -1799,6 +1799,126 @@ keaki_status keaki_hip_g2_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, 
   return curve_check_common(ctx, true, ctx->io_a.p, n, n_off_curve, first_off_curve);
 }
 
+// ---- compressed point wire format (point_codec.hip): compress, decompress with validation, G2 subgroup check --------------------------------
+// Rejected items are counted on the device: io_e = {count, first index}, added to by every launch of a call (the host forms run in chunks and
+// pass each chunk's first index). Host forms go through the stager of the KEM host batches (pipelined_regions); from PIPE_CHUNK items on that is
+// a pipeline of two halves, then of PIPE_CHUNK-item chunks.
+extern "C++" {
+namespace {
+struct CodecGroup { bool g2; size_t aff, wire; const char* name; };
+constexpr CodecGroup CODEC_G1 = {false, G1_AFF_BYTES, 32, "g1"}, CODEC_G2 = {true, G2_AFF_BYTES, 64, "g2"};
+size_t codec_chunk_items(const keaki_hip_ctx* ctx, size_t n) {
+  if (!ctx->tune.pipe_chunks || n < PIPE_CHUNK) return n;
+  return n >= 2 * PIPE_CHUNK ? PIPE_CHUNK : (((n + 1) / 2 + 63) & ~(size_t)63);
+}
+keaki_status codec_counter_begin(keaki_hip_ctx* ctx) {
+  ST_TRY(reserve(ctx, ctx->io_e, 16));
+  const uint64_t init[2] = {0, ~0ull};
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_e.p, init, 16, hipMemcpyHostToDevice, ctx->stream));
+  return KEAKI_OK;
+}
+keaki_status codec_counter_end(keaki_hip_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad) {
+  uint64_t res[2];
+  ST_TRY(download(ctx, res, ctx->io_e.p, 16));
+  *n_bad = res[0];
+  if (first_bad) *first_bad = res[1];
+  return KEAKI_OK;
+}
+keaki_status codec_n_check(keaki_hip_ctx* ctx, const char* what, size_t n) {
+  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n must be < 2^31 per call", what);
+  return KEAKI_OK;
+}
+keaki_status compress_dev(const CodecGroup& g, keaki_hip_ctx* ctx, const void* d_points, size_t n, void* d_bytes) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.point_compress");
+  if (n && (!d_points || !d_bytes)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s_compress: null pointer", g.name);
+  ST_TRY(codec_n_check(ctx, "compress", n));
+  return point_compress_run(ctx, g.g2, d_points, n, d_bytes);
+}
+keaki_status compress_host(const CodecGroup& g, keaki_hip_ctx* ctx, const uint64_t* points, size_t n, uint8_t* bytes) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.point_compress");
+  if (n == 0) return KEAKI_OK;
+  if (!points || !bytes) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s_compress: null pointer", g.name);
+  ST_TRY(codec_n_check(ctx, "compress", n));
+  return pipelined_regions(ctx, n, codec_chunk_items(ctx, n), {}, {{points, nullptr, g.aff}, {nullptr, bytes, g.wire}},
+    [&](size_t, size_t m, char* const*, char* const* d) { return point_compress_run(ctx, g.g2, d[0], m, d[1]); });
+}
+keaki_status decompress_args(const CodecGroup& g, keaki_hip_ctx* ctx, const void* bytes, size_t n, int32_t check_subgroup, const void* out, uint64_t* n_bad) {
+  if (check_subgroup != 0 && check_subgroup != 1) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s_decompress: check_subgroup = %d: must be 0 or 1", g.name, (int)check_subgroup);
+  if (!n_bad || (n && (!bytes || !out))) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s_decompress: null pointer", g.name);
+  return codec_n_check(ctx, "decompress", n);
+}
+// the kernels of items [lo, lo + m)
+keaki_status decompress_run(const CodecGroup& g, keaki_hip_ctx* ctx, const void* d_bytes, size_t lo, size_t m, bool check_subgroup, void* d_out, void* d_status) {
+  ST_TRY(point_decompress_run(ctx, g.g2, d_bytes, m, lo, d_out, d_status, ctx->io_e.p));
+  if (g.g2 && check_subgroup) ST_TRY(g2_subgroup_run(ctx, d_out, m, lo, d_status, true, ctx->io_e.p));
+  return KEAKI_OK;
+}
+keaki_status decompress_dev(const CodecGroup& g, keaki_hip_ctx* ctx, const void* d_bytes, size_t n, int32_t check_subgroup, void* d_out, void* d_status,
+                            uint64_t* n_bad, uint64_t* first_bad) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.point_decompress");
+  ST_TRY(decompress_args(g, ctx, d_bytes, n, check_subgroup, d_out, n_bad));
+  ST_TRY(codec_counter_begin(ctx));
+  ST_TRY(decompress_run(g, ctx, d_bytes, 0, n, check_subgroup != 0, d_out, d_status));
+  return codec_counter_end(ctx, n_bad, first_bad);
+}
+keaki_status decompress_host(const CodecGroup& g, keaki_hip_ctx* ctx, const uint8_t* bytes, size_t n, int32_t check_subgroup, uint64_t* out, uint8_t* status,
+                             uint64_t* n_bad, uint64_t* first_bad) {
+  CTX_GUARD(ctx);                 // one lock from staging to the last download: io_a and io_e belong to this call until it returns
+  TRACE_SCOPE("keaki.point_decompress");
+  ST_TRY(decompress_args(g, ctx, bytes, n, check_subgroup, out, n_bad));
+  ST_TRY(codec_counter_begin(ctx));
+  if (n)                          // the status bytes come last: every other region is a multiple of 16 B per item, so all of them stay aligned
+                                  // status == NULL: a region with neither `in` nor `out` is device scratch of the stager, so the kernels still get a valid
+                                  // d_status (they write it, nothing downloads it) -- never a null pointer, never a copy to NULL
+    ST_TRY(pipelined_regions(ctx, n, codec_chunk_items(ctx, n), {}, {{bytes, nullptr, g.wire}, {nullptr, out, g.aff}, {nullptr, status, 1}},
+      [&](size_t lo, size_t m, char* const*, char* const* d) { return decompress_run(g, ctx, d[0], lo, m, check_subgroup != 0, d[1], d[2]); }));
+  return codec_counter_end(ctx, n_bad, first_bad);
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_g1_compress(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint8_t* bytes_out) { return compress_host(CODEC_G1, ctx, points_aff, n, bytes_out); }
+keaki_status keaki_hip_g2_compress(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint8_t* bytes_out) { return compress_host(CODEC_G2, ctx, points_aff, n, bytes_out); }
+keaki_status keaki_hip_g1_compress_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, void* d_bytes_out) { return compress_dev(CODEC_G1, ctx, d_points_aff, n, d_bytes_out); }
+keaki_status keaki_hip_g2_compress_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, void* d_bytes_out) { return compress_dev(CODEC_G2, ctx, d_points_aff, n, d_bytes_out); }
+keaki_status keaki_hip_g1_decompress(keaki_hip_ctx* ctx, const uint8_t* bytes, size_t n, uint64_t* out_aff, uint8_t* status, uint64_t* n_bad, uint64_t* first_bad) {
+  return decompress_host(CODEC_G1, ctx, bytes, n, 0, out_aff, status, n_bad, first_bad);
+}
+keaki_status keaki_hip_g2_decompress(keaki_hip_ctx* ctx, const uint8_t* bytes, size_t n, int32_t check_subgroup, uint64_t* out_aff, uint8_t* status,
+                                     uint64_t* n_bad, uint64_t* first_bad) {
+  return decompress_host(CODEC_G2, ctx, bytes, n, check_subgroup, out_aff, status, n_bad, first_bad);
+}
+keaki_status keaki_hip_g1_decompress_dev(keaki_hip_ctx* ctx, const void* d_bytes, size_t n, void* d_out_aff, void* d_status, uint64_t* n_bad, uint64_t* first_bad) {
+  return decompress_dev(CODEC_G1, ctx, d_bytes, n, 0, d_out_aff, d_status, n_bad, first_bad);
+}
+keaki_status keaki_hip_g2_decompress_dev(keaki_hip_ctx* ctx, const void* d_bytes, size_t n, int32_t check_subgroup, void* d_out_aff, void* d_status,
+                                         uint64_t* n_bad, uint64_t* first_bad) {
+  return decompress_dev(CODEC_G2, ctx, d_bytes, n, check_subgroup, d_out_aff, d_status, n_bad, first_bad);
+}
+keaki_status keaki_hip_g2_subgroup_check_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, uint64_t* n_outside, uint64_t* first_outside) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.g2_subgroup_check");
+  if (!n_outside || (n && !d_points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_subgroup_check: null pointer");
+  ST_TRY(codec_n_check(ctx, "g2_subgroup_check", n));
+  ST_TRY(codec_counter_begin(ctx));
+  ST_TRY(g2_subgroup_run(ctx, const_cast<void*>(d_points_aff), n, 0, nullptr, false, ctx->io_e.p));     // clear = false: the points are only read
+  return codec_counter_end(ctx, n_outside, first_outside);
+}
+keaki_status keaki_hip_g2_subgroup_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint64_t* n_outside, uint64_t* first_outside) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.g2_subgroup_check");
+  if (!n_outside || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_subgroup_check: null pointer");
+  ST_TRY(codec_n_check(ctx, "g2_subgroup_check", n));
+  ST_TRY(codec_counter_begin(ctx));
+  if (n)
+    ST_TRY(pipelined_regions(ctx, n, codec_chunk_items(ctx, n), {}, {{points_aff, nullptr, G2_AFF_BYTES}},
+      [&](size_t lo, size_t m, char* const*, char* const* d) { return g2_subgroup_run(ctx, d[0], m, lo, nullptr, false, ctx->io_e.p); }));
+  return codec_counter_end(ctx, n_outside, first_outside);
+}
+
 // ---- self-test --------------------------------------------------------------------------------------------
 keaki_status keaki_hip_selftest_field(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, uint64_t* mismatches_out) {
   CTX_GUARD(ctx);

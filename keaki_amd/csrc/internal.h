@@ -255,6 +255,12 @@ keaki_status verify_batch_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, 
 // layout moves around the final sum (no arithmetic): n <= 64 affine points -> normalised Jacobian | the normalised Jacobian sums L, R -> d_out_lr_aff[0], [1] affine
 keaki_status verify_batch_aff_to_jac_run(keaki_hip_ctx* ctx, const void* d_in_aff, uint32_t n, void* d_out_jac);
 keaki_status verify_batch_jac_to_aff_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_r_jac, void* d_out_lr_aff);
+// compressed point wire format (point_codec.hip): one lane per point; n < 2^31. d_bad2: u64 count, u64 first index (over base + i: the host forms run in
+// chunks), added to by every launch; d_status (optional): one byte per item
+keaki_status point_compress_run(keaki_hip_ctx* ctx, bool g2, const void* d_pts, size_t n, void* d_out);
+keaki_status point_decompress_run(keaki_hip_ctx* ctx, bool g2, const void* d_bytes, size_t n, uint64_t base, void* d_out, void* d_status, void* d_bad2);
+// psi(Q) == [6 z^2]Q per point; an outsider gets status 3 (d_status given) and, with `clear`, all-zero words in place
+keaki_status g2_subgroup_run(keaki_hip_ctx* ctx, void* d_pts, size_t n, uint64_t base, void* d_status, bool clear, void* d_bad2);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 

@@ -25,7 +25,7 @@ EXPORTS = [
     "keaki_hip_encap_batch", "keaki_hip_encap_batch_dev", "keaki_hip_decap_batch", "keaki_hip_decap_batch_dev",
     "keaki_hip_encrypt_batch", "keaki_hip_encrypt_batch_dev", "keaki_hip_decrypt_batch", "keaki_hip_decrypt_batch_dev",
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
-    "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
+    "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
@@ -127,6 +127,11 @@ def load_library():
         lib.keaki_hip_srs_g1_check.argtypes = [vp, vp, vp, vp]
         lib.keaki_hip_kzg_open.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
         lib.keaki_hip_g2_check.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        for name in ("keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev"):
+            getattr(lib, name).argtypes = [vp, vp, sz, vp]
+        lib.keaki_hip_g1_decompress.argtypes = lib.keaki_hip_g1_decompress_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        lib.keaki_hip_g2_decompress.argtypes = lib.keaki_hip_g2_decompress_dev.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
+        lib.keaki_hip_g2_subgroup_check.argtypes = lib.keaki_hip_g2_subgroup_check_dev.argtypes = [vp, vp, sz, vp, vp]
         lib.keaki_hip_kzg_verify.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
         lib.keaki_hip_kzg_verify_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_kzg_verify_batch_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
@@ -476,6 +481,66 @@ class KeakiHip:
         pts = _np(points, 16)
         bad, first = C.c_uint64(0), C.c_uint64(0)
         self._ck(self.lib.keaki_hip_g2_check(self.ctx, _ptr(pts), pts.shape[0], C.byref(bad), C.byref(first)))
+        return bad.value, (None if bad.value == 0 else first.value)
+
+    # ---- compressed point wire format (ark-serialize `serialize_compressed`: 32 B per G1 point, 64 B per G2 point) ----
+    def _compress(self, points, g2: bool) -> np.ndarray:
+        pts = _np(points, 16 if g2 else 8); n = pts.shape[0]
+        out = np.zeros((n, 64 if g2 else 32), np.uint8)
+        self._ck((self.lib.keaki_hip_g2_compress if g2 else self.lib.keaki_hip_g1_compress)(self.ctx, _ptr(pts), n, _ptr(out)))
+        return out
+
+    def g1_compress(self, points_aff) -> np.ndarray:
+        """n affine G1 points (u64[n, 8], Montgomery limbs, zeros = identity) -> uint8[n, 32]"""
+        return self._compress(points_aff, False)
+
+    def g2_compress(self, points_aff) -> np.ndarray:
+        """n affine G2 points (u64[n, 16]) -> uint8[n, 64]"""
+        return self._compress(points_aff, True)
+
+    def _decompress(self, data, g2: bool, check_subgroup):
+        wire = 64 if g2 else 32
+        b = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, wire); n = b.shape[0]
+        out = np.zeros((n, 16 if g2 else 8), np.uint64); status = np.zeros(n, np.uint8)
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        if g2:
+            self._ck(self.lib.keaki_hip_g2_decompress(self.ctx, _ptr(b), n, int(check_subgroup), _ptr(out), _ptr(status), C.byref(bad), C.byref(first)))
+        else:
+            self._ck(self.lib.keaki_hip_g1_decompress(self.ctx, _ptr(b), n, _ptr(out), _ptr(status), C.byref(bad), C.byref(first)))
+        return out, status, bad.value, (None if bad.value == 0 else first.value)
+
+    def g1_decompress(self, data):
+        """uint8[n, 32] -> (points u64[n, 8], status uint8[n], n_bad, first_bad or None). status: 0 ok, 1 malformed, 2 not on the curve; a
+        rejected item's point is all zero"""
+        return self._decompress(data, False, 0)
+
+    def g2_decompress(self, data, check_subgroup: int = 1):
+        """uint8[n, 64] -> (points u64[n, 16], status, n_bad, first_bad or None); status 3: on the twist but outside the order-r subgroup
+        (tested when check_subgroup = 1)"""
+        return self._decompress(data, True, check_subgroup)
+
+    def g2_subgroup_check(self, points_aff):
+        """-> (number of points outside the order-r subgroup, index of the first or None); the points are assumed to be on the twist"""
+        pts = _np(points_aff, 16)
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_g2_subgroup_check(self.ctx, _ptr(pts), pts.shape[0], C.byref(bad), C.byref(first)))
+        return bad.value, (None if bad.value == 0 else first.value)
+
+    def point_codec_dev(self, what: str, d_in, n: int, d_out=None, d_status=None, check_subgroup: int = 1):
+        """the resident forms: `what` in g1_compress, g2_compress, g1_decompress, g2_decompress, g2_subgroup_check; device pointers (ints) or
+        torch tensors. compress -> None; the others -> (n_bad, first_bad or None) on the host (the call synchronises)"""
+        dp = lambda x: C.c_void_p(None if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else x))
+        fn = getattr(self.lib, "keaki_hip_%s_dev" % what)
+        if what.endswith("_compress"):
+            self._ck(fn(self.ctx, dp(d_in), int(n), dp(d_out)))
+            return None
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        if what == "g2_subgroup_check":
+            self._ck(fn(self.ctx, dp(d_in), int(n), C.byref(bad), C.byref(first)))
+        elif what == "g2_decompress":
+            self._ck(fn(self.ctx, dp(d_in), int(n), int(check_subgroup), dp(d_out), dp(d_status), C.byref(bad), C.byref(first)))
+        else:
+            self._ck(fn(self.ctx, dp(d_in), int(n), dp(d_out), dp(d_status), C.byref(bad), C.byref(first)))
         return bad.value, (None if bad.value == 0 else first.value)
 
     def fr_fft(self, data, log2n: int, omega, scale=None) -> np.ndarray:

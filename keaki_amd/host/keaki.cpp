@@ -291,6 +291,38 @@ Result<bool> verify_batch(Rng& rng, const KZGSetup& setup, const std::vector<G1>
                                             n ? proofs[0].w.data() : nullptr, n));
 }
 
+namespace {
+const char* wire_reason(int r) {
+  return r == 1 ? "malformed encoding (flags, or a coordinate >= p)" : r == 2 ? "no point of the curve has this x" : r == 3 ? "outside the order-r subgroup" : "rejected";
+}
+[[noreturn]] void throw_wire(const char* what, size_t index, int reason) {
+  throw WireError(index, reason, std::string(what) + ": item " + std::to_string(index) + ": " + wire_reason(reason));
+}
+}  // namespace
+void proofs_to_bytes_flat(const KZGSetup& setup, const uint64_t* proofs, size_t n, uint8_t* wire_out) {
+  const Device& dev = *setup.device();
+  dev.check(keaki_hip_g1_compress(dev.ctx(), proofs, n, wire_out));
+}
+void proofs_from_bytes_flat(const KZGSetup& setup, const uint8_t* wire, size_t n, uint64_t* proofs_out) {
+  const Device& dev = *setup.device();
+  std::vector<uint8_t> status(n);
+  uint64_t bad = 0, first = 0;
+  dev.check(keaki_hip_g1_decompress(dev.ctx(), wire, n, proofs_out, status.data(), &bad, &first));
+  if (bad) throw_wire("proofs_from_bytes", (size_t)first, status[(size_t)first]);
+}
+std::vector<uint8_t> proofs_to_bytes(const KZGSetup& setup, const std::vector<G1>& proofs) {
+  static_assert(sizeof(G1) == 64, "G1 is eight u64 words");
+  std::vector<uint8_t> out(proofs.size() * 32);
+  proofs_to_bytes_flat(setup, proofs.empty() ? nullptr : proofs[0].w.data(), proofs.size(), out.data());
+  return out;
+}
+std::vector<G1> proofs_from_bytes(const KZGSetup& setup, const std::vector<uint8_t>& bytes) {
+  if (bytes.size() % 32) throw std::invalid_argument("proofs_from_bytes: the length is not a multiple of 32");
+  std::vector<G1> out(bytes.size() / 32);
+  proofs_from_bytes_flat(setup, bytes.data(), out.size(), out.empty() ? nullptr : out[0].w.data());
+  return out;
+}
+
 void precompute_open_fk(const KZGSetup& setup, size_t d) {
   if (d < 1 || (d & (d - 1)) != 0 || d > setup.g1_pow().size()) return;   // open_fk falls back to per-point openings for such shapes
   unsigned log2d = 0;
@@ -376,6 +408,53 @@ std::vector<uint8_t> decrypt(const kzg::KZGSetup& setup, const G1& proof, const 
   std::vector<uint8_t> key = kem::decapsulate(setup, proof, ct.first, ct.second.size());
   for (size_t i = 0; i < key.size(); i++) key[i] ^= ct.second[i];
   return key;
+}
+// wire = n x (64 B point | body): the points are gathered into one contiguous array for the device call and scattered back
+void ciphertexts_to_bytes_flat(const kzg::KZGSetup& setup, const uint64_t* ct_g2, const uint8_t* bodies, size_t n, size_t msg_len, uint8_t* wire_out) {
+  const Device& dev = *setup.device();
+  std::vector<uint8_t> pts(n * 64);
+  dev.check(keaki_hip_g2_compress(dev.ctx(), ct_g2, n, pts.data()));
+  const size_t item = 64 + msg_len;
+  for (size_t i = 0; i < n; i++) {
+    memcpy(wire_out + i * item, pts.data() + i * 64, 64);
+    if (msg_len) memcpy(wire_out + i * item + 64, bodies + i * msg_len, msg_len);
+  }
+}
+void ciphertexts_from_bytes_flat(const kzg::KZGSetup& setup, const uint8_t* wire, size_t n, size_t msg_len, uint64_t* ct_g2_out, uint8_t* bodies_out) {
+  const Device& dev = *setup.device();
+  const size_t item = 64 + msg_len;
+  std::vector<uint8_t> pts(n * 64), status(n);
+  for (size_t i = 0; i < n; i++) memcpy(pts.data() + i * 64, wire + i * item, 64);
+  uint64_t bad = 0, first = 0;
+  dev.check(keaki_hip_g2_decompress(dev.ctx(), pts.data(), n, 1, ct_g2_out, status.data(), &bad, &first));
+  if (bad) kzg::throw_wire("ciphertexts_from_bytes", (size_t)first, status[(size_t)first]);
+  for (size_t i = 0; i < n; i++)
+    if (msg_len) memcpy(bodies_out + i * msg_len, wire + i * item + 64, msg_len);
+}
+std::vector<uint8_t> ciphertexts_to_bytes(const kzg::KZGSetup& setup, const std::vector<Ciphertext>& cts) {
+  const size_t n = cts.size(), msg_len = n ? cts[0].second.size() : 0;
+  std::vector<uint64_t> g2(n * 16);
+  std::vector<uint8_t> bodies(n * msg_len), out(n * (64 + msg_len));
+  for (size_t i = 0; i < n; i++) {
+    if (cts[i].second.size() != msg_len) throw std::invalid_argument("ciphertexts_to_bytes: the bodies of one batch must have one length");
+    memcpy(g2.data() + 16 * i, cts[i].first.w.data(), 128);
+    if (msg_len) memcpy(bodies.data() + i * msg_len, cts[i].second.data(), msg_len);
+  }
+  ciphertexts_to_bytes_flat(setup, g2.data(), bodies.data(), n, msg_len, out.data());
+  return out;
+}
+std::vector<Ciphertext> ciphertexts_from_bytes(const kzg::KZGSetup& setup, const std::vector<uint8_t>& bytes, size_t msg_len) {
+  if (bytes.size() % (64 + msg_len)) throw std::invalid_argument("ciphertexts_from_bytes: the length is not a multiple of 64 + msg_len");
+  const size_t n = bytes.size() / (64 + msg_len);
+  std::vector<uint64_t> g2(n * 16);
+  std::vector<uint8_t> bodies(n * msg_len);
+  ciphertexts_from_bytes_flat(setup, bytes.data(), n, msg_len, g2.data(), bodies.data());
+  std::vector<Ciphertext> out(n);
+  for (size_t i = 0; i < n; i++) {
+    memcpy(out[i].first.w.data(), g2.data() + 16 * i, 128);
+    out[i].second.assign(bodies.begin() + i * msg_len, bodies.begin() + (i + 1) * msg_len);
+  }
+  return out;
 }
 }  // namespace enc
 

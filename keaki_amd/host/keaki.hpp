@@ -67,6 +67,13 @@ struct HipError : std::runtime_error {
   int status;
   HipError(int s, const std::string& m) : std::runtime_error(m), status(s) {}
 };
+// What `*_from_bytes` throws for bytes that do not decode: the index of the first rejected item and why (1 malformed: flags or a coordinate
+// >= p; 2 no point of the curve has this x; 3 a G2 point outside the order-r subgroup) -- arkworks' SerializationError::InvalidData with a place
+struct WireError : std::runtime_error {
+  size_t index;
+  int reason;
+  WireError(size_t i, int r, const std::string& m) : std::runtime_error(m), index(i), reason(r) {}
+};
 
 // One GPU context shared by the setup objects created from it -- or, built from a LIST of ordinals, several GPUs of this process behind
 // one object (keaki_hip_group_*: one context and one host thread per entry inside the library; an ordinal may repeat). With a group,
@@ -167,6 +174,12 @@ Result<bool> verify_batch(Rng& rng, const KZGSetup& setup, const std::vector<G1>
 // the same on contiguous buffers. n_coms: 1 or n. roots_of_unity: `points` is ONE Fr omega and item i is opened at omega^i.
 bool verify_batch_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values,
                        const uint64_t* proofs, size_t n);
+// Proofs (any G1 points) on the wire: n x 32 B, `serialize_compressed`. `proofs_from_bytes` validates (canonical, on the curve; G1 has cofactor 1)
+// and throws WireError naming the first bad index.
+std::vector<uint8_t> proofs_to_bytes(const KZGSetup& setup, const std::vector<G1>& proofs);
+std::vector<G1> proofs_from_bytes(const KZGSetup& setup, const std::vector<uint8_t>& bytes);
+void proofs_to_bytes_flat(const KZGSetup& setup, const uint64_t* proofs, size_t n, uint8_t* wire_out);
+void proofs_from_bytes_flat(const KZGSetup& setup, const uint8_t* wire, size_t n, uint64_t* proofs_out);
 // all openings at the roots of unity of a size-d domain (src/kzg.rs:157-203): FK23 -- three G1 FFTs + 2d scalar-mults on
 // the GPU (keaki_hip_open_fk) when p.size() == domain_size is a power of two; per-point `open` otherwise.
 Result<std::vector<G1>> open_fk(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size);
@@ -189,6 +202,15 @@ namespace enc {
 using Ciphertext = std::pair<G2, std::vector<uint8_t>>;  // src/enc.rs:13
 Ciphertext encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr& point, const Fr& value, const std::vector<uint8_t>& msg);
 std::vector<uint8_t> decrypt(const kzg::KZGSetup& setup, const G1& proof, const Ciphertext& ct);
+// Ciphertexts on the wire: n x (64 B compressed G2 point + body), the point as ark-serialize `serialize_compressed` writes it
+// (include/keaki_hip.h: compressed point wire format), all bodies of one length. The points are compressed / decompressed on the device in one
+// call. `ciphertexts_from_bytes` VALIDATES like `deserialize_compressed`: canonical encoding, on the twist, in the order-r subgroup (the points
+// come from the other party and go into a pairing); bytes that fail throw WireError naming the first bad index. On a group device: member 0.
+std::vector<uint8_t> ciphertexts_to_bytes(const kzg::KZGSetup& setup, const std::vector<Ciphertext>& cts);
+std::vector<Ciphertext> ciphertexts_from_bytes(const kzg::KZGSetup& setup, const std::vector<uint8_t>& bytes, size_t msg_len);
+// the same on contiguous arrays: ct_g2 n x u64[16], bodies n x msg_len, wire n x (64 + msg_len)
+void ciphertexts_to_bytes_flat(const kzg::KZGSetup& setup, const uint64_t* ct_g2, const uint8_t* bodies, size_t n, size_t msg_len, uint8_t* wire_out);
+void ciphertexts_from_bytes_flat(const kzg::KZGSetup& setup, const uint8_t* wire, size_t n, size_t msg_len, uint64_t* ct_g2_out, uint8_t* bodies_out);
 }  // namespace enc
 
 namespace vec {

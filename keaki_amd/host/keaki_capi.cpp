@@ -35,6 +35,18 @@ int guard(F&& f) {
   catch (const HipError& e) { g_err = e.what(); return e.status; }
   catch (const std::exception& e) { g_err = e.what(); return -1000; }
 }
+// bytes that do not decode (WireError): status 2, the index of the first rejected item and the reason in bad_out[0], [1]
+template <class F>
+int wire_guard(uint64_t* bad_out, F&& f) {
+  return guard([&] {
+    try { f(); return 0; }
+    catch (const WireError& e) {
+      if (bad_out) { bad_out[0] = e.index; bad_out[1] = (uint64_t)e.reason; }
+      g_err = e.what();
+      return 2;
+    }
+  });
+}
 Fr fr_of(const uint64_t* p) { Fr r; memcpy(r.l, p, 32); return r; }
 std::vector<Fr> frs_of(const uint64_t* p, size_t n) { std::vector<Fr> v(n); for (size_t i = 0; i < n; i++) v[i] = fr_of(p + 4 * i); return v; }
 G1 g1_of(const uint64_t* p) { G1 r; memcpy(r.w.data(), p, 64); return r; }
@@ -232,6 +244,20 @@ int keaki_host_vec_verify(void* rng, void* s, const uint64_t* com, const uint64_
     *out_ok = vec::vec_verify_flat(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), reinterpret_cast<const Fr*>(v), n, proofs) ? 1 : 0;
     return 0;
   });
+}
+// the wire format (compressed points). Return 2: bytes that do not decode; bad_out[0] = index of the first rejected item, bad_out[1] = reason
+// (1 malformed, 2 not on the curve, 3 outside the subgroup)
+int keaki_host_proofs_to_bytes(void* s, const uint64_t* proofs, size_t n, uint8_t* wire_out) {
+  return guard([&] { kzg::proofs_to_bytes_flat(((Setup*)s)->s, proofs, n, wire_out); return 0; });
+}
+int keaki_host_proofs_from_bytes(void* s, const uint8_t* wire, size_t n, uint64_t* proofs_out, uint64_t* bad_out) {
+  return wire_guard(bad_out, [&] { kzg::proofs_from_bytes_flat(((Setup*)s)->s, wire, n, proofs_out); });
+}
+int keaki_host_ciphertexts_to_bytes(void* s, const uint64_t* ct_g2, const uint8_t* bodies, size_t n, size_t msg_len, uint8_t* wire_out) {
+  return guard([&] { enc::ciphertexts_to_bytes_flat(((Setup*)s)->s, ct_g2, bodies, n, msg_len, wire_out); return 0; });
+}
+int keaki_host_ciphertexts_from_bytes(void* s, const uint8_t* wire, size_t n, size_t msg_len, uint64_t* ct_g2_out, uint8_t* bodies_out, uint64_t* bad_out) {
+  return wire_guard(bad_out, [&] { enc::ciphertexts_from_bytes_flat(((Setup*)s)->s, wire, n, msg_len, ct_g2_out, bodies_out); });
 }
 int keaki_host_precompute_open_fk(void* s, size_t domain_size) {
   return guard([&] { kzg::precompute_open_fk(((Setup*)s)->s, domain_size); return 0; });

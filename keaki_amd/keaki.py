@@ -31,6 +31,15 @@ class KeakiHostError(RuntimeError):
     pass
 
 
+class WireFormatError(ValueError):
+    """bytes that do not decode (proofs_from_bytes, ciphertexts_from_bytes): `index` of the first rejected item, `reason` 1 malformed encoding,
+    2 no point of the curve has this x, 3 a G2 point outside the order-r subgroup"""
+
+    def __init__(self, index: int, reason: int, text: str):
+        super().__init__(text)
+        self.index, self.reason = index, reason
+
+
 class SetupFileError(Exception):
     """SetupFileError -- src/kzg/ptau.rs:360-376 (+ OffCurve, Truncated: what the reference does not detect / panics on)"""
     KINDS = ["ElementSizeMismatch", "EmptySection", "FileError", "InvalidFileType", "InvalidNumberOfSections", "ParseError",
@@ -340,6 +349,54 @@ def vec_verify(rng: "Rng", setup: "KZGSetup", com, v, proofs) -> bool:
     ok = C.c_int(0)
     _ck(_lib().keaki_host_vec_verify(rng.h, setup.h, _p(_u64(com)), _p(vals), C.c_size_t(n), _p(pr), C.byref(ok)))
     return bool(ok.value)
+
+
+def _ck_wire(st, bad):
+    if st == 2:
+        raise WireFormatError(int(bad[0]), int(bad[1]), _lib().keaki_host_last_error().decode())
+    _ck(st)
+
+
+def proofs_to_bytes(setup: "KZGSetup", proofs) -> bytes:
+    """kzg::proofs_to_bytes: n G1 points -> n x 32 B (`serialize_compressed`), compressed on the device"""
+    pr = np.ascontiguousarray(_u64(proofs, 8)); n = pr.shape[0]
+    out = np.zeros(n * 32, np.uint8)
+    _ck(_lib().keaki_host_proofs_to_bytes(setup.h, _p(pr), C.c_size_t(n), _p(out)))
+    return out.tobytes()
+
+
+def proofs_from_bytes(setup: "KZGSetup", data) -> np.ndarray:
+    """kzg::proofs_from_bytes: n x 32 B -> u64[n, 8], validated (canonical, on the curve); raises WireFormatError naming the first bad index"""
+    b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if b.size % 32:
+        raise ValueError("proofs_from_bytes: the length is not a multiple of 32")
+    n = b.size // 32
+    out = np.zeros((n, 8), np.uint64); bad = np.zeros(2, np.uint64)
+    _ck_wire(_lib().keaki_host_proofs_from_bytes(setup.h, _p(b), C.c_size_t(n), _p(out), _p(bad)), bad)
+    return out
+
+
+def ciphertexts_to_bytes(setup: "KZGSetup", ct_g2, ct_body) -> bytes:
+    """enc::ciphertexts_to_bytes on arrays (ct G2 points (n, 16) u64, bodies (n, len) u8) -> n x (64 B compressed point + body)"""
+    body = np.ascontiguousarray(ct_body, dtype=np.uint8); n, ml = body.shape
+    g2 = np.ascontiguousarray(_u64(ct_g2, 16)[:n])
+    if g2.shape[0] != n:
+        raise ValueError("ciphertexts_to_bytes: fewer points than bodies")
+    out = np.zeros(n * (64 + ml), np.uint8)
+    _ck(_lib().keaki_host_ciphertexts_to_bytes(setup.h, _p(g2), _p(body), C.c_size_t(n), C.c_size_t(ml), _p(out)))
+    return out.tobytes()
+
+
+def ciphertexts_from_bytes(setup: "KZGSetup", data, msg_len: int):
+    """enc::ciphertexts_from_bytes -> (ct G2 points (n, 16) u64, bodies (n, msg_len) u8). Every point is validated as arkworks'
+    deserialize_compressed does (canonical, on the twist, in the order-r subgroup); raises WireFormatError naming the first bad index"""
+    b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if b.size % (64 + msg_len):
+        raise ValueError("ciphertexts_from_bytes: the length is not a multiple of 64 + msg_len")
+    n = b.size // (64 + msg_len)
+    g2 = np.zeros((n, 16), np.uint64); body = np.zeros((n, msg_len), np.uint8); bad = np.zeros(2, np.uint64)
+    _ck_wire(_lib().keaki_host_ciphertexts_from_bytes(setup.h, _p(b), C.c_size_t(n), C.c_size_t(msg_len), _p(g2), _p(body), _p(bad)), bad)
+    return g2, body
 
 
 def precompute_open_fk(setup: "KZGSetup", domain_size: int) -> None:

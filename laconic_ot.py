@@ -37,7 +37,7 @@ sys.path.insert(0, ROOT)
 from keaki_amd.launch import self_launch, under_launcher  # noqa: E402  (standard library only: no torch, no HIP)
 
 
-def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_single=False, backend=None, verify_proofs=False):
+def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_single=False, backend=None, verify_proofs=False, wire=None):
     """The whole flow on the ranks of `shard` (one rank: the un-sharded calls). Every rank calls this; returns the report (a dict; the same on
     every rank except for `sharded_equals_single_process`, which only rank 0 computes) whose `all_messages_recovered` is the AND over all
     ranks. bench.py's `laconic` block is this function on the bench's own process group."""
@@ -90,6 +90,22 @@ def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_s
     _, g2_1, body_1 = sharded_vec_encrypt(K, rng, s, commitment, elements, ones, sets[1], shard)
     t_sender_send = phase_max(time.time() - t0)
 
+    wire_report = None
+    if wire == "compressed":
+        # opt-in, outside the three timed phases: the sender's two ciphertext sets cross the wire as n x (64 B compressed point + body) and the
+        # receiver decodes them WITH validation (canonical, on the twist, in the order-r subgroup) before any point goes into a pairing
+        t0 = time.time()
+        sent = [K.ciphertexts_to_bytes(s, g2_0, body_0), K.ciphertexts_to_bytes(s, g2_1, body_1)]
+        t_to = phase_max(time.time() - t0)
+        t0 = time.time()
+        (w_g2_0, w_body_0), (w_g2_1, w_body_1) = (K.ciphertexts_from_bytes(s, b, vb) for b in sent)
+        t_from = phase_max(time.time() - t0)
+        same = bool(np.array_equal(w_g2_0, g2_0) and np.array_equal(w_g2_1, g2_1) and np.array_equal(w_body_0, body_0) and np.array_equal(w_body_1, body_1))
+        wire_report = {"wire": "compressed", "wire_bytes": sum(len(b) for b in sent), "wire_point_bytes": sum(len(b) for b in sent) - int(body_0.nbytes + body_1.nbytes),
+                       "uncompressed_point_bytes": int(g2_0.nbytes + g2_1.nbytes), "wire_to_bytes_s": round(t_to, 4), "wire_from_bytes_s": round(t_from, 4),
+                       "wire_round_trip_exact": same}
+        g2_0, body_0, g2_1, body_1 = w_g2_0, w_body_0, w_g2_1, w_body_1                       # receive() works on what came off the wire
+
     pick = bits[lo:hi, None] == 0                                                              # Receiver::receive, this rank's items
     sel_g2, sel_body = np.where(pick, g2_0, g2_1), np.where(pick, body_0, body_1)             # the ciphertext of each bit (references in the reference's loop)
     t0 = time.time()
@@ -130,6 +146,9 @@ def run_flow(K, shard, device, log2n, value_bytes=32, fk_mode="sharded", check_s
         report["proofs_verified"] = verified
         report["verify_proofs_s"] = round(t_verify, 4)
         report["all_messages_recovered"] = bool(report["all_messages_recovered"] and verified)
+    if wire_report is not None:
+        report.update(wire_report)
+        report["all_messages_recovered"] = bool(report["all_messages_recovered"] and wire_report["wire_round_trip_exact"])
     if fk is not None:
         fk.close()
     s.close()
@@ -147,6 +166,9 @@ def main():
                     help="rank 0 also runs the un-sharded calls with the same seeds and compares commitment and ciphertexts bit for bit")
     ap.add_argument("--verify-proofs", action="store_true",
                     help="after Receiver::new, check all n proofs against the digest in one batch (vec_verify); its time is reported on its own")
+    ap.add_argument("--wire", default=None, choices=["compressed"],
+                    help="the sender's ciphertexts pass through the compressed wire format (64 B per G2 point) and are validated on decoding, "
+                         "before receive; bytes on the wire and the two added times are reported")
     args = ap.parse_args()
     if args.gpus > 1 and not under_launcher():
         # typed without torch.distributed.run: this process -- which has not imported torch or touched the GPU -- starts the N ranks as a
@@ -176,7 +198,7 @@ def main():
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)
     shard = Shard(rank, world, dist)
-    report = run_flow(K, shard, device, args.log2n, args.value_bytes, args.fk, args.check_single, args.backend, args.verify_proofs)
+    report = run_flow(K, shard, device, args.log2n, args.value_bytes, args.fk, args.check_single, args.backend, args.verify_proofs, args.wire)
     if rank == 0:
         print(json.dumps(report), flush=True)
     if world > 1:

@@ -129,6 +129,24 @@ extern "C" {
     pub fn keaki_hip_srs_g1_check(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, n_off_curve: *mut u64, first_off_curve: *mut u64) -> keaki_status;
     pub fn keaki_hip_g2_check(ctx: *mut keaki_hip_ctx, points_aff: *const u64, n: usize, n_off_curve: *mut u64, first_off_curve: *mut u64) -> keaki_status;
 
+    // ---- compressed point wire format (ark-serialize `serialize_compressed`: 32 B per G1 point, 64 B per G2 point); decompress validates:
+    // status 0 ok, 1 malformed, 2 not on the curve, 3 (G2, check_subgroup = 1) outside the order-r subgroup; one bad item does not fail the call
+    pub fn keaki_hip_g1_compress(ctx: *mut keaki_hip_ctx, points_aff: *const u64, n: usize, bytes_out: *mut u8) -> keaki_status;
+    pub fn keaki_hip_g2_compress(ctx: *mut keaki_hip_ctx, points_aff: *const u64, n: usize, bytes_out: *mut u8) -> keaki_status;
+    pub fn keaki_hip_g1_compress_dev(ctx: *mut keaki_hip_ctx, d_points_aff: *const c_void, n: usize, d_bytes_out: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_g2_compress_dev(ctx: *mut keaki_hip_ctx, d_points_aff: *const c_void, n: usize, d_bytes_out: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_g1_decompress(ctx: *mut keaki_hip_ctx, bytes: *const u8, n: usize, out_aff: *mut u64, status: *mut u8, n_bad: *mut u64,
+                                   first_bad: *mut u64) -> keaki_status;
+    pub fn keaki_hip_g2_decompress(ctx: *mut keaki_hip_ctx, bytes: *const u8, n: usize, check_subgroup: i32, out_aff: *mut u64, status: *mut u8,
+                                   n_bad: *mut u64, first_bad: *mut u64) -> keaki_status;
+    pub fn keaki_hip_g1_decompress_dev(ctx: *mut keaki_hip_ctx, d_bytes: *const c_void, n: usize, d_out_aff: *mut c_void, d_status: *mut c_void,
+                                       n_bad: *mut u64, first_bad: *mut u64) -> keaki_status;
+    pub fn keaki_hip_g2_decompress_dev(ctx: *mut keaki_hip_ctx, d_bytes: *const c_void, n: usize, check_subgroup: i32, d_out_aff: *mut c_void,
+                                       d_status: *mut c_void, n_bad: *mut u64, first_bad: *mut u64) -> keaki_status;
+    pub fn keaki_hip_g2_subgroup_check(ctx: *mut keaki_hip_ctx, points_aff: *const u64, n: usize, n_outside: *mut u64, first_outside: *mut u64) -> keaki_status;
+    pub fn keaki_hip_g2_subgroup_check_dev(ctx: *mut keaki_hip_ctx, d_points_aff: *const c_void, n: usize, n_outside: *mut u64,
+                                           first_outside: *mut u64) -> keaki_status;
+
     // ---- batched scalar multiplication (replaces `.mul(scalar)`, src/kem.rs:22,30,36,37)
     pub fn keaki_hip_g1_mul_batch(ctx: *mut keaki_hip_ctx, points_aff: *const u64, point_stride: i32, scalars: *const u64, n: usize, out_aff: *mut u64) -> keaki_status;
     pub fn keaki_hip_g2_mul_batch(ctx: *mut keaki_hip_ctx, points_aff: *const u64, point_stride: i32, scalars: *const u64, n: usize, out_aff: *mut u64) -> keaki_status;

@@ -434,6 +434,66 @@ pub fn verify_batch(commitments: &[G1Projective], tau_g2: &G2Projective, points:
     ok != 0
 }
 
+/// `serialize_compressed` of n G2 points on the device (`keaki_hip_g2_compress`): n x 64 bytes, what a `Ciphertext`'s point costs on the wire.
+pub fn g2_compress(points: &[G2Projective]) -> Vec<u8> {
+    let dev = Device::global();
+    let flat: Vec<u64> = G2Projective::normalize_batch(points).iter().flat_map(|p| g2_words(p)).collect();
+    let mut out = vec![0u8; points.len() * 64];
+    dev.check(unsafe { sys::keaki_hip_g2_compress(dev.ctx, flat.as_ptr(), points.len(), out.as_mut_ptr()) }, "g2_compress");
+    out
+}
+
+/// `deserialize_compressed` of n G2 points with arkworks' default validation (`keaki_hip_g2_decompress`, subgroup check on): the points, or the
+/// index of the first rejected item (malformed, not on the curve, or outside the order-r subgroup).
+pub fn g2_decompress_checked(bytes: &[u8]) -> Result<Vec<G2Projective>, usize> {
+    let dev = Device::global();
+    assert!(bytes.len() % 64 == 0);
+    let n = bytes.len() / 64;
+    let mut out = vec![0u64; n * 16];
+    let (mut bad, mut first) = (0u64, 0u64);
+    dev.check(
+        unsafe { sys::keaki_hip_g2_decompress(dev.ctx, bytes.as_ptr(), n, 1, out.as_mut_ptr(), core::ptr::null_mut(), &mut bad, &mut first) },
+        "g2_decompress",
+    );
+    if bad != 0 {
+        return Err(first as usize);
+    }
+    Ok(out.chunks_exact(16).map(|w| g2_from_words(w).into()).collect())
+}
+
+/// The same for G1 (32 bytes per point; cofactor 1: on the curve is in the group): proofs on the wire.
+pub fn g1_compress(points: &[G1Projective]) -> Vec<u8> {
+    let dev = Device::global();
+    let flat: Vec<u64> = G1Projective::normalize_batch(points).iter().flat_map(|p| g1_words(p)).collect();
+    let mut out = vec![0u8; points.len() * 32];
+    dev.check(unsafe { sys::keaki_hip_g1_compress(dev.ctx, flat.as_ptr(), points.len(), out.as_mut_ptr()) }, "g1_compress");
+    out
+}
+pub fn g1_decompress_checked(bytes: &[u8]) -> Result<Vec<G1Projective>, usize> {
+    let dev = Device::global();
+    assert!(bytes.len() % 32 == 0);
+    let n = bytes.len() / 32;
+    let mut out = vec![0u64; n * 8];
+    let (mut bad, mut first) = (0u64, 0u64);
+    dev.check(
+        unsafe { sys::keaki_hip_g1_decompress(dev.ctx, bytes.as_ptr(), n, out.as_mut_ptr(), core::ptr::null_mut(), &mut bad, &mut first) },
+        "g1_decompress",
+    );
+    if bad != 0 {
+        return Err(first as usize);
+    }
+    Ok(out.chunks_exact(8).map(|w| g1_from_words(w).into()).collect())
+}
+
+/// Are all points in the order-r subgroup of the twist (`keaki_hip_g2_subgroup_check`)? `Err(i)`: the first that is not.
+pub fn g2_subgroup_check(points: &[G2Projective]) -> Result<(), usize> {
+    let dev = Device::global();
+    let flat: Vec<u64> = G2Projective::normalize_batch(points).iter().flat_map(|p| g2_words(p)).collect();
+    let (mut bad, mut first) = (0u64, 0u64);
+    dev.check(unsafe { sys::keaki_hip_g2_subgroup_check(dev.ctx, flat.as_ptr(), points.len(), &mut bad, &mut first) }, "g2_subgroup_check");
+    if bad != 0 { Err(first as usize) } else { Ok(()) }
+}
+
 /// FK23: all `d = coeffs.len()` openings at the d-th roots of unity (d a power of two, d <= srs.len()). `omega_2d`, `omega_2d_inv`,
 /// `inv_2d` = `group_gen`, `group_gen_inv`, `size_inv` of `Radix2EvaluationDomain::new(2 d)`.
 pub fn open_fk(srs: &HipSrs, coeffs: &[Fr], omega_2d: &Fr, omega_2d_inv: &Fr, inv_2d: &Fr) -> Vec<G1Projective> {
