@@ -10,7 +10,8 @@
 //   K3c cnt_*    counting sort of the buckets by size (largest first) so waves have equal trip counts
 //   K4 accumulate one lane per bucket: gather affine points (64 B rows), XYZZ mixed adds -- the
 //                 dominant kernel: n * windows adds of 8M+2S
-//   K5 reduce     per-window weighted bucket sum  sum_b (b+1) S_b  by chunked running sums
+//   K5 reduce     per-window weighted bucket sum  sum_b (b+1) S_b  by chunked running sums; the one shared window of the table path
+//                 by row and column sums (K5r, k_msm_rowcol*)
 //   K6 finish     window sums -> Horner by 2^c -> one point, normalised
 //
 // Order of additions inside a bucket depends on LDS-atomic arrival order; EC addition is exact and
@@ -1349,6 +1350,118 @@ KDEV void store_norm_jac(F* out, const Xyzz<F>& p) {
     out[0] = a.x; out[1] = a.y; out[2] = f_one<F>();
   }
 }
+// ---- K5r: the weighted bucket sum of ONE window of B = 2^cr buckets by row and column sums (the shared-bucket path) ------------------
+// Bucket b = h 2^k + l, k = ceil(cr / 2):   sum_b (b + 1) S_b = 2^k sum_h h R_h + sum_l (l + 1) C_l   with the row sums R_h = sum_l S_(h,l)
+// and the column sums C_l = sum_h S_(h,l): two additions per bucket, every one of them independent of the others, where the chunked
+// running sums of k_msm_reduce spend 2 + (a double-and-add per chunk) on a serial chain. Four launches:
+//   k_msm_rowcol         a workgroup owns one 64 x 64 tile for its columns (type 0) or its rows (type 1): every lane sums a strip of
+//                        16 buckets into ONE accumulator, the four strips of a column / row meet through LDS
+//   k_msm_rowcol_sums    C_l, R_h from the per-tile sums (eight lanes per output, LDS tree)
+//   k_msm_rowcol_planes  bit planes instead of a running sum over the 2^k + 2^(cr-k) sums: sum_h h R_h = sum_j 2^j T_j with T_j the sum of
+//                        the R_h whose h has bit j set (likewise the columns, weight l + 1); workgroup = plane, a tree, then its 2^j
+//   k_msm_rowcol_final   the cr + 1 plane terms, one tree, normalised
+constexpr u32 ROWCOL_MIN_CR = 12;       // a window holds at least one tile
+// sum over the lanes t, t + stop, t + 2 stop, ... of a workgroup of n lanes (n, stop powers of two): the result is in lanes 0 .. stop - 1.
+// sh holds n / 2 points; every lane of the workgroup calls it.
+template <class O>
+KDEV typename O::P tail_tree(typename O::P acc, typename O::P* sh, u32 t, u32 n, u32 stop) {
+  for (u32 o = n >> 1; o >= stop; o >>= 1) {
+    if (t >= o && t < 2 * o) sh[t - o] = acc;
+    __syncthreads();
+    if (t < o) acc = O::add(acc, sh[t]);
+    __syncthreads();
+  }
+  return acc;
+}
+// three workgroups (three waves per SIMD) where the addition fits 168 registers
+template <class F> struct RowColOcc { static constexpr int WGS = 1; };
+template <> struct RowColOcc<Fq> { static constexpr int WGS = 3; };
+
+template <class F>
+__global__ void __launch_bounds__(256, RowColOcc<F>::WGS) k_msm_rowcol(const Xyzz<F>* __restrict__ buckets, u32 cr, Xyzz<F>* __restrict__ colp,
+                                                                      Xyzz<F>* __restrict__ rowp) {
+  typedef TailOps<F> O;
+  __shared__ typename O::P sh[128];
+  const u32 k = (cr + 1) >> 1, NC = 1u << k, ntc = NC >> 6, tiles = 1u << (cr - 12);
+  // the two workgroups of a tile are eight apart in launch order: close in time, and on the same XCD (L2) where workgroups go round the XCDs
+  const u32 g = tiles >= 8 ? 8u : 1u, x = blockIdx.x;
+  const u32 type = (x / g) & 1u, tile = (x / (2 * g)) * g + x % g;
+  const u32 tr = tile / ntc, tc = tile % ntc;
+  const u32 t = threadIdx.x, a = t & 63u, q = t >> 6;
+  // type 0: lane = column tc 64 + a, rows tr 64 + 16 q + i (lanes adjacent in l); type 1: lane = row tr 64 + a, columns tc 64 + q + 4 i
+  const Xyzz<F>* p = type == 0 ? buckets + ((size_t)(tr * 64 + q * 16) << k) + tc * 64 + a : buckets + ((size_t)(tr * 64 + a) << k) + tc * 64 + q;
+  const size_t step = type == 0 ? NC : 4;
+  typename O::P acc = O::inf();
+#pragma unroll 1
+  for (u32 i = 0; i < 16; i++) acc = O::add(acc, O::load(p[i * step]));
+  acc = tail_tree<O>(acc, sh, t, 256, 64);
+  if (t < 64) {
+    if (type == 0) colp[(size_t)tr * NC + tc * 64 + a] = O::store(acc);
+    else rowp[(size_t)(tr * 64 + a) * ntc + tc] = O::store(acc);
+  }
+}
+
+// sums[l] = C_l (l < 2^k), sums[2^k + h] = R_h: workgroup = 32 outputs, lane (a, q) adds the terms q, q + 8, ... of output a
+template <class F>
+__global__ void __launch_bounds__(256) k_msm_rowcol_sums(const Xyzz<F>* __restrict__ colp, const Xyzz<F>* __restrict__ rowp, u32 cr,
+                                                         Xyzz<F>* __restrict__ sums) {
+  typedef TailOps<F> O;
+  __shared__ typename O::P sh[128];
+  const u32 k = (cr + 1) >> 1, NC = 1u << k, NR = 1u << (cr - k), ntc = NC >> 6, ntr = NR >> 6;
+  const u32 t = threadIdx.x, a = t & 31u, q = t >> 5;
+  const u32 o = blockIdx.x * 32 + a;            // 2^k is a multiple of 32: a workgroup is all columns or all rows
+  const bool col = o < NC;
+  const Xyzz<F>* p = col ? colp + o : rowp + (size_t)(o - NC) * ntc;
+  const u32 terms = col ? ntr : ntc;
+  const size_t step = col ? NC : 1;
+  typename O::P acc = O::inf();
+#pragma unroll 1
+  for (u32 i = q; i < terms; i += 8) acc = O::add(acc, O::load(p[i * step]));
+  acc = tail_tree<O>(acc, sh, t, 256, 32);
+  if (t < 32) sums[o] = O::store(acc);
+}
+
+// plane p <= k: the columns whose weight l + 1 has bit p set (p == k: the last column alone), times 2^p; plane k + 1 + j: the rows whose h has
+// bit j set, times 2^(k + j). Lane 0 doubles after the tree: the doublings of the planes run side by side, cr - 1 in series at the most.
+template <class F>
+__global__ void __launch_bounds__(256) k_msm_rowcol_planes(const Xyzz<F>* __restrict__ sums, u32 cr, Xyzz<F>* __restrict__ planes) {
+  typedef TailOps<F> O;
+  __shared__ typename O::P sh[128];
+  const u32 k = (cr + 1) >> 1, NC = 1u << k, NR = 1u << (cr - k);
+  const u32 t = threadIdx.x, pl = blockIdx.x;
+  typename O::P acc = O::inf();
+  u32 nd = k;
+  if (pl == k) {
+    if (t == 0) acc = O::load(sums[NC - 1]);
+  } else {
+    const bool col = pl < k;
+    const u32 j = col ? pl : pl - k - 1, half = (col ? NC : NR) >> 1;
+    const u32 base = col ? 0u : NC + 1u;                    // weight v: column v - 1, row v
+    nd = col ? j : j + k;
+#pragma unroll 1
+    for (u32 m = t; m < half; m += 256) {
+      const u32 v = ((m >> j) << (j + 1)) | (1u << j) | (m & ((1u << j) - 1u));      // the m-th value with bit j set
+      acc = O::add(acc, O::load(sums[base + v - 1u]));
+    }
+  }
+  acc = tail_tree<O>(acc, sh, t, 256, 1);
+  if (t == 0) {
+    for (u32 d = 0; d < nd; d++) acc = O::dbl(acc);
+    planes[pl] = O::store(acc);
+  }
+}
+
+template <class F>
+__global__ void __launch_bounds__(64) k_msm_rowcol_final(const Xyzz<F>* __restrict__ planes, u32 np, F* __restrict__ out_jac) {
+  typedef TailOps<F> O;
+  __shared__ typename O::P sh[32];
+  const u32 t = threadIdx.x;
+  typename O::P acc = O::inf();
+  if (t < np) acc = O::load(planes[t]);
+  acc = tail_tree<O>(acc, sh, t, 64, 1);
+  if (t == 0) store_norm_jac(out_jac, O::store(acc));
+}
+
 // ---- K6b: add the window sums, normalise ------------------------------------------------------------
 template <class F>
 __global__ void __launch_bounds__(64) k_msm_final(const Xyzz<F>* __restrict__ window_sums, u32 W, F* __restrict__ out_jac) {

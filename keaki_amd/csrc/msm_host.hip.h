@@ -28,6 +28,10 @@ inline int choose_window(size_t n, int forced = 0) {
   return bc;
 }
 
+// smallest shared window (buckets) that automatic selection reduces by row and column sums; at least 2^ROWCOL_MIN_CR (one tile)
+constexpr u32 ROWCOL_MIN_B = 1u << 12;
+static_assert(ROWCOL_MIN_B >= (1u << ROWCOL_MIN_CR), "k_msm_rowcol needs one 64 x 64 tile");
+
 // d_table != nullptr: precomputed path (tables built by msm_build_tables with window target c_table for N = srs_len points)
 template <class F>
 keaki_status msm_dev(keaki_hip_ctx* ctx, const Aff<F>* d_points, size_t srs_len, const void* d_scalars, size_t n, void* d_out_jac,
@@ -56,14 +60,20 @@ keaki_status msm_dev(keaki_hip_ctx* ctx, const Aff<F>* d_points, size_t srs_len,
   }
   ctx->last_c = (int)s.c;
   if ((double)n * s.W >= 4294967295.0) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm: n * windows overflows 32-bit positions");
-  // reduce chunk length: the kernel is a serial chain of 2L additions (+ a scalar multiplication by the chunk index) per lane; measured
-  // (bench_tools/sweep_reduce_l.py, round 3, whole MSM with tables): 2^21 buckets (2^23, 2^24 points): 32 -- 9.42 / 17.69 ms against 9.60 /
-  // 17.88 with 16; 2^19 buckets (2^21, 2^22 points): 8 -- 2.92 / 5.31 ms against 2.99 / 5.41; 16 in between; 8 below
+  // bucket reduction. reduce_l == 0 (automatic): one shared window of at least ROWCOL_MIN_B buckets is reduced by row and column sums
+  // (k_msm_rowcol*), everything else by the chunked running sums (k_msm_reduce) with the chunk length L below; reduce_l >= 1 forces the running
+  // sums with that L. A lane of k_msm_reduce is a serial chain of 2 L additions plus a double-and-add by the chunk index (up to 2 log2(B / L)
+  // more), so L trades chain length against the number of lanes; measured (bench_tools/sweep_reduce_l.py, round 3, whole MSM with tables):
+  // 2^21 buckets (2^23, 2^24 points): 32 -- 9.42 / 17.69 ms against 9.60 / 17.88 with 16; 2^19 buckets (2^21, 2^22 points): 8 -- 2.92 /
+  // 5.31 ms against 2.99 / 5.41; 16 in between; 8 below
   // (G2, whose additions cost 2.3 x as much: 8 from 2^19 buckets on as well -- 5.10 vs 5.34 ms at 2^20 points)
   u32 L = sizeof(F) > sizeof(Fq) ? (plan.max_b >= 64 ? 8 : plan.max_b)
                                  : plan.max_b >= (1u << 21) ? 32 : plan.max_b >= (1u << 20) ? 16 : (plan.max_b >= 64 ? 8 : plan.max_b);
   if (ctx->tune.reduce_l >= 1 && ctx->tune.reduce_l <= 4096 && (u32)ctx->tune.reduce_l <= plan.max_b) L = (u32)ctx->tune.reduce_l;
   const u32 chunks = cdiv(plan.max_b, L);
+  const bool rowcol = ctx->tune.reduce_l == 0 && rs.W == 1 && plan.max_b >= ROWCOL_MIN_B;
+  // row / column tail: per-tile sums (2 per 64 buckets), the 2^k + 2^(cr-k) sums, the cr + 1 plane terms
+  const size_t rc_points = rowcol ? (size_t)plan.max_b / 32 + 2 * ((size_t)1 << ((rs.c + 1) / 2)) + 32 : 0;
   ST_TRY(reserve(ctx, ctx->wsums, (size_t)rs.W * sizeof(Xyzz<F>)));
   Xyzz<F>* wsums = (Xyzz<F>*)ctx->wsums.p;
   F* out = (F*)d_out_jac;
@@ -118,7 +128,7 @@ keaki_status msm_dev(keaki_hip_ctx* ctx, const Aff<F>* d_points, size_t srs_len,
   ST_TRY(reserve(ctx, ctx->offsets, w_offsets));
   ST_TRY(reserve(ctx, ctx->cursor, w_cursor));
   ST_TRY(reserve(ctx, ctx->buckets, nb * sizeof(Xyzz<F>)));
-  ST_TRY(reserve(ctx, ctx->partials, ((size_t)rs.W * chunks + (size_t)rs.W * 256) * sizeof(Xyzz<F>)));
+  ST_TRY(reserve(ctx, ctx->partials, std::max((size_t)rs.W * chunks + (size_t)rs.W * 256, rc_points) * sizeof(Xyzz<F>)));
   ST_TRY(reserve(ctx, ctx->perm, nb * 4 + 2 * CNT_BINS * 4 + sizeof(HeavyList)));
   // heavy-bucket list: [bucket[cap] | first[cap] | owner[slice_cap]] then the slice sums
   const u32 hv_cap = (u32)(w_pairs / HEAVY_MIN + 1), hv_slice_cap = (u32)(hv_cap + w_pairs / HEAVY_SLICE + 1);
@@ -238,19 +248,28 @@ keaki_status msm_dev(keaki_hip_ctx* ctx, const Aff<F>* d_points, size_t srs_len,
     ST_TRY(launch_check(ctx, "msm_heavy"));
   }
   if (ctx->timing) (void)hipEventRecord(ctx->ev[2], st);
-  hipLaunchKernelGGL((k_msm_reduce<F>), dim3(cdiv((size_t)rs.W * chunks, 64)), dim3(64), 0, st, (const Xyzz<F>*)buckets, rs, L, chunks, partials);
-  // chunk partials -> (at most 128 per window) -> window sums
-  const Xyzz<F>* fin_in = partials;
-  u32 fin_chunks = chunks;
-  if (chunks > 256) {
-    const u32 G = cdiv(chunks, 128);
-    const u32 chunks2 = cdiv(chunks, G);
-    Xyzz<F>* partials2 = partials + (size_t)rs.W * chunks;
-    hipLaunchKernelGGL((k_msm_partial_groups<F>), dim3(chunks2, rs.W), dim3(64), 0, st, (const Xyzz<F>*)partials, chunks, G, chunks2, partials2);
-    fin_in = partials2; fin_chunks = chunks2;
+  if (rowcol) {
+    const u32 cr = rs.c, kc = (cr + 1) / 2, NC = 1u << kc, NR = 1u << (cr - kc);
+    Xyzz<F>*colp = partials, *rowp = colp + (size_t)(NR / 64) * NC, *sums = rowp + (size_t)NR * (NC / 64), *planes = sums + NC + NR;
+    hipLaunchKernelGGL((k_msm_rowcol<F>), dim3(2u << (cr - 12)), dim3(256), 0, st, (const Xyzz<F>*)buckets, cr, colp, rowp);
+    hipLaunchKernelGGL((k_msm_rowcol_sums<F>), dim3((NC + NR) / 32), dim3(256), 0, st, (const Xyzz<F>*)colp, (const Xyzz<F>*)rowp, cr, sums);
+    hipLaunchKernelGGL((k_msm_rowcol_planes<F>), dim3(cr + 1), dim3(256), 0, st, (const Xyzz<F>*)sums, cr, planes);
+    hipLaunchKernelGGL((k_msm_rowcol_final<F>), dim3(1), dim3(64), 0, st, (const Xyzz<F>*)planes, cr + 1, out);
+  } else {
+    hipLaunchKernelGGL((k_msm_reduce<F>), dim3(cdiv((size_t)rs.W * chunks, 64)), dim3(64), 0, st, (const Xyzz<F>*)buckets, rs, L, chunks, partials);
+    // chunk partials -> (at most 128 per window) -> window sums
+    const Xyzz<F>* fin_in = partials;
+    u32 fin_chunks = chunks;
+    if (chunks > 256) {
+      const u32 G = cdiv(chunks, 128);
+      const u32 chunks2 = cdiv(chunks, G);
+      Xyzz<F>* partials2 = partials + (size_t)rs.W * chunks;
+      hipLaunchKernelGGL((k_msm_partial_groups<F>), dim3(chunks2, rs.W), dim3(64), 0, st, (const Xyzz<F>*)partials, chunks, G, chunks2, partials2);
+      fin_in = partials2; fin_chunks = chunks2;
+    }
+    hipLaunchKernelGGL((k_msm_window_finish<F>), dim3(rs.W), dim3(64), 0, st, fin_in, rs, fin_chunks, wsums, rs.W == 1 ? out : (F*)nullptr);
+    if (rs.W != 1) hipLaunchKernelGGL((k_msm_final<F>), dim3(1), dim3(64), 0, st, (const Xyzz<F>*)wsums, rs.W, out);
   }
-  hipLaunchKernelGGL((k_msm_window_finish<F>), dim3(rs.W), dim3(64), 0, st, fin_in, rs, fin_chunks, wsums, rs.W == 1 ? out : (F*)nullptr);
-  if (rs.W != 1) hipLaunchKernelGGL((k_msm_final<F>), dim3(1), dim3(64), 0, st, (const Xyzz<F>*)wsums, rs.W, out);
   ST_TRY(launch_check(ctx, "msm_reduce/final"));
   if (ctx->timing) {
     (void)hipEventRecord(ctx->ev[3], st);
