@@ -445,7 +445,8 @@ float keaki_hip_last_msm_total_ms(const keaki_hip_ctx* ctx);
 /* device time (ms) of the last keaki_hip_open_fk[_poly] call made while timing was enabled: out3 = [the 2d pointwise scalar-mults, the butterfly
  * stages of the two size-d group transforms (the dominant kernel k_g1_fft_stage_map), the whole device pipeline]; < 0 when there was none */
 keaki_status keaki_hip_last_fk_ms(keaki_hip_ctx* ctx, float* out3);
-/* window size (bits) the last MSM used */
+/* window size (bits) the last MSM used. An MSM over n = 0 terms uses none and measures nothing: after it, this and the two times above are
+ * still those of the last non-empty MSM (also when that one was still queued in front of the empty call). */
 int32_t keaki_hip_last_msm_window_bits(const keaki_hip_ctx* ctx);
 
 /* Test hook: final exponentiation alone. f_mont: n x 12 Fq (Montgomery limbs, order c0.c0.c0 ... c1.c2.c1), the output of a

@@ -58,7 +58,6 @@ keaki_status msm_dev(keaki_hip_ctx* ctx, const Aff<F>* d_points, size_t srs_len,
     d_points = d_table;
     if ((double)srs_len * s.W >= 2147483647.0) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm: precomputed table index overflows 31 bits");
   }
-  ctx->last_c = (int)s.c;
   if ((double)n * s.W >= 4294967295.0) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm: n * windows overflows 32-bit positions");
   // bucket reduction. reduce_l == 0 (automatic): one shared window of at least ROWCOL_MIN_B buckets is reduced by row and column sums
   // (k_msm_rowcol*), everything else by the chunked running sums (k_msm_reduce) with the chunk length L below; reduce_l >= 1 forces the running
@@ -78,11 +77,14 @@ keaki_status msm_dev(keaki_hip_ctx* ctx, const Aff<F>* d_points, size_t srs_len,
   Xyzz<F>* wsums = (Xyzz<F>*)ctx->wsums.p;
   F* out = (F*)d_out_jac;
   hipStream_t st = ctx->stream;
-  if (ctx->timing) (void)hipEventRecord(ctx->ev[0], st);
   if (n == 0) {
+    // an empty MSM runs no window and no bucket kernel: the instrumentation (window bits, the four timing events, of which this call would
+    // record the first only) stays that of the last non-empty call, also when that call is still queued in front of this one
     hipLaunchKernelGGL((k_msm_final<F>), dim3(1), dim3(64), 0, st, (const Xyzz<F>*)wsums, 0u, out);
     return launch_check(ctx, "msm_final");
   }
+  ctx->last_c = (int)s.c;
+  if (ctx->timing) (void)hipEventRecord(ctx->ev[0], st);
   // ---- the passes: one for a resident scalar vector, one per chunk of a pipelined call ----------------------------------------------
   const size_t K = pipe ? pipe->ranges.size() : 1;
   if (pipe && K < 1) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm: bad chunk bounds");

@@ -34,6 +34,9 @@ EXPORTS = [
 ]
 
 KEAKI_ERR_TOO_LARGE = -5
+# the `stream` argument of keaki_hip_ctx_create (include/keaki_hip.h): the context's own non-blocking stream | the device's legacy default stream
+KEAKI_HIP_STREAM_PRIVATE = None
+KEAKI_HIP_STREAM_LEGACY = 1
 
 
 class KeakiHipError(RuntimeError):
@@ -235,7 +238,7 @@ class FkShardHandle:
 class KeakiHip:
     """One context = one GPU (one process per GPU in multi-GPU runs)."""
 
-    STREAM_LEGACY = 1          # KEAKI_HIP_STREAM_LEGACY: the device's legacy default stream (torch's default stream has handle 0 = this one)
+    STREAM_LEGACY = KEAKI_HIP_STREAM_LEGACY          # the device's legacy default stream (torch's default stream has handle 0 = this one)
 
     def __init__(self, device: int = 0, stream: int | None = None):
         """stream: None -> private non-blocking stream (order *_dev calls with synchronize()); 0 or STREAM_LEGACY -> the legacy default
@@ -602,6 +605,16 @@ class KeakiHip:
     def encap_batch_dev(self, d_com, d_tau, d_points, d_values, d_r, n, d_ct, d_gt, d_key, msg_len):
         v = lambda x: C.c_void_p(x) if x else None
         self._ck(self.lib.keaki_hip_encap_batch_dev(self.ctx, v(d_com), v(d_tau), v(d_points), v(d_values), v(d_r), n, v(d_ct), v(d_gt), v(d_key), msg_len))
+
+    def encrypt_batch_dev(self, d_com, d_tau, d_points, d_values, d_r, n, d_ct, d_body_inout, msg_len):
+        """d_body_inout: n x msg_len bytes of device memory, the messages on entry and the ciphertext bodies on exit"""
+        v = lambda x: C.c_void_p(x) if x else None
+        self._ck(self.lib.keaki_hip_encrypt_batch_dev(self.ctx, v(d_com), v(d_tau), v(d_points), v(d_values), v(d_r), n, v(d_ct), v(d_body_inout), msg_len))
+
+    def decrypt_batch_dev(self, d_proofs, d_cts, n, d_body_inout, msg_len):
+        """d_body_inout: the ciphertext bodies on entry and the messages on exit"""
+        v = lambda x: C.c_void_p(x) if x else None
+        self._ck(self.lib.keaki_hip_decrypt_batch_dev(self.ctx, v(d_proofs), v(d_cts), n, v(d_body_inout), msg_len))
 
     def decap_batch(self, proofs, cts, msg_len: int = 32):
         p = _np(proofs, 8); c = _np(cts, 16); n = p.shape[0]
