@@ -238,6 +238,37 @@ keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs,
 keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* point, uint64_t* quotient_out,
                                     uint64_t* value_out);
 
+/* ---- batched commit and open: m polynomials over ONE SRS in one call ---------------------------------------------------------------------
+ * Generalises `commit` (reference src/kzg.rs:89-101) and `open` (src/kzg.rs:104-124) from one polynomial to m rows. A single MSM costs
+ * 0.4 .. 2.3 ms of launch latency whatever its length; m short rows in one call pay that floor once.
+ *   layout     row j is n Fr at scalars + 4 * stride * j (64-bit words), stride >= n in Fr units; the gap between rows is never read.
+ *              out_jac / proofs_out_jac: m x u64[12] normalised Jacobian; points: m Fr (z_j); values_out: m Fr or NULL.
+ *   lengths    rows of unequal length are padded with zero coefficients up to n: a zero scalar contributes nothing to the sum, which is what
+ *              the trimming of ark-poly's DensePolynomial means. For open_batch every row has length n after padding, the quotient n - 1
+ *              terms; the trailing zero terms of a shorter row's quotient are harmless, value and proof are those of the trimmed polynomial.
+ *   results    out[j] is byte for byte what keaki_hip_msm_g1 returns for row j alone, (proofs[j], values[j]) what keaki_hip_kzg_open returns
+ *              for (row j, points[j]) -- on a handle with window tables and on one without, and whichever route the call takes: rows of up to
+ *              16,384 coefficients (N_BATCH_MAX) run the batch kernels, which read the SRS points only; longer rows, and calls whose
+ *              workspace the device (or keaki_hip_debug_set_alloc_limit) refuses, run the single-MSM pipeline row by row.
+ *   errors     n > len(srs) (open_batch: n - 1 > len(srs)) -> KEAKI_ERR_TOO_LARGE (the caller raises PolynomialTooLarge first, src/kzg.rs:93-95,
+ *              :113-118). A null pointer, stride < n, m * n >= 2^31 -> KEAKI_ERR_BAD_ARG. m = 0 writes nothing and returns KEAKI_OK (only srs,
+ *              stride and the product are looked at). n = 0 writes m identities (R, R, 0), open_batch also m zero values.
+ *   host form  one upload of the rows in front (the span from row 0 to the end of row m - 1), the kernels, one download of m x 96 B (open_batch:
+ *              + m x 32 B): no chunk pipeline, the copy stream and the helper threads of the long single calls are not used.
+ *   _dev       every array is a device pointer (16-byte aligned); asynchronous on the ctx stream like keaki_hip_msm_g1_dev.
+ *   context    the ctx lock is held for the call and the caller's current device is put back. Workspace: 32 B per scalar of a pass (at most
+ *              256 MB unless one row is longer) + 128 B per row and window (open_batch: + the quotient rows), grow-only, counted in
+ *              keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim.
+ *   After a batch call the values of keaki_hip_last_msm_bucket_ms / _total_ms / _window_bits are unspecified. */
+keaki_status keaki_hip_msm_g1_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* scalars, size_t n, size_t m, size_t stride,
+                                    uint64_t* out_jac);          /* m x commit's MSM, src/kzg.rs:89-101 (:98) */
+keaki_status keaki_hip_msm_g1_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_scalars, size_t n, size_t m, size_t stride,
+                                        void* d_out_jac);        /* src/kzg.rs:89-101, device-resident rows */
+keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, size_t m, size_t stride,
+                                      const uint64_t* points, uint64_t* proofs_out_jac, uint64_t* values_out);    /* m x open, src/kzg.rs:104-124 */
+keaki_status keaki_hip_kzg_open_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, size_t m, size_t stride,
+                                          const void* d_points, void* d_proofs_out_jac, void* d_values_out);      /* src/kzg.rs:104-124, device-resident */
+
 /* ---- KZG `verify` in one call -------------------------------------------------------------------------------------
  * Replaces the body of `verify` (reference src/kzg.rs:127-146): e(com - value g1, g2) == e(proof, [tau]_2 - point g2).
  * Evaluated exactly in that form: the two inner points are fixed-base sums over 8-bit window tables of g1 and g2 (built at the first

@@ -571,7 +571,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v;
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums, &ctx->bsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->verify_io, &ctx->vb_io, &ctx->vb_s, &ctx->g2gen_lines, &ctx->fk_tab, &ctx->g2pow_lines, &ctx->g2pow_pts})
+                    &ctx->pair_ws, &ctx->verify_io, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->g2gen_lines, &ctx->fk_tab, &ctx->g2pow_lines, &ctx->g2pow_pts})
     v.push_back({b, 1});
   for (DevBuf* b : {&ctx->fb_bases, &ctx->fb_g1_gen, &ctx->fb_g2_gen, &ctx->fb_com, &ctx->fb_tau, &ctx->gt_tab_a, &ctx->gt_tab_b, &ctx->gt_base,
                     &ctx->fbs_g2_gen, &ctx->fbs_tau, &ctx->fbs_g1_gen})
@@ -1593,6 +1593,116 @@ keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, 
   if (value_out) HIP_TRY(ctx, hipMemcpyAsync(value_out, b + o_v, 32, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return KEAKI_OK;
+}
+
+// ---- batched commit / open: m rows over one SRS in one call (msm_batch.hip) ---------------------------------------------------------------
+extern "C++" {
+namespace {
+// the argument rules the four batch entries share; *empty: m = 0, nothing to do
+keaki_status batch_args(keaki_hip_ctx* ctx, const char* what, const void* srs, size_t n, size_t m, size_t stride, bool* empty) {
+  *empty = false;
+  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: srs is null", what);
+  if (stride < n) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: stride %zu is shorter than a row of %zu", what, stride, n);
+  if (n && m >= ((size_t)1 << 31) / n + (((size_t)1 << 31) % n ? 1 : 0)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: m * n must be < 2^31", what);
+  if (m >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: m must be < 2^31", what);
+  *empty = m == 0;
+  return KEAKI_OK;
+}
+// a failing host-form call, too, returns only when no copy reads the caller's arrays any more
+struct StreamFence { hipStream_t s; bool armed; ~StreamFence() { if (armed) (void)hipStreamSynchronize(s); } };
+inline size_t batch_span(size_t n, size_t m, size_t stride) { return n && m ? ((m - 1) * stride + n) * 32 : 0; }   // bytes from row 0 to the end of row m - 1
+
+keaki_status open_batch_core(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, size_t m, size_t stride, const void* d_points,
+                             void* d_proofs_out_jac, void* d_values_out) {
+  const size_t nq = n ? n - 1 : 0;
+  if (nq > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", nq, srs->n);
+  if (n == 0 && d_values_out) HIP_TRY(ctx, hipMemsetAsync(d_values_out, 0, m * 32, ctx->stream));      // the zero polynomial evaluates to 0
+  const auto tb = srs_tables(srs);
+  if (nq == 0) {
+    ST_TRY(fr_quotient_batch_run(ctx, d_coeffs, n, m, stride, d_points, nullptr, 0, d_values_out));
+    return msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, nullptr, 0, m, 0, d_proofs_out_jac);
+  }
+  // the quotient rows live in a workspace, as many rows at a time as it can hold: a refused reservation halves the rows; one row is what
+  // keaki_hip_kzg_open itself needs
+  size_t rows = std::min(m, std::max<size_t>(1, MSM_BATCH_CANON_BYTES / (nq * 32)));
+  for (;;) {
+    const keaki_status st = reserve(ctx, ctx->mb_q, rows * nq * 32);
+    if (st == KEAKI_OK) break;
+    if (st != KEAKI_ERR_OOM || rows == 1) return st;
+    ctx->err.clear();
+    rows = (rows + 1) / 2;
+  }
+  for (size_t r0 = 0; r0 < m; r0 += rows) {
+    const size_t k = std::min(rows, m - r0);
+    ST_TRY(fr_quotient_batch_run(ctx, (const char*)d_coeffs + r0 * stride * 32, n, k, stride, (const char*)d_points + r0 * 32, ctx->mb_q.p, nq,
+                                 d_values_out ? (char*)d_values_out + r0 * 32 : nullptr));
+    ST_TRY(msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, ctx->mb_q.p, nq, k, nq, (char*)d_proofs_out_jac + r0 * G1_JAC_BYTES));
+  }
+  return KEAKI_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_msm_g1_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_scalars, size_t n, size_t m, size_t stride,
+                                        void* d_out_jac) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.msm_g1_batch");
+  bool empty;
+  ST_TRY(batch_args(ctx, "msm_g1_batch", srs, n, m, stride, &empty));
+  if (empty) return KEAKI_OK;
+  SRS_CHECK(ctx, srs, "msm_g1_batch");
+  if (!d_out_jac || (n && !d_scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g1_batch: null pointer");
+  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
+  const auto tb = srs_tables(srs);
+  return msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, d_scalars, n, m, stride, d_out_jac);
+}
+keaki_status keaki_hip_msm_g1_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* scalars, size_t n, size_t m, size_t stride,
+                                    uint64_t* out_jac) {
+  CTX_GUARD(ctx);
+  bool empty;
+  ST_TRY(batch_args(ctx, "msm_g1_batch", srs, n, m, stride, &empty));
+  if (empty) return KEAKI_OK;
+  if (!out_jac || (n && !scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g1_batch: null pointer");
+  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
+  // one upload in front, the kernels, one download of m x 96 B: the rows are short, there is nothing for a chunk pipeline to hide
+  ST_TRY(reserve(ctx, ctx->io_b, m * G1_JAC_BYTES));
+  ST_TRY(upload(ctx, ctx->io_a, scalars, batch_span(n, m, stride)));
+  StreamFence fence{ctx->stream, true};
+  ST_TRY(keaki_hip_msm_g1_batch_dev(ctx, srs, ctx->io_a.p, n, m, stride, ctx->io_b.p));
+  prefault_out(ctx, out_jac, m * G1_JAC_BYTES);
+  fence.armed = false;
+  return download(ctx, out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
+}
+keaki_status keaki_hip_kzg_open_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, size_t m, size_t stride,
+                                          const void* d_points, void* d_proofs_out_jac, void* d_values_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_open_batch");
+  bool empty;
+  ST_TRY(batch_args(ctx, "kzg_open_batch", srs, n, m, stride, &empty));
+  if (empty) return KEAKI_OK;
+  SRS_CHECK(ctx, srs, "kzg_open_batch");
+  if (!d_points || !d_proofs_out_jac || (n && !d_coeffs)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_open_batch: null pointer");
+  return open_batch_core(ctx, srs, d_coeffs, n, m, stride, d_points, d_proofs_out_jac, d_values_out);
+}
+keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, size_t m, size_t stride,
+                                      const uint64_t* points, uint64_t* proofs_out_jac, uint64_t* values_out) {
+  CTX_GUARD(ctx);
+  bool empty;
+  ST_TRY(batch_args(ctx, "kzg_open_batch", srs, n, m, stride, &empty));
+  if (empty) return KEAKI_OK;
+  if (!points || !proofs_out_jac || (n && !coeffs)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_open_batch: null pointer");
+  if (n && n - 1 > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n - 1, srs->n);
+  ST_TRY(reserve(ctx, ctx->io_b, m * G1_JAC_BYTES));
+  ST_TRY(reserve(ctx, ctx->io_d, m * 32));
+  ST_TRY(reserve(ctx, ctx->io_a, std::max<size_t>(16, batch_span(n, m, stride))));
+  ST_TRY(reserve(ctx, ctx->io_c, m * 32));
+  StreamFence fence{ctx->stream, true};
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, coeffs, batch_span(n, m, stride), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_c.p, points, m * 32, hipMemcpyHostToDevice, ctx->stream));
+  ST_TRY(keaki_hip_kzg_open_batch_dev(ctx, srs, ctx->io_a.p, n, m, stride, ctx->io_c.p, ctx->io_b.p, ctx->io_d.p));
+  if (values_out) HIP_TRY(ctx, hipMemcpyAsync(values_out, ctx->io_d.p, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+  fence.armed = false;
+  return download(ctx, proofs_out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
 }
 
 // ---- KZG verify -----------------------------------------------------------------------------------------------------

@@ -97,6 +97,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf pair_ws;                   // per-item slots of the final exponentiation (pairing.hip.h)
   keaki_internal::DevBuf fk_tab;                    // window tables of the per-lane-scalar ladders of FK23: 1 KB per lane of a launch (64 x 16 B), at most 2 GB (fft_g1.hip)
   keaki_internal::DevBuf verify_io;                 // kzg verify: small in/out block
+  keaki_internal::DevBuf mb_canon, mb_wsums, mb_q;  // batched MSM / open (msm_batch.hip): biased canonical scalars of a pass (32 B each) | window sums (128 B per row and window) | quotient rows of open_batch
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
   bool verify_ready = false;
   bool verify_tables_ready = false;       // 8-bit window tables of g1 (fbs_g1_gen) and g2 (fbs_g2_gen) for the reference-form verify              // set only after every init step of kzg verify succeeded
@@ -261,6 +262,17 @@ keaki_status point_compress_run(keaki_hip_ctx* ctx, bool g2, const void* d_pts, 
 keaki_status point_decompress_run(keaki_hip_ctx* ctx, bool g2, const void* d_bytes, size_t n, uint64_t base, void* d_out, void* d_status, void* d_bad2);
 // psi(Q) == [6 z^2]Q per point; an outsider gets status 3 (d_status given) and, with `clear`, all-zero words in place
 keaki_status g2_subgroup_run(keaki_hip_ctx* ctx, void* d_pts, size_t n, uint64_t base, void* d_status, bool clear, void* d_bad2);
+// batched small MSM and batched quotient (msm_batch.hip). Rows of n <= N_BATCH_MAX scalars run the batch kernels, msm_batch_rows_per_pass rows
+// at a time (workspace: 32 B per scalar of a pass, at most MSM_BATCH_CANON_BYTES unless one row is longer, + 128 B per row and window); longer rows, and
+// calls whose workspace is refused with KEAKI_ERR_OOM, run msm_g1_run row by row. d_out_jac: m x 96 B. Asynchronous on ctx->stream.
+constexpr size_t N_BATCH_MAX = 16384, MSM_BATCH_CANON_BYTES = (size_t)1 << 28, MSM_BATCH_ROWS_MAX = 16384;
+int msm_batch_window(size_t n);                          // window bits c of the batch plan msm_make_plan(n, c): 4 .. 9
+size_t msm_batch_rows_per_pass(size_t n, size_t m);      // n >= 1
+keaki_status msm_g1_batch_run(keaki_hip_ctx* ctx, const void* d_points, size_t srs_len, const void* d_table, int c_table, const void* d_scalars, size_t n,
+                              size_t m, size_t stride, void* d_out_jac);
+// row j < m: d_q[j * qstride + i - 1] = Q_i (1 <= i < n), d_values[j] = Q_0 (d_values may be null) for Q_i = c_i + z_j Q_(i+1) over row j of d_coeffs
+keaki_status fr_quotient_batch_run(keaki_hip_ctx* ctx, const void* d_coeffs, size_t n, size_t m, size_t stride, const void* d_points, void* d_q, size_t qstride,
+                                   void* d_values);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 

@@ -19,6 +19,7 @@ EXPORTS = [
     "keaki_hip_srs_g1_upload", "keaki_hip_srs_g1_wrap_dev", "keaki_hip_srs_g1_slice", "keaki_hip_srs_g1_len", "keaki_hip_srs_g1_precompute", "keaki_hip_srs_g1_free",
     "keaki_hip_srs_g2_upload", "keaki_hip_srs_g2_wrap_dev", "keaki_hip_srs_g2_precompute", "keaki_hip_srs_g2_free",
     "keaki_hip_msm_g1", "keaki_hip_msm_g1_dev", "keaki_hip_msm_g2", "keaki_hip_msm_g2_dev",
+    "keaki_hip_msm_g1_batch", "keaki_hip_msm_g1_batch_dev", "keaki_hip_kzg_open_batch", "keaki_hip_kzg_open_batch_dev",
     "keaki_hip_g1_sum_dev", "keaki_hip_g1_sum",
     "keaki_hip_g1_mul_batch", "keaki_hip_g2_mul_batch", "keaki_hip_g1_mul_batch_dev", "keaki_hip_g2_mul_batch_dev",
     "keaki_hip_pairing_batch", "keaki_hip_pairing_batch_dev",
@@ -156,6 +157,10 @@ def load_library():
         lib.keaki_hip_ctx_device.argtypes = [vp]
         lib.keaki_hip_ctx_device.restype = C.c_int32
         lib.keaki_hip_kzg_quotient.argtypes = [vp, vp, sz, vp, vp, vp]
+        lib.keaki_hip_msm_g1_batch.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+        lib.keaki_hip_msm_g1_batch_dev.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+        lib.keaki_hip_kzg_open_batch.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
+        lib.keaki_hip_kzg_open_batch_dev.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
         lib.keaki_hip_encap_prepare.argtypes = [vp, vp, sz]
         lib.keaki_hip_vec_commit.argtypes = [vp, vp, vp, sz, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         lib.keaki_hip_group_create.argtypes = [C.POINTER(i32), sz, C.POINTER(vp)]
@@ -371,6 +376,39 @@ class KeakiHip:
 
     def msm_g1_dev(self, srs: SrsG1, d_scalars: int, n: int, d_out: int):
         self._ck(self.lib.keaki_hip_msm_g1_dev(self.ctx, srs.handle, C.c_void_p(d_scalars), n, C.c_void_p(d_out)))
+
+    def msm_g1_batch(self, srs: SrsG1, rows, n: int = None) -> np.ndarray:
+        """m MSMs over one SRS in one call (keaki_hip_msm_g1_batch). rows: (m, stride, 4) Montgomery Fr; the first n (default: stride) scalars
+        of every row count, the rest of a row is never read -> (m, 12) normalised Jacobian"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r = r if r.ndim == 3 else r.reshape(r.shape[0], -1, 4)
+        m, stride = r.shape[0], r.shape[1]
+        n = stride if n is None else int(n)
+        out = np.zeros((m, 12), np.uint64)
+        self._ck(self.lib.keaki_hip_msm_g1_batch(self.ctx, srs.handle, _ptr(r) if r.size else None, n, m, stride, _ptr(out) if m else None))
+        return out
+
+    def msm_g1_batch_dev(self, srs: SrsG1, d_rows: int, n: int, m: int, stride: int, d_out: int):
+        self._ck(self.lib.keaki_hip_msm_g1_batch_dev(self.ctx, srs.handle, C.c_void_p(d_rows), n, m, stride, C.c_void_p(d_out)))
+
+    def kzg_open_batch(self, srs: SrsG1, rows, points, n: int = None):
+        """m openings in one call (keaki_hip_kzg_open_batch): row j (the first n coefficients of it, low degree first, zero-padded) is opened at
+        points[j] -> (proofs (m, 12) normalised Jacobian, values (m, 4))"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r = r if r.ndim == 3 else r.reshape(r.shape[0], -1, 4)
+        m, stride = r.shape[0], r.shape[1]
+        n = stride if n is None else int(n)
+        z = _np(points, 4)
+        if z.shape[0] != m:
+            raise ValueError("kzg_open_batch: one point per row")
+        out = np.zeros((m, 12), np.uint64); val = np.zeros((m, 4), np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_open_batch(self.ctx, srs.handle, _ptr(r) if r.size else None, n, m, stride, _ptr(z) if m else None,
+                                                   _ptr(out) if m else None, _ptr(val) if m else None))
+        return out, val
+
+    def kzg_open_batch_dev(self, srs: SrsG1, d_rows: int, n: int, m: int, stride: int, d_points: int, d_proofs: int, d_values: int):
+        self._ck(self.lib.keaki_hip_kzg_open_batch_dev(self.ctx, srs.handle, C.c_void_p(d_rows), n, m, stride, C.c_void_p(d_points), C.c_void_p(d_proofs),
+                                                       C.c_void_p(d_values) if d_values else None))
 
     def msm_g2(self, srs: SrsG2, scalars) -> np.ndarray:
         sc = _np(scalars, 4); out = np.zeros(24, np.uint64)

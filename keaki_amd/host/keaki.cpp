@@ -250,6 +250,58 @@ Result<G1> open(const KZGSetup& setup, const DensePolynomial& p_in, const Fr& po
   return Result<G1>::Ok(jac_to_g1(jac));
 }
 
+// rows zero-padded to n coefficients each, as the batch entries read them (stride = n)
+static std::vector<uint64_t> pack_rows(const std::vector<DensePolynomial>& polys, size_t n) {
+  std::vector<uint64_t> rows(polys.size() * n * 4 + 4, 0);
+  for (size_t j = 0; j < polys.size(); j++)
+    for (size_t i = 0; i < polys[j].size() && i < n; i++) memcpy(&rows[(j * n + i) * 4], polys[j][i].l, 32);
+  return rows;
+}
+
+Result<std::vector<G1>> commit_batch(const KZGSetup& setup, const std::vector<DensePolynomial>& polys) {
+  typedef Result<std::vector<G1>> Res;
+  const size_t m = polys.size(), len = setup.g1_pow().size();
+  size_t n = 0;
+  for (const DensePolynomial& p : polys) {
+    if (p.size() > len) return Res::Err(KZGError{KZGError::PolynomialTooLarge, p.size(), len});
+    n = std::max(n, p.size());
+  }
+  std::vector<G1> out(m);
+  if (m < COMMIT_BATCH_MIN || setup.group_srs()) {
+    for (size_t j = 0; j < m; j++) out[j] = commit(setup, polys[j]).value;
+    return Res::Ok(std::move(out));
+  }
+  const std::vector<uint64_t> rows = pack_rows(polys, n);
+  std::vector<uint64_t> jac(m * 12);
+  setup.device()->check(keaki_hip_msm_g1_batch(setup.device()->ctx(), setup.srs(), rows.data(), n, m, n, jac.data()));
+  for (size_t j = 0; j < m; j++) out[j] = jac_to_g1(&jac[12 * j]);
+  return Res::Ok(std::move(out));
+}
+
+Result<std::vector<G1>> open_batch(const KZGSetup& setup, const std::vector<DensePolynomial>& polys_in, const std::vector<Fr>& points) {
+  typedef Result<std::vector<G1>> Res;
+  if (points.size() != polys_in.size()) throw std::invalid_argument("open_batch: one point per polynomial");
+  std::vector<DensePolynomial> polys = polys_in;
+  const size_t m = polys.size(), len = setup.g1_pow().size();
+  size_t n = 0;
+  for (DensePolynomial& p : polys) {
+    trim(p);
+    const size_t qlen = p.size() > 1 ? p.size() - 1 : 0;
+    if (qlen > len) return Res::Err(KZGError{KZGError::PolynomialTooLarge, qlen, len});
+    n = std::max(n, p.size());
+  }
+  std::vector<G1> out(m);
+  if (m < COMMIT_BATCH_MIN || setup.group_srs()) {
+    for (size_t j = 0; j < m; j++) out[j] = open(setup, polys[j], points[j]).value;
+    return Res::Ok(std::move(out));
+  }
+  const std::vector<uint64_t> rows = pack_rows(polys, n);
+  std::vector<uint64_t> jac(m * 12);
+  setup.device()->check(keaki_hip_kzg_open_batch(setup.device()->ctx(), setup.srs(), rows.data(), n, m, n, points[0].l, jac.data(), nullptr));
+  for (size_t j = 0; j < m; j++) out[j] = jac_to_g1(&jac[12 * j]);
+  return Res::Ok(std::move(out));
+}
+
 Result<bool> verify(const KZGSetup& setup, const G1& commitment, const Fr& point, const Fr& value, const G1& proof) {
   // src/kzg.rs:127-146, evaluated on the device in the same form (include/keaki_hip.h)
   const Device& dev = *setup.device();

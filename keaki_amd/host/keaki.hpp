@@ -162,6 +162,13 @@ class KZGSetup {
 Result<G1> commit(const KZGSetup& setup, const DensePolynomial& p);                          // src/kzg.rs:89-101
 Result<G1> open(const KZGSetup& setup, const DensePolynomial& p, const Fr& point);           // src/kzg.rs:104-124
 Result<bool> verify(const KZGSetup& setup, const G1& commitment, const Fr& point, const Fr& value, const G1& proof);  // :127-151
+// m polynomials over one setup in ONE device call each (no counterpart in the reference; generalise commit, :89-101, and open, :104-124):
+// keaki_hip_msm_g1_batch / keaki_hip_kzg_open_batch with the rows zero-padded to the longest polynomial (a zero coefficient contributes nothing,
+// which is what DensePolynomial's trimming means). PolynomialTooLarge is raised first, for the first polynomial that is too long, as commit /
+// open raise it. Results equal the loop over commit / open; below COMMIT_BATCH_MIN polynomials, and on a device group, that loop is what runs.
+constexpr size_t COMMIT_BATCH_MIN = 5;      // a batch call costs 1.8-2.5 ms up to m = 16 (profiles/msm_batch.txt), a single commit through the window tables a setup builds 0.4-0.7 ms
+Result<std::vector<G1>> commit_batch(const KZGSetup& setup, const std::vector<DensePolynomial>& polys);
+Result<std::vector<G1>> open_batch(const KZGSetup& setup, const std::vector<DensePolynomial>& polys, const std::vector<Fr>& points);
 // n openings at once (no counterpart in the reference; generalises :127-148): draws one gamma_i = Fr::rand per item from `rng` in index order
 // and checks e(L, g2) == e(R, [tau]_2) for L = sum gamma_i C_i - (sum gamma_i y_i) g1 + sum (gamma_i z_i) proof_i, R = sum gamma_i proof_i
 // in ONE device call (keaki_hip_kzg_verify_batch: two or three MSMs and two pairings whatever n is). All openings valid: always true. One

@@ -223,6 +223,31 @@ int keaki_host_open(void* s, const uint64_t* coeffs, size_t n, const uint64_t* p
     memcpy(out_g1, r.value.w.data(), 64); return 0;
   });
 }
+// m rows of n coefficients at coeffs + 4 * stride * j words (zero-padded rows: trailing zeros are not part of a polynomial); out_g1: m affine points
+static std::vector<DensePolynomial> rows_of(const uint64_t* coeffs, size_t n, size_t m, size_t stride) {
+  std::vector<DensePolynomial> polys(m);
+  for (size_t j = 0; j < m; j++) polys[j] = frs_of(coeffs + 4 * stride * j, n);
+  return polys;
+}
+int keaki_host_commit_batch(void* s, const uint64_t* coeffs, size_t n, size_t m, size_t stride, uint64_t* out_g1, uint64_t* err_out) {
+  return guard([&] {
+    auto r = kzg::commit_batch(((Setup*)s)->s, rows_of(coeffs, n, m, stride));
+    if (!r.ok) return kzg_err(r.error, err_out);
+    for (size_t j = 0; j < m; j++) memcpy(out_g1 + 8 * j, r.value[j].w.data(), 64);
+    return 0;
+  });
+}
+int keaki_host_open_batch(void* s, const uint64_t* coeffs, size_t n, size_t m, size_t stride, const uint64_t* points, uint64_t* out_g1, uint64_t* err_out) {
+  return guard([&] {
+    std::vector<Fr> z(m);
+    for (size_t j = 0; j < m; j++) z[j] = fr_of(points + 4 * j);
+    auto r = kzg::open_batch(((Setup*)s)->s, rows_of(coeffs, n, m, stride), z);
+    if (!r.ok) return kzg_err(r.error, err_out);
+    for (size_t j = 0; j < m; j++) memcpy(out_g1 + 8 * j, r.value[j].w.data(), 64);
+    return 0;
+  });
+}
+int keaki_host_commit_batch_min(void) { return (int)kzg::COMMIT_BATCH_MIN; }
 int keaki_host_verify(void* s, const uint64_t* com, const uint64_t* point, const uint64_t* value, const uint64_t* proof, int* out_ok) {
   return guard([&] {
     auto r = kzg::verify(((Setup*)s)->s, g1_of(com), fr_of(point), fr_of(value), g1_of(proof));

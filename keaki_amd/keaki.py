@@ -321,6 +321,44 @@ def open(setup: KZGSetup, p, point) -> np.ndarray:  # noqa: A001 (mirrors kzg::o
     return out
 
 
+def commit_batch_min() -> int:
+    """kzg::COMMIT_BATCH_MIN: from this many polynomials on commit_batch / open_batch make ONE device call; below it they loop over commit / open"""
+    return int(_lib().keaki_host_commit_batch_min())
+
+
+def commit_batch(setup: KZGSetup, polys) -> np.ndarray:
+    """m commitments over one setup (kzg::commit_batch). polys: (m, n, 4) zero-padded rows, or a list of polynomials of any lengths -> (m, 8)"""
+    rows = _rows(polys)
+    m, n = rows.shape[0], rows.shape[1]
+    out = np.zeros((m, 8), np.uint64); err = np.zeros(2, np.uint64)
+    _ck(_lib().keaki_host_commit_batch(setup.h, _p(rows), C.c_size_t(n), C.c_size_t(m), C.c_size_t(n), _p(out), _p(err)), err)
+    return out
+
+
+def open_batch(setup: KZGSetup, polys, points) -> np.ndarray:
+    """m opening proofs (kzg::open_batch): polynomial j at points[j] -> (m, 8)"""
+    rows = _rows(polys)
+    m, n = rows.shape[0], rows.shape[1]
+    z = _u64(points, 4)
+    if z.shape[0] != m:
+        raise ValueError("open_batch: one point per polynomial")
+    out = np.zeros((m, 8), np.uint64); err = np.zeros(2, np.uint64)
+    _ck(_lib().keaki_host_open_batch(setup.h, _p(rows), C.c_size_t(n), C.c_size_t(m), C.c_size_t(n), _p(z), _p(out), _p(err)), err)
+    return out
+
+
+def _rows(polys) -> np.ndarray:
+    """(m, n, 4) rows, zero-padded to the longest polynomial"""
+    if isinstance(polys, np.ndarray) and polys.ndim == 3:
+        return np.ascontiguousarray(polys, dtype=np.uint64)
+    ps = [_u64(p, 4) for p in polys]
+    n = max([p.shape[0] for p in ps], default=0)
+    rows = np.zeros((len(ps), n, 4), np.uint64)
+    for j, p in enumerate(ps):
+        rows[j, :p.shape[0]] = p
+    return rows
+
+
 def verify(setup: KZGSetup, commitment, point, value, proof) -> bool:
     ok = C.c_int(0)
     _ck(_lib().keaki_host_verify(setup.h, _p(_u64(commitment)), _p(_u64(point)), _p(_u64(value)), _p(_u64(proof)), C.byref(ok)))

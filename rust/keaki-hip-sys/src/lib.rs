@@ -115,6 +115,15 @@ extern "C" {
                               proof_out_jac: *mut u64, value_out: *mut u64) -> keaki_status;
     pub fn keaki_hip_kzg_quotient(ctx: *mut keaki_hip_ctx, coeffs: *const u64, n: usize, point: *const u64, quotient_out: *mut u64,
                                   value_out: *mut u64) -> keaki_status;
+    // m rows over one SRS in one call (generalises commit, src/kzg.rs:89-101, and open, src/kzg.rs:104-124): row j = n Fr at + 4 * stride * j words
+    pub fn keaki_hip_msm_g1_batch(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, scalars: *const u64, n: usize, m: usize, stride: usize,
+                                  out_jac: *mut u64) -> keaki_status;
+    pub fn keaki_hip_msm_g1_batch_dev(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, d_scalars: *const c_void, n: usize, m: usize, stride: usize,
+                                      d_out_jac: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_kzg_open_batch(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, coeffs: *const u64, n: usize, m: usize, stride: usize,
+                                    points: *const u64, proofs_out_jac: *mut u64, values_out: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_open_batch_dev(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, d_coeffs: *const c_void, n: usize, m: usize, stride: usize,
+                                        d_points: *const c_void, d_proofs_out_jac: *mut c_void, d_values_out: *mut c_void) -> keaki_status;
     pub fn keaki_hip_kzg_verify(ctx: *mut keaki_hip_ctx, com_aff: *const u64, tau_g2_aff: *const u64, point: *const u64, value: *const u64,
                                 proof_aff: *const u64, ok_out: *mut i32) -> keaki_status;
     // n openings in one call (generalises src/kzg.rs:127-148): e(L, g2) == e(R, [tau]_2) for the caller's gammas; sums_out_aff: u64[16] = L, R or null
