@@ -1,11 +1,14 @@
-"""Scalar model of the batched small MSM (keaki_amd/csrc/msm_batch.hip) -- TEST INFRASTRUCTURE, imported by tests/test_msm_batch_model.py
-and tests/test_gpu_msm_batch.py.
+"""Scalar model of the batched small MSM (keaki_amd/csrc/msm_batch.hip) -- TEST INFRASTRUCTURE, imported by tests/test_msm_batch_model.py,
+tests/test_gpu_msm_batch.py and tests/test_gpu_msm_batch_paths.py.
 
 Every base is k * G with k known (tests/structured_inputs.py), so a point is its scalar mod r and the model follows the kernels' documented
 order of operations on scalars: window choice from n, the biased signed digits, the (window, bucket) slot, the bucket loop, the weighted
 tree inside a workgroup and the Horner close. It counts the additions that meet equal operands, opposite operands or an identity
 accumulator, which is how the GPU test's adversarial rows are known to reach those branches. The route model says which calls take the batch
-kernels and which the row-by-row fallback; its constants are parsed out of the sources so that a changed limit fails the CPU test."""
+kernels and which the row-by-row fallback; its constants are parsed out of the sources so that a changed limit fails the CPU test.
+GPU_CASES lists the shapes tests/test_gpu_msm_batch_paths.py runs with what the model says each one reaches (window plan, passes, route,
+exceptional additions); the CPU test holds the list against the plans, boundaries and pass splits the sources have."""
+import functools
 import os
 import re
 
@@ -26,6 +29,7 @@ def parse_sources():
     """the same constants as the sources state them"""
     hip = open(os.path.join(CSRC, "msm_batch.hip")).read()
     hdr = open(os.path.join(CSRC, "internal.h")).read()
+    api = open(os.path.join(CSRC, "api.hip")).read()
 
     def num(text, pat):
         m = re.search(pat, text)
@@ -46,6 +50,13 @@ def parse_sources():
         "route_test": num(hip, r"bool batch = (n <= N_BATCH_MAX);"),
         "oom_falls_back": num(hip, r"if \(ws == KEAKI_ERR_OOM\) \{ (batch = false);"),
         "fallback_call": num(hip, r"ST_TRY\((msm_g1_run)\(ctx, d_points, srs_len, \(const Fr\*\)d_scalars \+ j \* stride, n, out \+ 3 \* j, d_table, c_table, nullptr\)\);"),
+        # open_batch_core: the rows the quotient workspace starts with, the halving step and its exit; reserve's request
+        "open_rows_start": num(api, r"size_t rows = (std::min\(m, std::max<size_t>\(1, MSM_BATCH_CANON_BYTES / \(nq \* 32\)\)\));"),
+        "open_reserve": num(api, r"const keaki_status st = (reserve\(ctx, ctx->mb_q, rows \* nq \* 32\));"),
+        "open_exit": num(api, r"if \((st != KEAKI_ERR_OOM \|\| rows == 1)\) return st;"),
+        "open_halve": num(api, r"rows = (\(rows \+ 1\) / 2);"),
+        "open_pass": num(api, r"for \(size_t r0 = 0; r0 < m; r0 \+= rows\) \{\s+const size_t k = (std::min\(rows, m - r0\));"),
+        "reserve_request": num(api, r"size_t want = (bytes \+ bytes / 8 \+ 256);"),
     }
 
 
@@ -158,6 +169,8 @@ def msm_row(dlogs, scalars, ev=None):
                 if sh == 0:
                     sh = None
                 wt = sh if k == 0 else _add(_add(wl, wr, ev, "tree"), sh, ev, "tree")
+                if k == logB - 1 and al is not None and ar is not None and (al == ar or (al + ar) % R == 0):
+                    ev.hit("tree_top_equal" if al == ar else "tree_top_opposite")        # the last merge A_l + A_r, counted again by _add
                 nxt.append((_add(al, ar, ev, "tree"), wt))
             nodes = nxt
         wsum.append(_add(nodes[0][0], nodes[0][1], ev, "tree"))
@@ -178,31 +191,191 @@ def rows_per_pass(n, m):
     return min(m, max(1, CANON_BYTES // (n * 32)), ROWS_MAX)
 
 
+def request(nbytes):
+    """what `reserve` asks the allocator for when a workspace has to grow"""
+    return nbytes + nbytes // 8 + 256
+
+
+def _reserve(need, have, alloc_limit):
+    """reserve(ctx, buf, need) on a buffer of capacity `have` -> (granted, capacity afterwards). A buffer that has to grow is freed first, so
+    a refused request leaves it empty."""
+    if need <= have:
+        return True, have
+    if alloc_limit and request(need) > alloc_limit:
+        return False, 0
+    return True, request(need)
+
+
 def workspace_requests(n, m):
     """the two reservations of the batch path in bytes, as `reserve` asks the allocator for them (bytes + bytes / 8 + 256)"""
     W = plan(window_bits(n))[1]
     rows = rows_per_pass(n, m)
-    return [b + b // 8 + 256 for b in (rows * n * 32, rows * W * 128)]
+    return [request(b) for b in (rows * n * 32, rows * W * 128)]
+
+
+def route_held(n, m, alloc_limit=0, held=(0, 0)):
+    """route of one msm_g1_batch_run and the capacities (mb_canon, mb_wsums) it leaves behind"""
+    if m == 0:
+        return "none", tuple(held)
+    if n == 0:
+        return "identity", tuple(held)
+    if n > N_BATCH_MAX:
+        return "fallback", tuple(held)
+    W = plan(window_bits(n))[1]
+    rows = rows_per_pass(n, m)
+    ok, canon = _reserve(rows * n * 32, held[0], alloc_limit)
+    if not ok:
+        return "fallback", (canon, held[1])
+    ok, wsums = _reserve(rows * W * 128, held[1], alloc_limit)
+    return ("batch" if ok else "fallback"), (canon, wsums)
 
 
 def route(n, m, tables=False, alloc_limit=0, held=(0, 0)):
     """'none' | 'identity' | 'batch' | 'fallback'. tables: the handle has window tables (no influence: the batch kernels read the points only);
     alloc_limit: keaki_hip_debug_set_alloc_limit; held: capacities of the two workspaces the context already holds (grow-only)"""
-    if m == 0:
-        return "none"
-    if n == 0:
-        return "identity"
-    if n > N_BATCH_MAX:
-        return "fallback"
-    W = plan(window_bits(n))[1]
+    return route_held(n, m, alloc_limit, held)[0]
+
+
+def inner_passes(n, m):
+    """launch rounds of msm_g1_batch_run on the batch route: [rows of each pass]"""
     rows = rows_per_pass(n, m)
-    for need, req, have in zip((rows * n * 32, rows * W * 128), workspace_requests(n, m), held):
-        if need > have and alloc_limit and req > alloc_limit:
-            return "fallback"
-    return "batch"
+    return [min(rows, m - r0) for r0 in range(0, m, rows)]
+
+
+def open_rows(nq, m, alloc_limit=0, held=(0, 0, 0)):
+    """open_batch_core for quotients of nq >= 1 coefficients: the rows of the quotient workspace start at min(m, max(1, CANON_BYTES / (nq * 32)))
+    and halve ((rows + 1) / 2) while `reserve` is refused; one row refused is KEAKI_ERR_OOM (None). held: capacities of (mb_q, mb_canon,
+    mb_wsums). -> {"rows": rows of each outer pass, "routes": route of the MSM of each outer pass, "held": capacities afterwards}"""
+    rows = min(m, max(1, CANON_BYTES // (nq * 32)))
+    q = held[0]
+    while True:
+        ok, q = _reserve(rows * nq * 32, q, alloc_limit)
+        if ok:
+            break
+        if rows == 1:
+            return None
+        rows = (rows + 1) // 2
+    inner = tuple(held[1:])
+    passes, routes = [], []
+    for r0 in range(0, m, rows):
+        k = min(rows, m - r0)
+        r, inner = route_held(nq, k, alloc_limit, inner)
+        passes.append(k)
+        routes.append(r)
+    return {"rows": passes, "routes": routes, "held": (q,) + inner}
 
 
 # ---- inputs that reach the exceptional branches ---------------------------------------------------------------------------------------------
 def adversarial_rows(n, seed_row):
     """[zero row, n equal scalars, r - 1 everywhere, the caller's random row]"""
     return [[0] * n, [0x1234567 % R] * n, [R - 1] * n, list(seed_row)]
+
+
+def _every_window_carries(ct):
+    _, _, _, _, offsets = plan(ct)
+    return (1 << offsets[-1]) - 1 + (1 << offsets[-1])          # all ones below the top window, one on top
+
+
+def edge_scalars(n):
+    """0, 1, r - 1, 2^(c-1) (window 0 goes negative with a carry) and the value whose every signed window carries, for the width of n"""
+    ct = window_bits(n)
+    return [0, 1, R - 1, 1 << (plan(ct)[0] - 1), _every_window_carries(ct)]
+
+
+def branch_rows(n, seed_row):
+    """adversarial_rows plus rows of two non-zero scalars that put chosen points into chosen buckets of window 0, so that on an SRS of equal
+    points (tau = 1) the tree meets equal and opposite operands whatever the width: at its first level (1 and 2: G in buckets 0 and 1; 1 and
+    2^c - 2: G and -G) and at its last level, the merge of the two halves of a window (1 and B / 2 + 1; 1 and 2^c - (B / 2 + 1)).
+    test_msm_batch_model.py proves the events for every width."""
+    c = plan(window_bits(n))[0]
+    far = (1 << (c - 2)) + 1                                      # bucket B / 2: the first of the upper half
+    pad = [0] * (n - 2)
+    return adversarial_rows(n, seed_row) + [[1, 2] + pad, [1, (1 << c) - 2] + pad, [1, far] + pad, [1, (1 << c) - far] + pad]
+
+
+# ---- the case table of tests/test_gpu_msm_batch_paths.py ------------------------------------------------------------------------------------
+def width_boundaries():
+    """[(n, n + 1)] where window_bits steps, found by walking n (not copied from the source)"""
+    return [(n, n + 1) for n in range(1, N_BATCH_MAX) if window_bits(n) != window_bits(n + 1)]
+
+
+BOUNDARY_N = [135, 136, 271, 272, 543, 544, 1087, 1088, 2175, 2176]
+BRANCH_N = [65, 257, 400, 1000, 1500, 2500]                      # one n per width 4 .. 9
+IDENTITY_N = [65, 1500]
+QUOTIENT_N = [255, 256, 512, 513]
+# allocation limits of the two limited open cases (bytes), chosen from open_rows: (a) admits 17 quotient rows of 256 coefficients but not 33,
+# (b) admits the quotient and canonical rows of 65 x 33 but not their 65 x 64 window sums
+OPEN_HALVING = {"n": 257, "m": 65, "limit": request(17 * 256 * 32) + 1000}
+OPEN_FALLBACK = {"n": 34, "m": 65, "limit": request(65 * 33 * 32) + 1000}
+
+
+def _cases():
+    """(id, entry, n, m, stride, srs kind, scalar set, alloc limit). entry 'commit': keaki_hip_msm_g1_batch*, n scalars a row; 'open':
+    keaki_hip_kzg_open_batch*, n coefficients a row (the MSM has n - 1). srs kinds: 'known' unrelated points of known discrete logs, 'one' /
+    'minus_one' / 'random' / 'zero' tau^i G, 'holes' known logs with identity points."""
+    out = []
+    for n in BOUNDARY_N:
+        out.append(("plan[n=%d]" % n, "commit", n, 3, n + 3, "known", "edge", 0))
+    for n in BRANCH_N:
+        for srs in ("one", "minus_one"):
+            out.append(("branches[n=%d,%s]" % (n, srs), "commit", n, 8, n, srs, "branch", 0))
+    for n in IDENTITY_N:
+        out.append(("identity_points[n=%d]" % n, "commit", n, 4, n, "holes", "holes", 0))
+        out.append(("identity_points[n=%d,zero]" % n, "commit", n, 4, n, "zero", "holes", 0))
+    for n in (1, 3):
+        out.append(("rows_max[n=%d]" % n, "commit", n, ROWS_MAX + 1, n, "random", "random", 0))
+        out.append(("rows_max[n=%d,stride]" % n, "commit", n, ROWS_MAX + 1, n + 1, "random", "random", 0))
+    out.append(("canon_bytes", "commit", N_BATCH_MAX, CANON_BYTES // (N_BATCH_MAX * 32) + 1, N_BATCH_MAX, "random", "numpy", 0))
+    out.append(("open_halving", "open", OPEN_HALVING["n"], OPEN_HALVING["m"], OPEN_HALVING["n"], "known", "random", OPEN_HALVING["limit"]))
+    out.append(("open_fallback", "open", OPEN_FALLBACK["n"], OPEN_FALLBACK["m"], OPEN_FALLBACK["n"], "known", "random", OPEN_FALLBACK["limit"]))
+    out.append(("open_dev[stride]", "open", 257, 3, 262, "known", "random", 0))
+    for n in (N_BATCH_MAX + 1, N_BATCH_MAX + 2):
+        out.append(("open_route[n=%d]" % n, "open", n, 2, n, "random", "random", 0))
+    for n in QUOTIENT_N:
+        out.append(("quotient[n=%d]" % n, "open", n, 3, n, "random", "z01", 0))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def branch_events(n, srs):
+    """events of branch_rows(n, a fixed pseudo-random row) on tau = 1 / -1, as sorted names"""
+    from conftest_helpers import rand_fr_ints
+    tau = {"one": 1, "minus_one": R - 1}[srs]
+    dl, x = [], 1
+    for _ in range(n):
+        dl.append(x)
+        x = x * tau % R
+    ev = Events()
+    for row in branch_rows(n, rand_fr_ints(n, 5 + n)):
+        msm_row(dl, row, ev)
+    return tuple(sorted(k for k in ev if ev[k]))
+
+
+def reach(case):
+    """what the model says a case reaches"""
+    cid, entry, n, m, stride, srs, scalars, limit = case
+    nq = n - 1 if entry == "open" else n
+    c = plan(window_bits(nq))[0]
+    out = {"c": c, "G": THREADS >> (c - 1), "depth": c - 1}
+    if entry == "open":
+        o = open_rows(nq, m, limit)
+        out.update(outer=o["rows"], routes=o["routes"], held=o["held"],
+                   inner=[len(inner_passes(nq, k)) if r == "batch" else 0 for k, r in zip(o["rows"], o["routes"])])
+    else:
+        r, held = route_held(nq, m, limit)
+        out.update(outer=[m], routes=[r], held=(0,) + held, inner=[len(inner_passes(nq, m)) if r == "batch" else 0])
+    out["events"] = branch_events(n, srs) if scalars == "branch" else ()
+    return out
+
+
+GPU_CASES = _cases()
+
+
+def case(cid):
+    hit = [k for k in GPU_CASES if k[0] == cid]
+    assert len(hit) == 1, "msm_batch_model: no GPU case %r" % cid
+    return hit[0]
+
+
+def cases_of(prefix):
+    return [k for k in GPU_CASES if k[0].split("[")[0] == prefix]

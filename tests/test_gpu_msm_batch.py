@@ -147,15 +147,13 @@ def test_state_between_calls(oc, hip, base):
     mem.put(d_rows, big)
     limit = M.workspace_requests(n, 65)[0] - 1
     assert M.route(n, 65, alloc_limit=limit) == "fallback" and M.route(n, 65) == "batch"
-    lib = hip.lib
-    lib.keaki_hip_debug_set_alloc_limit.argtypes = [C.c_void_p, C.c_size_t]
     before = hip.memory()["workspaces"]
-    assert lib.keaki_hip_debug_set_alloc_limit(hip.ctx, limit) == 0
+    hip.debug_set_alloc_limit(limit)
     try:
         hip.msm_g1_batch_dev(base["plain"], d_rows, n, 65, n, d_out)
         hip.synchronize()
     finally:
-        assert lib.keaki_hip_debug_set_alloc_limit(hip.ctx, 0) == 0
+        hip.debug_set_alloc_limit(0)
     assert np.array_equal(mem.get(d_out, 65 * 96).view(np.uint64).reshape(65, 12), ref_big)
     assert hip.memory()["workspaces"] == before, "the fallback allocated nothing: the batch workspace was refused, the rows ran in held memory"
     mem.free()
