@@ -535,7 +535,7 @@ bool msm_c_refuses(keaki_hip_ctx* ctx, const char* name, long long v) {         
                 name, v, MX, MX);
   return true;
 }
-bool gt_wb_b_refuses(keaki_hip_ctx* ctx, const char*, long long v) {          // the environment's width is taken as it is: encap_impl refuses it on use
+bool gt_wb_b_refuses(keaki_hip_ctx* ctx, const char*, long long v) {          // the environment's width is taken as it is: b_table refuses it on use
   if (!ctx || v == 0 || (v >= 8 && v <= 22 && gt_table_powers((uint32_t)v) <= 320)) return false;
   fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: gt_wb_b = %lld out of range", v);
   return true;
@@ -546,7 +546,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(reduce_l), TUNE_OPTION(part_shift), TUNE_OPTION(acc_u29), TUNE_OPTION(acc_u29_g2), TUNE_OPTION(acc_prefetch), TUNE_OPTION(acc_idxq),
     TUNE_OPTION(cs_masked), TUNE_OPTION(acc_nt), TUNE_OPTION(fk_uniform), TUNE_OPTION(fk_gtab), TUNE_OPTION(fk_radix4), TUNE_OPTION(fk_addsub29),
     TUNE_OPTION(fb_occ1), TUNE_OPTION(pair_wide_max), TUNE_OPTION(pair_two_waves),
-    TUNE_OPTION(gt_wb_b, gt_wb_b_refuses, [](keaki_hip_ctx* ctx) { ctx->gt_b_ready = ctx->gt_b_fallback = false; }),   // B's table: rebuilt at the new width on next use
+    TUNE_OPTION(gt_wb_b, gt_wb_b_refuses, [](keaki_hip_ctx* ctx) { ctx->kem.gt_b_ready = ctx->kem.gt_b_fallback = false; }),   // B's table: rebuilt at the new width on next use
     TUNE_OPTION(encap_gt), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
     TUNE_OPTION(msm_pipe_growth),
 #ifdef KEAKI_DIAG
@@ -568,14 +568,12 @@ void tune_from_env(Tuning& t) {
 }
 struct BufClass { DevBuf* b; int cls; };   // cls: 1 = workspace, 2 = GT / fixed-base tables of encapsulate
 std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
-  std::vector<BufClass> v;
+  std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums, &ctx->bsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->verify_io, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->g2gen_lines, &ctx->fk_tab, &ctx->g2pow_lines, &ctx->g2pow_pts})
+                    &ctx->pair_ws, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab})
     v.push_back({b, 1});
-  for (DevBuf* b : {&ctx->fb_bases, &ctx->fb_g1_gen, &ctx->fb_g2_gen, &ctx->fb_com, &ctx->fb_tau, &ctx->gt_tab_a, &ctx->gt_tab_b, &ctx->gt_base,
-                    &ctx->fbs_g2_gen, &ctx->fbs_tau, &ctx->fbs_g1_gen})
-    v.push_back({b, 2});
+  ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
 }
 }  // namespace
@@ -671,12 +669,7 @@ keaki_status keaki_hip_ctx_trim(keaki_hip_ctx* ctx) {
   if (ctx->copy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
   for (const BufClass& bc : all_bufs(ctx))
     if (bc.b->p) { (void)hipFree(bc.b->p); bc.b->p = nullptr; bc.b->cap = 0; }
-  ctx->gt_b_ready = ctx->gt_a_valid = ctx->gt_b_fallback = false;
-  ctx->gt_a_pending_aux = false;
-  ctx->seen_com_runs = 0;
-  ctx->verify_ready = ctx->verify_tables_ready = false;
-  ctx->fb_tau_valid = ctx->g2gen_lines_ready = ctx->fb_ready = ctx->g2pow_ready = false;
-  ctx->fbs_ready = ctx->fbs_tau_valid = false;
+  ctx->kem = KemState();         // the buffers are gone: no ready or valid bit outlives its table
   return KEAKI_OK;
 }
 keaki_status keaki_hip_ctx_memory(keaki_hip_ctx* ctx, size_t* out4) {
@@ -907,228 +900,230 @@ struct StreamSwap {
 };
 // signed-window table of e(P, g2) for a G1 point P in device memory: the powers of two e(P, g2)^(2^s) = e(P, 2^s g2) come from ONE pairing
 // launch of P against the tabulated line sequences of the multiples 2^s g2 (the latency of one pairing; the tables -- 320 x 18 KB -- are built
-// once per context: lane s doubles g2 s times, one k_g2_prepare workgroup per multiple). Until round 4 the chain ran on the
-// G1 side (2^s P by 260 doublings one after the other: 1.4 ms with the device idle, in every call with a new commitment).
+// once per context: lane s doubles g2 s times, one k_g2_prepare workgroup per multiple), not from 260 doublings of P one after the other (1.4 ms).
 constexpr uint32_t GT_POWERS_MAX = 320;
 static keaki_status g2pow_tables(keaki_hip_ctx* ctx) {
-  if (ctx->g2pow_ready) return KEAKI_OK;
-  ST_TRY(reserve(ctx, ctx->g2pow_lines, (size_t)GT_POWERS_MAX * g2_prepared_bytes()));
-  ST_TRY(reserve(ctx, ctx->g2pow_pts, (size_t)(GT_POWERS_MAX + 1) * G2_AFF_BYTES));
-  char* gen = (char*)ctx->g2pow_pts.p;
+  KemState& k = ctx->kem;
+  if (k.g2pow_ready) return KEAKI_OK;
+  ST_TRY(reserve(ctx, k.g2pow_lines, (size_t)GT_POWERS_MAX * g2_prepared_bytes()));
+  ST_TRY(reserve(ctx, k.g2pow_pts, (size_t)(GT_POWERS_MAX + 1) * G2_AFF_BYTES));
+  char* gen = (char*)k.g2pow_pts.p;
   char* pts = gen + G2_AFF_BYTES;
   ST_TRY(g2_generator_to(ctx, gen));
   ST_TRY(g2_pow2_multiples_run(ctx, gen, GT_POWERS_MAX, pts));
-  ST_TRY(g2_prepare_run(ctx, pts, ctx->g2pow_lines.p, GT_POWERS_MAX));
-  ctx->g2pow_ready = true;
+  ST_TRY(g2_prepare_run(ctx, pts, k.g2pow_lines.p, GT_POWERS_MAX));
+  k.g2pow_ready = true;
   return KEAKI_OK;
 }
 static keaki_status gt_table_of(keaki_hip_ctx* ctx, const void* d_p_aff, void* d_table, uint32_t wb) {
-  char* gb = (char*)ctx->gt_base.p;
+  char* gb = (char*)ctx->kem.gt_base.p;
   const uint32_t cnt = gt_table_powers(wb);
   if (cnt > GT_POWERS_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "gt_table_of: %u powers", cnt);
   void* pows = gb + G1_AFF_BYTES + 320 * G1_AFF_BYTES;
   ST_TRY(g2pow_tables(ctx));
-  ST_TRY(pairing_raw_fixed_run(ctx, d_p_aff, 0, cnt, ctx->g2pow_lines.p, g2_prepared_lines(), pows));
+  ST_TRY(pairing_raw_fixed_run(ctx, d_p_aff, 0, cnt, ctx->kem.g2pow_lines.p, g2_prepared_lines(), pows));
   return gt_table_run(ctx, pows, d_table, wb);
 }
 
 // ---- KEM composites ------------------------------------------------------------------------------------------
-// `prep`: build what depends on the SETUP only (generator tables, the line sequence of g2, the table of [tau]_2, the GT table of e(g1, g2)) for
-// batches of n items, and stop: keaki_hip_encap_prepare. Nothing per item, nothing per commitment.
 // what a host-pointer entry point knows without asking the device: the two constants of the batch (no read-back, no stream synchronisation
 // between the upload and the kernels), the size of the WHOLE batch this chunk belongs to, and whether it is its first chunk
 struct EncapHost { const uint64_t* com; const uint64_t* tau; size_t n_batch; bool first; };
-static keaki_status encap_impl(keaki_hip_ctx* ctx, bool prep, const void* d_com_aff, const void* d_tau_g2_aff, const void* d_points,
-                               const void* d_values, const void* d_r, size_t n, void* d_ct_out_aff, void* d_gt_out, void* d_key_out,
-                               size_t msg_len, bool xor_into = false, const EncapHost* host = nullptr) {
-  // a chunk of a larger batch takes the decisions of the whole batch (table widths, the GT path) and counts as ONE call with its commitment
-  const size_t n_policy = host ? host->n_batch : n;
-  const bool first_of_batch = !host || host->first;
-  if (!prep) ST_TRY(reserve(ctx, ctx->tmp_a, n * G1_AFF_BYTES));
+struct EncapArgs {
+  const void *d_com, *d_tau, *d_points, *d_values, *d_r;   // device inputs: the commitment, [tau]_2 | n x 32 B each
+  void *d_ct_out, *d_gt_out, *d_key_out;                   // n x 128 B | n x 384 B or null | n x msg_len B or null
+  size_t n, msg_len;
+  bool xor_into = false;                                   // the KDF XORs the key into d_key_out in place (the DEM)
+  const EncapHost* host = nullptr;
+};
+// window widths of the fixed-base tables: 16 bits for bases that outlive a batch (generators: per context, [tau]_2: per setup), 13 bits for the
+// commitment's table (rebuilt per batch in the per-item-pairing path), 8 bits for the small tables of batches below FB_TABLES_MIN = 256 items
+constexpr uint32_t FB_WB_LONG = 16, FB_WB_BATCH = 13, FB_WB_SMALL = 8, FB_TABLES_MIN = 256;
+// window widths of the GT tables. The constant B = e(g1, g2) is tabulated once per context: 20-bit windows (13 products per item, 2.6 GB; option
+// gt_wb_b picks another width). A = e(C, g2) per commitment: 13 bits on first sight (20 products per item, 31.5 MB: one launch of the twelve-lane pairing
+// kernel over the tabulated multiples of g2 + the fills, 1.7 ms); when it comes back, 16 bits (201 MB) from the powers still lying in gt_base (0.5 ms).
+constexpr uint32_t GT_WB_A_FIRST = 13, GT_WB_A_REPEAT = 16;
+// The batch policy (no HIP call) from the size of the WHOLE batch, Tuning::gt_wb_b and encap_gt, the consecutive calls that carried this commitment, whether
+// its A table is cached, and `prep` (keaki_hip_encap_prepare: no commitment). ALL calls take the GT path since the table of a new commitment costs 1.7 ms
+// beside the ciphertext kernel: ~30 Fq12 products per item instead of two G1 ladders and a pairing. Option encap_gt = N keeps the per-item pairing below
+// N items for a commitment without a table. B: 20-bit windows for batches of >= 65,536 items, else 16 (201 MB); widened once when a large batch comes
+struct EncapPolicy { bool use_tables, use_gt; uint32_t wb_b_req; };
+static EncapPolicy encap_policy(size_t n_policy, int gt_wb_b, long long encap_gt, uint32_t seen_com_runs, bool a_cached, bool prep) {
+  const bool gt_env = encap_gt >= 0;
+  const bool use_gt = n_policy >= (gt_env ? (size_t)encap_gt : (size_t)0) || (!prep && !gt_env && (a_cached || seen_com_runs >= 3));
+  return {n_policy >= FB_TABLES_MIN, use_gt, gt_wb_b != 0 ? (uint32_t)gt_wb_b : (n_policy >= 65536 ? 20u : 16u)};
+}
+static void note_commitment(KemState& k, const uint64_t* com_host, bool first_of_batch) {   // consecutive calls with one commitment (a host batch's chunks are ONE call)
+  const bool same = k.seen_com_runs && memcmp(com_host, k.seen_com, 64) == 0;
+  if (same && first_of_batch && k.seen_com_runs < 1000000) k.seen_com_runs++;
+  if (!same) { memcpy(k.seen_com, com_host, 64); k.seen_com_runs = 1; }
+}
+// g2 in tmp_c for the pairing's second slot (src/kem.rs:30), and once per context the generators' 16-bit tables and g2's line sequence (G2Prepared)
+static keaki_status generator_tables(keaki_hip_ctx* ctx, bool use_tables) {
+  KemState& k = ctx->kem;
   ST_TRY(reserve(ctx, ctx->tmp_c, G2_AFF_BYTES));
-  void* gt = d_gt_out;
-  if (!gt && !prep) { ST_TRY(reserve(ctx, ctx->tmp_b, n * 384)); gt = ctx->tmp_b.p; }
-  // generator g2 in device memory for the pairing's second slot (src/kem.rs:30 pairs with E::G2Affine::generator())
   ST_TRY(g2_generator_to(ctx, ctx->tmp_c.p));
-  // window widths of the fixed-base tables: 16 bits for bases that outlive a batch (generators: per context, [tau]_2: per setup),
-  // 13 bits for the commitment's table (rebuilt per batch in the per-item-pairing path)
-  constexpr uint32_t FB_WB_LONG = 16, FB_WB_BATCH = 13;
-  const size_t FBL = fb_table_entries(FB_WB_LONG), FBS = fb_table_entries(FB_WB_BATCH);
-  const bool use_tables = n_policy >= 256;
-  if (use_tables && !ctx->fb_ready) {
-    ST_TRY(reserve(ctx, ctx->fb_g1_gen, FBL * G1_AFF_BYTES + G1_AFF_BYTES));
-    ST_TRY(reserve(ctx, ctx->fb_g2_gen, FBL * G2_AFF_BYTES));
-    ST_TRY(reserve(ctx, ctx->fb_com, FBS * G1_AFF_BYTES));
-    ST_TRY(reserve(ctx, ctx->fb_tau, FBL * G2_AFF_BYTES));
-    void* g1pt = (char*)ctx->fb_g1_gen.p + FBL * G1_AFF_BYTES;   // scratch slot behind the table
+  if (use_tables && !k.fb_ready) {
+    const size_t FBL = fb_table_entries(FB_WB_LONG);
+    ST_TRY(reserve(ctx, k.fb_g1_gen, FBL * G1_AFF_BYTES + G1_AFF_BYTES));
+    ST_TRY(reserve(ctx, k.fb_g2_gen, FBL * G2_AFF_BYTES));
+    ST_TRY(reserve(ctx, k.fb_com, fb_table_entries(FB_WB_BATCH) * G1_AFF_BYTES));
+    ST_TRY(reserve(ctx, k.fb_tau.buf, FBL * G2_AFF_BYTES));
+    void* g1pt = (char*)k.fb_g1_gen.p + FBL * G1_AFF_BYTES;   // scratch slot behind the table
     ST_TRY(g1_generator_to(ctx, g1pt));
-    ST_TRY(g1_fb_table_run(ctx, g1pt, ctx->fb_g1_gen.p, FB_WB_LONG));
-    ST_TRY(g2_fb_table_run(ctx, ctx->tmp_c.p, ctx->fb_g2_gen.p, FB_WB_LONG));
-    ctx->fb_ready = true;
+    ST_TRY(g1_fb_table_run(ctx, g1pt, k.fb_g1_gen.p, FB_WB_LONG));
+    ST_TRY(g2_fb_table_run(ctx, ctx->tmp_c.p, k.fb_g2_gen.p, FB_WB_LONG));
+    k.fb_ready = true;
   }
-  // the second pairing slot is the constant generator g2: its line sequence (ark-ec's G2Prepared) is built once per context
-  if (!ctx->g2gen_lines_ready) {
-    ST_TRY(reserve(ctx, ctx->g2gen_lines, g2_prepared_bytes()));
-    ST_TRY(g2_prepare_run(ctx, ctx->tmp_c.p, ctx->g2gen_lines.p));
-    ctx->g2gen_lines_ready = true;
+  if (!k.g2gen_lines_ready) {
+    ST_TRY(reserve(ctx, k.g2gen_lines, g2_prepared_bytes()));
+    ST_TRY(g2_prepare_run(ctx, ctx->tmp_c.p, k.g2gen_lines.p));
+    k.g2gen_lines_ready = true;
   }
-  // the two constants of the batch on the host (one read-back, one synchronisation; none when the caller's host copies came along)
-  uint64_t tau_host[16], com_host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (host) {
-    memcpy(tau_host, host->tau, 128);
-    memcpy(com_host, host->com, 64);
-  } else {
-    HIP_TRY(ctx, hipMemcpyAsync(tau_host, d_tau_g2_aff, 128, hipMemcpyDeviceToHost, ctx->stream));
-    if (!prep) HIP_TRY(ctx, hipMemcpyAsync(com_host, d_com_aff, 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  // window widths of the GT tables. The constant B = e(g1, g2) is tabulated once per context: 20-bit windows (13 products per item, 2.6 GB;
-  // KEAKI_GT_WB_B picks another width). A = e(C, g2) per commitment: 13 bits on first sight (20 products per item, 31.5 MB: one launch of the
-  // twelve-lane pairing kernel over the tabulated multiples of g2 + the fills, 1.7 ms); when the SAME commitment comes back, its 16-bit table
-  // (16 products, 201 MB) is filled from the powers of two still lying in gt_base (0.5 ms, no pairing).
-  // Which calls take this path: ALL of them since the table of a new commitment costs 1.7 ms beside the ciphertext kernel (round 4; until then
-  // batches of >= 65,536 items and callers that kept encrypting to one commitment, from the third consecutive call on): an item costs ~30 Fq12
-  // products instead of two G1 ladders and a pairing, and a single `encapsulate` to a NEW commitment 2.0 ms instead of 4.2 (the G1 ladders alone
-  // took 1.8). KEAKI_ENCAP_GT / option encap_gt = N keeps the per-item pairing path for batches below N items whose commitment has no table yet.
-  constexpr uint32_t GT_WB_A_FIRST = 13, GT_WB_A_REPEAT = 16;
-  const bool wbb_env = ctx->tune.gt_wb_b != 0;          // Tuning::gt_wb_b / encap_gt (the environment is read in keaki_hip_ctx_create only)
-  const bool gt_env = ctx->tune.encap_gt >= 0;
-  const size_t gt_threshold = gt_env ? (size_t)ctx->tune.encap_gt : (size_t)0;
-  bool a_cached = false;
-  if (!prep) {
-    if (ctx->seen_com_runs && memcmp(com_host, ctx->seen_com, 64) == 0) {
-      if (first_of_batch && ctx->seen_com_runs < 1000000) ctx->seen_com_runs++;
-    } else {
-      memcpy(ctx->seen_com, com_host, 64);
-      ctx->seen_com_runs = 1;
-    }
-    a_cached = ctx->gt_b_ready && ctx->gt_a_valid && memcmp(com_host, ctx->gt_a_com, 64) == 0;
-  }
-  const bool use_gt = n_policy >= gt_threshold || (!prep && !gt_env && (a_cached || ctx->seen_com_runs >= 3));
-  bool a_on_aux = false, b_factor_done = false;
-  // the table of a new commitment is built on the aux stream; `gt_a_pending_aux` says that the context's stream has not been made to wait for
-  // that build yet. It survives an early error return, so a later call that finds the table published (same commitment) or rewrites gt_base
-  // orders itself behind the build first -- whatever happened in between.
-  auto wait_aux = [&]() -> keaki_status {
-    if (ctx->gt_a_pending_aux) {
-      HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));
-      ctx->gt_a_pending_aux = false;
-    }
-    return KEAKI_OK;
-  };
-  if (use_gt) {
-    ST_TRY(wait_aux());                                   // a build an earlier (failed) call left unawaited
-    // GT_i = A^(r_i) B^(-beta_i r_i) with A = e(C, g2), B = e(g1, g2) (see pairing.hip.h): no pairing per item
-    ST_TRY(reserve(ctx, ctx->gt_base, G1_AFF_BYTES + 320 * (G1_AFF_BYTES + 384)));   // a point | (unused since round 4) | the powers' pairings
-    char* gb = (char*)ctx->gt_base.p;
-    // B: 20-bit windows for a context that runs large batches, 16-bit (201 MB) for one that only ever made small calls; widened once when a large batch comes
-    const uint32_t wb_b_req = wbb_env ? (uint32_t)ctx->tune.gt_wb_b : (n_policy >= 65536 ? 20u : 16u);
-    if (!ctx->gt_b_ready || (!wbb_env && wb_b_req > ctx->gt_b_wb && !ctx->gt_b_fallback)) {
-      if (wb_b_req < 8 || wb_b_req > 22 || gt_table_powers(wb_b_req) > 320) return fail(ctx, KEAKI_ERR_BAD_ARG, "gt_wb_b = %u out of range", wb_b_req);
-      ctx->gt_b_ready = false;
-      ctx->gt_b_wb = wb_b_req;
-      keaki_status st_b = reserve(ctx, ctx->gt_tab_b, gt_table_bytes(ctx->gt_b_wb));
-      if (st_b == KEAKI_ERR_OOM && ctx->gt_b_wb > 16) {          // no room for the wide table: the 16-bit one is 201 MB
-        (void)hipGetLastError();
-        ctx->gt_b_wb = 16;
-        ctx->gt_b_fallback = true;
-        st_b = reserve(ctx, ctx->gt_tab_b, gt_table_bytes(ctx->gt_b_wb));
-      }
-      ST_TRY(st_b);
-      ST_TRY(g1_generator_to(ctx, gb));
-      ST_TRY(gt_table_of(ctx, gb, ctx->gt_tab_b.p, ctx->gt_b_wb));
-      ctx->gt_b_ready = true;
-      ctx->gt_a_valid = false;                    // gt_base now holds B's powers
-    }
-    // A depends on the commitment only: reuse the table while the caller keeps encrypting to the same commitment. A NEW commitment's table is
-    // a latency-bound job (65 waves for 1.4 ms, then the fills): it goes to a stream of its own, IN FRONT of the ciphertext kernel below, which
-    // fills the device for 0.56 ms at 2^16 items -- the two run side by side and the exponentiation waits for both.
-    if (!prep && (!ctx->gt_a_valid || memcmp(com_host, ctx->gt_a_com, 64) != 0)) {
-      ctx->gt_a_valid = false;
-      ST_TRY(reserve(ctx, ctx->gt_tab_a, gt_table_bytes(GT_WB_A_REPEAT)));
-      ST_TRY(aux_ready(ctx));
-      HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[0], ctx->stream));          // behind every earlier reader of the table and of gt_base
-      HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
-      {
-        StreamSwap on_aux(ctx, ctx->aux_stream);
-        ST_TRY(gt_table_of(ctx, d_com_aff, ctx->gt_tab_a.p, GT_WB_A_FIRST));
-      }
-      HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
-      ctx->gt_a_pending_aux = true;
-      a_on_aux = true;
-      if (n > 4096) {
-        // the constant base's factor FIRST on the main stream: it fills every SIMD (two waves of 256 registers each) and must be out of the way
-        // when the table's fill levels arrive; the ciphertext kernel behind it leaves half of each SIMD's registers to them
-        ST_TRY(reserve(ctx, ctx->tmp_a, n * 384));
-        ST_TRY(gt_encap_exp_run(ctx, nullptr, 0, ctx->gt_tab_b.p, ctx->gt_b_wb, d_values, d_r, n, nullptr, nullptr, ctx->tmp_a.p));
-        b_factor_done = true;
-      }
-      memcpy(ctx->gt_a_com, com_host, 64);
-      ctx->gt_a_wb = GT_WB_A_FIRST;
-      ctx->gt_a_valid = true;
-    } else if (!prep && first_of_batch && ctx->gt_a_wb != GT_WB_A_REPEAT) {
-      // same commitment again IN A LATER CALL (the chunks of one host batch keep the table their first chunk found or built): the powers
-      // A^(2^s), s < 260, of the first build cover the 256 the wider table needs
-      ST_TRY(gt_table_run(ctx, gb + G1_AFF_BYTES + 320 * G1_AFF_BYTES, ctx->gt_tab_a.p, GT_WB_A_REPEAT));
-      static_assert(GT_WB_A_REPEAT == 16 && GT_WB_A_FIRST == 13, "the power count of the first table must cover the second");
-      ctx->gt_a_wb = GT_WB_A_REPEAT;
-    }
-  }
-  // ciphertexts ct_i = r_i [tau]_2 - (r_i alpha_i) g2: two fixed-base sums. [tau]_2 belongs to the setup, not to the batch: its window table
-  // is rebuilt only when the point changes. Batches of >= 256 items use (and build) the 16-bit tables; smaller ones use them when they are
-  // there for this [tau]_2, else SMALL 8-bit tables (32 x 129 entries per base, 0.5 MB, built in the latency of one G2 scalar-mult):
-  // 64 mixed additions per item instead of two 254-step ladders (a single `encapsulate` call: 20.5 -> 10 ms).
-  {
-    const bool big_has_tau = ctx->fb_ready && ctx->fb_tau_valid && memcmp(tau_host, ctx->fb_tau_pt, 128) == 0;
-    if (use_tables || big_has_tau) {
-      if (!big_has_tau) {
-        ctx->fb_tau_valid = false;
-        ST_TRY(g2_fb_table_run(ctx, d_tau_g2_aff, ctx->fb_tau.p, FB_WB_LONG));
-        memcpy(ctx->fb_tau_pt, tau_host, 128);
-        ctx->fb_tau_valid = true;
-      }
-      if (!prep) ST_TRY(encap_g2_fixed_run(ctx, ctx->fb_tau.p, FB_WB_LONG, ctx->fb_g2_gen.p, FB_WB_LONG, d_points, d_r, n, d_ct_out_aff, a_on_aux));
-    } else {
-      constexpr uint32_t FB_WB_SMALL = 8;
-      const size_t FBX = fb_table_entries(FB_WB_SMALL);
-      if (!ctx->fbs_ready) {
-        ST_TRY(reserve(ctx, ctx->fbs_g2_gen, FBX * G2_AFF_BYTES));
-        ST_TRY(reserve(ctx, ctx->fbs_tau, FBX * G2_AFF_BYTES));
-        ST_TRY(g2_fb_table_run(ctx, ctx->tmp_c.p, ctx->fbs_g2_gen.p, FB_WB_SMALL));
-        ctx->fbs_ready = true;
-        ctx->fbs_tau_valid = false;
-      }
-      if (!ctx->fbs_tau_valid || memcmp(tau_host, ctx->fbs_tau_pt, 128) != 0) {
-        ctx->fbs_tau_valid = false;
-        ST_TRY(g2_fb_table_run(ctx, d_tau_g2_aff, ctx->fbs_tau.p, FB_WB_SMALL));
-        memcpy(ctx->fbs_tau_pt, tau_host, 128);
-        ctx->fbs_tau_valid = true;
-      }
-      if (!prep) ST_TRY(encap_g2_fixed_run(ctx, ctx->fbs_tau.p, FB_WB_SMALL, ctx->fbs_g2_gen.p, FB_WB_SMALL, d_points, d_r, n, d_ct_out_aff));
-    }
-  }
-  if (prep) return KEAKI_OK;
-  if (use_gt) {
-    if (b_factor_done) {
-      // the factor of the constant base ran while the commitment's table was on its way; the commitment's factor behind it
-      ST_TRY(wait_aux());
-      ST_TRY(gt_encap_exp_run(ctx, ctx->gt_tab_a.p, ctx->gt_a_wb, nullptr, 0, d_values, d_r, n, gt, ctx->tmp_a.p, nullptr));
-    } else {
-      ST_TRY(wait_aux());
-      ST_TRY(gt_encap_exp_run(ctx, ctx->gt_tab_a.p, ctx->gt_a_wb, ctx->gt_tab_b.p, ctx->gt_b_wb, d_values, d_r, n, gt));
-    }
-  } else {
-    // per-item pairing e(r_i (C - beta_i g1), g2) with the tabulated lines of g2
-    if (use_tables) {
-      ST_TRY(g1_fb_table_run(ctx, d_com_aff, ctx->fb_com.p, FB_WB_BATCH));
-      ST_TRY(encap_g1_fixed_run(ctx, ctx->fb_com.p, FB_WB_BATCH, ctx->fb_g1_gen.p, FB_WB_LONG, d_values, d_r, n, ctx->tmp_a.p));
-    } else {
-      ST_TRY(encap_g1_run(ctx, d_com_aff, d_values, d_r, n, ctx->tmp_a.p));
-    }
-    ST_TRY(pairing_run(ctx, ctx->tmp_a.p, ctx->tmp_c.p, 0, n, gt, ctx->g2gen_lines.p));
-  }
-  if (d_key_out && msg_len) ST_TRY(blake3_gt_run(ctx, gt, n, d_key_out, msg_len, xor_into));
   return KEAKI_OK;
+}
+// the small tables of g2 (from the generator at d_g2_generator) and room for [tau]_2's: encapsulate below FB_TABLES_MIN items and kzg verify
+static keaki_status small_g2_tables(keaki_hip_ctx* ctx, const void* d_g2_generator) {
+  KemState& k = ctx->kem;
+  if (k.fbs_ready) return KEAKI_OK;
+  const size_t FBX = fb_table_entries(FB_WB_SMALL);
+  ST_TRY(reserve(ctx, k.fbs_g2_gen, FBX * G2_AFF_BYTES));
+  ST_TRY(reserve(ctx, k.fbs_tau.buf, FBX * G2_AFF_BYTES));
+  ST_TRY(g2_fb_table_run(ctx, d_g2_generator, k.fbs_g2_gen.p, FB_WB_SMALL));
+  k.fbs_ready = true;                 // fbs_tau is not valid yet: it is only ever built behind this point
+  return KEAKI_OK;
+}
+// the two constants of the batch read back to the host: one synchronisation, for callers whose host copies did not come along. d_com null: [tau]_2 only
+static keaki_status read_constants(keaki_hip_ctx* ctx, const void* d_tau, const void* d_com, uint64_t* tau_host, uint64_t* com_host) {
+  HIP_TRY(ctx, hipMemcpyAsync(tau_host, d_tau, 128, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_com) HIP_TRY(ctx, hipMemcpyAsync(com_host, d_com, 64, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return KEAKI_OK;
+}
+// the table of a new commitment is built on the aux stream; `gt_a_pending_aux` says that the context's stream has not been made to wait for that build yet. It survives
+// an early error return, so a later call that finds the table published or rewrites gt_base orders itself behind the build first -- whatever happened in between.
+static keaki_status wait_aux(keaki_hip_ctx* ctx) {
+  if (ctx->kem.gt_a_pending_aux) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));
+  ctx->kem.gt_a_pending_aux = false;
+  return KEAKI_OK;
+}
+static keaki_status b_table(keaki_hip_ctx* ctx, uint32_t wb_b_req) {      // GT path, the part of the setup: gt_base and the table of B at (at least) this width
+  KemState& k = ctx->kem;
+  ST_TRY(wait_aux(ctx));                                   // a build an earlier (failed) call left unawaited
+  ST_TRY(reserve(ctx, k.gt_base, G1_AFF_BYTES + 320 * (G1_AFF_BYTES + 384)));   // a point | (unused since round 4) | the powers' pairings
+  if (k.gt_b_ready && (ctx->tune.gt_wb_b != 0 || wb_b_req <= k.gt_b_wb || k.gt_b_fallback)) return KEAKI_OK;   // a forced width is never widened
+  if (wb_b_req < 8 || wb_b_req > 22 || gt_table_powers(wb_b_req) > 320) return fail(ctx, KEAKI_ERR_BAD_ARG, "gt_wb_b = %u out of range", wb_b_req);
+  k.gt_b_ready = false; k.gt_b_wb = wb_b_req;
+  keaki_status st_b = reserve(ctx, k.gt_tab_b, gt_table_bytes(k.gt_b_wb));
+  if (st_b == KEAKI_ERR_OOM && k.gt_b_wb > 16) {           // no room for the wide table: the 16-bit one is 201 MB
+    (void)hipGetLastError();
+    k.gt_b_wb = 16; k.gt_b_fallback = true;
+    st_b = reserve(ctx, k.gt_tab_b, gt_table_bytes(k.gt_b_wb));
+  }
+  ST_TRY(st_b);
+  ST_TRY(g1_generator_to(ctx, k.gt_base.p));
+  ST_TRY(gt_table_of(ctx, k.gt_base.p, k.gt_tab_b.p, k.gt_b_wb));
+  k.gt_b_ready = true;
+  k.gt_a.invalidate();                                     // gt_base now holds B's powers
+  return KEAKI_OK;
+}
+// GT path, the part of the commitment: A is reused while the caller keeps encrypting to the same commitment. A NEW commitment's table is a latency-bound
+// job (65 waves for 1.4 ms, then the fills): it goes to a stream of its own, IN FRONT of the ciphertext kernel, which fills the device for 0.56 ms at
+// 2^16 items -- the two run side by side and the exponentiation waits for both.
+struct AuxBuild { bool a_on_aux = false, b_factor_done = false; };
+static keaki_status a_table(keaki_hip_ctx* ctx, const EncapArgs& a, const uint64_t* com_host, bool first_of_batch, AuxBuild* out) {
+  KemState& k = ctx->kem;
+  if (!k.gt_a.holds(com_host)) {
+    k.gt_a.invalidate();
+    ST_TRY(reserve(ctx, k.gt_a.buf, gt_table_bytes(GT_WB_A_REPEAT)));
+    ST_TRY(aux_ready(ctx));
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[0], ctx->stream));          // behind every earlier reader of the table and of gt_base
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
+    { StreamSwap on_aux(ctx, ctx->aux_stream); ST_TRY(gt_table_of(ctx, a.d_com, k.gt_a.buf.p, GT_WB_A_FIRST)); }
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
+    k.gt_a_pending_aux = out->a_on_aux = true;
+    if (a.n > 4096) {
+      // the constant base's factor FIRST on the main stream: it fills every SIMD (two waves of 256 registers each) and must be out of the way
+      // when the table's fill levels arrive; the ciphertext kernel behind it leaves half of each SIMD's registers to them
+      ST_TRY(reserve(ctx, ctx->tmp_a, a.n * 384));
+      ST_TRY(gt_encap_exp_run(ctx, nullptr, 0, k.gt_tab_b.p, k.gt_b_wb, a.d_values, a.d_r, a.n, nullptr, nullptr, ctx->tmp_a.p));
+      out->b_factor_done = true;
+    }
+    k.gt_a.publish(com_host, GT_WB_A_FIRST);
+  } else if (first_of_batch && k.gt_a.wb != GT_WB_A_REPEAT) {
+    // same commitment again IN A LATER CALL (the chunks of one host batch keep their first chunk's table): the 260 powers of the first build cover the 256 needed
+    ST_TRY(gt_table_run(ctx, (char*)k.gt_base.p + G1_AFF_BYTES + 320 * G1_AFF_BYTES, k.gt_a.buf.p, GT_WB_A_REPEAT));
+    k.gt_a.wb = GT_WB_A_REPEAT;
+  }
+  return KEAKI_OK;
+}
+// The tables behind the ciphertexts ct_i = r_i [tau]_2 - (r_i alpha_i) g2, two fixed-base sums. [tau]_2 belongs to the setup, not to the batch: its window
+// table is rebuilt only when the point changes. Batches of >= FB_TABLES_MIN items use (and build) the 16-bit tables; smaller ones use them when they hold
+// this [tau]_2, else SMALL 8-bit tables (32 x 129 entries per base, 0.5 MB, built in the latency of one G2 scalar-mult): 64 mixed additions per item
+// instead of two 254-step ladders (a single `encapsulate` call: 20.5 -> 10 ms). Afterwards the big table holds this [tau]_2, or else the small one does.
+static keaki_status tau_table(keaki_hip_ctx* ctx, bool use_tables, const void* d_tau, const uint64_t* tau_host) {
+  KemState& k = ctx->kem;
+  const bool big = use_tables || (k.fb_ready && k.fb_tau.holds(tau_host));
+  if (!big) ST_TRY(small_g2_tables(ctx, ctx->tmp_c.p));
+  KeyedTable<16>& t = big ? k.fb_tau : k.fbs_tau;
+  if (t.holds(tau_host)) return KEAKI_OK;
+  t.invalidate();
+  ST_TRY(g2_fb_table_run(ctx, d_tau, t.buf.p, big ? FB_WB_LONG : FB_WB_SMALL));
+  t.publish(tau_host, big ? FB_WB_LONG : FB_WB_SMALL);
+  return KEAKI_OK;
+}
+static keaki_status kem_setup(keaki_hip_ctx* ctx, const void* d_tau, size_t n_policy) {    // what depends on the SETUP only: nothing per item or commitment
+  const EncapPolicy pol = encap_policy(n_policy, ctx->tune.gt_wb_b, ctx->tune.encap_gt, 0, false, true);
+  ST_TRY(generator_tables(ctx, pol.use_tables));
+  uint64_t tau_host[16];
+  ST_TRY(read_constants(ctx, d_tau, nullptr, tau_host, nullptr));
+  if (pol.use_gt) ST_TRY(b_table(ctx, pol.wb_b_req));
+  return tau_table(ctx, pol.use_tables, d_tau, tau_host);
+}
+// per item: the ciphertext kernel, then GT_i = A^(r_i) B^(-beta_i r_i) with A = e(C, g2), B = e(g1, g2) (pairing.hip.h) or the pairing e(r_i (C - beta_i g1), g2), and the KDF
+static keaki_status encap_items(keaki_hip_ctx* ctx, const EncapArgs& a, const EncapPolicy& pol, const uint64_t* tau_host, const AuxBuild& aux) {
+  KemState& k = ctx->kem;
+  void* gt = a.d_gt_out ? a.d_gt_out : ctx->tmp_b.p;
+  const bool big = k.fb_tau.holds(tau_host);      // on the big-table path only, the ciphertext kernel shares its SIMDs with a table build on aux
+  const KeyedTable<16>& tau = big ? k.fb_tau : k.fbs_tau;
+  ST_TRY(encap_g2_fixed_run(ctx, tau.buf.p, tau.wb, (big ? k.fb_g2_gen : k.fbs_g2_gen).p, tau.wb, a.d_points, a.d_r, a.n, a.d_ct_out, big && aux.a_on_aux));
+  if (pol.use_gt) {
+    ST_TRY(wait_aux(ctx));
+    // b_factor_done: the factor of the constant base ran while the commitment's table was on its way; the commitment's factor behind it
+    if (aux.b_factor_done) ST_TRY(gt_encap_exp_run(ctx, k.gt_a.buf.p, k.gt_a.wb, nullptr, 0, a.d_values, a.d_r, a.n, gt, ctx->tmp_a.p, nullptr));
+    else ST_TRY(gt_encap_exp_run(ctx, k.gt_a.buf.p, k.gt_a.wb, k.gt_tab_b.p, k.gt_b_wb, a.d_values, a.d_r, a.n, gt));
+  } else {
+    if (pol.use_tables) {
+      ST_TRY(g1_fb_table_run(ctx, a.d_com, k.fb_com.p, FB_WB_BATCH));
+      ST_TRY(encap_g1_fixed_run(ctx, k.fb_com.p, FB_WB_BATCH, k.fb_g1_gen.p, FB_WB_LONG, a.d_values, a.d_r, a.n, ctx->tmp_a.p));
+    } else {
+      ST_TRY(encap_g1_run(ctx, a.d_com, a.d_values, a.d_r, a.n, ctx->tmp_a.p));
+    }
+    ST_TRY(pairing_run(ctx, ctx->tmp_a.p, ctx->tmp_c.p, 0, a.n, gt, k.g2gen_lines.p));
+  }
+  if (a.d_key_out && a.msg_len) ST_TRY(blake3_gt_run(ctx, gt, a.n, a.d_key_out, a.msg_len, a.xor_into));
+  return KEAKI_OK;
+}
+static keaki_status encap_impl(keaki_hip_ctx* ctx, const EncapArgs& a) {
+  KemState& k = ctx->kem;
+  // a chunk of a larger batch takes the decisions of the whole batch (table widths, the GT path) and counts as ONE call with its commitment
+  const size_t n_policy = a.host ? a.host->n_batch : a.n;
+  const bool first_of_batch = !a.host || a.host->first;
+  ST_TRY(reserve(ctx, ctx->tmp_a, a.n * G1_AFF_BYTES));
+  if (!a.d_gt_out) ST_TRY(reserve(ctx, ctx->tmp_b, a.n * 384));
+  ST_TRY(generator_tables(ctx, n_policy >= FB_TABLES_MIN));
+  uint64_t tau_dev[16], com_dev[8];
+  const uint64_t *tau_host = a.host ? a.host->tau : tau_dev, *com_host = a.host ? a.host->com : com_dev;
+  if (!a.host) ST_TRY(read_constants(ctx, a.d_tau, a.d_com, tau_dev, com_dev));
+  note_commitment(k, com_host, first_of_batch);
+  const EncapPolicy pol = encap_policy(n_policy, ctx->tune.gt_wb_b, ctx->tune.encap_gt, k.seen_com_runs, k.gt_b_ready && k.gt_a.holds(com_host), false);
+  AuxBuild aux;
+  if (pol.use_gt) {
+    ST_TRY(b_table(ctx, pol.wb_b_req));
+    ST_TRY(a_table(ctx, a, com_host, first_of_batch, &aux));
+  }
+  ST_TRY(tau_table(ctx, pol.use_tables, a.d_tau, tau_host));
+  return encap_items(ctx, a, pol, tau_host, aux);
 }
 keaki_status keaki_hip_encap_batch_dev(keaki_hip_ctx* ctx, const void* d_com_aff, const void* d_tau_g2_aff, const void* d_points,
                                        const void* d_values, const void* d_r, size_t n, void* d_ct_out_aff, void* d_gt_out, void* d_key_out,
@@ -1138,7 +1133,7 @@ keaki_status keaki_hip_encap_batch_dev(keaki_hip_ctx* ctx, const void* d_com_aff
   if (n == 0) return KEAKI_OK;
   if (!d_com_aff || !d_tau_g2_aff || !d_points || !d_values || !d_r || !d_ct_out_aff || (!d_gt_out && !d_key_out) || msg_len > 65536)
     return fail(ctx, KEAKI_ERR_BAD_ARG, "encap_batch: bad argument");
-  return encap_impl(ctx, false, d_com_aff, d_tau_g2_aff, d_points, d_values, d_r, n, d_ct_out_aff, d_gt_out, d_key_out, msg_len);
+  return encap_impl(ctx, {d_com_aff, d_tau_g2_aff, d_points, d_values, d_r, d_ct_out_aff, d_gt_out, d_key_out, n, msg_len});
 }
 // Setup-time: everything of encap_batch that depends on the setup only, for batches of `batch_hint` items (the KEM analogue of
 // keaki_hip_srs_g1_precompute): fixed-base window tables of g1, g2 and [tau]_2, the line sequence of g2, and -- for hints >= 65,536 (or the
@@ -1150,7 +1145,7 @@ keaki_status keaki_hip_encap_prepare(keaki_hip_ctx* ctx, const uint64_t* tau_g2_
   if (!tau_g2_aff) return fail(ctx, KEAKI_ERR_BAD_ARG, "encap_prepare: null pointer");
   if (batch_hint == 0) return KEAKI_OK;
   ST_TRY(upload(ctx, ctx->io_e, tau_g2_aff, 128));
-  ST_TRY(encap_impl(ctx, true, nullptr, ctx->io_e.p, nullptr, nullptr, nullptr, batch_hint, nullptr, nullptr, nullptr, 0));
+  ST_TRY(kem_setup(ctx, ctx->io_e.p, batch_hint));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return KEAKI_OK;
 }
@@ -1180,7 +1175,7 @@ keaki_status keaki_hip_encap_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff, 
      {nullptr, want_key ? key_out : nullptr, msg_len}},
     [&](size_t lo, size_t m, char* const* hd, char* const* d) {
       const EncapHost eh = {com_aff, tau_g2_aff, n, lo == 0};
-      return encap_impl(ctx, false, hd[0], hd[1], d[0], d[1], d[2], m, d[3], d[4], want_key ? d[5] : nullptr, msg_len, false, &eh);
+      return encap_impl(ctx, {hd[0], hd[1], d[0], d[1], d[2], d[3], d[4], want_key ? d[5] : nullptr, m, msg_len, false, &eh});
     });
 }
 keaki_status keaki_hip_decap_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_aff, const uint64_t* cts_aff, size_t n, uint8_t* gt_out,
@@ -1209,7 +1204,7 @@ keaki_status keaki_hip_encrypt_batch_dev(keaki_hip_ctx* ctx, const void* d_com_a
   if (n == 0) return KEAKI_OK;
   if (!d_com_aff || !d_tau_g2_aff || !d_points || !d_values || !d_r || !d_ct_out_aff || !d_body_inout || msg_len == 0 || msg_len > 65536)
     return fail(ctx, KEAKI_ERR_BAD_ARG, "encrypt_batch: bad argument");
-  return encap_impl(ctx, false, d_com_aff, d_tau_g2_aff, d_points, d_values, d_r, n, d_ct_out_aff, nullptr, d_body_inout, msg_len, true);
+  return encap_impl(ctx, {d_com_aff, d_tau_g2_aff, d_points, d_values, d_r, d_ct_out_aff, nullptr, d_body_inout, n, msg_len, true});
 }
 keaki_status keaki_hip_decrypt_batch_dev(keaki_hip_ctx* ctx, const void* d_proofs_aff, const void* d_cts_aff, size_t n, void* d_body_inout, size_t msg_len) {
   CTX_GUARD(ctx);
@@ -1232,7 +1227,7 @@ keaki_status keaki_hip_encrypt_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff
     {{points, nullptr, 32}, {values, nullptr, 32}, {r, nullptr, 32}, {nullptr, ct_out_aff, G2_AFF_BYTES}, {msgs, body_out, msg_len}},
     [&](size_t lo, size_t m, char* const* hd, char* const* d) {
       const EncapHost eh = {com_aff, tau_g2_aff, n, lo == 0};
-      return encap_impl(ctx, false, hd[0], hd[1], d[0], d[1], d[2], m, d[3], nullptr, d[4], msg_len, true, &eh);
+      return encap_impl(ctx, {hd[0], hd[1], d[0], d[1], d[2], d[3], nullptr, d[4], m, msg_len, true, &eh});
     });
 }
 keaki_status keaki_hip_decrypt_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_aff, const uint64_t* cts_aff, const uint8_t* bodies, size_t n,
@@ -1717,27 +1712,21 @@ keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, c
   // base ladder of 0.99 ms in front of 1.38 ms of pairings.)
   // io block: [qs: g2 128 | Q 128] [in: com 64 | proof 64 | value 32 | point 32 | tau_g2 128] [ps: A 64 | proof 64] [gt 768]
   constexpr size_t O_Q = 0, O_IN = 256, O_P = O_IN + 320, O_GT = O_P + 128, IO_BYTES = O_GT + 768;
-  constexpr uint32_t WB = 8;
-  if (!ctx->verify_ready) {
-    ST_TRY(reserve(ctx, ctx->verify_io, IO_BYTES));
-    ST_TRY(g2_generator_to(ctx, (char*)ctx->verify_io.p + O_Q));
-    ctx->verify_ready = true;               // only after every step succeeded (a failed init is retried by the next call)
+  KemState& k = ctx->kem;
+  if (!k.verify_ready) {
+    ST_TRY(reserve(ctx, k.verify_io, IO_BYTES));
+    ST_TRY(g2_generator_to(ctx, (char*)k.verify_io.p + O_Q));
+    k.verify_ready = true;                  // only after every step succeeded (a failed init is retried by the next call)
   }
-  char* io = (char*)ctx->verify_io.p;
-  if (!ctx->verify_tables_ready) {
-    const size_t FBX = fb_table_entries(WB);
-    ST_TRY(reserve(ctx, ctx->fbs_g1_gen, FBX * G1_AFF_BYTES + G1_AFF_BYTES));
-    void* g1pt = (char*)ctx->fbs_g1_gen.p + FBX * G1_AFF_BYTES;
+  char* io = (char*)k.verify_io.p;
+  if (!k.verify_tables_ready) {
+    const size_t FBX = fb_table_entries(FB_WB_SMALL);
+    ST_TRY(reserve(ctx, k.fbs_g1_gen, FBX * G1_AFF_BYTES + G1_AFF_BYTES));
+    void* g1pt = (char*)k.fbs_g1_gen.p + FBX * G1_AFF_BYTES;
     ST_TRY(g1_generator_to(ctx, g1pt));
-    ST_TRY(g1_fb_table_run(ctx, g1pt, ctx->fbs_g1_gen.p, WB));
-    if (!ctx->fbs_ready) {                  // shared with the small-batch path of encapsulate (which also keeps [tau]_2's table there)
-      ST_TRY(reserve(ctx, ctx->fbs_g2_gen, FBX * G2_AFF_BYTES));
-      ST_TRY(reserve(ctx, ctx->fbs_tau, FBX * G2_AFF_BYTES));
-      ST_TRY(g2_fb_table_run(ctx, io + O_Q, ctx->fbs_g2_gen.p, WB));
-      ctx->fbs_ready = true;
-      ctx->fbs_tau_valid = false;
-    }
-    ctx->verify_tables_ready = true;
+    ST_TRY(g1_fb_table_run(ctx, g1pt, k.fbs_g1_gen.p, FB_WB_SMALL));
+    ST_TRY(small_g2_tables(ctx, io + O_Q));   // shared with the small-batch path of encapsulate (which also keeps [tau]_2's table there)
+    k.verify_tables_ready = true;
   }
   uint64_t in[40];
   memcpy(in, com_aff, 64);
@@ -1747,7 +1736,7 @@ keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, c
   memcpy(in + 24, tau_g2_aff, 128);
   HIP_TRY(ctx, hipMemcpyAsync(io + O_IN, in, 320, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(io + O_P + 64, io + O_IN + 64, 64, hipMemcpyDeviceToDevice, ctx->stream));      // the proof into the pairing's first slot
-  ST_TRY(verify_points_run(ctx, ctx->fbs_g1_gen.p, ctx->fbs_g2_gen.p, WB, io + O_IN, io + O_IN + 192, io + O_IN + 128, io + O_IN + 160, io + O_P, io + O_Q + 128));
+  ST_TRY(verify_points_run(ctx, k.fbs_g1_gen.p, k.fbs_g2_gen.p, FB_WB_SMALL, io + O_IN, io + O_IN + 192, io + O_IN + 128, io + O_IN + 160, io + O_P, io + O_Q + 128));
   ST_TRY(pairing_run(ctx, io + O_P, io + O_Q, 1, 2, io + O_GT));
   uint8_t gt[768];
   ST_TRY(download(ctx, gt, io + O_GT, 768));                                       // synchronises: `in` stays alive until here

@@ -21,10 +21,6 @@ struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
 };
-
-}  // namespace keaki_internal
-
-namespace keaki_internal {
 // Widest forced windows. A plan with more than 2^22 buckets to sort (generic: the buckets of all windows; window tables: those of the largest
 // window) is beyond the two-pass bucket sort (msm.hip.h: part_make_shape, 2^11 bins of 2^11 buckets): generic 20 .. 24 and shared 24 bits
 // could never run. msm_g2.hip checks both limits against the plans. keaki_hip_ctx_set_option refuses the widths between a limit and 24,
@@ -66,6 +62,43 @@ struct Tuning {
 #endif
   size_t alloc_limit = 0;        // keaki_hip_debug_set_alloc_limit: single allocations above it fail with KEAKI_ERR_OOM; 0 = none
 };
+// A device table that belongs to ONE point, its key (the W affine words of the point): the window tables of [tau]_2 and the GT table of a
+// commitment. A rebuild runs invalidate() -> launches -> publish(), so a build that failed half way is never taken for valid.
+template <int W>
+struct KeyedTable {
+  DevBuf buf;
+  bool valid = false;
+  uint32_t wb = 0;                        // window bits of the table in buf
+  uint64_t key[W] = {};
+  bool holds(const uint64_t* k) const { return valid && memcmp(k, key, sizeof(key)) == 0; }
+  void invalidate() { valid = false; }
+  void publish(const uint64_t* k, uint32_t bits) { memcpy(key, k, sizeof(key)); wb = bits; valid = true; }
+};
+// The cache of encapsulate and kzg verify (api.hip: the KEM composites, keaki_hip_kzg_verify). A table built once per context stands beside its
+// ready bit, which is set only after EVERY step of the build succeeded; the tables of one point are KeyedTables.
+struct KemState {
+  // 16-bit window tables for batches of >= 256 items: of the generators (with room for the 13-bit table that the per-item-pairing path rebuilds for
+  // each batch's commitment) and of [tau]_2 | small (8-bit) tables for smaller batches and kzg verify: of g2 and [tau]_2 | of g1 (verify only)
+  DevBuf fb_g1_gen, fb_g2_gen, fb_com, fbs_g2_gen, fbs_g1_gen;
+  bool fb_ready = false, fbs_ready = false, verify_tables_ready = false;
+  KeyedTable<16> fb_tau, fbs_tau;
+  // kzg verify's small in/out block | line sequence of g2 | line tables and points of 2^s g2, s < 320 (api.hip: g2pow_tables)
+  DevBuf verify_io, g2gen_lines, g2pow_lines, g2pow_pts;
+  bool verify_ready = false, g2gen_lines_ready = false, g2pow_ready = false;
+  // GT tables: B = e(g1, g2) once per context at gt_b_wb bits, A = e(C, g2) per commitment; gt_base holds the powers of the LAST table built
+  DevBuf gt_base, gt_tab_b;
+  bool gt_b_ready = false, gt_b_fallback = false;   // fallback: the wide table of B did not fit once, stay at 16 bits
+  uint32_t gt_b_wb = 0;
+  KeyedTable<8> gt_a;
+  bool gt_a_pending_aux = false;          // the A-table build on aux_stream has not been waited for by `stream` yet (api.hip: wait_aux)
+  uint64_t seen_com[8] = {};              // commitment of the last encap call and how many consecutive calls carried it
+  uint32_t seen_com_runs = 0;
+  // every DevBuf above with its memory class (keaki_hip_ctx_memory: 1 = workspace, 2 = GT / fixed-base tables): a new table is added HERE
+  template <class F> void for_each_buf(F&& f) {
+    for (DevBuf* b : {&g2gen_lines, &g2pow_lines, &g2pow_pts, &verify_io}) f(b, 1);
+    for (DevBuf* b : {&fb_g1_gen, &fb_g2_gen, &fb_com, &fb_tau.buf, &fbs_g2_gen, &fbs_tau.buf, &fbs_g1_gen, &gt_a.buf, &gt_tab_b, &gt_base}) f(b, 2);
+  }
+};
 }  // namespace keaki_internal
 
 struct keaki_hip_ctx {
@@ -79,36 +112,13 @@ struct keaki_hip_ctx {
   bool own_stream = false;
   std::recursive_mutex mu;   // recursive: host-pointer entry points hold it across stage -> *_dev -> download
   std::string err;
-  // grow-only workspaces (all used in stream order)
-  keaki_internal::DevBuf digits, hist, offsets, cursor, sorted, buckets, acc29, partials, wsums, bsums, tmp_a, tmp_b, tmp_c, io_a, io_b, io_c, io_d, io_e;
-  // fixed-base window tables for encapsulate: generator tables are built once per context, the C / [tau]_2 tables per batch
-  keaki_internal::DevBuf fb_bases, fb_g1_gen, fb_g2_gen, fb_com, fb_tau, perm, g2gen_lines, gt_tab_a, gt_tab_b, gt_base, heavy;
-  bool gt_b_ready = false;
-  bool gt_a_valid = false;
-  bool gt_a_pending_aux = false;          // the A-table build on aux_stream has not been waited for by `stream` yet (api.hip: encap_impl)
-  bool gt_b_fallback = false;             // the wide table of B did not fit once: stay at 16 bits
-  uint64_t seen_com[8] = {};              // commitment of the last encap call and how many consecutive calls carried it
-  uint32_t seen_com_runs = 0;
-  uint32_t gt_a_wb = 0, gt_b_wb = 0;      // window widths of the GT tables in gt_tab_a / gt_tab_b
-  // line tables of 2^s g2, s < 320 (built once per context): e(C, g2)^(2^s) = e(C, 2^s g2) -- the powers behind a commitment's GT table are
-  // pairings of ONE point with fixed second arguments, no doubling chain of C in front of them
-  keaki_internal::DevBuf g2pow_lines, g2pow_pts;
-  bool g2pow_ready = false;
+  // grow-only workspaces (all used in stream order); fb_bases: scratch of g1/g2_fb_table_run
+  keaki_internal::DevBuf digits, hist, offsets, cursor, sorted, buckets, acc29, partials, wsums, bsums, tmp_a, tmp_b, tmp_c, io_a, io_b, io_c, io_d, io_e, perm, heavy, fb_bases;
+  keaki_internal::KemState kem;                     // every cached table of encapsulate and kzg verify
   keaki_internal::DevBuf pair_ws;                   // per-item slots of the final exponentiation (pairing.hip.h)
   keaki_internal::DevBuf fk_tab;                    // window tables of the per-lane-scalar ladders of FK23: 1 KB per lane of a launch (64 x 16 B), at most 2 GB (fft_g1.hip)
-  keaki_internal::DevBuf verify_io;                 // kzg verify: small in/out block
   keaki_internal::DevBuf mb_canon, mb_wsums, mb_q;  // batched MSM / open (msm_batch.hip): biased canonical scalars of a pass (32 B each) | window sums (128 B per row and window) | quotient rows of open_batch
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
-  bool verify_ready = false;
-  bool verify_tables_ready = false;       // 8-bit window tables of g1 (fbs_g1_gen) and g2 (fbs_g2_gen) for the reference-form verify              // set only after every init step of kzg verify succeeded
-  bool fb_tau_valid = false;          // window table of [tau]_2 (encap ciphertext side) is for this point
-  uint64_t fb_tau_pt[16] = {};
-  uint64_t gt_a_com[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // commitment the cached A-table belongs to
-  bool g2gen_lines_ready = false;
-  bool fb_ready = false;
-  keaki_internal::DevBuf fbs_g2_gen, fbs_tau, fbs_g1_gen;     // small (8-bit) tables of g2 and [tau]_2 for batches below 256 items
-  bool fbs_ready = false, fbs_tau_valid = false;
-  uint64_t fbs_tau_pt[16] = {};
   // instrumentation
   bool timing = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
