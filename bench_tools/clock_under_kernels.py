@@ -55,7 +55,7 @@ mont_fr = lambda v: np.frombuffer(((v << 256) % R_MOD).to_bytes(32, "little"), n
 om, omi, inv2d = mont_fr(w2d), mont_fr(pow(w2d, -1, R_MOD)), mont_fr(pow(2 * d, -1, R_MOD))
 fsrs = hip.srs_g1_wrap_dev(d_pts.data_ptr(), d)
 coeffs = random_fr_limbs(d, SEED + 4242)
-hip._ck(hip.lib.keaki_hip_srs_g1_precompute_fk(hip.ctx, fsrs.handle, lg, om.ctypes.data_as(C.c_void_p)))
+hip.srs_g1_precompute_fk(fsrs, lg, om)
 hip.open_fk_poly(fsrs, lg, coeffs, om, omi, inv2d)
 import threading
 for _ in range(2):

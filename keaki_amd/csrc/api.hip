@@ -14,34 +14,24 @@ using namespace keaki_internal;
 
 // An SRS handle is device memory, not context state: every context ON THE SAME DEVICE may pass it to msm / open / open_fk (read-only use
 // of the points, the window tables and the cached FK23 transform), so N host threads with a context each share ONE set of tables.
-// `mu` guards the lazily built members (table, fk_hat_s); `acct` is the context whose keaki_hip_ctx_memory counts them.
-struct keaki_hip_srs_g1 {
+// `mu` guards the lazily built members (table, fk); `acct` is the context whose keaki_hip_ctx_memory counts them.
+struct SrsHandle {
   const void* d = nullptr;
   size_t n = 0;
   bool owned = false;
   int device = -1;
   std::recursive_mutex mu;
   keaki_hip_ctx* acct = nullptr;
-  size_t fk_bytes = 0;
-  // precomputed window tables (keaki_hip_srs_g1_precompute): table[w * n + i] = 2^(offset_w) * P_i
+  // precomputed window tables (keaki_hip_srs_g*_precompute): table[w * n + i] = 2^(offset_w) * P_i
   void* table = nullptr;
   size_t table_bytes = 0;
   int c_table = 0;
-  // FK23: hat_s = DFT_2d(reversed SRS) for the last requested d (2d Jacobian points), reused by later keaki_hip_open_fk calls
-  void* fk_hat_s = nullptr;
-  int fk_log2d = -1;
 };
-struct keaki_hip_srs_g2 {
-  const void* d = nullptr;
-  size_t n = 0;
-  bool owned = false;
-  int device = -1;
-  std::recursive_mutex mu;
-  keaki_hip_ctx* acct = nullptr;
-  void* table = nullptr;          // window tables (keaki_hip_srs_g2_precompute), as for G1
-  size_t table_bytes = 0;
-  int c_table = 0;
-};
+// FK23: hat_s = DFT_2d(reversed SRS) for the last requested d (2d Jacobian points), reused by later FK23 calls on the handle. Owned by
+// fk_cache_ensure: log2d names a transform only when its build was enqueued in full, bytes is what hat_s holds (and `acct` counts).
+struct FkCache { void* hat_s = nullptr; int log2d = -1; size_t bytes = 0; };
+struct keaki_hip_srs_g1 : SrsHandle { FkCache fk; };
+struct keaki_hip_srs_g2 : SrsHandle {};
 
 #include <dlfcn.h>
 #include <sys/mman.h>
@@ -168,21 +158,15 @@ keaki_status download(keaki_hip_ctx* ctx, void* host, const void* dev, size_t by
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return KEAKI_OK;
 }
+// Drains `s` when the scope is left while armed: a FAILING host-form call, too, returns only when no copy reads the caller's arrays any more
+// and nothing of it is left on a side stream. The successful path disarms it where its own download synchronises.
+struct StreamFence { hipStream_t s; bool armed; ~StreamFence() { if (armed) (void)hipStreamSynchronize(s); } };
 
 // (table, window target) of a handle, read under its lock: another context may be building the tables right now
 template <class H>
 std::pair<const void*, int> srs_tables(const H* srs) {
   std::lock_guard<std::recursive_mutex> hl(const_cast<H*>(srs)->mu);
   return {srs->table, srs->c_table};
-}
-// bookkeeping after a call that may have (re)built the cached FK23 transform of a handle (2d Jacobian points)
-void fk_account(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs) {
-  const size_t now = srs->fk_hat_s && srs->fk_log2d >= 0 ? ((size_t)2 << srs->fk_log2d) * 96 : 0;
-  if (now == srs->fk_bytes) return;
-  if (!srs->acct) srs->acct = ctx;
-  const size_t before = srs->fk_bytes;
-  with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });   // whichever context rebuilt it
-  srs->fk_bytes = now;
 }
 template <class H>
 H* new_srs(keaki_hip_ctx* ctx, const void* d, size_t n, bool owned) {
@@ -194,6 +178,50 @@ H* new_srs(keaki_hip_ctx* ctx, const void* d, size_t n, bool owned) {
 #define SRS_CHECK(ctx, srs, what)                                                                                                     \
   if ((srs)->device != (ctx)->device)                                                                                                 \
     return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: the SRS handle lives on device %d, this context on device %d", what, (srs)->device, (ctx)->device)
+// ... and must hold the k points the call reads: `too_short` is the message of the MSM family or of the FK23 family
+constexpr const char *SRS_SHORT_MSM = "msm: %zu scalars but the SRS holds %zu points", *SRS_SHORT_FK = "open_fk: %zu coefficients but the SRS holds %zu points";
+keaki_status srs_holds(keaki_hip_ctx* ctx, const SrsHandle* srs, const char* what, size_t k, const char* too_short) {
+  SRS_CHECK(ctx, srs, what);
+  if (k > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, too_short, k, srs->n);
+  return KEAKI_OK;
+}
+// The ONE owner of a G1 handle's cached FK23 transform: afterwards srs->fk.hat_s is the transform for d = 2^log2d. d_tw: omega_2d^k, k < d,
+// ready in stream order; the caller holds srs->mu. A transform for another d is dropped first (after the stream's work that may read it), the
+// new one is allocated through dev_alloc and named (log2d) only once its build is enqueued; on every exit -- a refused allocation
+// included -- fk.bytes and the `tables` count of the handle's accounting context (srs->acct, as for the window tables) say what hat_s holds.
+keaki_status fk_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_tw) {
+  FkCache& c = srs->fk;
+  if (c.log2d == (int)log2d) return KEAKI_OK;
+  auto book = [&](size_t now) {
+    const size_t before = c.bytes;
+    with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
+    c.bytes = now;
+  };
+  c.log2d = -1;
+  if (c.hat_s) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.hat_s); c.hat_s = nullptr; book(0); }
+  const size_t bytes = ((size_t)2 << log2d) * G1_JAC_BYTES;
+  ST_TRY(dev_alloc(ctx, &c.hat_s, bytes));
+  book(bytes);
+  ST_TRY(fk_hat_s_run(ctx, srs->d, log2d, d_tw, c.hat_s));
+  c.log2d = (int)log2d;
+  return KEAKI_OK;
+}
+// How every FK23 entry starts: its pointers are there (`args_ok`) and log2d is in range, the handle lives on this device and holds the
+// d = 2^log2d points, and `hl` takes the handle's lock: the cached transform belongs to the handle, one FK23 call per handle at a time.
+keaki_status fk_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, const char* what, std::unique_lock<std::recursive_mutex>& hl) {
+  if (!srs || !args_ok || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", what);
+  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, SRS_SHORT_FK));
+  hl = std::unique_lock<std::recursive_mutex>(srs->mu);
+  return KEAKI_OK;
+}
+// the d openings of the polynomial at d_p (d Fr, device) -> d_proofs_aff: scalar half, the handle's transform, point half, in that order
+keaki_status open_fk_from_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_p, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
+                               const uint64_t* inv_2d, void* d_fr_work, void* d_g_work, void* d_proofs_aff) {
+  FkPolyScalars s;
+  ST_TRY(open_fk_poly_scalars_run(ctx, log2d, d_p, omega_2d, omega_2d_inv, inv_2d, d_fr_work, &s));
+  ST_TRY(fk_cache_ensure(ctx, srs, log2d, s.tw));
+  return open_fk_run(ctx, srs->fk.hat_s, log2d, s.hat_a, s.tw, s.twi, d_g_work, d_proofs_aff);
+}
 
 // The caller's OUTPUT buffer is usually fresh memory (calloc / vec![0; n] / numpy.zeros): its pages do not exist until first touched, and a
 // device-to-host copy into such pages crawls (160 MB of ciphertexts: 30 ms instead of 3). Touch one byte per page from the host WHILE the
@@ -389,18 +417,18 @@ static std::vector<size_t> msm_pipe_bounds(const Tuning& t, size_t n) {
   return b;
 }
 // the copy-stream side of a chunked upload: `begin` orders the copy stream behind the context's stream, `chunk` copies one piece and makes
-// the context's stream wait for it; on every exit no copy reads the caller's array any more (the destructor drains the copy stream)
+// the context's stream wait for it; on every exit no copy reads the caller's array any more (the fence drains the copy stream)
 struct ChunkUploader {
   keaki_hip_ctx* ctx;
   hipStream_t cs = nullptr;
+  StreamFence fence{nullptr, false};
   explicit ChunkUploader(keaki_hip_ctx* c) : ctx(c) {}
-  ~ChunkUploader() { if (cs) (void)hipStreamSynchronize(cs); }
   keaki_status begin() {
     ST_TRY(pipe_ready(ctx));
     // the copy stream starts behind whatever the context's stream holds (an earlier call's kernels may still read the destination)
     HIP_TRY(ctx, hipEventRecord(ctx->pipe_done[0], ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->pipe_done[0], 0));
-    cs = ctx->copy_stream;
+    fence.s = cs = ctx->copy_stream; fence.armed = true;
     return KEAKI_OK;
   }
   keaki_status chunk(size_t j, void* dst, const void* src, size_t bytes) {
@@ -440,15 +468,72 @@ static keaki_status msm_from_host(keaki_hip_ctx* ctx, const uint64_t* scalars, s
   keaki_internal::DeviceScope dev_((ctx)->device);              \
   if (!dev_.ok) return fail(ctx, KEAKI_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
 
-// What tells the G1 and G2 forms of the MSM and mul_batch entries apart: the point sizes, the launchers and the names in messages and traces.
+// What tells the G1 and G2 forms of the SRS, MSM and mul_batch entries apart: the point sizes, the launchers and the names in messages and traces.
 struct GroupEntries {
   size_t aff, jac;
-  const char *msm, *msm_trace, *mul, *mul_trace;
+  const char *srs, *precompute, *msm, *msm_trace, *mul, *mul_trace;
   decltype(&msm_g1_run) msm_run;
+  decltype(&msm_g1_precompute_run) precompute_run;
   decltype(&g1_mul_batch_run) mul_run;
 };
-constexpr GroupEntries G1E = {G1_AFF_BYTES, G1_JAC_BYTES, "msm_g1", "keaki.msm_g1", "g1_mul_batch", "keaki.g1_mul_batch", msm_g1_run, g1_mul_batch_run};
-constexpr GroupEntries G2E = {G2_AFF_BYTES, G2_JAC_BYTES, "msm_g2", "keaki.msm_g2", "g2_mul_batch", "keaki.g2_mul_batch", msm_g2_run, g2_mul_batch_run};
+constexpr GroupEntries G1E = {G1_AFF_BYTES, G1_JAC_BYTES, "srs_g1", "srs_g1_precompute", "msm_g1", "keaki.msm_g1", "g1_mul_batch", "keaki.g1_mul_batch", msm_g1_run, msm_g1_precompute_run, g1_mul_batch_run};
+constexpr GroupEntries G2E = {G2_AFF_BYTES, G2_JAC_BYTES, "srs_g2", "srs_g2_precompute", "msm_g2", "keaki.msm_g2", "g2_mul_batch", "keaki.g2_mul_batch", msm_g2_run, msm_g2_precompute_run, g2_mul_batch_run};
+// ---- SRS handles: the eight keaki_hip_srs_g*_ entries forward here ----
+template <class H>
+keaki_status srs_upload(const GroupEntries& g, keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, H** out) {
+  CTX_GUARD(ctx);
+  if (!out || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s_upload: null pointer", g.srs);
+  void* d = nullptr;
+  HIP_TRY(ctx, hipMalloc(&d, n ? n * g.aff : 16));          // the caller's points: outside keaki_hip_debug_set_alloc_limit (internal.h: dev_alloc)
+  if (n) {
+    // on the context's stream (non-blocking: not ordered behind the null stream a plain hipMemcpy uses), complete before the call returns
+    hipError_t e = hipMemcpyAsync(d, points_aff, n * g.aff, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, KEAKI_ERR_HIP, "srs upload copy failed: %s", hipGetErrorString(e)); }
+  }
+  *out = new_srs<H>(ctx, d, n, true);
+  return KEAKI_OK;
+}
+template <class H>
+keaki_status srs_wrap(const GroupEntries& g, keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, H** out) {
+  CTX_GUARD(ctx);
+  if (!out || (n && !d_points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s_wrap_dev: null pointer", g.srs);
+  *out = new_srs<H>(ctx, d_points_aff, n, false);
+  return KEAKI_OK;
+}
+template <class H>
+void srs_free(keaki_hip_ctx* ctx, H* srs) {
+  if (!srs) return;
+  if (ctx) { keaki_internal::DeviceScope dc_(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+  keaki_internal::DeviceScope dev_(srs->device);
+  if (srs->owned && srs->d) (void)hipFree((void*)srs->d);
+  if (srs->table) (void)hipFree(srs->table);
+  size_t held = srs->table_bytes;          // booked on the context that built them, whichever context (or NULL) frees the handle
+  if constexpr (std::is_same_v<H, keaki_hip_srs_g1>) {
+    if (srs->fk.hat_s) (void)hipFree(srs->fk.hat_s);
+    held += srs->fk.bytes;
+  }
+  with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, held); });
+  delete srs;
+}
+template <class H>
+keaki_status srs_precompute(const GroupEntries& g, keaki_hip_ctx* ctx, H* srs, size_t* table_bytes_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.srs_precompute");
+  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: srs is null", g.precompute);
+  SRS_CHECK(ctx, srs, g.precompute);
+  std::lock_guard<std::recursive_mutex> hl(srs->mu);       // contexts sharing the handle: the first one builds, the others find the tables
+  if (!srs->table && srs->n) {
+    int c = 0; size_t bytes = 0; void* t = nullptr;
+    ST_TRY(g.precompute_run(ctx, srs->d, srs->n, &c, &bytes, &t));
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(t); return fail(ctx, KEAKI_ERR_HIP, "%s: %s", g.precompute, hipGetErrorString(e)); }
+    srs->c_table = c; srs->table_bytes = bytes; srs->table = t;       // published only when complete
+    srs->acct = ctx; ctx->mem_tables += bytes;
+  }
+  if (table_bytes_out) *table_bytes_out = srs->table_bytes;
+  return KEAKI_OK;
+}
 template <class Srs>
 keaki_status msm_dev(const GroupEntries& g, keaki_hip_ctx* ctx, const Srs* srs, const void* d_scalars, size_t n, void* d_out_jac) {
   CTX_GUARD(ctx);
@@ -463,8 +548,7 @@ keaki_status msm_host(const GroupEntries& g, keaki_hip_ctx* ctx, const Srs* srs,
   CTX_GUARD(ctx);
   TRACE_SCOPE(g.msm_trace);
   if (!srs || !out_jac || (n && !scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", g.msm);
-  SRS_CHECK(ctx, srs, g.msm);
-  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
+  ST_TRY(srs_holds(ctx, srs, g.msm, n, SRS_SHORT_MSM));
   ST_TRY(reserve(ctx, ctx->io_b, g.jac));
   const auto tb = srs_tables(srs);
   ST_TRY(msm_from_host(ctx, scalars, n, [&](const MsmPipe* pipe) {
@@ -713,26 +797,14 @@ float keaki_hip_last_msm_total_ms(const keaki_hip_ctx* ctx) { return ctx ? ctx->
 int32_t keaki_hip_last_msm_window_bits(const keaki_hip_ctx* ctx) { return ctx ? ctx->last_c : 0; }
 
 // ---- SRS -----------------------------------------------------------------------------------------
-keaki_status keaki_hip_srs_g1_upload(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, keaki_hip_srs_g1** out) {
-  CTX_GUARD(ctx);
-  if (!out || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g1_upload: null pointer");
-  void* d = nullptr;
-  HIP_TRY(ctx, hipMalloc(&d, n ? n * G1_AFF_BYTES : 16));
-  if (n) {
-    // on the context's stream (non-blocking: not ordered behind the null stream a plain hipMemcpy uses), complete before the call returns
-    hipError_t e = hipMemcpyAsync(d, points_aff, n * G1_AFF_BYTES, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, KEAKI_ERR_HIP, "srs upload copy failed: %s", hipGetErrorString(e)); }
-  }
-  *out = new_srs<keaki_hip_srs_g1>(ctx, d, n, true);
-  return KEAKI_OK;
-}
-keaki_status keaki_hip_srs_g1_wrap_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, keaki_hip_srs_g1** out) {
-  CTX_GUARD(ctx);
-  if (!out || (n && !d_points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g1_wrap_dev: null pointer");
-  *out = new_srs<keaki_hip_srs_g1>(ctx, d_points_aff, n, false);
-  return KEAKI_OK;
-}
+keaki_status keaki_hip_srs_g1_upload(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, keaki_hip_srs_g1** out) { return srs_upload(G1E, ctx, points_aff, n, out); }
+keaki_status keaki_hip_srs_g2_upload(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, keaki_hip_srs_g2** out) { return srs_upload(G2E, ctx, points_aff, n, out); }
+keaki_status keaki_hip_srs_g1_wrap_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, keaki_hip_srs_g1** out) { return srs_wrap(G1E, ctx, d_points_aff, n, out); }
+keaki_status keaki_hip_srs_g2_wrap_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, keaki_hip_srs_g2** out) { return srs_wrap(G2E, ctx, d_points_aff, n, out); }
+void keaki_hip_srs_g1_free(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs) { srs_free(ctx, srs); }
+void keaki_hip_srs_g2_free(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs) { srs_free(ctx, srs); }
+keaki_status keaki_hip_srs_g1_precompute(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, size_t* table_bytes_out) { return srs_precompute(G1E, ctx, srs, table_bytes_out); }
+keaki_status keaki_hip_srs_g2_precompute(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t* table_bytes_out) { return srs_precompute(G2E, ctx, srs, table_bytes_out); }
 // non-owning view of points [offset, offset + n) of an uploaded SRS: the chunk a rank owns when an MSM is sharded by point range
 keaki_status keaki_hip_srs_g1_slice(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, size_t offset, size_t n, keaki_hip_srs_g1** out) {
   CTX_GUARD(ctx);
@@ -743,80 +815,6 @@ keaki_status keaki_hip_srs_g1_slice(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* 
   return KEAKI_OK;
 }
 size_t keaki_hip_srs_g1_len(const keaki_hip_srs_g1* srs) { return srs ? srs->n : 0; }
-void keaki_hip_srs_g1_free(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs) {
-  if (!srs) return;
-  if (ctx) { keaki_internal::DeviceScope dc_(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
-  keaki_internal::DeviceScope dev_(srs->device);
-  if (srs->owned && srs->d) (void)hipFree((void*)srs->d);
-  if (srs->table) (void)hipFree(srs->table);
-  if (srs->fk_hat_s) (void)hipFree(srs->fk_hat_s);
-  const size_t held = srs->table_bytes + srs->fk_bytes;          // booked on the context that built them, whichever context (or NULL) frees the handle
-  with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, held); });
-  delete srs;
-}
-keaki_status keaki_hip_srs_g1_precompute(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, size_t* table_bytes_out) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.srs_precompute");
-  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g1_precompute: srs is null");
-  SRS_CHECK(ctx, srs, "srs_g1_precompute");
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);       // contexts sharing the handle: the first one builds, the others find the tables
-  if (!srs->table && srs->n) {
-    int c = 0; size_t bytes = 0; void* t = nullptr;
-    ST_TRY(msm_g1_precompute_run(ctx, srs->d, srs->n, &c, &bytes, &t));
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(t); return fail(ctx, KEAKI_ERR_HIP, "srs_g1_precompute: %s", hipGetErrorString(e)); }
-    srs->c_table = c; srs->table_bytes = bytes; srs->table = t;       // published only when complete
-    srs->acct = ctx; ctx->mem_tables += bytes;
-  }
-  if (table_bytes_out) *table_bytes_out = srs->table_bytes;
-  return KEAKI_OK;
-}
-keaki_status keaki_hip_srs_g2_upload(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, keaki_hip_srs_g2** out) {
-  CTX_GUARD(ctx);
-  if (!out || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g2_upload: null pointer");
-  void* d = nullptr;
-  HIP_TRY(ctx, hipMalloc(&d, n ? n * G2_AFF_BYTES : 16));
-  if (n) {
-    hipError_t e = hipMemcpyAsync(d, points_aff, n * G2_AFF_BYTES, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, KEAKI_ERR_HIP, "srs upload copy failed: %s", hipGetErrorString(e)); }
-  }
-  *out = new_srs<keaki_hip_srs_g2>(ctx, d, n, true);
-  return KEAKI_OK;
-}
-keaki_status keaki_hip_srs_g2_wrap_dev(keaki_hip_ctx* ctx, const void* d_points_aff, size_t n, keaki_hip_srs_g2** out) {
-  CTX_GUARD(ctx);
-  if (!out || (n && !d_points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g2_wrap_dev: null pointer");
-  *out = new_srs<keaki_hip_srs_g2>(ctx, d_points_aff, n, false);
-  return KEAKI_OK;
-}
-void keaki_hip_srs_g2_free(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs) {
-  if (!srs) return;
-  if (ctx) { keaki_internal::DeviceScope dc_(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
-  keaki_internal::DeviceScope dev_(srs->device);
-  if (srs->owned && srs->d) (void)hipFree((void*)srs->d);
-  if (srs->table) (void)hipFree(srs->table);
-  const size_t held = srs->table_bytes;
-  with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, held); });
-  delete srs;
-}
-keaki_status keaki_hip_srs_g2_precompute(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t* table_bytes_out) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.srs_precompute");
-  if (!srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g2_precompute: srs is null");
-  SRS_CHECK(ctx, srs, "srs_g2_precompute");
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);
-  if (!srs->table && srs->n) {
-    int c = 0; size_t bytes = 0; void* t = nullptr;
-    ST_TRY(msm_g2_precompute_run(ctx, srs->d, srs->n, &c, &bytes, &t));
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(t); return fail(ctx, KEAKI_ERR_HIP, "srs_g2_precompute: %s", hipGetErrorString(e)); }
-    srs->c_table = c; srs->table_bytes = bytes; srs->table = t;
-    srs->acct = ctx; ctx->mem_tables += bytes;
-  }
-  if (table_bytes_out) *table_bytes_out = srs->table_bytes;
-  return KEAKI_OK;
-}
 
 // ---- MSM -----------------------------------------------------------------------------------------
 keaki_status keaki_hip_msm_g1_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_scalars, size_t n, void* d_out_jac) {
@@ -1250,13 +1248,11 @@ keaki_status keaki_hip_open_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32
                                const uint64_t* tw_2d_inv, const uint64_t* tw_d, uint64_t* proofs_out_aff) {
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.open_fk");
-  if (!srs || !hat_a || !tw_2d || !tw_2d_inv || !proofs_out_aff || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "open_fk: bad argument");
-  SRS_CHECK(ctx, srs, "open_fk");
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);        // the cached transform hat_s belongs to the handle: one FK23 call per handle at a time
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fk_enter(ctx, srs, log2d, hat_a && tw_2d && tw_2d_inv && proofs_out_aff, "open_fk", hl));
   const size_t d = (size_t)1 << log2d;
-  if (d > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "open_fk: %zu coefficients but the SRS holds %zu points", d, srs->n);
   // one staging buffer: hat_a (2d Fr) | tw_2d (d) | tw_2d_inv (d) | tw_d (d/2) | work (2d Jacobian) | proofs (d affine)
-  const size_t o_ha = 0, o_t1 = o_ha + 2 * d * 32, o_t2 = o_t1 + d * 32, o_t3 = o_t2 + d * 32, o_w = o_t3 + (d / 2 + 1) * 32, o_p = o_w + 2 * d * 96,
+  const size_t o_ha = 0, o_t1 = o_ha + 2 * d * 32, o_t2 = o_t1 + d * 32, o_t3 = o_t2 + d * 32, o_w = o_t3 + (d / 2 + 1) * 32, o_p = o_w + open_fk_poly_g_bytes(log2d),
                total = o_p + d * 64;
   ST_TRY(reserve(ctx, ctx->io_d, total));
   char* b = (char*)ctx->io_d.p;
@@ -1265,14 +1261,8 @@ keaki_status keaki_hip_open_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32
   HIP_TRY(ctx, hipMemcpyAsync(b + o_t1, tw_2d, d * 32, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(b + o_t2, tw_2d_inv, d * 32, hipMemcpyHostToDevice, st));
   (void)tw_d;                       // the size-d transforms take every second entry of the 2d tables
-  if (srs->fk_log2d != (int)log2d) {
-    if (srs->fk_hat_s) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void)hipFree(srs->fk_hat_s); srs->fk_hat_s = nullptr; srs->fk_log2d = -1; }
-    HIP_TRY(ctx, hipMalloc(&srs->fk_hat_s, 2 * d * 96));
-    ST_TRY(fk_hat_s_run(ctx, srs->d, log2d, b + o_t1, srs->fk_hat_s));
-    srs->fk_log2d = (int)log2d;
-    fk_account(ctx, srs);
-  }
-  ST_TRY(open_fk_run(ctx, srs->fk_hat_s, log2d, b + o_ha, b + o_t1, b + o_t2, b + o_w, b + o_p));
+  ST_TRY(fk_cache_ensure(ctx, srs, log2d, b + o_t1));
+  ST_TRY(open_fk_run(ctx, srs->fk.hat_s, log2d, b + o_ha, b + o_t1, b + o_t2, b + o_w, b + o_p));
   prefault_out(ctx, proofs_out_aff, d * 64);
   return download(ctx, proofs_out_aff, b + o_p, d * 64);
 }
@@ -1282,33 +1272,29 @@ keaki_status keaki_hip_open_fk_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, u
                                     const uint64_t* omega_2d_inv, const uint64_t* inv_2d, uint64_t* proofs_out_aff) {
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.open_fk");
-  if (!srs || !coeffs || !omega_2d || !omega_2d_inv || !inv_2d || !proofs_out_aff || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "open_fk_poly: bad argument");
-  SRS_CHECK(ctx, srs, "open_fk_poly");
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fk_enter(ctx, srs, log2d, coeffs && omega_2d && omega_2d_inv && inv_2d && proofs_out_aff, "open_fk_poly", hl));
   const size_t d = (size_t)1 << log2d;
-  if (d > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "open_fk: %zu coefficients but the SRS holds %zu points", d, srs->n);
-  const size_t o_p = 0, o_fr = o_p + d * 32, o_g = o_fr + (4 * d + d / 2 + 2) * 32, o_out = o_g + 2 * d * 96, total = o_out + d * 64;
+  // one staging block: coefficients (d Fr) | FK23 scalar work | FK23 point work | proofs (d affine)
+  const size_t o_p = 0, o_fr = o_p + d * 32, o_g = o_fr + open_fk_poly_fr_bytes(log2d), o_out = o_g + open_fk_poly_g_bytes(log2d), total = o_out + d * 64;
   ST_TRY(reserve(ctx, ctx->io_d, total));
   char* b = (char*)ctx->io_d.p;
   HIP_TRY(ctx, hipMemcpyAsync(b + o_p, coeffs, d * 32, hipMemcpyHostToDevice, ctx->stream));
-  const keaki_status st_fk = open_fk_poly_run(ctx, srs->d, &srs->fk_hat_s, &srs->fk_log2d, log2d, b + o_p, omega_2d, omega_2d_inv, inv_2d, b + o_fr, b + o_g, b + o_out);
-  fk_account(ctx, srs);
-  ST_TRY(st_fk);
+  ST_TRY(open_fk_from_poly(ctx, srs, log2d, b + o_p, omega_2d, omega_2d_inv, inv_2d, b + o_fr, b + o_g, b + o_out));
   prefault_out(ctx, proofs_out_aff, d * 64);
   return download(ctx, proofs_out_aff, b + o_out, d * 64);
 }
 // hat_s = DFT_2d(reversed SRS) for later open_fk calls with this d: setup-time work (the FK23 analogue of keaki_hip_srs_g1_precompute)
 keaki_status keaki_hip_srs_g1_precompute_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_2d) {
   CTX_GUARD(ctx);
-  if (!srs || !omega_2d || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g1_precompute_fk: bad argument");
-  SRS_CHECK(ctx, srs, "srs_g1_precompute_fk");
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);
-  const size_t d = (size_t)1 << log2d;
-  if (d > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "open_fk: %zu coefficients but the SRS holds %zu points", d, srs->n);
-  ST_TRY(reserve(ctx, ctx->io_d, d * 32));
-  const keaki_status st_fk = fk_precompute_run(ctx, srs->d, &srs->fk_hat_s, &srs->fk_log2d, log2d, omega_2d, ctx->io_d.p);
-  fk_account(ctx, srs);
-  ST_TRY(st_fk);
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fk_enter(ctx, srs, log2d, omega_2d != nullptr, "srs_g1_precompute_fk", hl));
+  const uint32_t d = 1u << log2d;
+  ST_TRY(reserve(ctx, ctx->io_d, (size_t)d * 32));
+  if (srs->fk.log2d != (int)log2d) {
+    fr_powers_run(ctx, omega_2d, d, ctx->io_d.p);
+    ST_TRY(fk_cache_ensure(ctx, srs, log2d, ctx->io_d.p));
+  }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // setup-time call: return when the table exists
   return KEAKI_OK;
 }
@@ -1331,15 +1317,12 @@ keaki_status keaki_hip_vec_commit(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, con
                                   const uint64_t* inv_2d, uint64_t* com_out_jac, uint64_t* proofs_out_aff) {
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.vec_commit");
-  if (!srs || (n && !values) || !omega_d_inv || !inv_d || !omega_2d || !omega_2d_inv || !inv_2d || !com_out_jac || !proofs_out_aff || log2d > 27)
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "vec_commit: bad argument");
-  SRS_CHECK(ctx, srs, "vec_commit");
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fk_enter(ctx, srs, log2d, (!n || values) && omega_d_inv && inv_d && omega_2d && omega_2d_inv && inv_2d && com_out_jac && proofs_out_aff, "vec_commit", hl));
   const size_t d = (size_t)1 << log2d, m = n + (pad ? 1 : 0);
   if (m > d) return fail(ctx, KEAKI_ERR_BAD_ARG, "vec_commit: %zu evaluations do not fit the domain of %zu", m, d);
-  if (d > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "open_fk: %zu coefficients but the SRS holds %zu points", d, srs->n);
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);
   // one staging block: coefficients (d Fr) | twiddles of the iFFT (d/2 + 1) | FK23 scalar work | FK23 point work (2d Jacobian) | proofs (d affine) | commitment
-  const size_t o_c = 0, o_tw = o_c + d * 32, o_fr = o_tw + (d / 2 + 1) * 32, o_g = o_fr + (4 * d + d / 2 + 2) * 32, o_out = o_g + 2 * d * 96,
+  const size_t o_c = 0, o_tw = o_c + d * 32, o_fr = o_tw + (d / 2 + 1) * 32, o_g = o_fr + open_fk_poly_fr_bytes(log2d), o_out = o_g + open_fk_poly_g_bytes(log2d),
                o_com = o_out + d * 64, total = o_com + 96;
   ST_TRY(reserve(ctx, ctx->io_d, total));
   char* b = (char*)ctx->io_d.p;
@@ -1348,9 +1331,7 @@ keaki_status keaki_hip_vec_commit(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, con
   if (n) HIP_TRY(ctx, hipMemcpyAsync(b + o_c, values, n * 32, hipMemcpyHostToDevice, st));
   if (pad) HIP_TRY(ctx, hipMemcpyAsync(b + o_c + n * 32, pad, 32, hipMemcpyHostToDevice, st));
   ST_TRY(fr_fft_run(ctx, b + o_c, log2d, omega_d_inv, inv_d, b + o_tw));                  // domain.ifft (src/vec.rs:37)
-  const keaki_status st_fk = open_fk_poly_run(ctx, srs->d, &srs->fk_hat_s, &srs->fk_log2d, log2d, b + o_c, omega_2d, omega_2d_inv, inv_2d, b + o_fr, b + o_g, b + o_out);   // :40
-  fk_account(ctx, srs);
-  ST_TRY(st_fk);
+  ST_TRY(open_fk_from_poly(ctx, srs, log2d, b + o_c, omega_2d, omega_2d_inv, inv_2d, b + o_fr, b + o_g, b + o_out));   // :40
   const auto tb = srs_tables(srs);
   ST_TRY(msm_g1_run(ctx, srs->d, srs->n, b + o_c, d, b + o_com, tb.first, tb.second));     // :46 (trailing zero coefficients contribute nothing)
   prefault_out(ctx, proofs_out_aff, d * 64);
@@ -1386,8 +1367,7 @@ keaki_status keaki_hip_fk_shard_create(keaki_hip_ctx* ctx, const keaki_hip_srs_g
   const size_t d = (size_t)1 << log2d;
   if (d < (size_t)world * world)
     return fail(ctx, KEAKI_ERR_BAD_ARG, "fk_shard_create: %zu openings are too few to shard over %u ranks (needs world^2); use keaki_hip_open_fk_poly", d, world);
-  if (d > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "open_fk: %zu coefficients but the SRS holds %zu points", d, srs->n);
-  SRS_CHECK(ctx, srs, "fk_shard_create");
+  ST_TRY(srs_holds(ctx, srs, "fk_shard_create", d, SRS_SHORT_FK));
   auto* fk = new keaki_hip_fk_shard();
   fk->srs = srs;
   fk->world = world;
@@ -1504,9 +1484,8 @@ keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs,
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.kzg_open");
   if (!srs || !point || !proof_out_jac || (n && !coeffs)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_open: null pointer");
-  SRS_CHECK(ctx, srs, "kzg_open");
-  if (n && n - 1 > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n - 1, srs->n);
   const size_t nq = n ? n - 1 : 0;
+  ST_TRY(srs_holds(ctx, srs, "kzg_open", nq, SRS_SHORT_MSM));
   const size_t o_q = 0, o_v = o_q + (nq + 1) * 32, o_w = o_v + 32, total = o_w + open_quotient_work_bytes(n + 1);
   ST_TRY(reserve(ctx, ctx->io_a, n ? n * 32 : 16));
   ST_TRY(reserve(ctx, ctx->io_c, total));
@@ -1528,7 +1507,7 @@ keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs,
   if (cch.size() <= 1 || nq == 0) {
     if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
     // a failing call, too, returns only when no copy reads `coeffs` any more (header): the successful path synchronises in `download` below
-    struct UploadFence { hipStream_t s; bool armed; ~UploadFence() { if (armed) (void)hipStreamSynchronize(s); } } fence{ctx->stream, n != 0};
+    StreamFence fence{ctx->stream, n != 0};
     if (n) ST_TRY(open_quotient_run(ctx, ctx->io_a.p, n, point, b + o_q, b + o_v, b + o_w));
     ST_TRY(msm_g1_run(ctx, srs->d, srs->n, b + o_q, nq, ctx->io_b.p, tb.first, tb.second));
     fence.armed = false;
@@ -1543,7 +1522,7 @@ keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs,
     hipStream_t ax = ctx->aux_stream, main_st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->open_ev[4], main_st));              // behind the value slot's memset and every earlier user of io_a / io_c
     HIP_TRY(ctx, hipStreamWaitEvent(ax, ctx->open_ev[4], 0));
-    struct AuxFence { hipStream_t s; ~AuxFence() { (void)hipStreamSynchronize(s); } } aux_fence{ax};      // nothing of this call is left on it at any exit
+    StreamFence aux_fence{ax, true};                                     // nothing of this call is left on it at any exit
     MsmPipe pipe;
     for (const auto& c : cch) pipe.ranges.push_back({c.first ? c.first - 1 : 0, c.second - 1 - (c.first ? c.first - 1 : 0)});   // q_i = Q_(i+1): chunk [lo, hi) yields q_(lo-1) .. q_(hi-2)
     char* a = (char*)ctx->io_a.p;
@@ -1603,14 +1582,12 @@ keaki_status batch_args(keaki_hip_ctx* ctx, const char* what, const void* srs, s
   *empty = m == 0;
   return KEAKI_OK;
 }
-// a failing host-form call, too, returns only when no copy reads the caller's arrays any more
-struct StreamFence { hipStream_t s; bool armed; ~StreamFence() { if (armed) (void)hipStreamSynchronize(s); } };
 inline size_t batch_span(size_t n, size_t m, size_t stride) { return n && m ? ((m - 1) * stride + n) * 32 : 0; }   // bytes from row 0 to the end of row m - 1
 
 keaki_status open_batch_core(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, size_t m, size_t stride, const void* d_points,
                              void* d_proofs_out_jac, void* d_values_out) {
   const size_t nq = n ? n - 1 : 0;
-  if (nq > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", nq, srs->n);
+  ST_TRY(srs_holds(ctx, srs, "kzg_open_batch", nq, SRS_SHORT_MSM));
   if (n == 0 && d_values_out) HIP_TRY(ctx, hipMemsetAsync(d_values_out, 0, m * 32, ctx->stream));      // the zero polynomial evaluates to 0
   const auto tb = srs_tables(srs);
   if (nq == 0) {
@@ -1645,9 +1622,8 @@ keaki_status keaki_hip_msm_g1_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_
   bool empty;
   ST_TRY(batch_args(ctx, "msm_g1_batch", srs, n, m, stride, &empty));
   if (empty) return KEAKI_OK;
-  SRS_CHECK(ctx, srs, "msm_g1_batch");
   if (!d_out_jac || (n && !d_scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g1_batch: null pointer");
-  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
+  ST_TRY(srs_holds(ctx, srs, "msm_g1_batch", n, SRS_SHORT_MSM));
   const auto tb = srs_tables(srs);
   return msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, d_scalars, n, m, stride, d_out_jac);
 }
@@ -1658,7 +1634,7 @@ keaki_status keaki_hip_msm_g1_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* 
   ST_TRY(batch_args(ctx, "msm_g1_batch", srs, n, m, stride, &empty));
   if (empty) return KEAKI_OK;
   if (!out_jac || (n && !scalars)) return fail(ctx, KEAKI_ERR_BAD_ARG, "msm_g1_batch: null pointer");
-  if (n > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n, srs->n);
+  ST_TRY(srs_holds(ctx, srs, "msm_g1_batch", n, SRS_SHORT_MSM));
   // one upload in front, the kernels, one download of m x 96 B: the rows are short, there is nothing for a chunk pipeline to hide
   ST_TRY(reserve(ctx, ctx->io_b, m * G1_JAC_BYTES));
   ST_TRY(upload(ctx, ctx->io_a, scalars, batch_span(n, m, stride)));
@@ -1675,7 +1651,6 @@ keaki_status keaki_hip_kzg_open_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_sr
   bool empty;
   ST_TRY(batch_args(ctx, "kzg_open_batch", srs, n, m, stride, &empty));
   if (empty) return KEAKI_OK;
-  SRS_CHECK(ctx, srs, "kzg_open_batch");
   if (!d_points || !d_proofs_out_jac || (n && !d_coeffs)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_open_batch: null pointer");
   return open_batch_core(ctx, srs, d_coeffs, n, m, stride, d_points, d_proofs_out_jac, d_values_out);
 }
@@ -1686,7 +1661,7 @@ keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1
   ST_TRY(batch_args(ctx, "kzg_open_batch", srs, n, m, stride, &empty));
   if (empty) return KEAKI_OK;
   if (!points || !proofs_out_jac || (n && !coeffs)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_open_batch: null pointer");
-  if (n && n - 1 > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, "msm: %zu scalars but the SRS holds %zu points", n - 1, srs->n);
+  ST_TRY(srs_holds(ctx, srs, "kzg_open_batch", n ? n - 1 : 0, SRS_SHORT_MSM));
   ST_TRY(reserve(ctx, ctx->io_b, m * G1_JAC_BYTES));
   ST_TRY(reserve(ctx, ctx->io_d, m * 32));
   ST_TRY(reserve(ctx, ctx->io_a, std::max<size_t>(16, batch_span(n, m, stride))));
@@ -1843,7 +1818,7 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
   if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
   char* io = (char*)ctx->vb_io.p;
   // a failing call, too, returns only when no copy reads the caller's arrays any more (the successful path synchronises in its download)
-  struct UploadFence { hipStream_t s; bool armed; ~UploadFence() { if (armed) (void)hipStreamSynchronize(s); } } fence{ctx->stream, true};
+  StreamFence fence{ctx->stream, true};
   if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_PTS, com_aff, 64, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_QS + 128, tau_g2_aff, 128, hipMemcpyHostToDevice, ctx->stream));
   if (point_mode) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_OMEGA, points, 32, hipMemcpyHostToDevice, ctx->stream));

@@ -607,30 +607,32 @@ keaki_status fr_fft_run(keaki_hip_ctx* ctx, void* d_data, u32 log2n, const uint6
   }
   return launch_check(ctx, "fr_fft_run");
 }
-// FK23 from the polynomial itself: everything (twiddles, hat_a) is derived on the device from three scalars.
-// d_p: d Fr coefficients. d_fr_work: room for (2d + d + d + 1) Fr. d_g_work: 2d Jacobian points. Output: d affine proofs.
-keaki_status open_fk_poly_run(keaki_hip_ctx* ctx, const void* d_srs, void** hat_s_cache, int* hat_s_log2d, u32 log2d, const void* d_p,
-                              const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d, void* d_fr_work, void* d_g_work,
-                              void* d_proofs_aff) {
+// d_out[k] = omega^k, k < n. Enqueues only: the launcher that reads the powers reports a failed launch.
+void fr_powers_run(keaki_hip_ctx* ctx, const uint64_t* omega, u32 n, void* d_out) {
+  Fr w;
+  memcpy(&w, omega, 32);
+  hipLaunchKernelGGL(k_fr_powers, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, w, n, (Fr*)d_out);
+}
+// FK23 from the polynomial itself, the scalar half: everything open_fk_run takes (twiddles, hat_a) is derived on the device from three
+// scalars; the caller puts the handle's hat_s beside it (built from out->tw when it is not cached) and runs open_fk_run.
+// d_p: d Fr coefficients. d_fr_work: open_fk_poly_fr_bytes(log2d); the point workspace of open_fk_run: open_fk_poly_g_bytes(log2d).
+size_t open_fk_poly_fr_bytes(u32 log2d) { const size_t d = (size_t)1 << log2d; return (4 * d + d / 2 + 2) * sizeof(Fr); }   // hat_a 2d | tw d | twi d, and slack
+size_t open_fk_poly_g_bytes(u32 log2d) { return ((size_t)2 << log2d) * sizeof(G1Jac); }
+keaki_status open_fk_poly_scalars_run(keaki_hip_ctx* ctx, u32 log2d, const void* d_p, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
+                                      const uint64_t* inv_2d, void* d_fr_work, FkPolyScalars* out) {
   const u32 d = 1u << log2d;
-  Fr w, wi, s;
-  memcpy(&w, omega_2d, 32); memcpy(&wi, omega_2d_inv, 32); memcpy(&s, inv_2d, 32);
+  Fr s;
+  memcpy(&s, inv_2d, 32);
   Fr* hat_a = (Fr*)d_fr_work;
   Fr* tw = hat_a + 2 * (size_t)d;       // omega_2d^k,  k < d
   Fr* twi = tw + d;                      // omega_2d^-k, k < d
-  hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_fr_powers, dim3(cdiv(d, 256)), dim3(256), 0, st, w, d, tw);
-  hipLaunchKernelGGL(k_fr_powers, dim3(cdiv(d, 256)), dim3(256), 0, st, wi, d, twi);
-  hipLaunchKernelGGL(k_fk_pad, dim3(cdiv(2 * d, 256)), dim3(256), 0, st, (const Fr*)d_p, d, hat_a);
+  fr_powers_run(ctx, omega_2d, d, tw);
+  fr_powers_run(ctx, omega_2d_inv, d, twi);
+  hipLaunchKernelGGL(k_fk_pad, dim3(cdiv(2 * d, 256)), dim3(256), 0, ctx->stream, (const Fr*)d_p, d, hat_a);
   ST_TRY(fr_fft(ctx, hat_a, log2d + 1, tw, 1));
-  hipLaunchKernelGGL(k_fr_scale, dim3(cdiv(2 * d, 256)), dim3(256), 0, st, hat_a, s, 2 * d);
-  if (*hat_s_log2d != (int)log2d) {
-    if (*hat_s_cache) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void)hipFree(*hat_s_cache); *hat_s_cache = nullptr; *hat_s_log2d = -1; }
-    HIP_TRY(ctx, hipMalloc(hat_s_cache, 2 * (size_t)d * sizeof(G1Jac)));
-    ST_TRY(fk_hat_s_run(ctx, d_srs, log2d, tw, *hat_s_cache));
-    *hat_s_log2d = (int)log2d;
-  }
-  return open_fk_run(ctx, *hat_s_cache, log2d, hat_a, tw, twi, d_g_work, d_proofs_aff);
+  hipLaunchKernelGGL(k_fr_scale, dim3(cdiv(2 * d, 256)), dim3(256), 0, ctx->stream, hat_a, s, 2 * d);
+  *out = {hat_a, tw, twi};
+  return KEAKI_OK;
 }
 
 // ---- FK23 sharded (keaki_hip_fk_shard_*): the steps between the caller's exchanges; tests/fk_shard_model.py::ShardModel step for step -----
@@ -712,22 +714,6 @@ keaki_status fk_shard_open_run(keaki_hip_ctx* ctx, FkShard& fk, int step, void* 
   }
   hipLaunchKernelGGL(k_aff_unscramble, dim3(cdiv(d, 256)), dim3(256), 0, st, (const G1Aff*)d_recv, fk.log2d, (G1Aff*)d_out_aff);
   return launch_check(ctx, "fk_shard_open 3");
-}
-
-// hat_s = DFT_2d(reversed SRS) ahead of time (it depends on the SRS and d only): setup-time work like the MSM window tables
-keaki_status fk_precompute_run(keaki_hip_ctx* ctx, const void* d_srs, void** hat_s_cache, int* hat_s_log2d, u32 log2d, const uint64_t* omega_2d,
-                               void* d_tw_work) {
-  const u32 d = 1u << log2d;
-  if (*hat_s_log2d == (int)log2d) return KEAKI_OK;
-  Fr w;
-  memcpy(&w, omega_2d, 32);
-  hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_fr_powers, dim3(cdiv(d, 256)), dim3(256), 0, st, w, d, (Fr*)d_tw_work);
-  if (*hat_s_cache) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void)hipFree(*hat_s_cache); *hat_s_cache = nullptr; *hat_s_log2d = -1; }
-  HIP_TRY(ctx, hipMalloc(hat_s_cache, 2 * (size_t)d * sizeof(G1Jac)));
-  ST_TRY(fk_hat_s_run(ctx, d_srs, log2d, d_tw_work, *hat_s_cache));
-  *hat_s_log2d = (int)log2d;
-  return KEAKI_OK;
 }
 
 // d_c: n coefficients (Fr). d_q: n - 1 quotient coefficients out (n >= 1; n == 1: nothing written). d_value: p(z) out (1 Fr).

@@ -163,7 +163,8 @@ keaki_status fail(keaki_hip_ctx* ctx, keaki_status code, const char* fmt, ...);
 keaki_status reserve(keaki_hip_ctx* ctx, DevBuf& b, size_t bytes);
 // hipMalloc behind the library's one allocation gate. keaki_hip_debug_set_alloc_limit(ctx, bytes) makes every single allocation of this
 // context above that size fail with KEAKI_ERR_OOM, which is how the tests exercise the optional-memory fallbacks (SRS window tables,
-// the wide GT table).
+// the wide GT table) and a refused rebuild of a handle's FK23 transform. One allocation stays outside on purpose: the points of
+// keaki_hip_srs_g*_upload (api.hip: srs_upload), which tests upload while a limit is set.
 keaki_status dev_alloc(keaki_hip_ctx* ctx, void** p, size_t bytes);
 keaki_status launch_check(keaki_hip_ctx* ctx, const char* what);
 inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
@@ -237,11 +238,14 @@ keaki_status g2_curve_check_run(keaki_hip_ctx* ctx, const void* d_pts, size_t n,
 keaki_status open_quotient_run(keaki_hip_ctx* ctx, const void* d_c, size_t n, const uint64_t* z, void* d_q, void* d_value, void* d_work, bool top_is_carry = false);
 size_t open_quotient_work_bytes(size_t n);           // size of d_work for n coefficients
 keaki_status fr_fft_run(keaki_hip_ctx* ctx, void* d_data, uint32_t log2n, const uint64_t* omega, const uint64_t* scale_or_null, void* d_tw);
-keaki_status open_fk_poly_run(keaki_hip_ctx* ctx, const void* d_srs, void** hat_s_cache, int* hat_s_log2d, uint32_t log2d, const void* d_p,
-                              const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d, void* d_fr_work, void* d_g_work,
-                              void* d_proofs_aff);
-keaki_status fk_precompute_run(keaki_hip_ctx* ctx, const void* d_srs, void** hat_s_cache, int* hat_s_log2d, uint32_t log2d, const uint64_t* omega_2d,
-                               void* d_tw_work);
+void fr_powers_run(keaki_hip_ctx* ctx, const uint64_t* omega, uint32_t n, void* d_out);      // d_out[k] = omega^k, k < n
+// FK23 from the coefficients (api.hip: open_fk_from_poly): the scalar half fills d_fr_work and says where hat_a and the twiddles of
+// fk_hat_s_run / open_fk_run lie in it. Workspace sizes of the scalars and of open_fk_run's 2d Jacobian points:
+size_t open_fk_poly_fr_bytes(uint32_t log2d);
+size_t open_fk_poly_g_bytes(uint32_t log2d);
+struct FkPolyScalars { const void *hat_a, *tw, *twi; };
+keaki_status open_fk_poly_scalars_run(keaki_hip_ctx* ctx, uint32_t log2d, const void* d_p, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
+                                      const uint64_t* inv_2d, void* d_fr_work, FkPolyScalars* out);
 keaki_status fk_hat_s_run(keaki_hip_ctx* ctx, const void* d_srs, uint32_t log2d, const void* d_tw2d, void* d_hat_s);
 keaki_status open_fk_run(keaki_hip_ctx* ctx, const void* d_hat_s, uint32_t log2d, const void* d_hat_a, const void* d_tw2d, const void* d_tw2d_inv,
                          void* d_work, void* d_proofs_aff);

@@ -605,6 +605,10 @@ class KeakiHip:
         self._ck(self.lib.keaki_hip_open_fk_poly(self.ctx, srs.handle, log2d, _ptr(p), _ptr(_np(omega_2d)), _ptr(_np(omega_2d_inv)), _ptr(_np(inv_2d)), _ptr(out)))
         return out
 
+    def srs_g1_precompute_fk(self, srs: "SrsG1", log2d: int, omega_2d):
+        """setup-time build of the handle's cached FK23 transform for d = 2^log2d (later open_fk / open_fk_poly / vec_commit calls at this d reuse it)"""
+        self._ck(self.lib.keaki_hip_srs_g1_precompute_fk(self.ctx, srs.handle, log2d, _ptr(_np(omega_2d))))
+
     # ---- KEM composites
     # FK23 sharded over `world` ranks: the steps between the caller's exchanges (keaki_amd/dist.py::ShardedFk drives them)
     def fk_shard_create(self, srs: "SrsG1", log2d: int, rank: int, world: int, omega_2d, omega_2d_inv, inv_2d) -> "FkShardHandle":

@@ -94,7 +94,7 @@ def fk_dlogs(tau, p, evals):
     return out
 
 
-# ---- FK23 group FFTs (keaki_amd/csrc/fft_g1.hip: open_fk_poly_run, open_fk_run, run_stages) --------------------------------------------
+# ---- FK23 group FFTs (keaki_amd/csrc/fft_g1.hip: open_fk_poly_scalars_run, fk_hat_s_run, open_fk_run, run_stages) --------------------------------------------
 def _bitrev(x, bits):
     r = 0
     for _ in range(bits):
@@ -184,7 +184,7 @@ FK_TRANSFORMS = ("hat_s", "inv", "fwd")
 
 
 def fk_model(tau, p, log2d, radix4=True):
-    """open_fk_poly_run over Fr: hat_s = DIF_2d(reversed powers of tau, padded with zeros); the pointwise products; DIT_d of the odd
+    """the FK23 pipeline from the coefficients (api.hip: open_fk_from_poly) over Fr: hat_s = DIF_2d(reversed powers of tau, padded with zeros); the pointwise products; DIT_d of the odd
     half, the twist, DIF_d; proofs[brev(q)] = E[q] + O[q]. Returns (proof scalars, {transform_event: count})."""
     d = 1 << log2d
     N = 2 * d
