@@ -29,13 +29,6 @@ keaki_status msm_g2_run(keaki_hip_ctx* ctx, const void* d_points, size_t srs_len
 // window tables of a fixed G2 basis: all windows share one bucket set, and the per-window Horner doublings -- a serial chain of ~240
 // Fq2 doublings on one lane, 4.4 ms -- disappear (profiles/r02_msm_g2_kernel_stats.csv)
 keaki_status msm_g2_precompute_run(keaki_hip_ctx* ctx, const void* d_points, size_t N, int* c_table_out, size_t* table_bytes_out, void** d_table_out) {
-  const int c = choose_window_shared(N, ctx->tune.msm_c_shared);
-  const size_t bytes = (size_t)msm_plan_windows(N, c) * N * sizeof(G2Aff);
-  void* t = nullptr;
-  ST_TRY(dev_alloc(ctx, &t, bytes ? bytes : 64));
-  keaki_status st = msm_build_tables<Fq2>(ctx, (const G2Aff*)d_points, N, c, (G2Aff*)t);
-  if (st != KEAKI_OK) { (void)hipFree(t); return st; }
-  *c_table_out = c; *table_bytes_out = bytes; *d_table_out = t;
-  return KEAKI_OK;
+  return msm_precompute<Fq2>(ctx, d_points, N, c_table_out, table_bytes_out, d_table_out);
 }
 }  // namespace keaki_internal

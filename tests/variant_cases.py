@@ -3,7 +3,7 @@ tests/test_variant_cases_model.py and tests/test_gpu_variants.py; no GPU import)
 
 The library ships several instantiations of its MSM, FK23 and fixed-base kernels; host code picks one from the input size and the tuning
 switches of keaki_hip_ctx_set_option (also settable through KEAKI_* at context creation). This module restates those host-side choices
-(keaki_amd/csrc/msm_host.hip.h: choose_window, choose_window_shared, msm_dev; msm.hip.h: msm_make_plan, part_make_shape; fft_g1.hip:
+(keaki_amd/csrc/msm_host.hip.h: choose_window, choose_window_shared, msm_plan_call, msm_launch_accumulate; msm.hip.h: msm_make_plan, part_make_shape; fft_g1.hip:
 stage_map, run_stages; ec_batch_g2.hip: encap_g2_fixed_run), builds scalars that drive every window of a plan through each branch of the
 digit walk, and lists the GPU cases of tests/test_gpu_variants.py with the instantiations each one reaches. The CPU test checks the list
 against the launches it parses out of the sources, so a variant added without a case fails there.
@@ -154,7 +154,7 @@ def part_make_shape(n, W, nb, lb_override=-1):
 
 
 def reduce_len(max_b, g2=False, reduce_l=0):
-    """the chunk length L of k_msm_reduce (msm_dev)"""
+    """the chunk length L of k_msm_reduce (msm_plan_call)"""
     if g2:
         L = 8 if max_b >= 64 else max_b
     else:
@@ -184,7 +184,7 @@ def acc_g1_name(nt, mode, pf=2):
 
 
 def accumulate_names(opts, passes):
-    """the G1 bucket kernel of each pass (msm_dev). opts: the switches; passes: K (1 = a whole MSM)"""
+    """the G1 bucket kernel of each pass (msm_launch_accumulate). opts: the switches; passes: K (1 = a whole MSM)"""
     if not opts.get("acc_u29", 1):
         return ["k_msm_accumulate<Fq>"] * passes
     if passes == 1:
@@ -199,7 +199,7 @@ def accumulate_names(opts, passes):
 
 
 def msm(n, opts=None, srs_len=None, table_c=None, g2=False, chunk_sizes=None):
-    """One MSM as msm_dev runs it. table_c: the window target the SRS tables were built with (None: no tables). chunk_sizes: the pass
+    """One MSM as msm_plan_call plans it and msm_dev runs it. table_c: the window target the SRS tables were built with (None: no tables). chunk_sizes: the pass
     lengths of a chunked call. -> dict(shared, plan, c, L, shapes, refused, kernels)"""
     opts = opts or {}
     srs_len = n if srs_len is None else srs_len
