@@ -116,8 +116,10 @@ const char* keaki_hip_version(void);
  *       "msm_pipe_chunks" at -1 (or sets it to 0).
  *   "msm_pipe_chunks" (-1 = automatic: 6 chunks from 2^22 scalars on, 4 from 2^21, 3 from "msm_pipe_min" = 2^20 on; 0 / 1 = one copy in front; k >= 2 = k chunks at
  *       any length), "msm_pipe_growth" (size of chunk j + 1 in percent of chunk j, default 160: a short first chunk starts the device early).
- *   A host-array call that FAILS (status != KEAKI_OK) leaves its output arrays unspecified: any prefix may hold results, and with
- *   "host_prefault" = 1 pages may hold the zeros of the first touch. Input arrays are never written.
+ *   A host-array call of ANY entry that FAILS (status != KEAKI_OK) returns, like a successful one, only when no copy reads or writes the
+ *   caller's arrays any more and nothing of the call is left on the context's side streams (pageable and pinned arrays alike). It leaves
+ *   its output arrays unspecified: any prefix may hold results, and with "host_prefault" = 1 pages may hold the zeros of the first touch.
+ *   Input arrays are never written.
  * Unknown name -> KEAKI_ERR_BAD_ARG. */
 keaki_status keaki_hip_ctx_set_option(keaki_hip_ctx* ctx, const char* name, int64_t value);
 /* Test hook: every single device allocation of this ctx above `bytes` fails with KEAKI_ERR_OOM (0 = no limit). This is how the tests

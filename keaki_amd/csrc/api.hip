@@ -2,6 +2,7 @@
 // launch plumbing: workspace management, stream ordering, error codes. No arithmetic happens on
 // the CPU here and there is no CPU fallback: without a gfx950 device every entry point fails.
 #include "internal.h"
+#include "host_plan.h"
 
 #include <algorithm>
 #include <cctype>
@@ -148,19 +149,55 @@ void resolve_fk_timing(keaki_hip_ctx* ctx) {
   ctx->fk_timing_pending = false;
 }
 
-keaki_status upload(keaki_hip_ctx* ctx, DevBuf& b, const void* host, size_t bytes) {
-  ST_TRY(reserve(ctx, b, bytes ? bytes : 16));
-  if (bytes) HIP_TRY(ctx, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return KEAKI_OK;
-}
 keaki_status download(keaki_hip_ctx* ctx, void* host, const void* dev, size_t bytes) {
   if (bytes) HIP_TRY(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return KEAKI_OK;
 }
-// Drains `s` when the scope is left while armed: a FAILING host-form call, too, returns only when no copy reads the caller's arrays any more
-// and nothing of it is left on a side stream. The successful path disarms it where its own download synchronises.
-struct StreamFence { hipStream_t s; bool armed; ~StreamFence() { if (armed) (void)hipStreamSynchronize(s); } };
+// How the caller's HOST arrays reach the device, for every host-array entry: the copies go on the context's stream, or after begin(true) on
+// the copy stream, where `put` makes the stream that reads a piece wait for it. The feed also keeps the rule of the header: a call that
+// FAILS returns, too, only when no copy reads the caller's arrays any more and nothing of it is left on a side stream -- unless the call
+// said `settled()` (where its own download has synchronised), the destructor drains every stream that carried a copy or was handed in.
+struct CopyFeed {
+  keaki_hip_ctx* ctx;
+  bool side = false;
+  hipStream_t drain[3] = {nullptr, nullptr, nullptr};
+  int n_drain = 0;
+  explicit CopyFeed(keaki_hip_ctx* c) : ctx(c) {}
+  ~CopyFeed() { for (int i = 0; i < n_drain; i++) (void)hipStreamSynchronize(drain[i]); }
+  CopyFeed(const CopyFeed&) = delete;
+  CopyFeed& operator=(const CopyFeed&) = delete;
+  void also_drain(hipStream_t s) { if (std::find(drain, drain + n_drain, s) == drain + n_drain) drain[n_drain++] = s; }
+  void settled() { n_drain = 0; }
+  keaki_status begin(bool side_stream) {
+    if (!side_stream) return KEAKI_OK;
+    ST_TRY(ctx->pipe.ready(ctx));
+    // the copy stream starts behind whatever the context's stream holds (an earlier call's kernels may still read the destination)
+    HIP_TRY(ctx, hipEventRecord(ctx->pipe.done[0], ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.copy_stream, ctx->pipe.done[0], 0));
+    side = true;
+    return KEAKI_OK;
+  }
+  // piece j of the call, host to device; `waiter` (default: the context's stream) is the stream whose kernels read it
+  keaki_status put(size_t j, void* dst, const void* src, size_t bytes, hipStream_t waiter = nullptr) {
+    const hipStream_t cs = side ? ctx->pipe.copy_stream : ctx->stream;
+    also_drain(cs);
+    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
+    if (!side) return KEAKI_OK;
+    HIP_TRY(ctx, hipEventRecord(ctx->pipe.in[j & 1], cs));
+    HIP_TRY(ctx, hipStreamWaitEvent(waiter ? waiter : ctx->stream, ctx->pipe.in[j & 1], 0));
+    return KEAKI_OK;
+  }
+};
+keaki_status upload(CopyFeed& feed, DevBuf& b, const void* host, size_t bytes) {
+  ST_TRY(reserve(feed.ctx, b, bytes ? bytes : 16));
+  return feed.put(0, b.p, host, bytes);
+}
+keaki_status download(CopyFeed& feed, void* host, const void* dev, size_t bytes) {     // the last step of a successful call
+  ST_TRY(download(feed.ctx, host, dev, bytes));
+  feed.settled();
+  return KEAKI_OK;
+}
 
 // (table, window target) of a handle, read under its lock: another context may be building the tables right now
 template <class H>
@@ -262,17 +299,6 @@ void prefault_out(const keaki_hip_ctx* ctx, void* p, size_t bytes) {
 // [lo, lo + m) into buffer half `half`, `run(lo, m, half)` the kernels (on ctx->stream), `down(lo, m, half, stream)` first-touches the
 // caller's output pages and enqueues the downloads.
 constexpr size_t PIPE_CHUNK = 65536;
-static keaki_status pipe_ready(keaki_hip_ctx* ctx) {
-  if (ctx->copy_stream) return KEAKI_OK;
-  hipStream_t cs = nullptr;
-  HIP_TRY(ctx, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-  for (int i = 0; i < 2; i++) {
-    if (!ctx->pipe_in[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_in[i], hipEventDisableTiming));
-    if (!ctx->pipe_done[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pipe_done[i], hipEventDisableTiming));
-  }
-  ctx->copy_stream = cs;
-  return KEAKI_OK;
-}
 // chunk size of a batch of n items: `unit` items (PIPE_CHUNK: two rounds of the GT exponentiation kernel; the pairing path passes its own launch
 // size -- 16 launches of 2^16 pairings take 3.6 ms longer than 8 of 2^17), the whole batch below two units
 inline size_t pipe_chunk_items(const keaki_hip_ctx* ctx, size_t n, size_t unit = PIPE_CHUNK) { return ctx->tune.pipe_chunks && n >= 2 * unit ? unit : n; }
@@ -281,10 +307,12 @@ inline size_t pipe_chunk_items(const keaki_hip_ctx* ctx, size_t n, size_t unit =
 // happens on the calling thread while the kernels run; with more, helper threads walk the chunks ahead of the downloads (one thread, three
 // when the outputs exceed 64 MB: GT bytes out are 384 B per item) and a download waits for its chunk's flag, so no touch can land on delivered bytes.
 template <class Up, class Run, class Touch, class Down>
-static keaki_status pipelined(keaki_hip_ctx* ctx, size_t n, size_t ch, size_t out_bytes_per_item, Up up, Run run, Touch touch, Down down) {
-  ST_TRY(pipe_ready(ctx));
+static keaki_status pipelined(CopyFeed& feed, size_t n, size_t ch, size_t out_bytes_per_item, Up up, Run run, Touch touch, Down down) {
+  keaki_hip_ctx* ctx = feed.ctx;
+  ST_TRY(ctx->pipe.ready(ctx));
+  feed.also_drain(ctx->pipe.copy_stream);       // an early exit leaves no copy of a chunk behind
   const size_t chunks = (n + ch - 1) / ch;
-  hipStream_t cs = ctx->copy_stream, st = ctx->stream;
+  hipStream_t cs = ctx->pipe.copy_stream, st = ctx->stream;
   const size_t n_helpers = chunks < 2 || !ctx->tune.host_prefault ? 0 : (n * out_bytes_per_item >= ((size_t)64 << 20) ? std::min<size_t>(3, chunks) : 1);
   std::unique_ptr<std::atomic<unsigned char>[]> touched(new std::atomic<unsigned char>[chunks]);
   for (size_t k = 0; k < chunks; k++) touched[k].store(0, std::memory_order_relaxed);
@@ -312,18 +340,18 @@ static keaki_status pipelined(keaki_hip_ctx* ctx, size_t n, size_t ch, size_t ou
       }
     });
   // the copy stream starts behind whatever the context's stream holds (an earlier call's kernels may still read the buffers)
-  HIP_TRY(ctx, hipEventRecord(ctx->pipe_done[0], st));
-  HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->pipe_done[0], 0));
+  HIP_TRY(ctx, hipEventRecord(ctx->pipe.done[0], st));
+  HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->pipe.done[0], 0));
   for (size_t k = 0; k <= chunks; k++) {
     if (k < chunks) {
       const size_t lo = k * ch, m = std::min(ch, n - lo);
       const int h = (int)(k & 1);
       ST_TRY(up(lo, m, h, cs));
       staged.store(k + 1, std::memory_order_release);
-      HIP_TRY(ctx, hipEventRecord(ctx->pipe_in[h], cs));
-      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->pipe_in[h], 0));
+      HIP_TRY(ctx, hipEventRecord(ctx->pipe.in[h], cs));
+      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->pipe.in[h], 0));
       ST_TRY(run(lo, m, h));
-      HIP_TRY(ctx, hipEventRecord(ctx->pipe_done[h], st));
+      HIP_TRY(ctx, hipEventRecord(ctx->pipe.done[h], st));
     }
     if (k >= 1) {
       const size_t lo = (k - 1) * ch, m = std::min(ch, n - lo);
@@ -332,11 +360,12 @@ static keaki_status pipelined(keaki_hip_ctx* ctx, size_t n, size_t ch, size_t ou
       else for (unsigned spins = 0; !touched[k - 1].load(std::memory_order_acquire); spins++) {
         if (spins < 20000) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(20));
       }
-      HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->pipe_done[h], 0));
+      HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->pipe.done[h], 0));
       ST_TRY(down(lo, m, h, cs));
     }
   }
   HIP_TRY(ctx, hipStreamSynchronize(cs));
+  feed.settled();                               // every download of the call was behind its kernels on cs
   return KEAKI_OK;
 }
 // One per-item region of a pipelined host batch, `bytes` per item: `in` is uploaded into it, `out` downloaded from it (both: in place --
@@ -357,16 +386,17 @@ static keaki_status pipelined_regions(keaki_hip_ctx* ctx, size_t n, size_t ch, s
   ST_TRY(reserve(ctx, ctx->io_a, head_bytes + 2 * half));
   std::vector<char*> d_head, d[2];
   char* p = (char*)ctx->io_a.p;
+  CopyFeed feed(ctx);
   for (const Region& x : head) {
     d_head.push_back(p);
-    HIP_TRY(ctx, hipMemcpyAsync(p, x.in, x.bytes, hipMemcpyHostToDevice, ctx->stream));
+    ST_TRY(feed.put(0, p, x.in, x.bytes));
     p += x.bytes;
   }
   for (int h = 0; h < 2; h++) {
     p = (char*)ctx->io_a.p + head_bytes + h * half;
     for (const Region& x : rg) { d[h].push_back(p); p += ch * x.bytes; }
   }
-  return pipelined(ctx, n, ch, out_bytes,
+  return pipelined(feed, n, ch, out_bytes,
     [&](size_t lo, size_t m, int h, hipStream_t cs) -> keaki_status {
       for (size_t i = 0; i < rg.size(); i++)
         if (rg[i].in) HIP_TRY(ctx, hipMemcpyAsync(d[h][i], (const char*)rg[i].in + lo * rg[i].bytes, m * rg[i].bytes, hipMemcpyHostToDevice, cs));
@@ -389,77 +419,26 @@ static keaki_status pipelined_regions(keaki_hip_ctx* ctx, size_t n, size_t ch, s
 // that order the 512 MiB of a 2^24-term polynomial cost 11.5 ms of copy in front of 16.7 ms of kernels (BENCH_r04: 5.96e8/s against
 // 1.007e9/s resident). From `msm_pipe_min` scalars on the vector goes up in point-range chunks through the copy stream and the MSM
 // runs chunk by chunk behind it (msm_host.hip.h: MsmPipe): the upload of chunk j + 1 hides under the kernels of chunk j, only the
-// first chunk's copy stays in front. Chunks GROW (the copy is faster than the kernels, so a short first chunk starts the device early
-// and every later copy still finishes before the device asks for it); `run(pipe)` enqueues the MSM over ctx->io_a.
+// first chunk's copy stays in front; `run(pipe)` enqueues the MSM over ctx->io_a.
 // A pageable source makes every copy call return once its bytes are staged; a pinned one returns at once -- the order of the host's
 // calls (copy j, kernels j, copy j + 1, ...) serves both.
-static std::vector<size_t> msm_pipe_bounds(const Tuning& t, size_t n) {
-  size_t k = 1;
-  if (t.msm_pipe_chunks >= 2) k = (size_t)t.msm_pipe_chunks;
-  else if (t.msm_pipe_chunks < 0 && t.pipe_chunks && n >= (size_t)t.msm_pipe_min) k = n >= ((size_t)1 << 22) ? 6 : n >= ((size_t)1 << 21) ? 4 : 3;      // measured: profiles/r05_msm_pipe_sweep_*.txt
-  if (k > 64) k = 64;
-  if (k > n) k = n ? n : 1;
-  std::vector<size_t> b{0};
-  if (k >= 2) {
-    const double g = std::max(100, std::min(400, t.msm_pipe_growth)) / 100.0;
-    double tot = 0, w = 1;
-    for (size_t j = 0; j < k; j++, w *= g) tot += w;
-    double acc = 0;
-    w = 1;
-    for (size_t j = 0; j + 1 < k; j++, w *= g) {
-      acc += w;
-      size_t e = (size_t)((double)n * acc / tot);
-      if (n >= 65536) e &= ~(size_t)4095;                   // whole pages of scalars, whole tiles of the first sort
-      if (e > b.back() && e < n) b.push_back(e);
-    }
-  }
-  b.push_back(n);
-  return b;
-}
-// the copy-stream side of a chunked upload: `begin` orders the copy stream behind the context's stream, `chunk` copies one piece and makes
-// the context's stream wait for it; on every exit no copy reads the caller's array any more (the fence drains the copy stream)
-struct ChunkUploader {
-  keaki_hip_ctx* ctx;
-  hipStream_t cs = nullptr;
-  StreamFence fence{nullptr, false};
-  explicit ChunkUploader(keaki_hip_ctx* c) : ctx(c) {}
-  keaki_status begin() {
-    ST_TRY(pipe_ready(ctx));
-    // the copy stream starts behind whatever the context's stream holds (an earlier call's kernels may still read the destination)
-    HIP_TRY(ctx, hipEventRecord(ctx->pipe_done[0], ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->pipe_done[0], 0));
-    fence.s = cs = ctx->copy_stream; fence.armed = true;
-    return KEAKI_OK;
-  }
-  keaki_status chunk(size_t j, void* dst, const void* src, size_t bytes) {
-    const int h = (int)(j & 1);
-    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
-    HIP_TRY(ctx, hipEventRecord(ctx->pipe_in[h], cs));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->pipe_in[h], 0));
-    return KEAKI_OK;
-  }
-};
+// The chunk bounds: host_plan.h (msm_pipe_bounds). One piece is begin(false) and one put in front of the MSM.
 template <class Run>
-static keaki_status msm_from_host(keaki_hip_ctx* ctx, const uint64_t* scalars, size_t n, Run run) {
+static keaki_status msm_from_host(CopyFeed& feed, const uint64_t* scalars, size_t n, Run run) {
+  keaki_hip_ctx* ctx = feed.ctx;
   ST_TRY(reserve(ctx, ctx->io_a, n ? n * 32 : 16));
   MsmPipe pipe;
   const std::vector<size_t> bounds = msm_pipe_bounds(ctx->tune, n);
   for (size_t j = 0; j + 1 < bounds.size(); j++) pipe.ranges.push_back({bounds[j], bounds[j + 1] - bounds[j]});
-  if (pipe.ranges.size() <= 1) {
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    const keaki_status st = run(nullptr);
-    // a FAILED call returns as well only when no copy reads the caller's array any more (header; with a pinned source the copy above is truly
-    // asynchronous): the successful path synchronises when it downloads the result, the failing one here
-    if (st != KEAKI_OK && n) (void)hipStreamSynchronize(ctx->stream);
-    return st;
-  }
-  ChunkUploader up(ctx);
-  ST_TRY(up.begin());
+  const bool chunked = pipe.ranges.size() >= 2;
+  ST_TRY(feed.begin(chunked));
   pipe.stage = [&](size_t j) -> keaki_status {
     const size_t lo = pipe.ranges[j].first, m = pipe.ranges[j].second;
-    return up.chunk(j, (char*)ctx->io_a.p + lo * 32, (const char*)scalars + lo * 32, m * 32);
+    return feed.put(j, (char*)ctx->io_a.p + lo * 32, (const char*)scalars + lo * 32, m * 32);
   };
-  return run(&pipe);
+  if (chunked) return run(&pipe);
+  ST_TRY(pipe.stage(0));
+  return run(nullptr);
 }
 
 #define CTX_GUARD(ctx)                                \
@@ -551,10 +530,11 @@ keaki_status msm_host(const GroupEntries& g, keaki_hip_ctx* ctx, const Srs* srs,
   ST_TRY(srs_holds(ctx, srs, g.msm, n, SRS_SHORT_MSM));
   ST_TRY(reserve(ctx, ctx->io_b, g.jac));
   const auto tb = srs_tables(srs);
-  ST_TRY(msm_from_host(ctx, scalars, n, [&](const MsmPipe* pipe) {
+  CopyFeed feed(ctx);
+  ST_TRY(msm_from_host(feed, scalars, n, [&](const MsmPipe* pipe) {
     return g.msm_run(ctx, srs->d, srs->n, ctx->io_a.p, n, ctx->io_b.p, tb.first, tb.second, pipe);
   }));
-  ST_TRY(download(ctx, out_jac, ctx->io_b.p, g.jac));
+  ST_TRY(download(feed, out_jac, ctx->io_b.p, g.jac));
   resolve_timing(ctx);
   return KEAKI_OK;
 }
@@ -569,12 +549,13 @@ keaki_status mul_batch_host(const GroupEntries& g, keaki_hip_ctx* ctx, const uin
   CTX_GUARD(ctx);                 // held across stage -> kernel -> download: io_a/io_b/io_c belong to this call until it returns
   if (n == 0) return KEAKI_OK;
   if (!points_aff || !scalars || !out_aff || (point_stride != 0 && point_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", g.mul);
-  ST_TRY(upload(ctx, ctx->io_a, points_aff, (point_stride ? n : 1) * g.aff));
-  ST_TRY(upload(ctx, ctx->io_b, scalars, n * 32));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, points_aff, (point_stride ? n : 1) * g.aff));
+  ST_TRY(upload(feed, ctx->io_b, scalars, n * 32));
   ST_TRY(reserve(ctx, ctx->io_c, n * g.aff));
   ST_TRY(mul_batch_dev(g, ctx, ctx->io_a.p, point_stride, ctx->io_b.p, n, ctx->io_c.p));
   prefault_out(ctx, out_aff, n * g.aff);
-  return download(ctx, out_aff, ctx->io_c.p, n * g.aff);
+  return download(feed, out_aff, ctx->io_c.p, n * g.aff);
 }
 
 }  // namespace
@@ -653,7 +634,7 @@ void tune_from_env(Tuning& t) {
 struct BufClass { DevBuf* b; int cls; };   // cls: 1 = workspace, 2 = GT / fixed-base tables of encapsulate
 std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
-  for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums, &ctx->bsums,
+  for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
                     &ctx->pair_ws, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab})
     v.push_back({b, 1});
@@ -704,12 +685,8 @@ void keaki_hip_ctx_destroy(keaki_hip_ctx* ctx) {
     if (bc.b->p) (void)hipFree(bc.b->p);
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->fk_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->pipe_in) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->pipe_done) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->open_ev) if (e) (void)hipEventDestroy(e);
-  if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-  for (auto& e : ctx->aux_ev) if (e) (void)hipEventDestroy(e);
-  if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
+  ctx->pipe.destroy();
+  ctx->aux.destroy();
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   }
   delete ctx;
@@ -749,8 +726,8 @@ keaki_status keaki_hip_debug_set_alloc_limit(keaki_hip_ctx* ctx, size_t bytes) {
 keaki_status keaki_hip_ctx_trim(keaki_hip_ctx* ctx) {
   CTX_GUARD(ctx);
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));      // a table build a failed call left behind
-  if (ctx->copy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
+  if (ctx->aux.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux.stream));      // a table build a failed call left behind
+  if (ctx->pipe.copy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe.copy_stream));
   for (const BufClass& bc : all_bufs(ctx))
     if (bc.b->p) { (void)hipFree(bc.b->p); bc.b->p = nullptr; bc.b->cap = 0; }
   ctx->kem = KemState();         // the buffers are gone: no ready or valid bit outlives its table
@@ -838,10 +815,11 @@ keaki_status keaki_hip_g1_sum_dev(keaki_hip_ctx* ctx, const void* d_points_jac, 
 keaki_status keaki_hip_g1_sum(keaki_hip_ctx* ctx, const uint64_t* points_jac, size_t k, uint64_t* out_jac) {
   CTX_GUARD(ctx);
   if (!out_jac || (k && !points_jac)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g1_sum: null pointer");
-  ST_TRY(upload(ctx, ctx->io_a, points_jac, k * 96));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, points_jac, k * 96));
   ST_TRY(reserve(ctx, ctx->io_b, 96));
   ST_TRY(g1_sum_run(ctx, ctx->io_a.p, k, ctx->io_b.p));
-  return download(ctx, out_jac, ctx->io_b.p, 96);
+  return download(feed, out_jac, ctx->io_b.p, 96);
 }
 
 // ---- batched scalar multiplication -------------------------------------------------------------------
@@ -872,24 +850,17 @@ keaki_status keaki_hip_pairing_batch(keaki_hip_ctx* ctx, const uint64_t* g1_aff,
   CTX_GUARD(ctx);
   if (n == 0) return KEAKI_OK;
   if (!g1_aff || !g2_aff || !gt_out || (g2_stride != 0 && g2_stride != 1)) return fail(ctx, KEAKI_ERR_BAD_ARG, "pairing_batch: bad argument");
-  ST_TRY(upload(ctx, ctx->io_a, g1_aff, n * 64));
-  ST_TRY(upload(ctx, ctx->io_b, g2_aff, (g2_stride ? n : 1) * 128));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, g1_aff, n * 64));
+  ST_TRY(upload(feed, ctx->io_b, g2_aff, (g2_stride ? n : 1) * 128));
   ST_TRY(reserve(ctx, ctx->io_c, n * 384));
   ST_TRY(keaki_hip_pairing_batch_dev(ctx, ctx->io_a.p, ctx->io_b.p, g2_stride, n, ctx->io_c.p));
   prefault_out(ctx, gt_out, n * 384);
-  return download(ctx, gt_out, ctx->io_c.p, n * 384);
+  return download(feed, gt_out, ctx->io_c.p, n * 384);
 }
 
-// a second stream of the context for work that is bound by latency, not by the device (the table of a new commitment), and the means to
+// the context's second stream (internal.h: AuxLane) is for work that is bound by latency, not by the device; this is the means to
 // send the launchers -- which all enqueue on ctx->stream -- there for a scope (the caller holds the context lock)
-static keaki_status aux_ready(keaki_hip_ctx* ctx) {
-  if (ctx->aux_stream) return KEAKI_OK;
-  hipStream_t s = nullptr;
-  HIP_TRY(ctx, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  for (auto& e : ctx->aux_ev) if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  ctx->aux_stream = s;
-  return KEAKI_OK;
-}
 struct StreamSwap {
   keaki_hip_ctx* ctx;
   hipStream_t saved;
@@ -1001,7 +972,7 @@ static keaki_status read_constants(keaki_hip_ctx* ctx, const void* d_tau, const 
 // the table of a new commitment is built on the aux stream; `gt_a_pending_aux` says that the context's stream has not been made to wait for that build yet. It survives
 // an early error return, so a later call that finds the table published or rewrites gt_base orders itself behind the build first -- whatever happened in between.
 static keaki_status wait_aux(keaki_hip_ctx* ctx) {
-  if (ctx->kem.gt_a_pending_aux) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));
+  if (ctx->kem.gt_a_pending_aux) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux.ev[1], 0));
   ctx->kem.gt_a_pending_aux = false;
   return KEAKI_OK;
 }
@@ -1034,11 +1005,11 @@ static keaki_status a_table(keaki_hip_ctx* ctx, const EncapArgs& a, const uint64
   if (!k.gt_a.holds(com_host)) {
     k.gt_a.invalidate();
     ST_TRY(reserve(ctx, k.gt_a.buf, gt_table_bytes(GT_WB_A_REPEAT)));
-    ST_TRY(aux_ready(ctx));
-    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[0], ctx->stream));          // behind every earlier reader of the table and of gt_base
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
-    { StreamSwap on_aux(ctx, ctx->aux_stream); ST_TRY(gt_table_of(ctx, a.d_com, k.gt_a.buf.p, GT_WB_A_FIRST)); }
-    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
+    ST_TRY(ctx->aux.ready(ctx));
+    HIP_TRY(ctx, hipEventRecord(ctx->aux.ev[0], ctx->stream));          // behind every earlier reader of the table and of gt_base
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux.stream, ctx->aux.ev[0], 0));
+    { StreamSwap on_aux(ctx, ctx->aux.stream); ST_TRY(gt_table_of(ctx, a.d_com, k.gt_a.buf.p, GT_WB_A_FIRST)); }
+    HIP_TRY(ctx, hipEventRecord(ctx->aux.ev[1], ctx->aux.stream));
     k.gt_a_pending_aux = out->a_on_aux = true;
     if (a.n > 4096) {
       // the constant base's factor FIRST on the main stream: it fills every SIMD (two waves of 256 registers each) and must be out of the way
@@ -1142,9 +1113,11 @@ keaki_status keaki_hip_encap_prepare(keaki_hip_ctx* ctx, const uint64_t* tau_g2_
   TRACE_SCOPE("keaki.encap_prepare");
   if (!tau_g2_aff) return fail(ctx, KEAKI_ERR_BAD_ARG, "encap_prepare: null pointer");
   if (batch_hint == 0) return KEAKI_OK;
-  ST_TRY(upload(ctx, ctx->io_e, tau_g2_aff, 128));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_e, tau_g2_aff, 128));
   ST_TRY(kem_setup(ctx, ctx->io_e.p, batch_hint));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  feed.settled();
   return KEAKI_OK;
 }
 keaki_status keaki_hip_decap_batch_dev(keaki_hip_ctx* ctx, const void* d_proofs_aff, const void* d_cts_aff, size_t n, void* d_gt_out,
@@ -1256,15 +1229,15 @@ keaki_status keaki_hip_open_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32
                total = o_p + d * 64;
   ST_TRY(reserve(ctx, ctx->io_d, total));
   char* b = (char*)ctx->io_d.p;
-  hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(b + o_ha, hat_a, 2 * d * 32, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(b + o_t1, tw_2d, d * 32, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(b + o_t2, tw_2d_inv, d * 32, hipMemcpyHostToDevice, st));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, b + o_ha, hat_a, 2 * d * 32));
+  ST_TRY(feed.put(0, b + o_t1, tw_2d, d * 32));
+  ST_TRY(feed.put(0, b + o_t2, tw_2d_inv, d * 32));
   (void)tw_d;                       // the size-d transforms take every second entry of the 2d tables
   ST_TRY(fk_cache_ensure(ctx, srs, log2d, b + o_t1));
   ST_TRY(open_fk_run(ctx, srs->fk.hat_s, log2d, b + o_ha, b + o_t1, b + o_t2, b + o_w, b + o_p));
   prefault_out(ctx, proofs_out_aff, d * 64);
-  return download(ctx, proofs_out_aff, b + o_p, d * 64);
+  return download(feed, proofs_out_aff, b + o_p, d * 64);
 }
 
 // FK23 from the coefficients: twiddles and hat_a are derived on the device (row f-4)
@@ -1279,10 +1252,11 @@ keaki_status keaki_hip_open_fk_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, u
   const size_t o_p = 0, o_fr = o_p + d * 32, o_g = o_fr + open_fk_poly_fr_bytes(log2d), o_out = o_g + open_fk_poly_g_bytes(log2d), total = o_out + d * 64;
   ST_TRY(reserve(ctx, ctx->io_d, total));
   char* b = (char*)ctx->io_d.p;
-  HIP_TRY(ctx, hipMemcpyAsync(b + o_p, coeffs, d * 32, hipMemcpyHostToDevice, ctx->stream));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, b + o_p, coeffs, d * 32));
   ST_TRY(open_fk_from_poly(ctx, srs, log2d, b + o_p, omega_2d, omega_2d_inv, inv_2d, b + o_fr, b + o_g, b + o_out));
   prefault_out(ctx, proofs_out_aff, d * 64);
-  return download(ctx, proofs_out_aff, b + o_out, d * 64);
+  return download(feed, proofs_out_aff, b + o_out, d * 64);
 }
 // hat_s = DFT_2d(reversed SRS) for later open_fk calls with this d: setup-time work (the FK23 analogue of keaki_hip_srs_g1_precompute)
 keaki_status keaki_hip_srs_g1_precompute_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_2d) {
@@ -1306,9 +1280,10 @@ keaki_status keaki_hip_fr_fft(keaki_hip_ctx* ctx, uint64_t* data, uint32_t log2n
   const size_t n = (size_t)1 << log2n;
   ST_TRY(reserve(ctx, ctx->io_d, n * 32 + (n / 2 + 1) * 32));
   char* b = (char*)ctx->io_d.p;
-  HIP_TRY(ctx, hipMemcpyAsync(b, data, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, b, data, n * 32));
   ST_TRY(fr_fft_run(ctx, b, log2n, omega, scale_or_null, b + n * 32));
-  return download(ctx, data, b, n * 32);
+  return download(feed, data, b, n * 32);
 }
 
 // ---- vec_commit in one call (src/vec.rs:22-49 behind the padding draw): iFFT -> FK23 openings -> commit, coefficients never leave the device ----
@@ -1328,15 +1303,16 @@ keaki_status keaki_hip_vec_commit(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, con
   char* b = (char*)ctx->io_d.p;
   hipStream_t st = ctx->stream;
   if (m < d) HIP_TRY(ctx, hipMemsetAsync(b + o_c + m * 32, 0, (d - m) * 32, st));          // evaluations beyond the padded vector are zero (ark-poly's ifft resizes)
-  if (n) HIP_TRY(ctx, hipMemcpyAsync(b + o_c, values, n * 32, hipMemcpyHostToDevice, st));
-  if (pad) HIP_TRY(ctx, hipMemcpyAsync(b + o_c + n * 32, pad, 32, hipMemcpyHostToDevice, st));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, b + o_c, values, n * 32));
+  if (pad) ST_TRY(feed.put(0, b + o_c + n * 32, pad, 32));
   ST_TRY(fr_fft_run(ctx, b + o_c, log2d, omega_d_inv, inv_d, b + o_tw));                  // domain.ifft (src/vec.rs:37)
   ST_TRY(open_fk_from_poly(ctx, srs, log2d, b + o_c, omega_2d, omega_2d_inv, inv_2d, b + o_fr, b + o_g, b + o_out));   // :40
   const auto tb = srs_tables(srs);
   ST_TRY(msm_g1_run(ctx, srs->d, srs->n, b + o_c, d, b + o_com, tb.first, tb.second));     // :46 (trailing zero coefficients contribute nothing)
   prefault_out(ctx, proofs_out_aff, d * 64);
   HIP_TRY(ctx, hipMemcpyAsync(com_out_jac, b + o_com, 96, hipMemcpyDeviceToHost, st));
-  ST_TRY(download(ctx, proofs_out_aff, b + o_out, d * 64));
+  ST_TRY(download(feed, proofs_out_aff, b + o_out, d * 64));
   resolve_timing(ctx);
   return KEAKI_OK;
 }
@@ -1445,14 +1421,15 @@ keaki_status keaki_hip_fk_shard_open(keaki_hip_ctx* ctx, keaki_hip_fk_shard* fk,
 keaki_status keaki_hip_g2_prepare(keaki_hip_ctx* ctx, const uint64_t* g2_aff, uint64_t* lines_out, size_t lines_out_bytes) {
   CTX_GUARD(ctx);
   if (!g2_aff || !lines_out || lines_out_bytes < g2_prepared_bytes()) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_prepare: bad argument");
-  ST_TRY(upload(ctx, ctx->io_a, g2_aff, 128));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, g2_aff, 128));
   ST_TRY(reserve(ctx, ctx->io_b, g2_prepared_bytes()));
   HIP_TRY(ctx, hipMemsetAsync(ctx->io_b.p, 0, g2_prepared_bytes(), ctx->stream));
   ST_TRY(g2_prepare_run(ctx, ctx->io_a.p, ctx->io_b.p));
   ST_TRY(reserve(ctx, ctx->io_c, g2_prepared_bytes()));
   HIP_TRY(ctx, hipMemsetAsync(ctx->io_c.p, 0, g2_prepared_bytes(), ctx->stream));
   ST_TRY(lines_to256_run(ctx, ctx->io_b.p, ctx->io_c.p));
-  return download(ctx, lines_out, ctx->io_c.p, g2_prepared_bytes());
+  return download(feed, lines_out, ctx->io_c.p, g2_prepared_bytes());
 }
 
 // ---- test hook: Miller loop alone (n x 12 Fq Montgomery out)
@@ -1460,11 +1437,12 @@ keaki_status keaki_hip_miller_loop_batch(keaki_hip_ctx* ctx, const uint64_t* g1_
   CTX_GUARD(ctx);
   if (n == 0) return KEAKI_OK;
   if (!g1_aff || !g2_aff || !f_mont_out) return fail(ctx, KEAKI_ERR_BAD_ARG, "miller_loop_batch: null pointer");
-  ST_TRY(upload(ctx, ctx->io_a, g1_aff, n * 64));
-  ST_TRY(upload(ctx, ctx->io_b, g2_aff, n * 128));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, g1_aff, n * 64));
+  ST_TRY(upload(feed, ctx->io_b, g2_aff, n * 128));
   ST_TRY(reserve(ctx, ctx->io_c, n * 384));
   ST_TRY(miller_only_run(ctx, ctx->io_a.p, ctx->io_b.p, n, ctx->io_c.p));
-  return download(ctx, f_mont_out, ctx->io_c.p, n * 384);
+  return download(feed, f_mont_out, ctx->io_c.p, n * 384);
 }
 
 // ---- test hook: final exponentiation of caller-supplied Miller-loop outputs (n x 12 Fq, Montgomery) -> n x 384 GT bytes
@@ -1472,13 +1450,62 @@ keaki_status keaki_hip_final_exp_batch(keaki_hip_ctx* ctx, const uint64_t* f_mon
   CTX_GUARD(ctx);
   if (n == 0) return KEAKI_OK;
   if (!f_mont || !gt_out) return fail(ctx, KEAKI_ERR_BAD_ARG, "final_exp_batch: null pointer");
-  ST_TRY(upload(ctx, ctx->io_a, f_mont, n * 384));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, f_mont, n * 384));
   ST_TRY(reserve(ctx, ctx->io_b, n * 384));
   ST_TRY(final_exp_only_run(ctx, ctx->io_a.p, n, ctx->io_b.p));
-  return download(ctx, gt_out, ctx->io_b.p, n * 384);
+  return download(feed, gt_out, ctx->io_b.p, n * 384);
 }
 
 // ---- KZG open on the device (row f-4): value = p(z), proof = commit((p - p(z)) / (x - z)) ------------------------------------------
+// io_c of open and quotient: [quotient nq + 1 Fr | value | work of open_quotient_run for work_n coefficients]
+struct OpenLayout { size_t o_q, o_v, o_w, total; };
+static OpenLayout open_layout(size_t nq, size_t work_n) {
+  const size_t o_v = (nq + 1) * 32, o_w = o_v + 32;
+  return {0, o_v, o_w, o_w + open_quotient_work_bytes(work_n)};
+}
+// one copy in front, on the context's stream: coefficients -> quotient -> MSM
+static keaki_status open_resident(CopyFeed& feed, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, const uint64_t* point, char* b, const OpenLayout& L) {
+  keaki_hip_ctx* ctx = feed.ctx;
+  const auto tb = srs_tables(srs);
+  ST_TRY(feed.put(0, ctx->io_a.p, coeffs, n * 32));
+  if (n) ST_TRY(open_quotient_run(ctx, ctx->io_a.p, n, point, b + L.o_q, b + L.o_v, b + L.o_w));
+  return msm_g1_run(ctx, srs->d, srs->n, b + L.o_q, n ? n - 1 : 0, ctx->io_b.p, tb.first, tb.second);
+}
+// Three streams (host_plan.h: open_plan): the copy stream brings chunk j up while chunk j - 1's quotient and MSM pass run, the AUX stream
+// turns it into quotient coefficients (a handful of short, latency-bound kernels that depend on the chunk above only through its carry Q_hi,
+// planted as one more "coefficient" behind the chunk), the context's stream runs the MSM passes, which consume the quotient chunk by
+// chunk (msm_host.hip.h: MsmPipe). The quotient of chunk j + 1 therefore runs beside the MSM pass of chunk j instead of in front of its own
+// (2^24 coefficients: 20.8 -> 18.5 ms).
+static keaki_status open_chunked(CopyFeed& feed, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, const uint64_t* point, char* b, const OpenLayout& L,
+                                 const OpenPlan& plan) {
+  keaki_hip_ctx* ctx = feed.ctx;
+  const auto tb = srs_tables(srs);
+  ST_TRY(feed.begin(true));
+  ST_TRY(ctx->aux.ready(ctx));
+  hipStream_t ax = ctx->aux.stream, main_st = ctx->stream;
+  hipEvent_t* ev = ctx->aux.open_ev;                                   // [chunk's quotient ready x 2 | start]
+  HIP_TRY(ctx, hipEventRecord(ev[2], main_st));                        // behind the value slot's memset and every earlier user of io_a / io_c
+  HIP_TRY(ctx, hipStreamWaitEvent(ax, ev[2], 0));
+  feed.also_drain(ax);                                                 // nothing of this call is left on it at any exit
+  MsmPipe pipe;
+  pipe.ranges = plan.ranges;
+  char* a = (char*)ctx->io_a.p;
+  pipe.stage = [&](size_t j) -> keaki_status {
+    const size_t lo = plan.chunks[j].first, hi = plan.chunks[j].second;
+    ST_TRY(feed.put(j, a + lo * 32, (const char*)coeffs + lo * 32, (hi - lo) * 32, ax));
+    {
+      StreamSwap on_aux(ctx, ax);                                      // the launchers enqueue on ctx->stream
+      // the carry: Q_hi = q_(hi-1), written by the chunk above; it takes the place of c_hi, which that chunk has consumed
+      if (j) HIP_TRY(ctx, hipMemcpyAsync(a + hi * 32, b + L.o_q + (hi - 1) * 32, 32, hipMemcpyDeviceToDevice, ax));
+      ST_TRY(open_quotient_run(ctx, a + lo * 32, hi - lo + (j ? 1 : 0), point, b + L.o_q + lo * 32, lo ? b + L.o_q + (lo - 1) * 32 : b + L.o_v, b + L.o_w, j != 0));
+    }
+    HIP_TRY(ctx, hipEventRecord(ev[j & 1], ax));
+    HIP_TRY(ctx, hipStreamWaitEvent(main_st, ev[j & 1], 0));
+    return KEAKI_OK;
+  };
+  return msm_g1_run(ctx, srs->d, srs->n, b + L.o_q, n - 1, ctx->io_b.p, tb.first, tb.second, &pipe);
+}
 keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, const uint64_t* point,
                                 uint64_t* proof_out_jac, uint64_t* value_out) {
   CTX_GUARD(ctx);
@@ -1486,66 +1513,17 @@ keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs,
   if (!srs || !point || !proof_out_jac || (n && !coeffs)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_open: null pointer");
   const size_t nq = n ? n - 1 : 0;
   ST_TRY(srs_holds(ctx, srs, "kzg_open", nq, SRS_SHORT_MSM));
-  const size_t o_q = 0, o_v = o_q + (nq + 1) * 32, o_w = o_v + 32, total = o_w + open_quotient_work_bytes(n + 1);
+  const OpenLayout L = open_layout(nq, n + 1);
   ST_TRY(reserve(ctx, ctx->io_a, n ? n * 32 : 16));
-  ST_TRY(reserve(ctx, ctx->io_c, total));
+  ST_TRY(reserve(ctx, ctx->io_c, L.total));
   ST_TRY(reserve(ctx, ctx->io_b, 96));
   char* b = (char*)ctx->io_c.p;
-  HIP_TRY(ctx, hipMemsetAsync(b + o_v, 0, 32, ctx->stream));                     // the zero polynomial evaluates to 0
-  const auto tb = srs_tables(srs);
-  // Long polynomials come up in chunks FROM THE TOP (the quotient's recurrence Q_i = c_i + z Q_(i+1) runs downwards): chunk j's coefficients are
-  // uploaded on the copy stream while chunk j - 1's quotient and MSM pass run; its quotient starts from the carry Q_hi the chunk above left
-  // (planted as one more "coefficient" behind the chunk), and the MSM consumes the quotient chunk by chunk (msm_host.hip.h: MsmPipe).
-  std::vector<std::pair<size_t, size_t>> cch;                                    // coefficient chunks [lo, hi), top first
-  // (automatic from 2^21 coefficients on: the first chunk's quotient stays in front of the first pass; 2^20: 2.71 ms in three chunks against 2.64
-  // with the copy in front, 2^21: 4.05 / 4.36, 2^22: 6.43 / 8.10, 2^24: 19.2 / 28.0 ms -- profiles/r05_open_chunked.txt)
-  if (ctx->tune.msm_pipe_chunks >= 2 || (ctx->tune.msm_pipe_chunks < 0 && ctx->tune.pipe_chunks && n >= ((size_t)1 << 21))) {     // "pipe_chunks" = 0 or "msm_pipe_chunks" = 0 / 1: one copy in front, on the context's stream
-    const std::vector<size_t> bounds = msm_pipe_bounds(ctx->tune, n);
-    for (size_t j = 0; j + 1 < bounds.size(); j++) cch.push_back({n - bounds[j + 1], n - bounds[j]});
-    if (cch.size() >= 2 && cch.back().second == 1) { cch[cch.size() - 2].first = 0; cch.pop_back(); }     // the lowest chunk must leave a quotient coefficient
-  }
-  if (cch.size() <= 1 || nq == 0) {
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    // a failing call, too, returns only when no copy reads `coeffs` any more (header): the successful path synchronises in `download` below
-    StreamFence fence{ctx->stream, n != 0};
-    if (n) ST_TRY(open_quotient_run(ctx, ctx->io_a.p, n, point, b + o_q, b + o_v, b + o_w));
-    ST_TRY(msm_g1_run(ctx, srs->d, srs->n, b + o_q, nq, ctx->io_b.p, tb.first, tb.second));
-    fence.armed = false;
-  } else {
-    // Three streams: the copy stream brings chunk j up, the AUX stream turns it into quotient coefficients (a handful of short,
-    // latency-bound kernels that depend on the chunk above only through its carry), the context's stream runs the MSM passes. The quotient of
-    // chunk j + 1 therefore runs beside the MSM pass of chunk j instead of in front of its own (2^24 coefficients: 20.8 -> 18.5 ms).
-    ChunkUploader up(ctx);
-    ST_TRY(up.begin());
-    ST_TRY(aux_ready(ctx));
-    for (auto& e : ctx->open_ev) if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hipStream_t ax = ctx->aux_stream, main_st = ctx->stream;
-    HIP_TRY(ctx, hipEventRecord(ctx->open_ev[4], main_st));              // behind the value slot's memset and every earlier user of io_a / io_c
-    HIP_TRY(ctx, hipStreamWaitEvent(ax, ctx->open_ev[4], 0));
-    StreamFence aux_fence{ax, true};                                     // nothing of this call is left on it at any exit
-    MsmPipe pipe;
-    for (const auto& c : cch) pipe.ranges.push_back({c.first ? c.first - 1 : 0, c.second - 1 - (c.first ? c.first - 1 : 0)});   // q_i = Q_(i+1): chunk [lo, hi) yields q_(lo-1) .. q_(hi-2)
-    char* a = (char*)ctx->io_a.p;
-    pipe.stage = [&](size_t j) -> keaki_status {
-      const size_t lo = cch[j].first, hi = cch[j].second;
-      const int h = (int)(j & 1);
-      HIP_TRY(ctx, hipMemcpyAsync(a + lo * 32, (const char*)coeffs + lo * 32, (hi - lo) * 32, hipMemcpyHostToDevice, up.cs));
-      HIP_TRY(ctx, hipEventRecord(ctx->open_ev[h], up.cs));
-      HIP_TRY(ctx, hipStreamWaitEvent(ax, ctx->open_ev[h], 0));
-      {
-        StreamSwap on_aux(ctx, ax);                                      // the launchers enqueue on ctx->stream
-        // the carry: Q_hi = q_(hi-1), written by the chunk above; it takes the place of c_hi, which that chunk has consumed
-        if (j) HIP_TRY(ctx, hipMemcpyAsync(a + hi * 32, b + o_q + (hi - 1) * 32, 32, hipMemcpyDeviceToDevice, ax));
-        ST_TRY(open_quotient_run(ctx, a + lo * 32, hi - lo + (j ? 1 : 0), point, b + o_q + lo * 32, lo ? b + o_q + (lo - 1) * 32 : b + o_v, b + o_w, j != 0));
-      }
-      HIP_TRY(ctx, hipEventRecord(ctx->open_ev[2 + h], ax));
-      HIP_TRY(ctx, hipStreamWaitEvent(main_st, ctx->open_ev[2 + h], 0));
-      return KEAKI_OK;
-    };
-    ST_TRY(msm_g1_run(ctx, srs->d, srs->n, b + o_q, nq, ctx->io_b.p, tb.first, tb.second, &pipe));
-  }
-  ST_TRY(download(ctx, proof_out_jac, ctx->io_b.p, 96));
-  if (value_out) ST_TRY(download(ctx, value_out, b + o_v, 32));
+  HIP_TRY(ctx, hipMemsetAsync(b + L.o_v, 0, 32, ctx->stream));                   // the zero polynomial evaluates to 0
+  const OpenPlan plan = open_plan(ctx->tune, n);
+  CopyFeed feed(ctx);
+  ST_TRY(plan.chunked() ? open_chunked(feed, srs, coeffs, n, point, b, L, plan) : open_resident(feed, srs, coeffs, n, point, b, L));
+  ST_TRY(download(feed, proof_out_jac, ctx->io_b.p, 96));
+  if (value_out) ST_TRY(download(ctx, value_out, b + L.o_v, 32));
   resolve_timing(ctx);
   return KEAKI_OK;
 }
@@ -1557,16 +1535,15 @@ keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, 
   TRACE_SCOPE("keaki.kzg_quotient");
   if (!point || (n && !coeffs) || (n > 1 && !quotient_out)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_quotient: null pointer");
   const size_t nq = n ? n - 1 : 0;
-  const size_t o_q = 0, o_v = o_q + (nq + 1) * 32, o_w = o_v + 32, total = o_w + open_quotient_work_bytes(n);
-  ST_TRY(upload(ctx, ctx->io_a, coeffs, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_c, total));
+  const OpenLayout L = open_layout(nq, n);
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, coeffs, n * 32));
+  ST_TRY(reserve(ctx, ctx->io_c, L.total));
   char* b = (char*)ctx->io_c.p;
-  HIP_TRY(ctx, hipMemsetAsync(b + o_v, 0, 32, ctx->stream));
-  if (n) ST_TRY(open_quotient_run(ctx, ctx->io_a.p, n, point, b + o_q, b + o_v, b + o_w));
-  if (nq) HIP_TRY(ctx, hipMemcpyAsync(quotient_out, b + o_q, nq * 32, hipMemcpyDeviceToHost, ctx->stream));
-  if (value_out) HIP_TRY(ctx, hipMemcpyAsync(value_out, b + o_v, 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return KEAKI_OK;
+  HIP_TRY(ctx, hipMemsetAsync(b + L.o_v, 0, 32, ctx->stream));
+  if (n) ST_TRY(open_quotient_run(ctx, ctx->io_a.p, n, point, b + L.o_q, b + L.o_v, b + L.o_w));
+  if (nq) HIP_TRY(ctx, hipMemcpyAsync(quotient_out, b + L.o_q, nq * 32, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, value_out, b + L.o_v, value_out ? 32 : 0);
 }
 
 // ---- batched commit / open: m rows over one SRS in one call (msm_batch.hip) ---------------------------------------------------------------
@@ -1637,12 +1614,11 @@ keaki_status keaki_hip_msm_g1_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* 
   ST_TRY(srs_holds(ctx, srs, "msm_g1_batch", n, SRS_SHORT_MSM));
   // one upload in front, the kernels, one download of m x 96 B: the rows are short, there is nothing for a chunk pipeline to hide
   ST_TRY(reserve(ctx, ctx->io_b, m * G1_JAC_BYTES));
-  ST_TRY(upload(ctx, ctx->io_a, scalars, batch_span(n, m, stride)));
-  StreamFence fence{ctx->stream, true};
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, scalars, batch_span(n, m, stride)));
   ST_TRY(keaki_hip_msm_g1_batch_dev(ctx, srs, ctx->io_a.p, n, m, stride, ctx->io_b.p));
   prefault_out(ctx, out_jac, m * G1_JAC_BYTES);
-  fence.armed = false;
-  return download(ctx, out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
+  return download(feed, out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
 }
 keaki_status keaki_hip_kzg_open_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, size_t m, size_t stride,
                                           const void* d_points, void* d_proofs_out_jac, void* d_values_out) {
@@ -1666,13 +1642,12 @@ keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1
   ST_TRY(reserve(ctx, ctx->io_d, m * 32));
   ST_TRY(reserve(ctx, ctx->io_a, std::max<size_t>(16, batch_span(n, m, stride))));
   ST_TRY(reserve(ctx, ctx->io_c, m * 32));
-  StreamFence fence{ctx->stream, true};
-  if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->io_a.p, coeffs, batch_span(n, m, stride), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_c.p, points, m * 32, hipMemcpyHostToDevice, ctx->stream));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, ctx->io_a.p, coeffs, batch_span(n, m, stride)));
+  ST_TRY(feed.put(0, ctx->io_c.p, points, m * 32));
   ST_TRY(keaki_hip_kzg_open_batch_dev(ctx, srs, ctx->io_a.p, n, m, stride, ctx->io_c.p, ctx->io_b.p, ctx->io_d.p));
   if (values_out) HIP_TRY(ctx, hipMemcpyAsync(values_out, ctx->io_d.p, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-  fence.armed = false;
-  return download(ctx, proofs_out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
+  return download(feed, proofs_out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
 }
 
 // ---- KZG verify -----------------------------------------------------------------------------------------------------
@@ -1817,22 +1792,15 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
   if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
   if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
   char* io = (char*)ctx->vb_io.p;
-  // a failing call, too, returns only when no copy reads the caller's arrays any more (the successful path synchronises in its download)
-  StreamFence fence{ctx->stream, true};
-  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_PTS, com_aff, 64, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_QS + 128, tau_g2_aff, 128, hipMemcpyHostToDevice, ctx->stream));
-  if (point_mode) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_OMEGA, points, 32, hipMemcpyHostToDevice, ctx->stream));
+  CopyFeed feed(ctx);
+  if (!com_stride) ST_TRY(feed.put(0, io + VbLayout::O_PTS, com_aff, 64));
+  ST_TRY(feed.put(0, io + VbLayout::O_QS + 128, tau_g2_aff, 128));
+  if (point_mode) ST_TRY(feed.put(0, io + VbLayout::O_OMEGA, points, 32));
   // Large batches (160 B per item) go up on the context's copy stream in the order the kernels ask for them: gammas and proofs, then -- under
   // the first MSM -- commitments, points and values. Small ones, and a context told to use no other stream (pipe_chunks = 0), copy in front.
-  ChunkUploader up(ctx);
-  const bool on_copy_stream = ctx->tune.pipe_chunks && n >= PIPE_CHUNK;
-  if (on_copy_stream) ST_TRY(up.begin());
+  ST_TRY(feed.begin(ctx->tune.pipe_chunks && n >= PIPE_CHUNK));
   size_t piece = 0;
-  auto put = [&](void* dst, const void* src, size_t bytes) -> keaki_status {
-    if (on_copy_stream) return up.chunk(piece++, dst, src, bytes);
-    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return KEAKI_OK;
-  };
+  auto put = [&](void* dst, const void* src, size_t bytes) { return feed.put(piece++, dst, src, bytes); };
   const std::function<keaki_status(int)> stage = [&](int phase) -> keaki_status {
     if (phase == 0) {
       ST_TRY(put(ctx->io_a.p, gammas, n * 32));
@@ -1843,10 +1811,9 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
     if (com_stride) ST_TRY(put(ctx->io_e.p, com_aff, n * G1_AFF_BYTES));
     return KEAKI_OK;
   };
-  const keaki_status st = verify_batch_core(ctx, ctx->io_e.p, com_stride, ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, ctx->io_a.p, n, stage, ok_out,
-                                            sums_out_aff);
-  if (st == KEAKI_OK) fence.armed = false;
-  return st;
+  ST_TRY(verify_batch_core(ctx, ctx->io_e.p, com_stride, ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, ctx->io_a.p, n, stage, ok_out, sums_out_aff));
+  feed.settled();                 // verify_batch_core has downloaded the result
+  return KEAKI_OK;
 }
 
 // ---- SRS ingest: on-curve check (row f-3) ------------------------------------------------------------------------
@@ -1869,8 +1836,11 @@ keaki_status keaki_hip_srs_g1_check(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* 
 keaki_status keaki_hip_g2_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint64_t* n_off_curve, uint64_t* first_off_curve) {
   CTX_GUARD(ctx);
   if (!n_off_curve || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_check: null pointer");
-  ST_TRY(upload(ctx, ctx->io_a, points_aff, n * 128));
-  return curve_check_common(ctx, true, ctx->io_a.p, n, n_off_curve, first_off_curve);
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, points_aff, n * 128));
+  ST_TRY(curve_check_common(ctx, true, ctx->io_a.p, n, n_off_curve, first_off_curve));
+  feed.settled();                 // curve_check_common has downloaded the counters
+  return KEAKI_OK;
 }
 
 // ---- compressed point wire format (point_codec.hip): compress, decompress with validation, G2 subgroup check --------------------------------

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -90,7 +91,7 @@ struct KemState {
   bool gt_b_ready = false, gt_b_fallback = false;   // fallback: the wide table of B did not fit once, stay at 16 bits
   uint32_t gt_b_wb = 0;
   KeyedTable<8> gt_a;
-  bool gt_a_pending_aux = false;          // the A-table build on aux_stream has not been waited for by `stream` yet (api.hip: wait_aux)
+  bool gt_a_pending_aux = false;          // the A-table build on aux.stream has not been waited for by `stream` yet (api.hip: wait_aux)
   uint64_t seen_com[8] = {};              // commitment of the last encap call and how many consecutive calls carried it
   uint32_t seen_com_runs = 0;
   // every DevBuf above with its memory class (keaki_hip_ctx_memory: 1 = workspace, 2 = GT / fixed-base tables): a new table is added HERE
@@ -98,6 +99,47 @@ struct KemState {
     for (DevBuf* b : {&g2gen_lines, &g2pow_lines, &g2pow_pts, &verify_io}) f(b, 1);
     for (DevBuf* b : {&fb_g1_gen, &fb_g2_gen, &fb_com, &fb_tau.buf, &fbs_g2_gen, &fbs_tau.buf, &fbs_g1_gen, &gt_a.buf, &gt_tab_b, &gt_base}) f(b, 2);
   }
+};
+keaki_status fail(keaki_hip_ctx* ctx, keaki_status code, const char* fmt, ...);
+#define HIP_TRY(ctx, call)                                                                              \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess)                                                                               \
+      return keaki_internal::fail(ctx, e_ == hipErrorOutOfMemory ? KEAKI_ERR_OOM : KEAKI_ERR_HIP, "%s failed: %s (%s:%d)", #call, \
+                  hipGetErrorString(e_), __FILE__, __LINE__);                                           \
+  } while (0)
+#define ST_TRY(call)                 \
+  do {                               \
+    keaki_status s_ = (call);        \
+    if (s_ != KEAKI_OK) return s_;   \
+  } while (0)
+
+// A side stream of a context with its events, created on first use and released with the context (the stream LAST: it says that all exist).
+inline keaki_status lane_ready(keaki_hip_ctx* ctx, hipStream_t& s, std::initializer_list<hipEvent_t*> evs) {
+  if (s) return KEAKI_OK;
+  for (hipEvent_t* e : evs) if (!*e) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  HIP_TRY(ctx, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  return KEAKI_OK;
+}
+inline void lane_destroy(hipStream_t& s, std::initializer_list<hipEvent_t*> evs) {
+  for (hipEvent_t* e : evs) if (*e) (void)hipEventDestroy(*e);
+  if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+}
+// host-pointer calls in chunks (api.hip: CopyFeed, pipelined): uploads and downloads of the neighbouring chunks on a stream of their own.
+// [in: chunk staged | done: chunk computed], one pair per buffer half
+struct HostPipe {
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t in[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
+  keaki_status ready(keaki_hip_ctx* ctx) { return lane_ready(ctx, copy_stream, {&in[0], &in[1], &done[0], &done[1]}); }
+  void destroy() { lane_destroy(copy_stream, {&in[0], &in[1], &done[0], &done[1]}); }
+};
+// latency-bound side jobs: the GT table of a new commitment (api.hip: a_table) with ev = [go | done], and the quotients of a chunked
+// kzg_open (api.hip: open_chunked) with open_ev = [chunk's quotient ready x 2 | start]
+struct AuxLane {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr}, open_ev[3] = {nullptr, nullptr, nullptr};
+  keaki_status ready(keaki_hip_ctx* ctx) { return lane_ready(ctx, stream, {&ev[0], &ev[1], &open_ev[0], &open_ev[1], &open_ev[2]}); }
+  void destroy() { lane_destroy(stream, {&ev[0], &ev[1], &open_ev[0], &open_ev[1], &open_ev[2]}); }
 };
 }  // namespace keaki_internal
 
@@ -113,7 +155,7 @@ struct keaki_hip_ctx {
   std::recursive_mutex mu;   // recursive: host-pointer entry points hold it across stage -> *_dev -> download
   std::string err;
   // grow-only workspaces (all used in stream order); fb_bases: scratch of g1/g2_fb_table_run
-  keaki_internal::DevBuf digits, hist, offsets, cursor, sorted, buckets, acc29, partials, wsums, bsums, tmp_a, tmp_b, tmp_c, io_a, io_b, io_c, io_d, io_e, perm, heavy, fb_bases;
+  keaki_internal::DevBuf digits, hist, offsets, cursor, sorted, buckets, acc29, partials, wsums, tmp_a, tmp_b, tmp_c, io_a, io_b, io_c, io_d, io_e, perm, heavy, fb_bases;
   keaki_internal::KemState kem;                     // every cached table of encapsulate and kzg verify
   keaki_internal::DevBuf pair_ws;                   // per-item slots of the final exponentiation (pairing.hip.h)
   keaki_internal::DevBuf fk_tab;                    // window tables of the per-lane-scalar ladders of FK23: 1 KB per lane of a launch (64 x 16 B), at most 2 GB (fft_g1.hip)
@@ -129,13 +171,8 @@ struct keaki_hip_ctx {
   hipEvent_t fk_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool fk_timing_pending = false;
   float last_fk_ms[3] = {-1.f, -1.f, -1.f};      // pointwise products, butterfly stages (k_g1_fft_stage_map), whole device pipeline
-  // host-pointer batches run in chunks (api.hip: pipelined): uploads and downloads of the neighbouring chunks on a stream of their own.
-  // Created on first use. [in: chunk staged | done: chunk computed], one pair per buffer half
-  hipStream_t aux_stream = nullptr;              // latency-bound side jobs (api.hip: the GT table of a new commitment), with [go | done]
-  hipEvent_t aux_ev[2] = {nullptr, nullptr};
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t pipe_in[2] = {nullptr, nullptr}, pipe_done[2] = {nullptr, nullptr};
-  hipEvent_t open_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // chunked kzg_open: [chunk uploaded x 2 | chunk's quotient ready x 2 | start]
+  keaki_internal::HostPipe pipe;                    // the copy stream of the chunked host-pointer calls
+  keaki_internal::AuxLane aux;                      // the stream of the latency-bound side jobs
 };
 
 namespace keaki_internal {
@@ -159,7 +196,6 @@ struct DeviceScope {
   DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
-keaki_status fail(keaki_hip_ctx* ctx, keaki_status code, const char* fmt, ...);
 keaki_status reserve(keaki_hip_ctx* ctx, DevBuf& b, size_t bytes);
 // hipMalloc behind the library's one allocation gate. keaki_hip_debug_set_alloc_limit(ctx, bytes) makes every single allocation of this
 // context above that size fail with KEAKI_ERR_OOM, which is how the tests exercise the optional-memory fallbacks (SRS window tables,
@@ -168,19 +204,6 @@ keaki_status reserve(keaki_hip_ctx* ctx, DevBuf& b, size_t bytes);
 keaki_status dev_alloc(keaki_hip_ctx* ctx, void** p, size_t bytes);
 keaki_status launch_check(keaki_hip_ctx* ctx, const char* what);
 inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
-
-#define HIP_TRY(ctx, call)                                                                              \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return keaki_internal::fail(ctx, e_ == hipErrorOutOfMemory ? KEAKI_ERR_OOM : KEAKI_ERR_HIP, "%s failed: %s (%s:%d)", #call, \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                                           \
-  } while (0)
-#define ST_TRY(call)                 \
-  do {                               \
-    keaki_status s_ = (call);        \
-    if (s_ != KEAKI_OK) return s_;   \
-  } while (0)
 
 // Chunked form of one MSM (the host-pointer entries, api.hip): the (scalar, point) pairs are cut into point-range chunks; every chunk
 // runs its own tile sort -> chunk sort -> size order -> bucket pass, the bucket pass going on from what the earlier chunks left in the

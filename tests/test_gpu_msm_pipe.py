@@ -424,6 +424,30 @@ def test_a_chunked_call_that_fails_leaves_the_context_usable(oc, rand_fr):
         h.close()
 
 
+def test_a_plain_call_that_fails_behind_its_uploads_leaves_the_context_usable(oc, hip, rand_fr):
+    """the failure rule of the host-array calls holds for the plain forms too (api.hip: CopyFeed): pairing_batch of 1,024 pairs on a fresh
+    context whose allocation limit admits the two input buffers (requests of 73,984 and 147,712 bytes, both uploads enqueued) and refuses
+    the output buffer (442,624 bytes) returns KEAKI_ERR_OOM with its stream drained, and the same call on the same context is right once
+    the limit is lifted"""
+    from keaki_amd.hip import KeakiHip, KeakiHipError
+    n = 1024
+    g1, g2 = oc.generators()
+    P = hip.g1_mul_batch(g1, _mont(oc, rand_fr(n, 7710)))
+    Q = hip.g2_mul_batch(g2, _mont(oc, rand_fr(n, 7711)))
+    some = [0, 517, n - 1]
+    exp = oc.pairing_batch(P[some], Q[some], threads=3)
+    h = KeakiHip(0)
+    try:
+        h.debug_set_alloc_limit(200000)
+        with pytest.raises(KeakiHipError) as e:
+            h.pairing_batch(P, Q)
+        assert e.value.status == -3 and "442624" in e.value.message
+        h.debug_set_alloc_limit(0)
+        assert np.array_equal(h.pairing_batch(P, Q)[some], exp)
+    finally:
+        h.close()
+
+
 @pytest.mark.parametrize("nb,length", [(7, 3000), (64, 468), (15, 2000), (3, 8000), (1, 5000)])
 def test_index_groups_when_neighbouring_lanes_step_over_empty_segments(oc, piped, nb, length):
     """Round 6: the G1 / G2 bucket kernels read their index stream by aligned 64-byte groups through a lane-private LDS slot (csrc/msm.hip.h segq_*).
