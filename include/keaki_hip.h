@@ -271,6 +271,41 @@ keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1
 keaki_status keaki_hip_kzg_open_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, size_t m, size_t stride,
                                           const void* d_points, void* d_proofs_out_jac, void* d_values_out);      /* src/kzg.rs:104-124, device-resident */
 
+/* ---- batched FK23 openings and vec_commit: m small vectors over ONE domain in one call ------------------------------------------------------
+ * keaki_hip_open_fk_poly and keaki_hip_vec_commit are built for one large domain; at d = 2^8 a call is ~67 launches of 128 lanes. Here m rows
+ * pay every launch once, and because the rows of a pass share the twiddle of every butterfly, all stages run the shared-scalar ladder.
+ *   layout     as keaki_hip_msm_g1_batch: row j at base + 4 * stride * j (64-bit words), stride in Fr units; the gap between rows is never read.
+ *              open_fk_poly_batch: a row is d = 2^log2d coefficients, stride >= d. vec_commit_batch: a row is its first n <= d evaluations,
+ *              stride >= n, with the padding scalar of src/vec.rs:31-33 already appended by the caller (row j = vec_j | r_j | 0...: vectors of
+ *              unequal length share one call); evaluations n .. d - 1 are zero, as ark-poly's ifft resizes. There is no `pad` argument.
+ *              proofs_out_aff: m x d affine points, row j's proofs in natural order at proofs + 8 * d * j; com_out_jac: m x u64[12] normalised Jacobian.
+ *   results    row j is byte for byte what keaki_hip_open_fk_poly returns for that row alone, and what keaki_hip_vec_commit returns for it with
+ *              values = the row and pad = NULL -- whichever route the call takes, on a handle with window tables and on one without.
+ *   routes     d = 2 .. 4,096 (FKB_LOG2D_MAX = 12) run the batch kernels in passes of whole rows: at most 256 MB of workspace (288 d bytes per
+ *              row, rows in groups of 64) and 16,384 rows a pass; a workspace the device (or keaki_hip_debug_set_alloc_limit) refuses halves the
+ *              pass. Larger domains, d = 1, and calls refused down to a single row run the single pipeline row by row, unchanged. The m
+ *              commitments are keaki_hip_msm_g1_batch_dev over the coefficient rows, with its own routes.
+ *   errors     a null pointer, stride too small, n > d, m * d >= 2^31, log2d > 27 -> KEAKI_ERR_BAD_ARG; d > len(srs) -> KEAKI_ERR_TOO_LARGE, as
+ *              the single calls. m = 0 writes nothing and returns KEAKI_OK.
+ *   host form  one upload of the rows (the span from row 0 to the end of row m - 1), the kernels, one download; no chunk pipeline. A failing
+ *              call returns only when nothing reads or writes caller memory any more.
+ *   _dev       every array is a device pointer (16-byte aligned); the three to five domain constants stay host pointers (read before the call
+ *              returns); asynchronous on the ctx stream like keaki_hip_msm_g1_batch_dev.
+ *   context    the ctx lock and the handle's lock are held for the call; the handle's cached transform is used and, at another d, replaced
+ *              exactly as by a single call. Workspace grow-only, counted in keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim. */
+keaki_status keaki_hip_open_fk_poly_batch(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* coeffs, size_t m, size_t stride,
+                                          const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d,
+                                          uint64_t* proofs_out_aff);     /* m x kzg::open_fk, src/kzg.rs:157-203 */
+keaki_status keaki_hip_open_fk_poly_batch_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_coeffs, size_t m, size_t stride,
+                                              const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d, void* d_proofs_out_aff);
+keaki_status keaki_hip_vec_commit_batch(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const uint64_t* evals, size_t n, size_t m, size_t stride,
+                                        uint32_t log2d, const uint64_t* omega_d_inv, const uint64_t* inv_d, const uint64_t* omega_2d,
+                                        const uint64_t* omega_2d_inv, const uint64_t* inv_2d, uint64_t* com_out_jac,
+                                        uint64_t* proofs_out_aff);       /* m x the body of vec::vec_commit, src/vec.rs:36-46 */
+keaki_status keaki_hip_vec_commit_batch_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const void* d_evals, size_t n, size_t m, size_t stride,
+                                            uint32_t log2d, const uint64_t* omega_d_inv, const uint64_t* inv_d, const uint64_t* omega_2d,
+                                            const uint64_t* omega_2d_inv, const uint64_t* inv_2d, void* d_com_out_jac, void* d_proofs_out_aff);
+
 /* ---- KZG `verify` in one call -------------------------------------------------------------------------------------
  * Replaces the body of `verify` (reference src/kzg.rs:127-146): e(com - value g1, g2) == e(proof, [tau]_2 - point g2).
  * Evaluated exactly in that form: the two inner points are fixed-base sums over 8-bit window tables of g1 and g2 (built at the first

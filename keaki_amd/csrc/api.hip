@@ -636,7 +636,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab})
+                    &ctx->pair_ws, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
     v.push_back({b, 1});
   ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
@@ -1648,6 +1648,135 @@ keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1
   ST_TRY(keaki_hip_kzg_open_batch_dev(ctx, srs, ctx->io_a.p, n, m, stride, ctx->io_c.p, ctx->io_b.p, ctx->io_d.p));
   if (values_out) HIP_TRY(ctx, hipMemcpyAsync(values_out, ctx->io_d.p, m * 32, hipMemcpyDeviceToHost, ctx->stream));
   return download(feed, proofs_out_jac, ctx->io_b.p, m * G1_JAC_BYTES);
+}
+
+// ---- batched FK23 openings / vec_commit: m rows over one domain in one call (fk_batch.hip) --------------------------------------------------
+extern "C++" {
+namespace {
+// the domain constants of a call (host pointers, read before the call returns); omega_d_inv / inv_d: vec_commit only
+struct FkbConsts { const uint64_t *omega_d_inv, *inv_d, *omega_2d, *omega_2d_inv, *inv_2d; };
+// How the four entries start: fk_enter, then the row layout. n: elements read of a row (d for open_fk_poly_batch). *empty: m = 0.
+keaki_status fkb_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool ptrs_ok, const char* what, size_t n, size_t m, size_t stride,
+                       std::unique_lock<std::recursive_mutex>& hl, bool* empty) {
+  *empty = false;
+  ST_TRY(fk_enter(ctx, srs, log2d, ptrs_ok || m == 0, what, hl));
+  const size_t d = (size_t)1 << log2d;
+  if (n > d) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %zu evaluations do not fit the domain of %zu", what, n, d);
+  if (stride < n) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: stride %zu is shorter than a row of %zu", what, stride, n);
+  if (m >= ((size_t)1 << (31 - log2d))) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: m * d must be < 2^31", what);
+  *empty = m == 0;
+  return KEAKI_OK;
+}
+// row by row through the single pipeline (device rows): the steps of keaki_hip_open_fk_poly / keaki_hip_vec_commit between their copies
+keaki_status fkb_row_single(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_row, size_t n, const FkbConsts& k, void* d_com, void* d_proofs) {
+  const size_t d = (size_t)1 << log2d;
+  const size_t o_c = 0, o_tw = o_c + d * 32, o_fr = o_tw + (d / 2 + 1) * 32, o_g = o_fr + open_fk_poly_fr_bytes(log2d), total = o_g + open_fk_poly_g_bytes(log2d);
+  ST_TRY(reserve(ctx, ctx->io_d, total));
+  char* b = (char*)ctx->io_d.p;
+  if (!d_com) return open_fk_from_poly(ctx, srs, log2d, d_row, k.omega_2d, k.omega_2d_inv, k.inv_2d, b + o_fr, b + o_g, d_proofs);
+  if (n < d) HIP_TRY(ctx, hipMemsetAsync(b + o_c + n * 32, 0, (d - n) * 32, ctx->stream));
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(b + o_c, d_row, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+  ST_TRY(fr_fft_run(ctx, b + o_c, log2d, k.omega_d_inv, k.inv_d, b + o_tw));
+  ST_TRY(open_fk_from_poly(ctx, srs, log2d, b + o_c, k.omega_2d, k.omega_2d_inv, k.inv_2d, b + o_fr, b + o_g, d_proofs));
+  const auto tb = srs_tables(srs);
+  return msm_g1_run(ctx, srs->d, srs->n, b + o_c, d, d_com, tb.first, tb.second);
+}
+// d_com == null: open_fk_poly_batch (rows of d coefficients); else vec_commit_batch (rows of n evaluations). Everything on the device.
+keaki_status fkb_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_rows, size_t n, size_t m, size_t stride, const FkbConsts& k,
+                      void* d_com, void* d_proofs) {
+  const size_t d = (size_t)1 << log2d;
+  // the pass: as many rows as the cap allows; a refused reservation halves it, a refused single row sends the call through the single pipeline
+  size_t rows = 0;
+  if (log2d >= 1 && log2d <= FKB_LOG2D_MAX) {
+    rows = fkb_rows_per_pass(log2d, m);
+    for (;;) {
+      const keaki_status st = fkb_reserve(ctx, log2d, rows);
+      if (st == KEAKI_OK) break;
+      if (st != KEAKI_ERR_OOM) return st;
+      ctx->err.clear();
+      if (rows == 1) { rows = 0; break; }
+      rows = (rows + 1) / 2;
+    }
+  }
+  if (rows == 0) {
+    for (size_t j = 0; j < m; j++)
+      ST_TRY(fkb_row_single(ctx, srs, log2d, (const char*)d_rows + j * stride * 32, n, k, d_com ? (char*)d_com + j * G1_JAC_BYTES : nullptr,
+                            (char*)d_proofs + j * d * G1_AFF_BYTES));
+    return KEAKI_OK;
+  }
+  const void* tw = fkb_tables_run(ctx, log2d, rows, k.omega_2d, k.omega_2d_inv, d_com ? k.omega_d_inv : nullptr);
+  ST_TRY(fk_cache_ensure(ctx, srs, log2d, tw));
+  const auto tb = srs_tables(srs);
+  for (size_t r0 = 0; r0 < m; r0 += rows) {
+    const size_t cnt = std::min(rows, m - r0);
+    const void* coeffs = nullptr;
+    ST_TRY(fkb_pass_run(ctx, srs->fk.hat_s, log2d, rows, (const char*)d_rows + r0 * stride * 32, n, (uint32_t)cnt, stride, d_com ? k.inv_d : nullptr, k.inv_2d,
+                        (char*)d_proofs + r0 * d * G1_AFF_BYTES, &coeffs));
+    if (d_com) ST_TRY(msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, coeffs, d, cnt, d, (char*)d_com + r0 * G1_JAC_BYTES));
+  }
+  return KEAKI_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_open_fk_poly_batch_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_coeffs, size_t m, size_t stride,
+                                              const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d, void* d_proofs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.open_fk_batch");
+  std::unique_lock<std::recursive_mutex> hl;
+  bool empty;
+  ST_TRY(fkb_enter(ctx, srs, log2d, d_coeffs && omega_2d && omega_2d_inv && inv_2d && d_proofs_out_aff, "open_fk_poly_batch", (size_t)1 << std::min(log2d, 27u), m, stride, hl, &empty));
+  if (empty) return KEAKI_OK;
+  return fkb_core(ctx, srs, log2d, d_coeffs, (size_t)1 << log2d, m, stride, {nullptr, nullptr, omega_2d, omega_2d_inv, inv_2d}, nullptr, d_proofs_out_aff);
+}
+keaki_status keaki_hip_open_fk_poly_batch(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* coeffs, size_t m, size_t stride,
+                                          const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d, uint64_t* proofs_out_aff) {
+  CTX_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> hl;
+  bool empty;
+  ST_TRY(fkb_enter(ctx, srs, log2d, coeffs && omega_2d && omega_2d_inv && inv_2d && proofs_out_aff, "open_fk_poly_batch", (size_t)1 << std::min(log2d, 27u), m, stride, hl, &empty));
+  if (empty) return KEAKI_OK;
+  // one upload of the rows in front, the kernels, one download: the rows are short, there is nothing for a chunk pipeline to hide
+  const size_t d = (size_t)1 << log2d, out_bytes = m * d * G1_AFF_BYTES;
+  ST_TRY(reserve(ctx, ctx->io_b, out_bytes));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, coeffs, batch_span(d, m, stride)));
+  ST_TRY(keaki_hip_open_fk_poly_batch_dev(ctx, srs, log2d, ctx->io_a.p, m, stride, omega_2d, omega_2d_inv, inv_2d, ctx->io_b.p));
+  prefault_out(ctx, proofs_out_aff, out_bytes);
+  return download(feed, proofs_out_aff, ctx->io_b.p, out_bytes);
+}
+keaki_status keaki_hip_vec_commit_batch_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const void* d_evals, size_t n, size_t m, size_t stride, uint32_t log2d,
+                                            const uint64_t* omega_d_inv, const uint64_t* inv_d, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
+                                            const uint64_t* inv_2d, void* d_com_out_jac, void* d_proofs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.vec_commit_batch");
+  std::unique_lock<std::recursive_mutex> hl;
+  bool empty;
+  ST_TRY(fkb_enter(ctx, srs, log2d, (!n || d_evals) && omega_d_inv && inv_d && omega_2d && omega_2d_inv && inv_2d && d_com_out_jac && d_proofs_out_aff,
+                   "vec_commit_batch", n, m, stride, hl, &empty));
+  if (empty) return KEAKI_OK;
+  return fkb_core(ctx, srs, log2d, d_evals, n, m, stride, {omega_d_inv, inv_d, omega_2d, omega_2d_inv, inv_2d}, d_com_out_jac, d_proofs_out_aff);
+}
+keaki_status keaki_hip_vec_commit_batch(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const uint64_t* evals, size_t n, size_t m, size_t stride, uint32_t log2d,
+                                        const uint64_t* omega_d_inv, const uint64_t* inv_d, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
+                                        const uint64_t* inv_2d, uint64_t* com_out_jac, uint64_t* proofs_out_aff) {
+  CTX_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> hl;
+  bool empty;
+  ST_TRY(fkb_enter(ctx, srs, log2d, (!n || evals) && omega_d_inv && inv_d && omega_2d && omega_2d_inv && inv_2d && com_out_jac && proofs_out_aff,
+                   "vec_commit_batch", n, m, stride, hl, &empty));
+  if (empty) return KEAKI_OK;
+  const size_t d = (size_t)1 << log2d, out_bytes = m * d * G1_AFF_BYTES;
+  ST_TRY(reserve(ctx, ctx->io_b, out_bytes));
+  ST_TRY(reserve(ctx, ctx->io_c, m * G1_JAC_BYTES));
+  CopyFeed feed(ctx);
+  ST_TRY(upload(feed, ctx->io_a, evals, batch_span(n, m, stride)));
+  ST_TRY(keaki_hip_vec_commit_batch_dev(ctx, srs, ctx->io_a.p, n, m, stride, log2d, omega_d_inv, inv_d, omega_2d, omega_2d_inv, inv_2d, ctx->io_c.p, ctx->io_b.p));
+  prefault_out(ctx, proofs_out_aff, out_bytes);
+  HIP_TRY(ctx, hipMemcpyAsync(com_out_jac, ctx->io_c.p, m * G1_JAC_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  ST_TRY(download(feed, proofs_out_aff, ctx->io_b.p, out_bytes));
+  resolve_timing(ctx);
+  return KEAKI_OK;
 }
 
 // ---- KZG verify -----------------------------------------------------------------------------------------------------

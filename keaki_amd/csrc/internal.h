@@ -160,6 +160,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf pair_ws;                   // per-item slots of the final exponentiation (pairing.hip.h)
   keaki_internal::DevBuf fk_tab;                    // window tables of the per-lane-scalar ladders of FK23: 1 KB per lane of a launch (64 x 16 B), at most 2 GB (fft_g1.hip)
   keaki_internal::DevBuf mb_canon, mb_wsums, mb_q;  // batched MSM / open (msm_batch.hip): biased canonical scalars of a pass (32 B each) | window sums (128 B per row and window) | quotient rows of open_batch
+  keaki_internal::DevBuf fkb_pts, fkb_fr;           // batched FK23 (fk_batch.hip): the 2d x M Jacobian points of a pass, position-major | its scalar rows (96 B per coefficient) and the call's twiddle tables
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
   // instrumentation
   bool timing = false;
@@ -310,6 +311,17 @@ keaki_status msm_g1_batch_run(keaki_hip_ctx* ctx, const void* d_points, size_t s
 // row j < m: d_q[j * qstride + i - 1] = Q_i (1 <= i < n), d_values[j] = Q_0 (d_values may be null) for Q_i = c_i + z_j Q_(i+1) over row j of d_coeffs
 keaki_status fr_quotient_batch_run(keaki_hip_ctx* ctx, const void* d_coeffs, size_t n, size_t m, size_t stride, const void* d_points, void* d_q, size_t qstride,
                                    void* d_values);
+// batched FK23 (fk_batch.hip): domains of 2 .. 2^FKB_LOG2D_MAX run the batch kernels in passes of whole rows, fkb_rows_per_pass at a time (a
+// multiple of 64 unless m is smaller; FKB_ROW_BYTES << log2d bytes of workspace per row, at most FKB_PASS_BYTES a pass). The caller (api.hip)
+// reserves for `cap` rows, halving on KEAKI_ERR_OOM, runs fkb_tables_run once (-> omega_2d^k, the table fk_cache_ensure takes) and every pass
+// with the same cap; larger domains, d = 1 and refused workspaces run the single pipeline row by row. Asynchronous on ctx->stream.
+constexpr uint32_t FKB_LOG2D_MAX = 12;
+constexpr size_t FKB_PASS_BYTES = (size_t)1 << 28, FKB_ROW_BYTES = 288, FKB_ROWS_MAX = 16384;
+size_t fkb_rows_per_pass(uint32_t log2d, size_t m);
+keaki_status fkb_reserve(keaki_hip_ctx* ctx, uint32_t log2d, size_t rows);
+const void* fkb_tables_run(keaki_hip_ctx* ctx, uint32_t log2d, size_t rows, const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* omega_d_inv_or_null);
+keaki_status fkb_pass_run(keaki_hip_ctx* ctx, const void* d_hat_s, uint32_t log2d, size_t cap, const void* d_rows, size_t n, uint32_t rows, size_t stride,
+                          const uint64_t* inv_d_or_null, const uint64_t* inv_2d, void* d_proofs, const void** d_coeffs_out);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 

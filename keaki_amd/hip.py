@@ -20,6 +20,7 @@ EXPORTS = [
     "keaki_hip_srs_g2_upload", "keaki_hip_srs_g2_wrap_dev", "keaki_hip_srs_g2_precompute", "keaki_hip_srs_g2_free",
     "keaki_hip_msm_g1", "keaki_hip_msm_g1_dev", "keaki_hip_msm_g2", "keaki_hip_msm_g2_dev",
     "keaki_hip_msm_g1_batch", "keaki_hip_msm_g1_batch_dev", "keaki_hip_kzg_open_batch", "keaki_hip_kzg_open_batch_dev",
+    "keaki_hip_open_fk_poly_batch", "keaki_hip_open_fk_poly_batch_dev", "keaki_hip_vec_commit_batch", "keaki_hip_vec_commit_batch_dev",
     "keaki_hip_g1_sum_dev", "keaki_hip_g1_sum",
     "keaki_hip_g1_mul_batch", "keaki_hip_g2_mul_batch", "keaki_hip_g1_mul_batch_dev", "keaki_hip_g2_mul_batch_dev",
     "keaki_hip_pairing_batch", "keaki_hip_pairing_batch_dev",
@@ -161,6 +162,10 @@ def load_library():
         lib.keaki_hip_msm_g1_batch_dev.argtypes = [vp, vp, vp, sz, sz, sz, vp]
         lib.keaki_hip_kzg_open_batch.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
         lib.keaki_hip_kzg_open_batch_dev.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
+        lib.keaki_hip_open_fk_poly_batch.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, vp, vp, vp]
+        lib.keaki_hip_open_fk_poly_batch_dev.argtypes = [vp, vp, C.c_uint32, vp, sz, sz, vp, vp, vp, vp]
+        lib.keaki_hip_vec_commit_batch.argtypes = [vp, vp, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+        lib.keaki_hip_vec_commit_batch_dev.argtypes = [vp, vp, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         lib.keaki_hip_encap_prepare.argtypes = [vp, vp, sz]
         lib.keaki_hip_vec_commit.argtypes = [vp, vp, vp, sz, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         lib.keaki_hip_group_create.argtypes = [C.POINTER(i32), sz, C.POINTER(vp)]
@@ -409,6 +414,41 @@ class KeakiHip:
     def kzg_open_batch_dev(self, srs: SrsG1, d_rows: int, n: int, m: int, stride: int, d_points: int, d_proofs: int, d_values: int):
         self._ck(self.lib.keaki_hip_kzg_open_batch_dev(self.ctx, srs.handle, C.c_void_p(d_rows), n, m, stride, C.c_void_p(d_points), C.c_void_p(d_proofs),
                                                        C.c_void_p(d_values) if d_values else None))
+
+    def open_fk_poly_batch(self, srs: SrsG1, log2d: int, rows, omega_2d, omega_2d_inv, inv_2d) -> np.ndarray:
+        """all d = 2^log2d FK23 proofs of each of m polynomials in one call (keaki_hip_open_fk_poly_batch). rows: (m, stride, 4) Montgomery Fr,
+        the first d coefficients of every row count, the rest of a row is never read -> (m, d, 8) affine proofs in natural order"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r = r if r.ndim == 3 else r.reshape(r.shape[0], -1, 4)
+        m, stride, d = r.shape[0], r.shape[1], 1 << log2d
+        out = np.zeros((m, d, 8), np.uint64)
+        self._ck(self.lib.keaki_hip_open_fk_poly_batch(self.ctx, srs.handle, log2d, _ptr(r) if r.size else None, m, stride, _ptr(_np(omega_2d)),
+                                                       _ptr(_np(omega_2d_inv)), _ptr(_np(inv_2d)), _ptr(out) if m else None))
+        return out
+
+    def open_fk_poly_batch_dev(self, srs: SrsG1, log2d: int, d_rows: int, m: int, stride: int, omega_2d, omega_2d_inv, inv_2d, d_proofs: int):
+        self._ck(self.lib.keaki_hip_open_fk_poly_batch_dev(self.ctx, srs.handle, log2d, C.c_void_p(d_rows), m, stride, _ptr(_np(omega_2d)),
+                                                           _ptr(_np(omega_2d_inv)), _ptr(_np(inv_2d)), C.c_void_p(d_proofs)))
+
+    def vec_commit_batch(self, srs: SrsG1, rows, log2d: int, omega_d_inv, inv_d, omega_2d, omega_2d_inv, inv_2d, n: int = None):
+        """the body of vec::vec_commit for m vectors over one domain (keaki_hip_vec_commit_batch). rows: (m, stride, 4) Montgomery Fr; the first n
+        (default: stride) evaluations of every row count -- the vector, its padding scalar, zeros -- -> (commitments (m, 12) normalised Jacobian,
+        proofs (m, d, 8) affine)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r = r if r.ndim == 3 else r.reshape(r.shape[0], -1, 4)
+        m, stride, d = r.shape[0], r.shape[1], 1 << log2d
+        n = stride if n is None else int(n)
+        com = np.zeros((m, 12), np.uint64); proofs = np.zeros((m, d, 8), np.uint64)
+        self._ck(self.lib.keaki_hip_vec_commit_batch(self.ctx, srs.handle, _ptr(r) if r.size and n else None, n, m, stride, log2d, _ptr(_np(omega_d_inv)),
+                                                     _ptr(_np(inv_d)), _ptr(_np(omega_2d)), _ptr(_np(omega_2d_inv)), _ptr(_np(inv_2d)),
+                                                     _ptr(com) if m else None, _ptr(proofs) if m else None))
+        return com, proofs
+
+    def vec_commit_batch_dev(self, srs: SrsG1, d_rows: int, n: int, m: int, stride: int, log2d: int, omega_d_inv, inv_d, omega_2d, omega_2d_inv, inv_2d,
+                             d_com: int, d_proofs: int):
+        self._ck(self.lib.keaki_hip_vec_commit_batch_dev(self.ctx, srs.handle, C.c_void_p(d_rows) if d_rows else None, n, m, stride, log2d,
+                                                         _ptr(_np(omega_d_inv)), _ptr(_np(inv_d)), _ptr(_np(omega_2d)), _ptr(_np(omega_2d_inv)),
+                                                         _ptr(_np(inv_2d)), C.c_void_p(d_com), C.c_void_p(d_proofs)))
 
     def msm_g2(self, srs: SrsG2, scalars) -> np.ndarray:
         sc = _np(scalars, 4); out = np.zeros(24, np.uint64)

@@ -638,6 +638,32 @@ std::pair<G1, std::vector<G1>> vec_commit(Rng& rng, const kzg::KZGSetup& setup, 
   return {com, std::move(proofs)};
 }
 
+std::vector<std::pair<G1, std::vector<G1>>> vec_commit_batch(Rng& rng, const kzg::KZGSetup& setup, const std::vector<std::vector<Fr>>& vecs) {
+  const Device& dev = *setup.device();
+  if (dev.group()) throw std::invalid_argument("vec_commit_batch: a group device commits vector by vector (vec_commit)");
+  size_t longest = 0;
+  for (const auto& v : vecs) longest = std::max(longest, v.size());
+  const size_t n = longest + PADDING_LEN, m = vecs.size();
+  const Radix2Domain domain = Radix2Domain::create(n), d2 = Radix2Domain::create(2 * domain.size);
+  unsigned log_size = 0;
+  while ((size_t(1) << log_size) < domain.size) log_size++;
+  // row j = vecs[j] | its padding scalar (src/vec.rs:31-33, drawn in index order) | zeros: the evaluations ark-poly's ifft would pad with
+  std::vector<Fr> rows(m * n);
+  for (size_t j = 0; j < m; j++) {
+    std::copy(vecs[j].begin(), vecs[j].end(), rows.begin() + j * n);
+    rows[j * n + vecs[j].size()] = fr_rand(rng);
+  }
+  std::vector<uint64_t> jac(12 * m);
+  std::vector<std::pair<G1, std::vector<G1>>> out(m);
+  std::vector<G1> proofs(m * domain.size);
+  if (m)
+    dev.check(keaki_hip_vec_commit_batch(dev.ctx(), setup.srs(), rows[0].l, n, m, n, log_size, domain.group_gen_inv.l, domain.size_inv.l, d2.group_gen.l,
+                                         d2.group_gen_inv.l, d2.size_inv.l, jac.data(), proofs[0].w.data()));
+  for (size_t j = 0; j < m; j++)
+    out[j] = {jac_to_g1(&jac[12 * j]), std::vector<G1>(proofs.begin() + j * domain.size, proofs.begin() + (j + 1) * domain.size)};
+  return out;
+}
+
 bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs) {
   const Radix2Domain domain = Radix2Domain::create(n + PADDING_LEN);      // the domain vec_commit interpolated over (src/vec.rs:36)
   return kzg::verify_batch_flat(rng, setup, com.w.data(), 1, &domain.group_gen, true, v, proofs, n);

@@ -236,6 +236,10 @@ std::pair<G1, std::vector<G1>> vec_commit(Rng& rng, const kzg::KZGSetup& setup, 
 // device everything behind the padding draw is ONE device call (keaki_hip_vec_commit: iFFT, FK23 openings, commit; the coefficients never
 // return to the host); smaller domains and group devices take the steps one by one. Same values either way.
 G1 vec_commit_flat(Rng& rng, const kzg::KZGSetup& setup, const Fr* v, size_t n, uint64_t* proofs_out);
+// m vectors over ONE domain -- Radix2Domain::create(longest + PADDING_LEN), which is every vector's own domain when their lengths round to the
+// same power of two -- in one device call (keaki_hip_vec_commit_batch; domains up to 2^12 run its batch kernels). One padding scalar per vector,
+// drawn in index order, the rule vec_commit follows; (commitment, proofs) per vector as vec_commit returns them over that domain. Single device only.
+std::vector<std::pair<G1, std::vector<G1>>> vec_commit_batch(Rng& rng, const kzg::KZGSetup& setup, const std::vector<std::vector<Fr>>& vecs);
 // lines :27-37 of it (padding draw, iFFT): the coefficient vector over the whole domain, not trimmed
 std::vector<Fr> vec_commit_coeffs(Rng& rng, const kzg::KZGSetup& setup, const std::vector<Fr>& v);
 // lines :27-44 of it (padding draw, iFFT, open_fk): the dense coefficient vector and the proofs, without the final commit

@@ -340,6 +340,21 @@ int keaki_host_vec_commit(void* rng, void* s, const uint64_t* v, size_t n, uint6
     return 0;
   });
 }
+// vec_commit_batch: m vectors of `lens[j]` scalars, concatenated in v; com_out: m x 8 words, proofs_out: m x keaki_host_domain(longest + 1) x 8 words
+int keaki_host_vec_commit_batch(void* rng, void* s, const uint64_t* v, const size_t* lens, size_t m, uint64_t* com_out, uint64_t* proofs_out) {
+  return guard([&] {
+    std::vector<std::vector<Fr>> vecs(m);
+    size_t at = 0;
+    for (size_t j = 0; j < m; at += lens[j], j++) vecs[j] = frs_of(v + 4 * at, lens[j]);
+    auto r = vec::vec_commit_batch(*(Rng*)rng, ((Setup*)s)->s, vecs);
+    for (size_t j = 0; j < m; j++) {
+      memcpy(com_out + 8 * j, r[j].first.w.data(), 64);
+      const size_t d = r[j].second.size();
+      if (d) memcpy(proofs_out + 8 * d * j, r[j].second[0].w.data(), 64 * d);
+    }
+    return 0;
+  });
+}
 // vec_encrypt with equal-length messages (msg_len each, concatenated)
 int keaki_host_vec_encrypt(void* rng, void* s, const uint64_t* com, const uint64_t* points, const uint64_t* values, const uint8_t* msgs,
                            size_t n, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {

@@ -489,6 +489,19 @@ def vec_commit(rng: Rng, setup: KZGSetup, v):
     return com, proofs
 
 
+def vec_commit_batch(rng: Rng, setup: KZGSetup, vecs):
+    """m vectors over one domain (that of the longest + PADDING_LEN) in one device call -> (commitments (m, 8), proofs (m, size, 8)); one
+    padding scalar per vector, drawn in index order; see keaki::vec::vec_commit_batch"""
+    vecs = [_u64(v, 4) for v in vecs]
+    m = len(vecs)
+    lens = (C.c_size_t * max(m, 1))(*[v.shape[0] for v in vecs])
+    size = _lib().keaki_host_domain(max([v.shape[0] for v in vecs], default=0) + PADDING_LEN, None)
+    flat = np.ascontiguousarray(np.concatenate(vecs) if m and sum(v.shape[0] for v in vecs) else np.zeros((1, 4), np.uint64))
+    com = np.zeros((m, 8), np.uint64); proofs = np.zeros((m, size, 8), np.uint64)
+    _ck(_lib().keaki_host_vec_commit_batch(rng.h, setup.h, _p(flat), lens, C.c_size_t(m), _p(com), _p(proofs)))
+    return com, proofs
+
+
 def vec_encrypt(rng: Rng, setup: KZGSetup, com, points, values, messages):
     n = len(messages); ml = len(messages[0]) if n else 0
     assert all(len(m) == ml for m in messages)

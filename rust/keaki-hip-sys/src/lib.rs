@@ -124,6 +124,17 @@ extern "C" {
                                     points: *const u64, proofs_out_jac: *mut u64, values_out: *mut u64) -> keaki_status;
     pub fn keaki_hip_kzg_open_batch_dev(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, d_coeffs: *const c_void, n: usize, m: usize, stride: usize,
                                         d_points: *const c_void, d_proofs_out_jac: *mut c_void, d_values_out: *mut c_void) -> keaki_status;
+    // m rows over one domain in one call: all FK23 proofs of m polynomials (src/kzg.rs:157-203, m times) | the body of vec_commit for m vectors
+    pub fn keaki_hip_open_fk_poly_batch(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, coeffs: *const u64, m: usize, stride: usize,
+                                        omega_2d: *const u64, omega_2d_inv: *const u64, inv_2d: *const u64, proofs_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_open_fk_poly_batch_dev(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, d_coeffs: *const c_void, m: usize, stride: usize,
+                                            omega_2d: *const u64, omega_2d_inv: *const u64, inv_2d: *const u64, d_proofs_out_aff: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_vec_commit_batch(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, evals: *const u64, n: usize, m: usize, stride: usize, log2d: u32,
+                                      omega_d_inv: *const u64, inv_d: *const u64, omega_2d: *const u64, omega_2d_inv: *const u64, inv_2d: *const u64,
+                                      com_out_jac: *mut u64, proofs_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_vec_commit_batch_dev(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, d_evals: *const c_void, n: usize, m: usize, stride: usize,
+                                          log2d: u32, omega_d_inv: *const u64, inv_d: *const u64, omega_2d: *const u64, omega_2d_inv: *const u64,
+                                          inv_2d: *const u64, d_com_out_jac: *mut c_void, d_proofs_out_aff: *mut c_void) -> keaki_status;
     pub fn keaki_hip_kzg_verify(ctx: *mut keaki_hip_ctx, com_aff: *const u64, tau_g2_aff: *const u64, point: *const u64, value: *const u64,
                                 proof_aff: *const u64, ok_out: *mut i32) -> keaki_status;
     // n openings in one call (generalises src/kzg.rs:127-148): e(L, g2) == e(R, [tau]_2) for the caller's gammas; sums_out_aff: u64[16] = L, R or null

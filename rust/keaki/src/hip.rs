@@ -567,6 +567,39 @@ pub fn vec_commit(srs: &HipSrs, padded: &[Fr], size: usize) -> (G1Projective, Ve
     (g1_from_jac(&com), out.chunks_exact(8).map(|w| g1_from_words(w).into()).collect())
 }
 
+/// The body of `vec_commit` for m vectors over ONE domain in one device call (`keaki_hip_vec_commit_batch`): `padded[j]` = vector j and its
+/// padding scalar (the caller draws them in index order, as `vec_commit` does), every one at most `size` long. Returns (commitment, `size`
+/// proofs) per vector, each what `vec_commit(srs, &padded[j], size)` returns. Domains up to 2^12 run the batch kernels.
+pub fn vec_commit_batch(srs: &HipSrs, padded: &[Vec<Fr>], size: usize) -> Vec<(G1Projective, Vec<G1Projective>)> {
+    use ark_poly::{EvaluationDomain, Radix2EvaluationDomain};
+    let dev = Device::global();
+    let n = padded.iter().map(|v| v.len()).max().unwrap_or(0);
+    assert!(size.is_power_of_two() && n <= size && size <= srs.len());
+    let m = padded.len();
+    let dom = Radix2EvaluationDomain::<Fr>::new(size).unwrap();
+    let dom2 = Radix2EvaluationDomain::<Fr>::new(2 * size).unwrap();
+    let one = |x: &Fr| fr_ptr(core::slice::from_ref(x));
+    // row j = padded[j] followed by zeros up to the longest row: the evaluations ark-poly's ifft would pad with
+    let mut rows = vec![Fr::from(0u64); m * n];
+    for (j, v) in padded.iter().enumerate() {
+        rows[j * n..j * n + v.len()].copy_from_slice(v);
+    }
+    let mut com = vec![0u64; 12 * m];
+    let mut out = vec![0u64; 8 * size * m];
+    dev.check(
+        unsafe {
+            sys::keaki_hip_vec_commit_batch(
+                dev.ctx, srs.srs(), fr_ptr(&rows), n, m, n, size.trailing_zeros(), one(&dom.group_gen_inv), one(&dom.size_inv), one(&dom2.group_gen),
+                one(&dom2.group_gen_inv), one(&dom2.size_inv), com.as_mut_ptr(), out.as_mut_ptr(),
+            )
+        },
+        "vec_commit_batch",
+    );
+    (0..m)
+        .map(|j| (g1_from_jac(com[12 * j..12 * j + 12].try_into().unwrap()),out[8 * size * j..8 * size * (j + 1)].chunks_exact(8).map(|w| g1_from_words(w).into()).collect()))
+        .collect()
+}
+
 /// The collectives a sharded `open_fk` owes between its steps: implemented by the application over its communication library (RCCL:
 /// `ncclAllToAll`-style exchange with equal splits, `ncclAllGather`) on DEVICE buffers; both must have completed when they return.
 pub trait FkExchange {
