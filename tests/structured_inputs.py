@@ -1,5 +1,6 @@
 """Bases with known discrete logs, their references, and models of where the group kernels meet exceptional additions -- TEST
-INFRASTRUCTURE (a plain module, imported by tests/test_structured_inputs_model.py and tests/test_gpu_structured_srs.py).
+INFRASTRUCTURE (a plain module, imported by tests/test_structured_inputs_model.py, tests/test_gpu_structured_srs.py and
+tests/test_gpu_fb_digit_edges.py).
 
 Every base is k * G with k known, so an expected result is scalar arithmetic mod r and only its last step needs a point. The models follow
 the kernels' documented order of operations on those scalars and count the additions that take an exceptional branch: equal or opposite
@@ -343,11 +344,17 @@ def encap_ct_events(tau, r, z, wb, wide):
     entries window by window, table A first (k_encap_fixed); the wide kernel gives window w of the concatenated list to lane w & 15,
     then adds the sixteen partial sums in a tree (lane l meets lane l ^ step). -> (ct dlog, {'equal', 'opposite'}) over the additions
     whose result reaches the output."""
+    return fb_sum_events(tau, r % R, wb, 1, -(r * z) % R, wb, wide)
+
+
+def fb_sum_events(base_a, ka, wb_a, base_b, kb, wb_b, wide):
+    """encap_ct_events for any two tables: the sum ka (base_a G) + kb (base_b G) over a wb_a-bit table of base_a G and a wb_b-bit
+    table of base_b G (also the G1 sum r C + (-(r v)) g1 of k_encap_fixed<Fq,1>: wide = False, 13 and 16 bits)"""
     ents = []
-    for j, dg in enumerate(fb_digits(r % R, wb)):
-        ents.append(dg * (tau << (wb * j)) % R)
-    for j, dg in enumerate(fb_digits(-(r * z) % R, wb)):
-        ents.append(dg * (1 << (wb * j)) % R)
+    for j, dg in enumerate(fb_digits(ka, wb_a)):
+        ents.append(dg * (base_a << (wb_a * j)) % R)
+    for j, dg in enumerate(fb_digits(kb, wb_b)):
+        ents.append(dg * (base_b << (wb_b * j)) % R)
     ev = {"equal": 0, "opposite": 0}
     if not wide:
         acc = 0
@@ -366,3 +373,124 @@ def encap_ct_events(tau, r, z, wb, wide):
         lanes = [(lanes[l] + lanes[l ^ step]) % R for l in range(16)]
         step <<= 1
     return lanes[0], ev
+
+
+# ---- digit-edge scalars of the fixed-base walks (fb_accumulate, fb_accumulate_g2_u29, fb_pick_digits, gt_table_exp, w_gt_table_exp) ----
+# Every walk forms coef = (the window's bits) + (carry in) and branches on it: coef <= half adds slot coef; coef > half adds the negated
+# slot 2^wb - coef and carries; coef == 2^wb adds nothing and carries; coef == 0 adds nothing. The classes name coef values whose branch or
+# table slot is special: slot `half` (the scatter of powers in the GT table, the doublings-only ladder in the EC table), slot half - 1 (the
+# last entry of the top fill level wb - 2, reached with either sign), slots 2^L and 2^L + 1 (a level boundary of the fill), +-1, the two
+# zeros. The order is the one a scalar walks through, window by window: each class leaves the carry its successor is meant to receive
+# (`full` needs one; `zero` must not get one and sits between two non-zero digits; `pow+1` and `one` are formed by a carry).
+FB_EDGE_CLASSES = ("one", "zero", "half", "half-1", "pow", "neg_first", "full", "pow+1", "minus_one")
+
+
+def fb_edge_level(wb):
+    """the interior fill level L whose boundary slots 2^L and 2^L + 1 the classes `pow` and `pow+1` read"""
+    return wb // 2
+
+
+def _fb_edge_coef(name, wb):
+    full, half, p = 1 << wb, 1 << (wb - 1), 1 << fb_edge_level(wb)
+    return {"one": 1, "zero": 0, "half": half, "half-1": half - 1, "pow": p, "pow+1": p + 1, "neg_first": half + 1, "full": full,
+            "minus_one": full - 1}[name]
+
+
+def fb_digit_classes(k, wb):
+    """{(window, class)} of the walk over canonical k, the top window included. `zero` is a zero window without a carry in whose
+    neighbours (the left one where there is one) have non-zero digits; any other zero window is `zero_run`, any other coef `other`."""
+    W, full, half = fb_windows(wb), 1 << wb, 1 << (wb - 1)
+    digs = fb_digits(k, wb)
+    names = {_fb_edge_coef(c, wb): c for c in FB_EDGE_CLASSES}
+    out, carry = set(), 0
+    for j in range(W):
+        coef = ((k >> (wb * j)) & (full - 1)) + carry
+        carry = 1 if coef > half else 0
+        name = names.get(coef, "other")
+        if coef == 0 and not ((j == 0 or digs[j - 1]) and j + 1 < W and digs[j + 1]):
+            name = "zero_run"
+        out.add((j, name))
+    return out
+
+
+def fb_edge_required(wb):
+    """the (window, class) pairs a set of edge scalars must reach: every class in every non-top window. No carry enters window 0, so
+    coef = 2^wb cannot occur there: (0, 'full') is the one pair that does not exist."""
+    return {(j, c) for j in range(fb_windows(wb) - 1) for c in FB_EDGE_CLASSES} - {(0, "full")}
+
+
+def fb_edge_covered(scalars, wb):
+    """the pairs of fb_edge_required(wb) that the scalars reach"""
+    seen = set()
+    for k in scalars:
+        seen |= fb_digit_classes(k, wb)
+    return seen & fb_edge_required(wb)
+
+
+def fb_edge_scalars(wb):
+    """Canonical scalars < r, all non-zero, that put every non-top window of the wb-bit walk through every class of FB_EDGE_CLASSES
+    (fb_edge_required). Scalar s drives window j to class (j + s) mod 9; the bits are coef minus the carry that actually arrives. The
+    top window follows the same schedule as far as a scalar below r allows, else it is lowered to the largest value that fits. Then
+    r - 1, r - 2 and 1; the largest top-window digit that still takes a carry in; and a carry chain through every non-top window
+    (half + 1 in window 0, all ones above it)."""
+    W, full, half = fb_windows(wb), 1 << wb, 1 << (wb - 1)
+    top_off = wb * (W - 1)
+    nc = len(FB_EDGE_CLASSES)
+    out = []
+    for s in range(nc):
+        low, carry = 0, 0
+        for j in range(W - 1):
+            raw = min(max(_fb_edge_coef(FB_EDGE_CLASSES[(j + s) % nc], wb) - carry, 0), full - 1)
+            low |= raw << (wb * j)
+            carry = 1 if raw + carry > half else 0
+        fits = (R - 1 - low) >> top_off
+        top = min(max(_fb_edge_coef(FB_EDGE_CLASSES[(W - 1 + s) % nc], wb) - carry, 0), fits)
+        out.append(low + (top << top_off))
+    out += [R - 1, R - 2, 1]
+    # the top window of r - 1 is T; a carry enters it from window W - 2 when that one holds more than half. Where r - 1 itself has at
+    # least half + 1 there, T + 1 is reached; else T - 1 under an all-ones window gives T
+    T, off2 = (R - 1) >> top_off, wb * (W - 2)
+    if ((R - 1) >> off2) & (full - 1) >= half + 1:
+        out.append((T << top_off) | ((half + 1) << off2))
+    else:
+        out.append(((T - 1) << top_off) | ((full - 1) << off2))
+    chain = (half + 1) + sum((full - 1) << (wb * j) for j in range(1, W - 1))
+    out.append(chain + (((R - 1 - chain) >> top_off) << top_off))
+    seen = set()
+    return [k for k in out if not (k in seen or seen.add(k))]
+
+
+def fb_edge_report(wb):
+    """what fb_edge_scalars(wb) reaches: the number of (non-top window, class) pairs, the classes of the top window (which holds only
+    what a scalar below r allows) and its largest digit"""
+    sc = fb_edge_scalars(wb)
+    W = fb_windows(wb)
+    top = set()
+    for k in sc:
+        top |= {c for j, c in fb_digit_classes(k, wb) if j == W - 1}
+    return {"scalars": len(sc), "pairs": len(fb_edge_covered(sc, wb)), "required": len(fb_edge_required(wb)),
+            "top_classes": sorted(top), "top_max_digit": max(fb_digits(k, wb)[-1] for k in sc), "top_limit": (R - 1) >> (wb * (W - 1))}
+
+
+def fb_edge_union(widths):
+    seen = set()
+    return [k for wb in widths for k in fb_edge_scalars(wb) if not (k in seen or seen.add(k))]
+
+
+def fb_edge_batch(r_widths, b2_widths, b1_widths):
+    """Encapsulation items (r, point, value) that carry three edge scalars each: r itself walks the tables of [tau]_2 and of the
+    commitment (or A = e(C, g2)); the device's -(r point) and -(r value) are the chosen scalars for the tables of g2 and of g1 (or
+    B = e(g1, g2)). Each side is the union of fb_edge_scalars over its widths; the three lists are crossed cyclically (one step apart,
+    so that an item never carries the same scalar twice in a row of equal lists) until the longest is used up."""
+    ta, tb2, tb1 = fb_edge_union(r_widths), fb_edge_union(b2_widths), fb_edge_union(b1_widths)
+    items = []
+    for i in range(max(len(ta), len(tb2), len(tb1))):
+        r = ta[i % len(ta)]
+        inv = pow(r, -1, R)
+        items.append((r, -tb2[(i + 1) % len(tb2)] * inv % R, -tb1[(i + 2) % len(tb1)] * inv % R))
+    return items
+
+
+def fb_edge_sides(items):
+    """the three scalars the device walks for each item: (r, -(r point), -(r value))"""
+    return [it[0] % R for it in items], [-(it[0] * it[1]) % R for it in items], [-(it[0] * it[2]) % R for it in items]

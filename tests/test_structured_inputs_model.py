@@ -1,6 +1,7 @@
 """CPU half of the structured-input tests (tests/structured_inputs.py): (a) the models of the kernels' order of operations reach the
 exceptional additions the GPU tests of tests/test_gpu_structured_srs.py are meant to exercise -- and the random control reaches none;
-(b) the discrete-log references and the oracle agree with the pure-Python group arithmetic on small structured instances."""
+(b) the discrete-log references and the oracle agree with the pure-Python group arithmetic on small structured instances; (c) the
+digit-edge scalars of tests/test_gpu_fb_digit_edges.py rebuild under the recoding model and reach every class in every non-top window."""
 import random
 
 import numpy as np
@@ -162,6 +163,107 @@ def test_encap_model_random_control():
             tau, r, z = rnd.randrange(R), rnd.randrange(R), rnd.randrange(R)
             ct, ev = S.encap_ct_events(tau, r, z, wb, wide)
             assert ct == r * (tau - z) % R and ev == {"equal": 0, "opposite": 0}
+
+
+# ---- the digit-edge scalars of the fixed-base walks ----------------------------------------------------------------------------------
+FB_WIDTHS = list(range(8, 23))
+
+
+def test_fb_windows_is_the_window_count_of_both_table_shapes():
+    """fb_shape (ec_batch.hip.h) and gt_shape (pairing.hip.h) count windows as fb_windows does, and hold 2^(wb-1) + 1 slots each"""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "keaki_amd", "csrc")
+    for fname, shape in (("ec_batch.hip.h", "FbShape fb_shape"), ("pairing.hip.h", "GtShape gt_shape")):
+        with open(os.path.join(csrc, fname)) as f:
+            m = re.search(r"inline %s\(u32 wb\) \{ return \{wb, ([^,]+), ([^,]+)\}; \}" % shape, f.read())
+        assert m, fname
+        c_int = lambda e, wb: eval(re.sub(r"(\d+)u", r"\1", e).replace("/", "//").replace("?", "and").replace(":", "or"), {"wb": wb})
+        assert m.group(1) == "(254u + wb - 1u) / wb + ((254u % wb) == 0u ? 1u : 0u)", (fname, m.group(1))
+        for wb in list(range(2, 32)) + [127, 254]:
+            assert c_int(m.group(1), wb) == S.fb_windows(wb), (fname, wb)
+            assert wb > 30 or c_int(m.group(2), wb) == (1 << (wb - 1)) + 1, (fname, wb)
+
+
+@pytest.mark.parametrize("wb", FB_WIDTHS)
+def test_fb_digits_rebuild_the_scalar(wb):
+    """sum d_j 2^(wb j) == k with every digit in (-half, half] and no carry out of the last window"""
+    rnd = random.Random(100 + wb)
+    half = 1 << (wb - 1)
+    for k in S.fb_edge_scalars(wb) + [rnd.randrange(R) for _ in range(200)] + [0]:
+        digs = S.fb_digits(k, wb)
+        assert len(digs) == S.fb_windows(wb)
+        assert all(-half < d <= half for d in digs), (wb, k)
+        assert sum(d << (wb * j) for j, d in enumerate(digs)) == k, (wb, k)       # a carry out of the top window would leave k - 2^(wb W)
+        assert 0 <= digs[-1] <= half, (wb, k)
+
+
+@pytest.mark.parametrize("wb", FB_WIDTHS)
+def test_fb_edge_scalars_reach_every_class_in_every_window(wb):
+    sc = S.fb_edge_scalars(wb)
+    assert all(0 < k < R for k in sc) and len(set(sc)) == len(sc) <= 16, wb
+    W = S.fb_windows(wb)
+    need = S.fb_edge_required(wb)
+    assert need == {(j, c) for j in range(W - 1) for c in S.FB_EDGE_CLASSES if (j, c) != (0, "full")}
+    got = S.fb_edge_covered(sc, wb)
+    assert got == need, (wb, sorted(need - got))
+    # the classes are what they say, on the digits: window j of some scalar has each of these digits, with the stated carry out
+    full, half, p = 1 << wb, 1 << (wb - 1), 1 << S.fb_edge_level(wb)
+    assert 1 <= S.fb_edge_level(wb) <= wb - 2 and len({1, half, half - 1, p, p + 1}) == 5
+    # class -> (bits + carry in, digit)
+    want = {"one": (1, 1), "zero": (0, 0), "half": (half, half), "half-1": (half - 1, half - 1), "pow": (p, p), "neg_first": (half + 1, -(half - 1)),
+            "full": (full, 0), "pow+1": (p + 1, p + 1), "minus_one": (full - 1, -1)}
+    carried_tops = []
+    for k in sc:
+        digs = S.fb_digits(k, wb)
+        # a carry enters window j iff the digits below it sum to (k mod 2^(wb j)) - 2^(wb j), i.e. to something negative
+        cin = [1 if sum(d << (wb * i) for i, d in enumerate(digs[:j])) < 0 else 0 for j in range(W)]
+        if cin[W - 1]:
+            carried_tops.append(digs[-1])
+        for j, c in S.fb_digit_classes(k, wb):
+            if c in want:
+                assert (((k >> (wb * j)) & (full - 1)) + cin[j], digs[j]) == want[c], (wb, k, j, c)
+                if c == "zero":
+                    assert (j == 0 or digs[j - 1]) and digs[j + 1]
+                if j < W - 1:
+                    assert cin[j + 1] == (1 if c in ("neg_first", "full", "minus_one") else 0)
+    # the specials: r - 1, r - 2, 1; a carry chain through every non-top window; the largest top digit that takes a carry in
+    assert {R - 1, R - 2, 1} <= set(sc)
+    chain = (half + 1) + sum((full - 1) << (wb * j) for j in range(1, W - 1))
+    assert any(k % (1 << (wb * (W - 1))) == chain and {(j, "full") for j in range(1, W - 1)} <= S.fb_digit_classes(k, wb) for k in sc), wb
+    rep = S.fb_edge_report(wb)
+    assert rep["pairs"] == rep["required"] == len(need)
+    T = (R - 1) >> (wb * (W - 1))
+    assert rep["top_limit"] == T and T <= rep["top_max_digit"] <= T + 1
+    # no scalar below r has a larger top digit behind a carry: the top bits T need window W - 2 <= that of r - 1
+    best = T + 1 if ((R - 1) >> (wb * (W - 2))) & (full - 1) > half else T
+    assert max(carried_tops) == best, (wb, max(carried_tops), best)
+
+
+def test_fb_edge_top_window_limits():
+    """what a scalar below r leaves to the top window"""
+    assert {wb: S.fb_edge_report(wb)["top_limit"] for wb in (8, 11, 13, 16, 20)} == {8: 48, 11: 1, 13: 96, 16: 12388, 20: 12388}
+    assert all(254 % wb for wb in FB_WIDTHS)                 # no width of the range has an extra, empty top window
+
+
+def test_fb_edge_batch_items_carry_their_scalars_on_every_side():
+    """-(r point) and -(r value) are the chosen scalars, and each side's scalars cover every width it is built for"""
+    items = S.fb_edge_batch((8, 13, 16), (8, 16), (16, 20))
+    assert len(set(items)) == len(items) < 128
+    rs, b2, b1 = S.fb_edge_sides(items)
+    assert set(rs) == set(S.fb_edge_union((8, 13, 16))) and set(b2) == set(S.fb_edge_union((8, 16))) and set(b1) == set(S.fb_edge_union((16, 20)))
+    for side, widths in ((rs, (8, 13, 16)), (b2, (8, 16)), (b1, (16, 20))):
+        for wb in widths:
+            assert S.fb_edge_covered(side, wb) == S.fb_edge_required(wb), wb
+    # a random tau meets nothing: every sum of the GPU cases, in the lane and in the sixteen-lane order
+    rnd = random.Random(77)
+    tau, c = rnd.randrange(R), rnd.randrange(R)
+    for r, z, v in items:
+        for wb, wide in ((8, True), (16, True), (16, False)):
+            ct, ev = S.encap_ct_events(tau, r, z, wb, wide)
+            assert ct == r * (tau - z) % R and ev == {"equal": 0, "opposite": 0}
+        k, ev = S.fb_sum_events(c, r, 13, 1, -(r * v) % R, 16, False)
+        assert k == r * (c - v) % R and ev == {"equal": 0, "opposite": 0}
 
 
 # ---- (b) the references against the pure-Python group arithmetic -------------------------------------------------------------------

@@ -42,6 +42,20 @@ def launchable():
         out.add("k_g1_fft_stage4<%s,%s>" % (dit, a))
     for occ in re.findall(r"k_encap_fixed<Fq2, (\d)>", _src("ec_batch_g2.hip")):
         out.add("k_encap_fixed<Fq2,%s>" % occ)
+    for occ in re.findall(r"k_encap_fixed<Fq, (\d)>", _src("ec_batch_g1.hip")):
+        out.add("k_encap_fixed<Fq,%s>" % occ)
+    out.add("k_encap_fixed_g2_wide" if "hipLaunchKernelGGL(k_encap_fixed_g2_wide," in _src("ec_batch_g2.hip") else "?")
+    # the GT exponentiation: the kernels gt_encap_exp_run launches, and the forms its callers ask for (both tables; B alone into an
+    # accumulator; A alone from it)
+    run = re.search(r"keaki_status gt_encap_exp_run\(.*?\n}\n", _src("pairing.hip"), re.S).group(0)
+    out |= set(re.findall(r"hipLaunchKernelGGL\(((?:pw::)?k_gt_encap_exp\w*),", run))
+    for args in re.findall(r"gt_encap_exp_run\(ctx, ([^;]*)\)\);", _src("api.hip")):
+        a = [x.strip() for x in args.split(",")]
+        assert len(a) in (8, 10), args                   # tab_a, wb_a, tab_b, wb_b, betas, rs, n, gt [, acc_in, acc_out]
+        acc_in, acc_out = (a + ["nullptr", "nullptr"])[8:10]
+        assert (a[0] == "nullptr") == (acc_out != "nullptr") and (a[2] == "nullptr") == (acc_in != "nullptr"), args
+        if acc_in != "nullptr" or acc_out != "nullptr":
+            out.add("k_gt_encap_exp[%s]" % ("acc_in" if acc_in != "nullptr" else "acc_out"))
     return out
 
 
@@ -53,7 +67,10 @@ def test_the_launch_sites_parse_into_the_expected_families():
     assert len(fam("k_msm_accumulate_g1_u29<")) == 7
     assert len(fam("k_g1_fft_stage_map<")) == 12
     assert len(fam("k_g1_fft_stage4<")) == 4
-    assert fam("k_encap_fixed<") == {"k_encap_fixed<Fq2,1>", "k_encap_fixed<Fq2,2>"}
+    assert fam("k_encap_fixed<") == {"k_encap_fixed<Fq2,1>", "k_encap_fixed<Fq2,2>", "k_encap_fixed<Fq,1>"}
+    assert fam("k_encap_fixed_g2") == {"k_encap_fixed_g2_wide"}
+    assert fam("k_gt_encap_exp") | fam("pw::k_gt_encap_exp") == {"k_gt_encap_exp", "pw::k_gt_encap_exp_wide", "k_gt_encap_exp[acc_in]",
+                                                                 "k_gt_encap_exp[acc_out]"}
 
 
 def test_the_case_table_reaches_every_launchable_instantiation():
@@ -171,6 +188,43 @@ def test_every_automatic_shape_is_reached_by_a_test():
     assert auto <= reached, sorted(auto - reached)
     # geometries 0, 1, 2 are automatic only at 2^19 points or more
     assert {g for _, g in auto} == {0, 1, 2, 3}
+
+
+def test_gt_exponentiation_model_restates_the_host_code_and_every_form_has_a_case():
+    """gt_encap_exp_name against gt_encap_exp_run (pairing.hip) and the split of a_table (api.hip); each of the three forms -- two lanes
+    per item, twelve lanes per item, and the two launches around an accumulator -- is reached by a listed case of
+    tests/test_gpu_fb_digit_edges.py, whose functions must exist"""
+    pairing, api = _src("pairing.hip"), _src("api.hip")
+    assert "constexpr size_t GT_EXP_WIDE_AUTO = %d;" % V.GT_EXP_WIDE_AUTO in pairing
+    assert "const size_t wide_max = ctx->tune.pair_wide_max < 0 ? GT_EXP_WIDE_AUTO : (size_t)ctx->tune.pair_wide_max;" in pairing
+    assert "if (n <= wide_max && d_tab_a && d_tab_b && !d_acc_in && !d_acc_out)" in pairing
+    body = re.search(r"static keaki_status a_table\(.*?\n}\n", api, re.S).group(0)
+    assert "if (a.n > %d) {" % V.GT_SPLIT_ABOVE in body and body.index("if (!k.gt_a.holds(com_host)) {") < body.index("if (a.n > %d) {" % V.GT_SPLIT_ABOVE)
+    assert "FB_TABLES_MIN = %d;" % V.FB_TABLES_MIN in api
+    assert V.gt_encap_exp_name(2048) == V.gt_encap_exp_name(2048, split=True) == {"pw::k_gt_encap_exp_wide"}
+    assert V.gt_encap_exp_name(2049) == V.gt_encap_exp_name(4096, split=True) == V.gt_encap_exp_name(5, 0) == {"k_gt_encap_exp"}
+    assert V.gt_encap_exp_name(4097, split=True) == V.gt_encap_exp_name(4097, 1 << 20, True) == {"k_gt_encap_exp[acc_out]", "k_gt_encap_exp[acc_in]"}
+    assert V.gt_encap_exp_name(4097) == {"k_gt_encap_exp"}
+    edge = {cid: ks for cid, ks in V.cases() if cid.startswith("fb_edge[")}
+    for want in ("k_gt_encap_exp", "pw::k_gt_encap_exp_wide", "k_gt_encap_exp[acc_in]", "k_gt_encap_exp[acc_out]", "k_encap_fixed_g2_wide",
+                 "k_encap_fixed<Fq2,1>", "k_encap_fixed<Fq2,2>", "k_encap_fixed<Fq,1>"):
+        assert any(want in ks for ks in edge.values()), want
+    # the sizes sit where the cases say: 8-bit tables below FB_TABLES_MIN, the twelve-lane form up to GT_EXP_WIDE_AUTO, the split above it
+    for wb in V.FB_EDGE_B_WIDTHS:
+        assert V.fb_edge_small_n((wb,)) < V.FB_TABLES_MIN
+    assert V.fb_edge_small_n() < V.FB_TABLES_MIN <= V.FB_EDGE_WIDE16_N <= V.GT_EXP_WIDE_AUTO < V.GT_SPLIT_ABOVE < V.FB_EDGE_SPLIT_N <= 65536
+    assert V.FB_EDGE_WIDE16_N % 4 and V.FB_EDGE_WIDE16_N % 64 and V.FB_EDGE_SPLIT_N % 64          # a ragged last row and block
+    with open(os.path.join(V.ROOT, "tests", "test_gpu_fb_digit_edges.py")) as f:
+        text = f.read()
+    assert "V.fb_edge_runs()" in text
+    for name, _, _, _, _ in V.fb_edge_runs():
+        assert 'run(h, b, "%s' % name.split("[")[0] in text or 'batches(), "%s"' % name in text, name
+    # every width a case walks is covered in full by the side that walks it
+    for b1 in [V.FB_EDGE_B1_WIDTHS] + [(wb,) for wb in V.FB_EDGE_B_WIDTHS]:
+        rs, b2, b1s = S.fb_edge_sides(S.fb_edge_batch(V.FB_EDGE_R_WIDTHS, V.FB_EDGE_B2_WIDTHS, b1))
+        for side, widths in ((rs, V.FB_EDGE_R_WIDTHS), (b2, V.FB_EDGE_B2_WIDTHS), (b1s, b1)):
+            for wb in widths:
+                assert S.fb_edge_covered(side, wb) == S.fb_edge_required(wb), (b1, wb)
 
 
 def test_fk_and_encap_models_follow_the_switches():

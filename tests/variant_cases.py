@@ -4,9 +4,10 @@ tests/test_variant_cases_model.py and tests/test_gpu_variants.py; no GPU import)
 The library ships several instantiations of its MSM, FK23 and fixed-base kernels; host code picks one from the input size and the tuning
 switches of keaki_hip_ctx_set_option (also settable through KEAKI_* at context creation). This module restates those host-side choices
 (keaki_amd/csrc/msm_host.hip.h: choose_window, choose_window_shared, msm_plan_call, msm_launch_accumulate; msm.hip.h: msm_make_plan, part_make_shape; fft_g1.hip:
-stage_map, run_stages; ec_batch_g2.hip: encap_g2_fixed_run), builds scalars that drive every window of a plan through each branch of the
-digit walk, and lists the GPU cases of tests/test_gpu_variants.py with the instantiations each one reaches. The CPU test checks the list
-against the launches it parses out of the sources, so a variant added without a case fails there.
+stage_map, run_stages; ec_batch_g2.hip: encap_g2_fixed_run; pairing.hip: gt_encap_exp_run; api.hip: a_table), builds scalars that drive
+every window of a plan through each branch of the digit walk, and lists the GPU cases of tests/test_gpu_variants.py and
+tests/test_gpu_fb_digit_edges.py with the instantiations each one reaches. The CPU test checks the list against the launches it parses out
+of the sources, so a variant added without a case fails there.
 """
 import os
 import re
@@ -338,6 +339,48 @@ def encap_g2_fixed_name(n, share_simds, fb_occ1, wide_max=2048):
     return "k_encap_fixed<Fq2,%d>" % (1 if (n <= 65536 and not share_simds) or fb_occ1 else 2)
 
 
+# ---- GT fixed-base exponentiation of encapsulate ---------------------------------------------------------------------------------------
+GT_EXP_WIDE_AUTO, GT_SPLIT_ABOVE, FB_TABLES_MIN = 2048, 4096, 256
+
+
+def gt_encap_exp_name(n, wide_max=GT_EXP_WIDE_AUTO, split=False):
+    """the launches of GT_i = A^(r_i) B^(-(r_i v_i)) (pairing.hip: gt_encap_exp_run; api.hip: a_table, encap_items). split: the call
+    builds the table of a new commitment; above 4096 items it then runs B's factor first (tab_a null, acc_out) and A's factor behind it
+    (tab_b null, acc_in), and a launch with an accumulator or a single table is never the twelve-lane one. -> the set of launches"""
+    if split and n > GT_SPLIT_ABOVE:
+        return {"k_gt_encap_exp[acc_out]", "k_gt_encap_exp[acc_in]"}
+    return {"pw::k_gt_encap_exp_wide" if n <= wide_max else "k_gt_encap_exp"}
+
+
+# the cases of tests/test_gpu_fb_digit_edges.py: (id, items, pair_wide_max, the commitment is new to the context, GT path). The small
+# batches are the unique items of S.fb_edge_batch plus the item r = 0; the larger ones tile them.
+FB_EDGE_R_WIDTHS, FB_EDGE_B2_WIDTHS, FB_EDGE_B1_WIDTHS = (8, 13, 16), (8, 16), (16,)
+FB_EDGE_B_WIDTHS = [8, 11, 13, 16, 20]
+FB_EDGE_WIDE16_N, FB_EDGE_SPLIT_N = 261, GT_SPLIT_ABOVE + 3
+
+
+def fb_edge_small_n(b1_widths=FB_EDGE_B1_WIDTHS):
+    return len(S.fb_edge_batch(FB_EDGE_R_WIDTHS, FB_EDGE_B2_WIDTHS, b1_widths)) + 1
+
+
+def fb_edge_runs():
+    ns = fb_edge_small_n()
+    out = [("small", ns, -1, True, True), ("repeat", ns, -1, False, True), ("wide16", FB_EDGE_WIDE16_N, -1, True, True),
+           ("lane", FB_EDGE_WIDE16_N, 0, True, True), ("lane_repeat", FB_EDGE_WIDE16_N, 0, False, True),
+           ("split", FB_EDGE_SPLIT_N, -1, True, True), ("split_repeat", FB_EDGE_SPLIT_N, -1, False, True),
+           ("pairing", FB_EDGE_WIDE16_N, -1, True, False)]
+    for wb in FB_EDGE_B_WIDTHS:
+        out += [("b_width[%d,wide]" % wb, fb_edge_small_n((wb,)), -1, True, True), ("b_width[%d,lane]" % wb, fb_edge_small_n((wb,)), 0, False, True)]
+    return out
+
+
+def fb_edge_kernels(n, pair_wide_max, new, gt):
+    """the per-item kernels of one encap_batch call on a context whose [tau]_2 tables hold the call's setup"""
+    wide_max = GT_EXP_WIDE_AUTO if pair_wide_max < 0 else pair_wide_max
+    ks = {encap_g2_fixed_name(n, n >= FB_TABLES_MIN and new and gt, 0, wide_max)}
+    return ks | (gt_encap_exp_name(n, wide_max, new) if gt else {"k_encap_fixed<Fq,1>"})
+
+
 # ---- the case table of tests/test_gpu_variants.py ----------------------------------------------------------------------------------------
 N_SMALL, N_LARGE = 500, 1 << 14
 G1_WINDOW_C = list(range(3, 25))
@@ -381,7 +424,8 @@ def pipe_chunk_sizes(n, k, growth=100):
 
 
 def cases():
-    """[(case id, model result or kernel set)]: every GPU case of tests/test_gpu_variants.py with what it reaches"""
+    """[(case id, model result or kernel set)]: every GPU case of tests/test_gpu_variants.py and tests/test_gpu_fb_digit_edges.py with
+    what it reaches"""
     out = []
     for n in (N_SMALL, N_LARGE):
         for c in G1_WINDOW_C:
@@ -404,6 +448,8 @@ def cases():
             out.append(("fk[%d,%s]" % (log2d, sorted(o.items())), fk_stage_kernels(log2d, o)))
     for occ, new in ENCAP_RUNS:
         out.append(("encap[fb_occ1=%d,new=%s]" % (occ, new), {encap_g2_fixed_name(ENCAP_N, new, occ)}))
+    for name, n, wide, new, gt in fb_edge_runs():          # tests/test_gpu_fb_digit_edges.py
+        out.append(("fb_edge[%s]" % name, fb_edge_kernels(n, wide, new, gt)))
     return out
 
 
