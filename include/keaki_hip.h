@@ -100,6 +100,8 @@ const char* keaki_hip_version(void);
  * 64-byte groups through a lane-private LDS slot; 0 = one 4-byte load per entry as until round 5), "cs_masked", "fk_uniform", "fk_gtab", "fk_addsub29", "fk_radix4", "fb_occ1", "gt_wb_b" (window bits of the table of
  * e(g1, g2), 0 = automatic; a change rebuilds the table on the next use), "encap_gt" (batch size from which encap_batch takes the GT
  * fixed-base path and below which -- for a commitment that has no table yet -- it runs a pairing per item; -1 = automatic: always the GT path),
+ * "encap_multi_single_min" (encap_multi / encrypt_multi: a group of at least this many items runs the single-commitment path, smaller groups the
+ * fused route with a pairing per item; 0 = never the single path; default 16,384, measured -- see keaki_hip_encap_multi),
  * "pair_wide_max" (pairing batches up to this size run the twelve-lanes-per-pairing kernel; -1 = automatic (4096), 0 = never), "pair_two_waves"
  * (up to 1,024 pairings: the line side of the Miller loop on a second wave; 0 = one wave), "msm_short_tables" (an MSM over less than half of an SRS
  * with window tables: 0 = the generic path as before round 4, 1 / -1 = the tables).
@@ -450,6 +452,47 @@ keaki_status keaki_hip_decrypt_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_
                                      uint8_t* msgs_out, size_t msg_len);
 keaki_status keaki_hip_decrypt_batch_dev(keaki_hip_ctx* ctx, const void* d_proofs_aff, const void* d_cts_aff, size_t n, void* d_body_inout,
                                          size_t msg_len);
+
+/* ---- encap_multi / encrypt_multi: encapsulate and encrypt to MANY commitments in one call -------------------------------------------------
+ * The sender of a many-party flow answers m receivers, each with its own commitment (vec_encrypt, src/vec.rs:52-69, once per receiver). One
+ * call replaces m calls of encap_batch / encrypt_batch, each of which pays the launch floor and, for a commitment seen for the first time, a
+ * GT table of e(C, g2) (1.7 ms, 31.5 MB).
+ * Layout: coms_aff = m affine G1 points (u64[8] each, (0,0) = the identity); offsets = uint64_t[m + 1], group j = items
+ *   [offsets[j], offsets[j + 1]), empty groups allowed anywhere; every other array item-major as in encap_batch / encrypt_batch.
+ *   r[i] drawn by the caller, one per item in GLOBAL index order: the stream that m consecutive vec_encrypt calls draw.
+ * Results: for every group j the ct, gt, key and body bytes of its items are byte for byte those of keaki_hip_encap_batch /
+ *   keaki_hip_encrypt_batch for (coms[j], the group's items) alone -- whichever route the group takes, with long or small tables.
+ * Routes: a group of at least "encap_multi_single_min" items (keaki_hip_ctx_set_option; 0 = never) runs the single-commitment path on its
+ *   item range (GT tables: worth their build from some thousand items on). Every other item runs the FUSED route, in maximal runs of
+ *   consecutive small groups: the ciphertext kernel of encap_batch, one G1 kernel that finds each item's commitment in `offsets` and computes
+ *   r_i C_j + (-(r_i beta_i)) g1 with one inversion, a pairing per item against g2's tabulated lines, the KDF. It builds no table per
+ *   commitment and leaves the single-commitment path's cache (its GT table, its count of repeated commitments) alone.
+ *   The default of "encap_multi_single_min", 16,384, is MEASURED (profiles/encap_multi_times.txt, written by bench_tools/bench_encap_multi.py):
+ *   with 16 groups of k items the fused route wins at k = 1,024 and 4,096 (0.75 against 2.2 ms per group at 4,096) and the single route at
+ *   16,384 and 65,536 (2.05 against 2.95 ms per group at 16,384); no k between 4,096 and 16,384 was measured. The estimate before the sweep
+ *   (a 1.7 ms table, partly overlapped, against ~0.13 us saved per item) was 8,192.
+ * Errors: KEAKI_ERR_BAD_ARG with nothing written for a null pointer (gt_out or key_out may be NULL, not both, as in encap_batch),
+ *   offsets[0] != 0, a decreasing offset, offsets[m] != n, n >= 2^31, m >= 2^31, msg_len > 65536 (encrypt: also msg_len == 0). n == 0
+ *   (m == 0 included) writes nothing and returns KEAKI_OK.
+ * Host form: one fused run is one pipelined batch (chunks of 2^15 items from 2^16 items on; a chunk may begin inside a group); a large group
+ *   is the host form of encap_batch / encrypt_batch on its sub-range of the caller's arrays. A failing call returns only when nothing reads
+ *   or writes caller memory any more.
+ * _dev: `offsets` is a HOST pointer here too, read before the call returns (as the domain constants of open_fk_poly_batch_dev). The call
+ *   synchronises where encap_batch_dev does -- the one read-back of [tau]_2 that keys its table -- and reads back a commitment only for a
+ *   group that takes the single-commitment route. d_body_inout: messages in, bodies out, in place.
+ * Context: one context, one device; sharding over a device group is not offered. */
+keaki_status keaki_hip_encap_multi(keaki_hip_ctx* ctx, const uint64_t* coms_aff, const uint64_t* offsets, size_t m, const uint64_t* tau_g2_aff,
+                                   const uint64_t* points, const uint64_t* values, const uint64_t* r, size_t n, uint64_t* ct_out_aff,
+                                   uint8_t* gt_out, uint8_t* key_out, size_t msg_len);
+keaki_status keaki_hip_encap_multi_dev(keaki_hip_ctx* ctx, const void* d_coms_aff, const uint64_t* offsets, size_t m, const void* d_tau_g2_aff,
+                                       const void* d_points, const void* d_values, const void* d_r, size_t n, void* d_ct_out_aff,
+                                       void* d_gt_out, void* d_key_out, size_t msg_len);
+keaki_status keaki_hip_encrypt_multi(keaki_hip_ctx* ctx, const uint64_t* coms_aff, const uint64_t* offsets, size_t m, const uint64_t* tau_g2_aff,
+                                     const uint64_t* points, const uint64_t* values, const uint64_t* r, const uint8_t* msgs, size_t n,
+                                     uint64_t* ct_out_aff, uint8_t* body_out, size_t msg_len);
+keaki_status keaki_hip_encrypt_multi_dev(keaki_hip_ctx* ctx, const void* d_coms_aff, const uint64_t* offsets, size_t m, const void* d_tau_g2_aff,
+                                         const void* d_points, const void* d_values, const void* d_r, size_t n, void* d_ct_out_aff,
+                                         void* d_body_inout, size_t msg_len);
 
 /* ---- device group: in-process multi-GPU (SURVEY 8b `_create(n_devices)`, 8e "single process, one host thread per GPU") -----------------
  * What a Rust caller of keaki gets with more than one GPU and no PyTorch / RCCL: the library keeps one ctx and one host worker thread per

@@ -3,6 +3,7 @@
 // the CPU here and there is no CPU fallback: without a gfx950 device every entry point fails.
 #include "internal.h"
 #include "host_plan.h"
+#include "encap_multi_plan.h"
 
 #include <algorithm>
 #include <cctype>
@@ -612,7 +613,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(cs_masked), TUNE_OPTION(acc_nt), TUNE_OPTION(fk_uniform), TUNE_OPTION(fk_gtab), TUNE_OPTION(fk_radix4), TUNE_OPTION(fk_addsub29),
     TUNE_OPTION(fb_occ1), TUNE_OPTION(pair_wide_max), TUNE_OPTION(pair_two_waves),
     TUNE_OPTION(gt_wb_b, gt_wb_b_refuses, [](keaki_hip_ctx* ctx) { ctx->kem.gt_b_ready = ctx->kem.gt_b_fallback = false; }),   // B's table: rebuilt at the new width on next use
-    TUNE_OPTION(encap_gt), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
+    TUNE_OPTION(encap_gt), TUNE_OPTION(encap_multi_single_min), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
     TUNE_OPTION(msm_pipe_growth),
 #ifdef KEAKI_DIAG
     TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
@@ -636,7 +637,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
+                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
     v.push_back({b, 1});
   ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
@@ -962,6 +963,18 @@ static keaki_status small_g2_tables(keaki_hip_ctx* ctx, const void* d_g2_generat
   k.fbs_ready = true;                 // fbs_tau is not valid yet: it is only ever built behind this point
   return KEAKI_OK;
 }
+// the small table of g1: kzg verify, and the fused route of encap_multi while the context has no long tables
+static keaki_status small_g1_table(keaki_hip_ctx* ctx) {
+  KemState& k = ctx->kem;
+  if (k.fbs_g1_ready) return KEAKI_OK;
+  const size_t FBX = fb_table_entries(FB_WB_SMALL);
+  ST_TRY(reserve(ctx, k.fbs_g1_gen, FBX * G1_AFF_BYTES + G1_AFF_BYTES));
+  void* g1pt = (char*)k.fbs_g1_gen.p + FBX * G1_AFF_BYTES;    // scratch slot behind the table
+  ST_TRY(g1_generator_to(ctx, g1pt));
+  ST_TRY(g1_fb_table_run(ctx, g1pt, k.fbs_g1_gen.p, FB_WB_SMALL));
+  k.fbs_g1_ready = true;
+  return KEAKI_OK;
+}
 // the two constants of the batch read back to the host: one synchronisation, for callers whose host copies did not come along. d_com null: [tau]_2 only
 static keaki_status read_constants(keaki_hip_ctx* ctx, const void* d_tau, const void* d_com, uint64_t* tau_host, uint64_t* com_host) {
   HIP_TRY(ctx, hipMemcpyAsync(tau_host, d_tau, 128, hipMemcpyDeviceToHost, ctx->stream));
@@ -1214,6 +1227,145 @@ keaki_status keaki_hip_decrypt_batch(keaki_hip_ctx* ctx, const uint64_t* proofs_
       ST_TRY(pairing_run(ctx, d[0], d[1], 1, m, ctx->tmp_b.p));
       return blake3_gt_run(ctx, ctx->tmp_b.p, m, d[2], msg_len, true);
     });
+}
+
+// ---- encap_multi / encrypt_multi: the sender's side of a many-party flow, a commitment per GROUP of items (src/vec.rs:52-69 once per receiver) ----
+// A group of at least "encap_multi_single_min" items runs the single-commitment path above on its item range (encap_impl: GT tables, 1.7 ms
+// and 31.5 MB for a commitment seen for the first time). Every other item runs the FUSED route, in maximal runs of consecutive small groups
+// (encap_multi_plan.h): the ciphertext kernel as it is, one G1 kernel that finds each item's commitment from the offsets (kem_multi.hip), a
+// pairing per item against g2's tabulated lines and the KDF. The fused route builds no table per commitment and leaves seen_com, gt_a and
+// fb_com of KemState alone; table widths follow the size of the WHOLE call, as the chunks of a host batch follow their batch.
+// d_coms / d_offsets: the commitments and offsets of the run's groups (n_groups, n_groups + 1 words); `first`: global index of the first item
+struct EncapMultiRun { const void *d_coms, *d_offsets; size_t n_groups; uint64_t first; };
+static keaki_status encap_multi_fused(keaki_hip_ctx* ctx, const EncapMultiRun& run, const EncapArgs& a, size_t n_policy, const uint64_t* tau_host) {
+  KemState& k = ctx->kem;
+  const bool use_tables = n_policy >= FB_TABLES_MIN;
+  ST_TRY(reserve(ctx, ctx->tmp_a, a.n * G1_AFF_BYTES));
+  if (!a.d_gt_out) ST_TRY(reserve(ctx, ctx->tmp_b, a.n * 384));
+  ST_TRY(generator_tables(ctx, use_tables));
+  ST_TRY(tau_table(ctx, use_tables, a.d_tau, tau_host));
+  if (!k.fb_ready) ST_TRY(small_g1_table(ctx));
+  void* gt = a.d_gt_out ? a.d_gt_out : ctx->tmp_b.p;
+  const bool big = k.fb_tau.holds(tau_host);
+  const KeyedTable<16>& tau = big ? k.fb_tau : k.fbs_tau;
+  ST_TRY(encap_g2_fixed_run(ctx, tau.buf.p, tau.wb, (big ? k.fb_g2_gen : k.fbs_g2_gen).p, tau.wb, a.d_points, a.d_r, a.n, a.d_ct_out));
+  ST_TRY(encap_multi_g1_run(ctx, run.d_coms, run.d_offsets, run.n_groups, run.first, (k.fb_ready ? k.fb_g1_gen : k.fbs_g1_gen).p,
+                            k.fb_ready ? FB_WB_LONG : FB_WB_SMALL, a.d_values, a.d_r, a.n, ctx->tmp_a.p));
+  ST_TRY(pairing_run(ctx, ctx->tmp_a.p, ctx->tmp_c.p, 0, a.n, gt, k.g2gen_lines.p));
+  if (a.d_key_out && a.msg_len) ST_TRY(blake3_gt_run(ctx, gt, a.n, a.d_key_out, a.msg_len, a.xor_into));
+  return KEAKI_OK;
+}
+// items [lo, lo + n) of the caller's per-item arrays (device)
+static EncapArgs encap_multi_slice(const EncapArgs& a, size_t lo, size_t n) {
+  EncapArgs s = a;
+  s.d_points = (const char*)a.d_points + lo * 32; s.d_values = (const char*)a.d_values + lo * 32; s.d_r = (const char*)a.d_r + lo * 32;
+  s.d_ct_out = (char*)a.d_ct_out + lo * G2_AFF_BYTES;
+  if (a.d_gt_out) s.d_gt_out = (char*)a.d_gt_out + lo * 384;
+  if (a.d_key_out) s.d_key_out = (char*)a.d_key_out + lo * a.msg_len;
+  s.n = n;
+  return s;
+}
+// `a` holds the arrays of ALL items (d_com: the m commitments); offsets: the caller's HOST array, validated
+static keaki_status encap_multi_dev(keaki_hip_ctx* ctx, const EncapArgs& a, const uint64_t* offsets, size_t m) {
+  const std::vector<EncapMultiPiece> pieces = encap_multi_plan(offsets, m, ctx->tune.encap_multi_single_min);
+  // the offsets go up in front of the one read-back, whose synchronisation also ends the read of the caller's array
+  ST_TRY(reserve(ctx, ctx->em_offsets, (m + 1) * 8));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->em_offsets.p, offsets, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  uint64_t tau_host[16];
+  ST_TRY(read_constants(ctx, a.d_tau, nullptr, tau_host, nullptr));
+  for (const EncapMultiPiece& p : pieces) {
+    if (p.i_hi == p.i_lo) continue;
+    EncapArgs s = encap_multi_slice(a, p.i_lo, p.i_hi - p.i_lo);
+    if (p.single) {
+      s.d_com = (const char*)a.d_com + p.g_lo * G1_AFF_BYTES;
+      ST_TRY(encap_impl(ctx, s));                          // reads this group's commitment back: it keys the GT table
+    } else {
+      const EncapMultiRun run = {(const char*)a.d_com + p.g_lo * G1_AFF_BYTES, (const char*)ctx->em_offsets.p + p.g_lo * 8, p.g_hi - p.g_lo, p.i_lo};
+      ST_TRY(encap_multi_fused(ctx, run, s, a.n, tau_host));
+    }
+  }
+  return KEAKI_OK;
+}
+keaki_status keaki_hip_encap_multi_dev(keaki_hip_ctx* ctx, const void* d_coms_aff, const uint64_t* offsets, size_t m, const void* d_tau_g2_aff,
+                                       const void* d_points, const void* d_values, const void* d_r, size_t n, void* d_ct_out_aff, void* d_gt_out,
+                                       void* d_key_out, size_t msg_len) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.encap_multi");
+  if (n == 0) return KEAKI_OK;
+  if (!d_coms_aff || !d_tau_g2_aff || !d_points || !d_values || !d_r || !d_ct_out_aff || (!d_gt_out && !d_key_out) || msg_len > 65536 ||
+      !encap_multi_offsets_ok(offsets, m, n))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "encap_multi: bad argument");
+  return encap_multi_dev(ctx, {d_coms_aff, d_tau_g2_aff, d_points, d_values, d_r, d_ct_out_aff, d_gt_out, d_key_out, n, msg_len}, offsets, m);
+}
+keaki_status keaki_hip_encrypt_multi_dev(keaki_hip_ctx* ctx, const void* d_coms_aff, const uint64_t* offsets, size_t m, const void* d_tau_g2_aff,
+                                         const void* d_points, const void* d_values, const void* d_r, size_t n, void* d_ct_out_aff,
+                                         void* d_body_inout, size_t msg_len) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.encrypt_multi");
+  if (n == 0) return KEAKI_OK;
+  if (!d_coms_aff || !d_tau_g2_aff || !d_points || !d_values || !d_r || !d_ct_out_aff || !d_body_inout || msg_len == 0 || msg_len > 65536 ||
+      !encap_multi_offsets_ok(offsets, m, n))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "encrypt_multi: bad argument");
+  return encap_multi_dev(ctx, {d_coms_aff, d_tau_g2_aff, d_points, d_values, d_r, d_ct_out_aff, nullptr, d_body_inout, n, msg_len, true}, offsets, m);
+}
+// Host forms. A fused run is ONE pipelined batch with the run's commitments, its offsets and [tau]_2 as head constants (a chunk may begin
+// anywhere inside a group: the kernel takes the global index of the chunk's first item); a large group is the single-commitment host call
+// on its sub-range of the caller's arrays. Each piece fences its own copies, so a failing call returns with nothing in flight.
+// Chunks of a fused run: 2^15 items (4.6 ms of pairings at 7.1 M/s against 3 MB up and up to 17 MB down), from two chunks on. Not measured against 2^16 / 2^17.
+constexpr size_t ENCAP_MULTI_CHUNK = 32768;
+// msgs: null for encap (gt / key out), else the messages of encrypt (bodies to key_or_body_out)
+static keaki_status encap_multi_host(keaki_hip_ctx* ctx, const uint64_t* coms, const uint64_t* offsets, size_t m, const uint64_t* tau, const uint64_t* points,
+                                     const uint64_t* values, const uint64_t* r, const uint8_t* msgs, size_t n, uint64_t* ct_out, uint8_t* gt_out,
+                                     uint8_t* key_or_body_out, size_t msg_len) {
+  const bool want_key = key_or_body_out && msg_len;
+  for (const EncapMultiPiece& p : encap_multi_plan(offsets, m, ctx->tune.encap_multi_single_min)) {
+    const size_t lo = p.i_lo, cnt = p.i_hi - p.i_lo;
+    if (!cnt) continue;
+    const uint64_t *pts = points + lo * 4, *vals = values + lo * 4, *rs = r + lo * 4;
+    uint64_t* ct = ct_out + lo * 16;
+    uint8_t* gt = gt_out ? gt_out + lo * 384 : nullptr;
+    uint8_t* kb = key_or_body_out ? key_or_body_out + lo * msg_len : nullptr;
+    const uint8_t* ms = msgs ? msgs + lo * msg_len : nullptr;
+    if (p.single) {
+      ST_TRY(msgs ? keaki_hip_encrypt_batch(ctx, coms + p.g_lo * 8, tau, pts, vals, rs, ms, cnt, ct, kb, msg_len)
+                  : keaki_hip_encap_batch(ctx, coms + p.g_lo * 8, tau, pts, vals, rs, cnt, ct, gt, kb, msg_len));
+      continue;
+    }
+    const size_t ng = p.g_hi - p.g_lo;
+    ST_TRY(pipelined_regions(ctx, cnt, pipe_chunk_items(ctx, cnt, ENCAP_MULTI_CHUNK),
+      {{coms + p.g_lo * 8, nullptr, ng * G1_AFF_BYTES}, {tau, nullptr, G2_AFF_BYTES}, {offsets + p.g_lo, nullptr, (ng + 1) * 8}},
+      {{pts, nullptr, 32}, {vals, nullptr, 32}, {rs, nullptr, 32}, {nullptr, ct, G2_AFF_BYTES}, {nullptr, gt, msgs ? 0 : (size_t)384},
+       {ms, want_key ? kb : nullptr, msg_len}},
+      [&](size_t clo, size_t cm, char* const* hd, char* const* d) {
+        const EncapMultiRun run = {hd[0], hd[2], ng, lo + clo};
+        // encrypt keeps its GT values in the context's workspace (d_gt_out null), as encrypt_batch does
+        return encap_multi_fused(ctx, run, {nullptr, hd[1], d[0], d[1], d[2], d[3], msgs ? nullptr : d[4], want_key ? d[5] : nullptr, cm, msg_len, msgs != nullptr},
+                                 n, tau);
+      }));
+  }
+  return KEAKI_OK;
+}
+keaki_status keaki_hip_encap_multi(keaki_hip_ctx* ctx, const uint64_t* coms_aff, const uint64_t* offsets, size_t m, const uint64_t* tau_g2_aff,
+                                   const uint64_t* points, const uint64_t* values, const uint64_t* r, size_t n, uint64_t* ct_out_aff, uint8_t* gt_out,
+                                   uint8_t* key_out, size_t msg_len) {
+  CTX_GUARD(ctx);                 // one lock over every piece of the call
+  TRACE_SCOPE("keaki.encap_multi");
+  if (n == 0) return KEAKI_OK;
+  if (!coms_aff || !tau_g2_aff || !points || !values || !r || !ct_out_aff || (!gt_out && !key_out) || msg_len > 65536 ||
+      !encap_multi_offsets_ok(offsets, m, n))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "encap_multi: bad argument");
+  return encap_multi_host(ctx, coms_aff, offsets, m, tau_g2_aff, points, values, r, nullptr, n, ct_out_aff, gt_out, key_out, msg_len);
+}
+keaki_status keaki_hip_encrypt_multi(keaki_hip_ctx* ctx, const uint64_t* coms_aff, const uint64_t* offsets, size_t m, const uint64_t* tau_g2_aff,
+                                     const uint64_t* points, const uint64_t* values, const uint64_t* r, const uint8_t* msgs, size_t n,
+                                     uint64_t* ct_out_aff, uint8_t* body_out, size_t msg_len) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.encrypt_multi");
+  if (n == 0) return KEAKI_OK;
+  if (!coms_aff || !tau_g2_aff || !points || !values || !r || !msgs || !ct_out_aff || !body_out || msg_len == 0 || msg_len > 65536 ||
+      !encap_multi_offsets_ok(offsets, m, n))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "encrypt_multi: bad argument");
+  return encap_multi_host(ctx, coms_aff, offsets, m, tau_g2_aff, points, values, r, msgs, n, ct_out_aff, nullptr, body_out, msg_len);
 }
 
 // ---- FK23 batch openings: replaces kzg::open_fk (src/kzg.rs:157-203) ----------------------------------------------------------
@@ -1799,11 +1951,7 @@ keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, c
   }
   char* io = (char*)k.verify_io.p;
   if (!k.verify_tables_ready) {
-    const size_t FBX = fb_table_entries(FB_WB_SMALL);
-    ST_TRY(reserve(ctx, k.fbs_g1_gen, FBX * G1_AFF_BYTES + G1_AFF_BYTES));
-    void* g1pt = (char*)k.fbs_g1_gen.p + FBX * G1_AFF_BYTES;
-    ST_TRY(g1_generator_to(ctx, g1pt));
-    ST_TRY(g1_fb_table_run(ctx, g1pt, k.fbs_g1_gen.p, FB_WB_SMALL));
+    ST_TRY(small_g1_table(ctx));
     ST_TRY(small_g2_tables(ctx, io + O_Q));   // shared with the small-batch path of encapsulate (which also keeps [tau]_2's table there)
     k.verify_tables_ready = true;
   }

@@ -52,6 +52,7 @@ struct Tuning {
   int pair_wide_max = -1;        // KEAKI_PAIR_WIDE_MAX / "pair_wide_max": pairing batches up to this size run the twelve-lanes-per-pairing kernel; -1 = automatic, 0 = never
   bool pair_two_waves = true;    // KEAKI_PAIR_TWO_WAVES / "pair_two_waves": up to 1,024 pairings with lines on the fly run the line functions on a second wave (A/B switch)
   int gt_wb_b = 0;               // KEAKI_GT_WB_B / "gt_wb_b": window bits of the table of e(g1, g2), 0 = automatic (20 / 16)
+  long long encap_multi_single_min = 16384;   // KEAKI_ENCAP_MULTI_SINGLE_MIN / "encap_multi_single_min": a group of encap_multi / encrypt_multi with at least this many items runs the single-commitment path (GT tables), smaller groups the fused per-item pairing; 0 = never the single path (measured: the smallest k of 1,024 / 4,096 / 16,384 / 65,536 at which the single route wins, profiles/encap_multi_times.txt; the estimate before the sweep was 8,192)
   long long encap_gt = -1;       // KEAKI_ENCAP_GT / "encap_gt": batch size from which encap takes the GT fixed-base path; -1 = automatic (always, since round 4)
   bool host_prefault = true;     // KEAKI_HOST_PREFAULT / "host_prefault": first-touch (write zeros into) and madvise(MADV_HUGEPAGE) the caller's OUTPUT arrays while the kernels run, on helper threads for chunked batches; 0 = the library never touches caller memory except through the device copies
   bool pipe_chunks = true;       // KEAKI_PIPE_CHUNKS / "pipe_chunks": host-pointer batches (KEM, MSM) run as chunk pipelines over a copy stream; 0 = upload, kernels, download in that order on the context's stream
@@ -81,7 +82,7 @@ struct KemState {
   // 16-bit window tables for batches of >= 256 items: of the generators (with room for the 13-bit table that the per-item-pairing path rebuilds for
   // each batch's commitment) and of [tau]_2 | small (8-bit) tables for smaller batches and kzg verify: of g2 and [tau]_2 | of g1 (verify only)
   DevBuf fb_g1_gen, fb_g2_gen, fb_com, fbs_g2_gen, fbs_g1_gen;
-  bool fb_ready = false, fbs_ready = false, verify_tables_ready = false;
+  bool fb_ready = false, fbs_ready = false, fbs_g1_ready = false, verify_tables_ready = false;
   KeyedTable<16> fb_tau, fbs_tau;
   // kzg verify's small in/out block | line sequence of g2 | line tables and points of 2^s g2, s < 320 (api.hip: g2pow_tables)
   DevBuf verify_io, g2gen_lines, g2pow_lines, g2pow_pts;
@@ -161,6 +162,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf fk_tab;                    // window tables of the per-lane-scalar ladders of FK23: 1 KB per lane of a launch (64 x 16 B), at most 2 GB (fft_g1.hip)
   keaki_internal::DevBuf mb_canon, mb_wsums, mb_q;  // batched MSM / open (msm_batch.hip): biased canonical scalars of a pass (32 B each) | window sums (128 B per row and window) | quotient rows of open_batch
   keaki_internal::DevBuf fkb_pts, fkb_fr;           // batched FK23 (fk_batch.hip): the 2d x M Jacobian points of a pass, position-major | its scalar rows (96 B per coefficient) and the call's twiddle tables
+  keaki_internal::DevBuf em_offsets;                // encap_multi / encrypt_multi, _dev forms: the device copy of the caller's group offsets (8 B per group)
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
   // instrumentation
   bool timing = false;
@@ -256,6 +258,10 @@ keaki_status g2_fb_table_run(keaki_hip_ctx* ctx, const void* d_base, void* d_tab
 keaki_status g2_pow2_multiples_run(keaki_hip_ctx* ctx, const void* d_base, uint32_t count, void* d_out);   // out[s] = 2^s base (affine), lane s doubles s times
 keaki_status encap_g1_fixed_run(keaki_hip_ctx* ctx, const void* d_tab_a, uint32_t wb_a, const void* d_tab_b, uint32_t wb_b, const void* d_xs, const void* d_rs, size_t n, void* d_out);
 keaki_status encap_g2_fixed_run(keaki_hip_ctx* ctx, const void* d_tab_a, uint32_t wb_a, const void* d_tab_b, uint32_t wb_b, const void* d_xs, const void* d_rs, size_t n, void* d_out, bool share_simds = false);
+// encap_multi, G1 side (kem_multi.hip): out[i] = r_i (C_j - beta_i g1) for item first + i of group j, offsets[j] <= first + i < offsets[j + 1];
+// d_offsets: m + 1 u64 (device), d_tab_g1: the wb-bit window table of g1; n < 2^31
+keaki_status encap_multi_g1_run(keaki_hip_ctx* ctx, const void* d_coms, const void* d_offsets, size_t m, uint64_t first, const void* d_tab_g1, uint32_t wb,
+                                const void* d_values, const void* d_r, size_t n, void* d_out);
 keaki_status g1_curve_check_run(keaki_hip_ctx* ctx, const void* d_pts, size_t n, void* d_bad2);   // d_bad2: u64 count, u64 first index
 keaki_status g2_curve_check_run(keaki_hip_ctx* ctx, const void* d_pts, size_t n, void* d_bad2);
 // top_is_carry: d_c[n - 1] is not a coefficient but the suffix value carried in from the chunk above (its quotient slot is left alone)

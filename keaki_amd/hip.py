@@ -27,6 +27,7 @@ EXPORTS = [
     "keaki_hip_encap_batch", "keaki_hip_encap_batch_dev", "keaki_hip_decap_batch", "keaki_hip_decap_batch_dev",
     "keaki_hip_encrypt_batch", "keaki_hip_encrypt_batch_dev", "keaki_hip_decrypt_batch", "keaki_hip_decrypt_batch_dev",
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
+    "keaki_hip_encap_multi", "keaki_hip_encap_multi_dev", "keaki_hip_encrypt_multi", "keaki_hip_encrypt_multi_dev",
     "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
@@ -192,6 +193,10 @@ def load_library():
         lib.keaki_hip_group_decap_batch.argtypes = [vp, vp, vp, sz, vp, vp, sz]
         lib.keaki_hip_encrypt_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz]
         lib.keaki_hip_encrypt_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp, sz]
+        lib.keaki_hip_encap_multi.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz]
+        lib.keaki_hip_encap_multi_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, sz]
+        lib.keaki_hip_encrypt_multi.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz]
+        lib.keaki_hip_encrypt_multi_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, vp, sz]
         lib.keaki_hip_decrypt_batch.argtypes = [vp, vp, vp, vp, sz, vp, sz]
         lib.keaki_hip_decrypt_batch_dev.argtypes = [vp, vp, vp, sz, vp, sz]
         lib.keaki_hip_group_encrypt_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, sz]
@@ -727,6 +732,46 @@ class KeakiHip:
     def decap_batch_dev(self, d_proofs, d_cts, n, d_gt, d_key, msg_len):
         v = lambda x: C.c_void_p(x) if x else None
         self._ck(self.lib.keaki_hip_decap_batch_dev(self.ctx, v(d_proofs), v(d_cts), n, v(d_gt), v(d_key), msg_len))
+
+    # ---- a commitment per GROUP of items (keaki_hip_encap_multi / keaki_hip_encrypt_multi): group j = items [offsets[j], offsets[j + 1])
+    @staticmethod
+    def _offsets(offsets):
+        o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if o.size == 0:
+            raise ValueError("offsets holds m + 1 words: at least one")
+        return o
+
+    def encap_multi(self, coms, offsets, tau_g2, points, values, rs, msg_len: int = 32, want_gt: bool = True):
+        """-> (ct, gt, key), or (ct, key) with want_gt=False; coms: (m, 8) u64, offsets: m + 1 item bounds"""
+        c = _np(coms, 8); o = self._offsets(offsets); pts = _np(points, 4); vals = _np(values, 4); rs = _np(rs, 4)
+        n = pts.shape[0]
+        ct = np.zeros((n, 16), np.uint64); key = np.zeros((n, max(msg_len, 1)), np.uint8)
+        gt = np.zeros((n, 384), np.uint8) if want_gt else None
+        self._ck(self.lib.keaki_hip_encap_multi(self.ctx, _ptr(c) if c.size else None, _ptr(o), o.size - 1, _ptr(_np(tau_g2)), _ptr(pts), _ptr(vals), _ptr(rs), n,
+                                                _ptr(ct), _ptr(gt) if want_gt else None, _ptr(key) if msg_len else None, msg_len))
+        return (ct, gt, key[:, :msg_len]) if want_gt else (ct, key[:, :msg_len])
+
+    def encrypt_multi(self, coms, offsets, tau_g2, points, values, rs, msgs, in_place: bool = False):
+        """-> (ct points (n, 16) u64, bodies (n, msg_len) u8) of msgs, an (n, msg_len) uint8 array"""
+        c = _np(coms, 8); o = self._offsets(offsets); p, v, r = _np(points, 4), _np(values, 4), _np(rs, 4)
+        m = np.ascontiguousarray(msgs, dtype=np.uint8)
+        n, msg_len = m.shape
+        ct = np.zeros((n, 16), np.uint64)
+        body = m if in_place else np.zeros((n, msg_len), np.uint8)
+        self._ck(self.lib.keaki_hip_encrypt_multi(self.ctx, _ptr(c) if c.size else None, _ptr(o), o.size - 1, _ptr(_np(tau_g2)), _ptr(p), _ptr(v), _ptr(r), _ptr(m), n,
+                                                  _ptr(ct), _ptr(body), msg_len))
+        return ct, body
+
+    def encap_multi_dev(self, d_coms, offsets, d_tau, d_points, d_values, d_r, n, d_ct, d_gt, d_key, msg_len):
+        """offsets: a HOST array of m + 1 item bounds (read before the call returns); everything else device addresses"""
+        v = lambda x: C.c_void_p(x) if x else None
+        o = self._offsets(offsets)
+        self._ck(self.lib.keaki_hip_encap_multi_dev(self.ctx, v(d_coms), _ptr(o), o.size - 1, v(d_tau), v(d_points), v(d_values), v(d_r), n, v(d_ct), v(d_gt), v(d_key), msg_len))
+
+    def encrypt_multi_dev(self, d_coms, offsets, d_tau, d_points, d_values, d_r, n, d_ct, d_body_inout, msg_len):
+        v = lambda x: C.c_void_p(x) if x else None
+        o = self._offsets(offsets)
+        self._ck(self.lib.keaki_hip_encrypt_multi_dev(self.ctx, v(d_coms), _ptr(o), o.size - 1, v(d_tau), v(d_points), v(d_values), v(d_r), n, v(d_ct), v(d_body_inout), msg_len))
 
 
 class GroupSrsG1:

@@ -749,6 +749,30 @@ void vec_encrypt_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const
     if (ahead.joinable()) ahead.join();
   }
 }
+// vec_encrypt to m commitments in ONE device call (keaki_hip_encrypt_multi): group j = the next counts[j] items, under coms[j]. One r per item
+// in global index order -- the stream m consecutive vec_encrypt calls draw -- so points and bodies equal those of that loop.
+void vec_encrypt_batch(Rng& rng, const kzg::KZGSetup& setup, const G1* coms, const size_t* counts, size_t m, const Fr* points, const Fr* values,
+                       const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  const Device& dev = *setup.device();
+  if (dev.group()) throw std::invalid_argument("vec_encrypt_batch: a group device encrypts commitment by commitment (vec_encrypt)");
+  std::vector<uint64_t> offsets(m + 1, 0), cw(8 * std::max<size_t>(m, 1));
+  for (size_t j = 0; j < m; j++) {
+    offsets[j + 1] = offsets[j] + counts[j];
+    memcpy(&cw[8 * j], coms[j].w.data(), 64);
+  }
+  const size_t n = (size_t)offsets[m];
+  if (!n) return;
+  std::vector<Fr> rs(n);
+  for (size_t i = 0; i < n; i++) rs[i] = fr_rand(rng);
+  if (msg_len) {
+    dev.check(keaki_hip_encrypt_multi(dev.ctx(), cw.data(), offsets.data(), m, setup.tau_g2().w.data(), points[0].l, values[0].l, rs[0].l, msgs, n, ct_g2_out,
+                                      ct_msg_out, msg_len));
+  } else {
+    std::vector<uint8_t> gt_unused(n * 384);       // the ABI wants at least one of gt / key
+    dev.check(keaki_hip_encap_multi(dev.ctx(), cw.data(), offsets.data(), m, setup.tau_g2().w.data(), points[0].l, values[0].l, rs[0].l, n, ct_g2_out,
+                                    gt_unused.data(), nullptr, 0));
+  }
+}
 void vec_decrypt_flat(const kzg::KZGSetup& setup, const uint64_t* proofs, const uint64_t* ct_g2, const uint8_t* ct_msgs, size_t n, size_t msg_len,
                       uint8_t* msgs_out) {
   if (!n || !msg_len) return;

@@ -255,6 +255,11 @@ std::vector<enc::Ciphertext> vec_encrypt(Rng& rng, const kzg::KZGSetup& setup, c
 // src/vec.rs:72-81
 void vec_encrypt_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* points, const Fr* values, const uint8_t* msgs, size_t n,
                       size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out);
+// vec_encrypt to m commitments in one device call (keaki_hip_encrypt_multi; flat like vec_encrypt_flat): group j = the next counts[j] items of the
+// item-major arrays, encrypted under coms[j]; n = the sum of counts. One r per item in GLOBAL index order, which is the stream of m consecutive
+// vec_encrypt calls, so ct_g2_out (n x 16 words) and ct_msg_out (n x msg_len) hold what that loop returns. Single device only.
+void vec_encrypt_batch(Rng& rng, const kzg::KZGSetup& setup, const G1* coms, const size_t* counts, size_t m, const Fr* points, const Fr* values,
+                       const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out);
 void vec_decrypt_flat(const kzg::KZGSetup& setup, const uint64_t* proofs, const uint64_t* ct_g2, const uint8_t* ct_msgs, size_t n, size_t msg_len,
                       uint8_t* msgs_out);
 std::vector<std::vector<uint8_t>> vec_decrypt(const kzg::KZGSetup& setup, const std::vector<G1>& proofs,

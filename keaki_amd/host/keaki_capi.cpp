@@ -365,6 +365,17 @@ int keaki_host_vec_encrypt(void* rng, void* s, const uint64_t* com, const uint64
     return 0;
   });
 }
+// vec_encrypt_batch: m commitments (m x 8 words), counts[j] items each, item-major arrays over all n = sum(counts) items
+int keaki_host_vec_encrypt_batch(void* rng, void* s, const uint64_t* coms, const size_t* counts, size_t m, const uint64_t* points, const uint64_t* values,
+                                 const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  return guard([&] {
+    std::vector<G1> cs(m);
+    for (size_t j = 0; j < m; j++) cs[j] = g1_of(coms + 8 * j);
+    vec::vec_encrypt_batch(*(Rng*)rng, ((Setup*)s)->s, cs.data(), counts, m, reinterpret_cast<const Fr*>(points), reinterpret_cast<const Fr*>(values), msgs,
+                           msg_len, ct_g2_out, ct_msg_out);
+    return 0;
+  });
+}
 int keaki_host_vec_decrypt(void* s, const uint64_t* proofs, const uint64_t* ct_g2, const uint8_t* ct_msgs, size_t n, size_t msg_len,
                            uint8_t* msgs_out) {
   return guard([&] {

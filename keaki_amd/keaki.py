@@ -513,6 +513,23 @@ def vec_encrypt(rng: Rng, setup: KZGSetup, com, points, values, messages):
     return [(g2[i].copy(), body[i * ml:(i + 1) * ml].tobytes()) for i in range(n)]
 
 
+def vec_encrypt_batch(rng: Rng, setup: KZGSetup, coms, counts, points, values, messages: np.ndarray):
+    """vec_encrypt to m commitments in one device call: group j = the next counts[j] items, encrypted under coms[j]; messages is an
+    (n, len) uint8 array over all n = sum(counts) items -> (ct G2 points (n, 16) u64, ct bodies (n, len) u8). One r per item in global index
+    order: the draws and bytes of m consecutive vec_encrypt calls; see keaki::vec::vec_encrypt_batch"""
+    msgs = np.ascontiguousarray(messages, dtype=np.uint8)
+    n, ml = msgs.shape
+    cnt = [int(c) for c in counts]
+    m = len(cnt)
+    assert sum(cnt) == n, "counts must add up to the number of messages"
+    cs = np.ascontiguousarray(_u64(coms, 8)[:m]) if m else np.zeros((1, 8), np.uint64)
+    pts = np.ascontiguousarray(_u64(points, 4)[:n]); vals = np.ascontiguousarray(_u64(values, 4)[:n])
+    g2 = np.zeros((n, 16), np.uint64); body = np.zeros((n, max(ml, 1)), np.uint8)
+    _ck(_lib().keaki_host_vec_encrypt_batch(rng.h, setup.h, _p(cs), (C.c_size_t * max(m, 1))(*cnt), C.c_size_t(m), _p(pts), _p(vals), _p(msgs), C.c_size_t(ml),
+                                           _p(g2), _p(body)))
+    return g2, body[:, :ml]
+
+
 def vec_encrypt_arrays(rng: Rng, setup: KZGSetup, com, points, values, messages: np.ndarray):
     """vec_encrypt on contiguous arrays (n equal-length messages as an (n, len) uint8 array) -> (ct G2 points (n, 16) u64,
     ct bodies (n, len) u8): the same call without a Python object per item."""

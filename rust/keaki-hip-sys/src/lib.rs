@@ -198,6 +198,19 @@ extern "C" {
                                    msg_len: usize) -> keaki_status;
     pub fn keaki_hip_decrypt_batch_dev(ctx: *mut keaki_hip_ctx, d_proofs_aff: *const c_void, d_cts_aff: *const c_void, n: usize,
                                        d_body_inout: *mut c_void, msg_len: usize) -> keaki_status;
+    // a commitment per group of items: group j = items [offsets[j], offsets[j + 1]); `offsets` (m + 1 words) is a HOST pointer in the _dev forms too
+    pub fn keaki_hip_encap_multi(ctx: *mut keaki_hip_ctx, coms_aff: *const u64, offsets: *const u64, m: usize, tau_g2_aff: *const u64, points: *const u64,
+                                 values: *const u64, r: *const u64, n: usize, ct_out_aff: *mut u64, gt_out: *mut u8, key_out: *mut u8,
+                                 msg_len: usize) -> keaki_status;
+    pub fn keaki_hip_encap_multi_dev(ctx: *mut keaki_hip_ctx, d_coms_aff: *const c_void, offsets: *const u64, m: usize, d_tau_g2_aff: *const c_void,
+                                     d_points: *const c_void, d_values: *const c_void, d_r: *const c_void, n: usize, d_ct_out_aff: *mut c_void,
+                                     d_gt_out: *mut c_void, d_key_out: *mut c_void, msg_len: usize) -> keaki_status;
+    pub fn keaki_hip_encrypt_multi(ctx: *mut keaki_hip_ctx, coms_aff: *const u64, offsets: *const u64, m: usize, tau_g2_aff: *const u64, points: *const u64,
+                                   values: *const u64, r: *const u64, msgs: *const u8, n: usize, ct_out_aff: *mut u64, body_out: *mut u8,
+                                   msg_len: usize) -> keaki_status;
+    pub fn keaki_hip_encrypt_multi_dev(ctx: *mut keaki_hip_ctx, d_coms_aff: *const c_void, offsets: *const u64, m: usize, d_tau_g2_aff: *const c_void,
+                                       d_points: *const c_void, d_values: *const c_void, d_r: *const c_void, n: usize, d_ct_out_aff: *mut c_void,
+                                       d_body_inout: *mut c_void, msg_len: usize) -> keaki_status;
 
     // ---- device group: several GPUs of ONE process (one context + one host thread per member inside the library)
     pub fn keaki_hip_group_create(devices: *const i32, n_devices: usize, out: *mut *mut keaki_hip_group) -> keaki_status;
