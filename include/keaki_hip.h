@@ -348,6 +348,40 @@ keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_co
                                             const void* d_points, int32_t point_mode, const void* d_values, const void* d_proofs_aff,
                                             const void* d_gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff);
 
+/* ---- KZG verify_each: one verdict per opening, n openings in one call ---------------------------------------------------
+ * verify_batch answers "are all n openings valid?"; this call says WHICH are not. Per item, by bilinearity (z_i proof_i moved across the
+ * pairing, as in verify_batch):
+ *     L_i = C_i - y_i g1 + z_i proof_i          status[i] = 0  <=>  e(L_i, g2) * e(-proof_i, [tau]_2) == 1
+ * Both second arguments are fixed for the call, so both line sequences are tables ([tau]_2's is built on first use and kept in the context
+ * until another [tau]_2 arrives); the two Miller loops share their 64 squarings and ONE final exponentiation, and the result is compared with
+ * one on the device. The verdict is exact -- no gammas, no error probability -- and always equals that of keaki_hip_kzg_verify on the item.
+ *   com_aff, com_stride, tau_g2_aff, points, point_mode, values, proofs_aff     exactly as in keaki_hip_kzg_verify_batch
+ *   status       n bytes: 0 = the equation holds (accepted, as in _decompress), 1 = it does not
+ *   n_bad        the number of ones (required);   first_bad   index of the first one, UINT64_MAX if none (may be NULL)
+ *   lhs_out_aff  n affine G1 points L_i ((0,0) = identity), or NULL: what the first pairing slot was evaluated on
+ * Identities are ordinary inputs: L_i and proof_i both the identity is valid (a constant polynomial: C = y g1, proof = 0), exactly one of them
+ * is invalid; [tau]_2 = identity: valid_i <=> L_i is the identity. Points are assumed to be on the curve (decode untrusted ones with
+ * _decompress first). A bad item never fails the call.
+ * n = 0: *n_bad = 0, *first_bad = UINT64_MAX, nothing else written. com_stride or point_mode outside {0, 1}, a null required pointer with n > 0,
+ * n >= 2^31: KEAKI_ERR_BAD_ARG, nothing written.
+ * Host form: one upload in front, the kernels in launch chunks of at most 2^17 items, one download of n bytes (+ 64 n with lhs_out_aff); no
+ * chunk pipeline -- the inputs are at most 192 B per item against >= 140 ns of pairing work per item, a few per cent. The call returns when
+ * nothing reads or writes caller memory any more, also on failure.
+ * _dev: every array is a device pointer (the commitment, [tau]_2 and omega too); n_bad and first_bad stay HOST pointers, so this form
+ * synchronises, like _decompress_dev.
+ * Workspace: 3,968 B per item of a launch chunk, grow-only; a refused reservation halves the chunk, and the call fails (the context stays
+ * usable) only when 32 items do not fit.
+ * Measured (profiles/verify_each_times.txt, resident, medians of alternating rounds in one process): 2^16 items 10.5 ms, 2^20 items 156.7 ms
+ * (160.5 ms from host arrays). Against ONE pairing with lines on the fly per item (keaki_hip_pairing_batch_dev over n items): 1.15 x / 1.13 x
+ * its time at 2^16 / 2^20 (0.57 x / 0.56 x the time of two), 3.97 x at 2^10 where the call is one lane-pair pairing's latency (6.1 ms).
+ * Against n single keaki_hip_kzg_verify calls, EXTRAPOLATED from the mean of 64 (1.68 ms): 1/284 at 2^10, 1/10,500 at 2^16, 1/11,300 at 2^20. */
+keaki_status keaki_hip_kzg_verify_each(keaki_hip_ctx* ctx, const uint64_t* com_aff, int32_t com_stride, const uint64_t* tau_g2_aff,
+                                       const uint64_t* points, int32_t point_mode, const uint64_t* values, const uint64_t* proofs_aff, size_t n,
+                                       uint8_t* status, uint64_t* n_bad, uint64_t* first_bad, uint64_t* lhs_out_aff);
+keaki_status keaki_hip_kzg_verify_each_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff,
+                                           const void* d_points, int32_t point_mode, const void* d_values, const void* d_proofs_aff, size_t n,
+                                           void* d_status, uint64_t* n_bad, uint64_t* first_bad, void* d_lhs_out_aff);
+
 /* ---- SRS ingest (scope row f-3) -----------------------------------------------------------------------------------------
  * The reference reads .ptau points with `deserialize_uncompressed_unchecked` (src/kzg/ptau.rs:266,314): no curve check at all.
  * A snarkjs .ptau stores coordinates as Montgomery limbs, which is this ABI's point layout, so sections 2 and 3 are uploaded

@@ -637,7 +637,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
+                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
     v.push_back({b, 1});
   ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
@@ -2091,6 +2091,129 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
   ST_TRY(verify_batch_core(ctx, ctx->io_e.p, com_stride, ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, ctx->io_a.p, n, stage, ok_out, sums_out_aff));
   feed.settled();                 // verify_batch_core has downloaded the result
   return KEAKI_OK;
+}
+
+// ---- KZG verify_each: n openings, one verdict each ---------------------------------------------------------------------------------------
+// L_i = C_i - y_i g1 + z_i proof_i, valid_i <=> e(L_i, g2) e(-proof_i, [tau]_2) == 1: the predicate of src/kzg.rs:135-148 with z_i proof_i moved
+// across the pairing, so that BOTH second arguments are fixed for the call and both line sequences are tables (g2's is the context's g2gen_lines,
+// [tau]_2's is built on first use and kept until another [tau]_2 arrives). Kernel sequence per launch chunk of at most pairing_launch_items()
+// items, all on ctx->stream: k_ve_g1 (L and -proof, kzg_each.hip) | k_pairing2 (kzg_each_pair.hip: one Miller loop over both tables, one final
+// exponentiation, one status byte); then k_ve_count over the n bytes. [tau]_2 = identity is decided here: no pairing, valid_i <=> L_i = identity.
+// The host form is one upload in front, the kernels, one download of n bytes (+ 64 n with lhs_out_aff), with no chunk pipeline: the inputs are
+// at most 192 B per item against >= 140 ns of pairing work (7.1 M pairings/s), a few per cent, which is not worth the stager's machinery.
+// ve_io block: [bad2 16] [com 64] [tau 128] [omega 32]
+extern "C++" {
+namespace {
+struct VeLayout { static constexpr size_t O_BAD = 0, O_COM = 16, O_TAU = 80, O_OMEGA = 208, BYTES = 240; };
+keaki_status verify_each_args(keaki_hip_ctx* ctx, const void* com, int32_t com_stride, const void* tau, const void* points, int32_t point_mode,
+                              const void* values, const void* proofs, size_t n, const void* status, const uint64_t* n_bad) {
+  if ((com_stride != 0 && com_stride != 1) || (point_mode != 0 && point_mode != 1))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: com_stride = %d, point_mode = %d: both must be 0 or 1", (int)com_stride, (int)point_mode);
+  if (!n_bad) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: n_bad is null");
+  if (n && (!com || !tau || !points || !values || !proofs || !status)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: null pointer");
+  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: n must be < 2^31 per device");
+  return KEAKI_OK;
+}
+void verify_each_empty(uint64_t* n_bad, uint64_t* first_bad) {
+  *n_bad = 0;
+  if (first_bad) *first_bad = ~0ull;
+}
+// Everything is device memory: d_com / d_tau / d_omega_or_points as the kernels read them, tau_host = the 128 bytes of [tau]_2 (the key of its line
+// table). d_lhs: n x 64 B for the L_i, or null (they stay in the chunk's workspace). Ends with the read-back of the counters: synchronises.
+keaki_status verify_each_core(keaki_hip_ctx* ctx, const void* d_coms, int32_t com_stride, const void* d_tau, const uint64_t* tau_host, const void* d_points,
+                              int32_t point_mode, const void* d_values, const void* d_proofs, size_t n, void* d_status, void* d_lhs, uint64_t* n_bad,
+                              uint64_t* first_bad) {
+  KemState& k = ctx->kem;
+  bool tau_inf = true;
+  for (int j = 0; j < 16; j++) tau_inf = tau_inf && tau_host[j] == 0;
+  // the launch chunk: the final exponentiation's slots and the two points per item; a refused reservation halves it, down to one wave of items
+  size_t ch = std::min(n, pairing_launch_items());
+  for (;;) {
+    keaki_status st = reserve(ctx, ctx->ve_pts, ch * 2 * G1_AFF_BYTES);
+    if (st == KEAKI_OK && !tau_inf) st = reserve(ctx, ctx->pair_ws, ch * pairing_slot_bytes());
+    if (st == KEAKI_OK) break;
+    if (st != KEAKI_ERR_OOM || ch <= 32) return st;
+    ctx->err.clear();
+    ch = std::max<size_t>(32, ((ch + 1) / 2 + 31) & ~(size_t)31);
+  }
+  ST_TRY(generator_tables(ctx, false));               // g2's line sequence
+  if (!k.fb_ready) ST_TRY(small_g1_table(ctx));
+  if (!tau_inf && !k.tau_lines.holds(tau_host)) {
+    k.tau_lines.invalidate();
+    ST_TRY(reserve(ctx, k.tau_lines.buf, g2_prepared_bytes()));
+    ST_TRY(g2_prepare_run(ctx, d_tau, k.tau_lines.buf.p));
+    k.tau_lines.publish(tau_host, 0);
+  }
+  char* io = (char*)ctx->ve_io.p;
+  const uint64_t init[2] = {0, ~0ull};
+  HIP_TRY(ctx, hipMemcpyAsync(io + VeLayout::O_BAD, init, 16, hipMemcpyHostToDevice, ctx->stream));
+  const void* tab_g1 = (k.fb_ready ? k.fb_g1_gen : k.fbs_g1_gen).p;
+  const uint32_t wb = k.fb_ready ? FB_WB_LONG : FB_WB_SMALL;
+  char* pts = (char*)ctx->ve_pts.p;
+  for (size_t lo = 0; lo < n; lo += ch) {
+    const size_t m = std::min(ch, n - lo);
+    void* lhs = d_lhs ? (char*)d_lhs + lo * G1_AFF_BYTES : pts;
+    void* neg = pts + ch * G1_AFF_BYTES;
+    ST_TRY(verify_each_g1_run(ctx, d_coms, com_stride, tab_g1, wb, d_points, point_mode, d_values, d_proofs, lo, m, lhs, neg));
+    if (tau_inf)
+      ST_TRY(verify_each_tau_inf_run(ctx, lhs, m, (char*)d_status + lo));
+    else
+      ST_TRY(pairing2_fixed_run(ctx, lhs, neg, m, k.g2gen_lines.p, k.tau_lines.buf.p, ctx->pair_ws.p, ch, (char*)d_status + lo));
+  }
+  ST_TRY(verify_each_count_run(ctx, d_status, n, io + VeLayout::O_BAD));
+  uint64_t res[2];
+  ST_TRY(download(ctx, res, io + VeLayout::O_BAD, 16));
+  *n_bad = res[0];
+  if (first_bad) *first_bad = res[1];
+  return KEAKI_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_kzg_verify_each_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff, const void* d_points,
+                                           int32_t point_mode, const void* d_values, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
+                                           uint64_t* first_bad, void* d_lhs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_each");
+  ST_TRY(verify_each_args(ctx, d_com_aff, com_stride, d_tau_g2_aff, d_points, point_mode, d_values, d_proofs_aff, n, d_status, n_bad));
+  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
+  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
+  uint64_t tau_host[16];
+  ST_TRY(read_constants(ctx, d_tau_g2_aff, nullptr, tau_host, nullptr));          // the key of the line table
+  return verify_each_core(ctx, d_com_aff, com_stride, d_tau_g2_aff, tau_host, d_points, point_mode, d_values, d_proofs_aff, n, d_status, d_lhs_out_aff, n_bad,
+                          first_bad);
+}
+
+keaki_status keaki_hip_kzg_verify_each(keaki_hip_ctx* ctx, const uint64_t* com_aff, int32_t com_stride, const uint64_t* tau_g2_aff, const uint64_t* points,
+                                       int32_t point_mode, const uint64_t* values, const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad,
+                                       uint64_t* first_bad, uint64_t* lhs_out_aff) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_verify_each");
+  ST_TRY(verify_each_args(ctx, com_aff, com_stride, tau_g2_aff, points, point_mode, values, proofs_aff, n, status, n_bad));
+  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
+  // every buffer is reserved before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only
+  const size_t lhs_off = (n + 63) & ~(size_t)63, out_bytes = lhs_off + (lhs_out_aff ? n * G1_AFF_BYTES : 0);
+  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
+  ST_TRY(reserve(ctx, ctx->ve_out, out_bytes));
+  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
+  ST_TRY(reserve(ctx, ctx->io_d, n * 32));
+  if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
+  if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
+  char* io = (char*)ctx->ve_io.p;
+  CopyFeed feed(ctx);             // one upload in front, on the context's stream; a failing call drains it before it returns
+  ST_TRY(feed.put(0, io + VeLayout::O_TAU, tau_g2_aff, 128));
+  if (com_stride) ST_TRY(feed.put(0, ctx->io_e.p, com_aff, n * G1_AFF_BYTES)); else ST_TRY(feed.put(0, io + VeLayout::O_COM, com_aff, 64));
+  if (point_mode) ST_TRY(feed.put(0, io + VeLayout::O_OMEGA, points, 32)); else ST_TRY(feed.put(0, ctx->io_c.p, points, n * 32));
+  ST_TRY(feed.put(0, ctx->io_d.p, values, n * 32));
+  ST_TRY(feed.put(0, ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES));
+  char* out = (char*)ctx->ve_out.p;
+  ST_TRY(verify_each_core(ctx, com_stride ? ctx->io_e.p : (void*)(io + VeLayout::O_COM), com_stride, io + VeLayout::O_TAU, tau_g2_aff,
+                          point_mode ? (void*)(io + VeLayout::O_OMEGA) : ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, n, out,
+                          lhs_out_aff ? out + lhs_off : nullptr, n_bad, first_bad));
+  // the counters are back, so the status bytes are final: one download (status and L lie in one buffer, but go to two arrays of the caller)
+  prefault_out(ctx, lhs_out_aff, lhs_out_aff ? n * G1_AFF_BYTES : 0);
+  if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out + lhs_off, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, status, out, n);
 }
 
 // ---- SRS ingest: on-curve check (row f-3) ------------------------------------------------------------------------

@@ -93,11 +93,12 @@ struct KemState {
   uint32_t gt_b_wb = 0;
   KeyedTable<8> gt_a;
   bool gt_a_pending_aux = false;          // the A-table build on aux.stream has not been waited for by `stream` yet (api.hip: wait_aux)
+  KeyedTable<16> tau_lines;               // kzg verify_each: line sequence of the last [tau]_2 (rebuilt when another one arrives)
   uint64_t seen_com[8] = {};              // commitment of the last encap call and how many consecutive calls carried it
   uint32_t seen_com_runs = 0;
   // every DevBuf above with its memory class (keaki_hip_ctx_memory: 1 = workspace, 2 = GT / fixed-base tables): a new table is added HERE
   template <class F> void for_each_buf(F&& f) {
-    for (DevBuf* b : {&g2gen_lines, &g2pow_lines, &g2pow_pts, &verify_io}) f(b, 1);
+    for (DevBuf* b : {&g2gen_lines, &g2pow_lines, &g2pow_pts, &verify_io, &tau_lines.buf}) f(b, 1);
     for (DevBuf* b : {&fb_g1_gen, &fb_g2_gen, &fb_com, &fb_tau.buf, &fbs_g2_gen, &fbs_tau.buf, &fbs_g1_gen, &gt_a.buf, &gt_tab_b, &gt_base}) f(b, 2);
   }
 };
@@ -164,6 +165,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf fkb_pts, fkb_fr;           // batched FK23 (fk_batch.hip): the 2d x M Jacobian points of a pass, position-major | its scalar rows (96 B per coefficient) and the call's twiddle tables
   keaki_internal::DevBuf em_offsets;                // encap_multi / encrypt_multi, _dev forms: the device copy of the caller's group offsets (8 B per group)
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
+  keaki_internal::DevBuf ve_io, ve_pts, ve_out;     // kzg verify_each: the small in/out block (counters, commitment, [tau]_2, omega) | L and -proof of a launch chunk (128 B per item) | host form: the status bytes and L of the whole call
   // instrumentation
   bool timing = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -300,6 +302,18 @@ keaki_status verify_batch_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, 
 // layout moves around the final sum (no arithmetic): n <= 64 affine points -> normalised Jacobian | the normalised Jacobian sums L, R -> d_out_lr_aff[0], [1] affine
 keaki_status verify_batch_aff_to_jac_run(keaki_hip_ctx* ctx, const void* d_in_aff, uint32_t n, void* d_out_jac);
 keaki_status verify_batch_jac_to_aff_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_r_jac, void* d_out_lr_aff);
+// kzg verify_each (kzg_each.hip, kzg_each_pair.hip). Items [first, first + n) of the caller's arrays (first + n < 2^31):
+// d_lhs_out[i] = C_((first + i) * com_stride) - y g1 + z proof and d_neg_proof_out[i] = -proof, affine, i < n; point_mode 1: z = d_points[0]^(first + i);
+// d_tab_g1: the wb-bit window table of g1
+keaki_status verify_each_g1_run(keaki_hip_ctx* ctx, const void* d_coms, int com_stride, const void* d_tab_g1, uint32_t wb, const void* d_points, int point_mode,
+                                const void* d_values, const void* d_proofs, size_t first, size_t n, void* d_lhs_out, void* d_neg_proof_out);
+// d_status[i] = 0 iff e(p1_i, A) e(p2_i, B) == 1, A and B given by their line tables; ONE launch of n <= ws_items <= pairing_launch_items() items over
+// the final exponentiation's slots at d_ws (pairing_slot_bytes() per item of ws_items). An identity in either slot: 0 iff both are.
+keaki_status pairing2_fixed_run(keaki_hip_ctx* ctx, const void* d_p1, const void* d_p2, size_t n, const void* d_lines_a, const void* d_lines_b, void* d_ws,
+                                size_t ws_items, void* d_status);
+size_t pairing_slot_bytes();
+keaki_status verify_each_tau_inf_run(keaki_hip_ctx* ctx, const void* d_lhs, size_t n, void* d_status);   // [tau]_2 = identity: status = (lhs is not the identity)
+keaki_status verify_each_count_run(keaki_hip_ctx* ctx, const void* d_status, size_t n, void* d_bad2);    // d_bad2: u64 count, u64 first index, added to
 // compressed point wire format (point_codec.hip): one lane per point; n < 2^31. d_bad2: u64 count, u64 first index (over base + i: the host forms run in
 // chunks), added to by every launch; d_status (optional): one byte per item
 keaki_status point_compress_run(keaki_hip_ctx* ctx, bool g2, const void* d_pts, size_t n, void* d_out);

@@ -9,22 +9,11 @@
 #include <algorithm>
 #include "internal.h"
 #include "bn254_curve.hip.h"
+#include "kzg_fr.hip.h"
 
 namespace bn254 {
 
 constexpr u32 VB_THREADS = 256, VB_WAVES = VB_THREADS / 64;
-
-// base^e by square-and-multiply from the low bit (e < 2^32: at most 32 squarings)
-KDEV Fr fr_pow_u32(Fr base, u32 e) {
-  Fr acc = fp_one<FrParams>();
-#pragma unroll 1
-  while (e) {
-    if (e & 1u) acc = fp_mul<FrParams>(acc, base);
-    base = fp_mul<FrParams>(base, base);
-    e >>= 1;
-  }
-  return acc;
-}
 
 // sum over the 64 lanes of a wave by cross-lane moves; every lane ends up with the total
 KDEV Fr fr_wave_sum(Fr a) {

@@ -28,7 +28,7 @@ EXPORTS = [
     "keaki_hip_encrypt_batch", "keaki_hip_encrypt_batch_dev", "keaki_hip_decrypt_batch", "keaki_hip_decrypt_batch_dev",
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
     "keaki_hip_encap_multi", "keaki_hip_encap_multi_dev", "keaki_hip_encrypt_multi", "keaki_hip_encrypt_multi_dev",
-    "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
+    "keaki_hip_selftest_field", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
@@ -141,6 +141,7 @@ def load_library():
         lib.keaki_hip_kzg_verify.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
         lib.keaki_hip_kzg_verify_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_kzg_verify_batch_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_kzg_verify_each.argtypes = lib.keaki_hip_kzg_verify_each_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, sz, vp, vp, vp, vp]
         lib.keaki_hip_final_exp_batch.argtypes = [vp, vp, sz, vp]
         lib.keaki_hip_miller_loop_batch.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_set_timing.argtypes = [vp, i32]
@@ -556,6 +557,30 @@ class KeakiHip:
         self._ck(self.lib.keaki_hip_kzg_verify_batch_dev(self.ctx, dp(d_com), int(com_stride), dp(d_tau_g2), dp(d_points), int(point_mode), dp(d_values),
                                                          dp(d_proofs), dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
         return bool(ok.value), sums[:8].copy(), sums[8:].copy()
+
+    def kzg_verify_each(self, com_aff, tau_g2_aff, points, values, proofs_aff, point_mode: int = 0, want_lhs: bool = False):
+        """one verdict per opening (keaki_hip_kzg_verify_each) -> (status uint8[n]: 0 valid / 1 invalid, n_bad, first_bad or None), and with
+        want_lhs a fourth element: the L_i = C_i - y_i g1 + z_i proof_i (u64[n, 8]). Arguments as kzg_verify_batch, without gammas"""
+        v = _np(values, 4); n = v.shape[0]
+        pr, c, z = _np(proofs_aff, 8), _np(com_aff, 8), _np(points, 4)
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if pr.shape[0] != n or (com_stride and c.shape[0] != n) or z.shape[0] != (1 if point_mode else n):
+            raise ValueError("kzg_verify_each: array lengths disagree")
+        status = np.zeros(n, np.uint8); lhs = np.zeros((n, 8), np.uint64) if want_lhs else None
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_kzg_verify_each(self.ctx, _ptr(c), com_stride, _ptr(_np(tau_g2_aff)), _ptr(z), int(point_mode), _ptr(v), _ptr(pr), n,
+                                                    _ptr(status), C.byref(bad), C.byref(first), _ptr(lhs) if want_lhs else None))
+        res = (status, bad.value, (None if bad.value == 0 else first.value))
+        return res + (lhs,) if want_lhs else res
+
+    def kzg_verify_each_dev(self, d_com, com_stride: int, d_tau_g2, d_points, point_mode: int, d_values, d_proofs, n: int, d_status, d_lhs=None):
+        """the same with every array resident: device pointers (ints) or torch tensors; the status bytes (and the L_i) stay on the device ->
+        (n_bad, first_bad or None) on the host (the call synchronises)"""
+        dp = lambda x: C.c_void_p(None if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else x))
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_kzg_verify_each_dev(self.ctx, dp(d_com), int(com_stride), dp(d_tau_g2), dp(d_points), int(point_mode), dp(d_values),
+                                                        dp(d_proofs), int(n), dp(d_status), C.byref(bad), C.byref(first), dp(d_lhs)))
+        return bad.value, (None if bad.value == 0 else first.value)
 
     def srs_g1_check(self, srs: "SrsG1"):
         """-> (number of off-curve points, index of the first or None)"""

@@ -343,6 +343,42 @@ Result<bool> verify_batch(Rng& rng, const KZGSetup& setup, const std::vector<G1>
                                             n ? proofs[0].w.data() : nullptr, n));
 }
 
+size_t verify_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values, const uint64_t* proofs,
+                        size_t n, uint8_t* status_out) {
+  if (n_coms != 1 && n_coms != n) throw std::invalid_argument("verify_each: one commitment, or one per item");
+  if (n == 0) return 0;
+  const Device& dev = *setup.device();
+  uint64_t bad = 0;
+  dev.check(keaki_hip_kzg_verify_each(dev.ctx(), coms, n_coms == 1 ? 0 : 1, setup.tau_g2().w.data(), points[0].l, roots_of_unity ? 1 : 0, values[0].l, proofs, n,
+                                      status_out, &bad, nullptr, nullptr));
+  return (size_t)bad;
+}
+Result<std::vector<uint8_t>> verify_each(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& points, const std::vector<Fr>& values,
+                                         const std::vector<G1>& proofs) {
+  const size_t n = values.size();
+  if (points.size() != n || proofs.size() != n || (commitments.size() != 1 && commitments.size() != n))
+    throw std::invalid_argument("verify_each: points, values and proofs must have one entry per item, commitments one or n");
+  std::vector<uint8_t> status(n);
+  verify_each_flat(setup, commitments.empty() ? nullptr : commitments[0].w.data(), commitments.size(), points.data(), false, values.data(), n ? proofs[0].w.data() : nullptr, n, status.data());
+  return Result<std::vector<uint8_t>>::Ok(std::move(status));
+}
+std::vector<size_t> locate_invalid_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values,
+                                        const uint64_t* proofs, size_t n) {
+  std::vector<size_t> out;
+  if (verify_batch_flat(rng, setup, coms, n_coms, points, roots_of_unity, values, proofs, n)) return out;
+  std::vector<uint8_t> status(n);
+  out.reserve(verify_each_flat(setup, coms, n_coms, points, roots_of_unity, values, proofs, n, status.data()));
+  for (size_t i = 0; i < n; i++) if (status[i]) out.push_back(i);
+  return out;
+}
+std::vector<size_t> locate_invalid(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& points, const std::vector<Fr>& values,
+                                   const std::vector<G1>& proofs) {
+  const size_t n = values.size();
+  if (points.size() != n || proofs.size() != n || (commitments.size() != 1 && commitments.size() != n))
+    throw std::invalid_argument("locate_invalid: points, values and proofs must have one entry per item, commitments one or n");
+  return locate_invalid_flat(rng, setup, commitments.empty() ? nullptr : commitments[0].w.data(), commitments.size(), points.data(), false, values.data(), n ? proofs[0].w.data() : nullptr, n);
+}
+
 namespace {
 const char* wire_reason(int r) {
   return r == 1 ? "malformed encoding (flags, or a coordinate >= p)" : r == 2 ? "no point of the curve has this x" : r == 3 ? "outside the order-r subgroup" : "rejected";
@@ -667,6 +703,16 @@ std::vector<std::pair<G1, std::vector<G1>>> vec_commit_batch(Rng& rng, const kzg
 bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs) {
   const Radix2Domain domain = Radix2Domain::create(n + PADDING_LEN);      // the domain vec_commit interpolated over (src/vec.rs:36)
   return kzg::verify_batch_flat(rng, setup, com.w.data(), 1, &domain.group_gen, true, v, proofs, n);
+}
+size_t vec_verify_each_flat(const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs, uint8_t* status_out) {
+  const Radix2Domain domain = Radix2Domain::create(n + PADDING_LEN);
+  return kzg::verify_each_flat(setup, com.w.data(), 1, &domain.group_gen, true, v, proofs, n, status_out);
+}
+std::vector<uint8_t> vec_verify_each(const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs) {
+  if (proofs.size() < v.size()) throw std::invalid_argument("vec_verify_each: fewer proofs than values");
+  std::vector<uint8_t> status(v.size());
+  vec_verify_each_flat(setup, com, v.data(), v.size(), v.empty() ? nullptr : proofs[0].w.data(), status.data());
+  return status;
 }
 bool vec_verify(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs) {
   if (proofs.size() < v.size()) throw std::invalid_argument("vec_verify: fewer proofs than values");

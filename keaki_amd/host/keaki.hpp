@@ -181,6 +181,21 @@ Result<bool> verify_batch(Rng& rng, const KZGSetup& setup, const std::vector<G1>
 // the same on contiguous buffers. n_coms: 1 or n. roots_of_unity: `points` is ONE Fr omega and item i is opened at omega^i.
 bool verify_batch_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values,
                        const uint64_t* proofs, size_t n);
+// One verdict per opening (no counterpart in the reference): out[i] = 0 iff e(C_i - y_i g1 + z_i proof_i, g2) e(-proof_i, [tau]_2) == 1, the
+// predicate of :135-148 with z_i proof_i moved across the pairing, in ONE device call (keaki_hip_kzg_verify_each: both G2 arguments are fixed,
+// so both line sequences are tables, and the two Miller loops share one final exponentiation). Exact: no draws, no error probability; the
+// verdict equals `verify` on the item. commitments: one (shared) or one per item. On a group device: member 0.
+Result<std::vector<uint8_t>> verify_each(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& points, const std::vector<Fr>& values,
+                                         const std::vector<G1>& proofs);
+// the same on contiguous buffers (arguments as verify_batch_flat); status_out: n bytes. Returns the number of invalid items.
+size_t verify_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values, const uint64_t* proofs,
+                        size_t n, uint8_t* status_out);
+// Which openings are invalid? verify_batch first -- it draws from `rng` exactly what verify_batch draws -- and verify_each only if that rejects:
+// the indices of the invalid items in ascending order, empty for a clean batch.
+std::vector<size_t> locate_invalid(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& points, const std::vector<Fr>& values,
+                                   const std::vector<G1>& proofs);
+std::vector<size_t> locate_invalid_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* points, bool roots_of_unity, const Fr* values,
+                                        const uint64_t* proofs, size_t n);
 // Proofs (any G1 points) on the wire: n x 32 B, `serialize_compressed`. `proofs_from_bytes` validates (canonical, on the curve; G1 has cofactor 1)
 // and throws WireError naming the first bad index.
 std::vector<uint8_t> proofs_to_bytes(const KZGSetup& setup, const std::vector<G1>& proofs);
@@ -249,6 +264,9 @@ std::pair<DensePolynomial, std::vector<G1>> vec_commit_openings(Rng& rng, const 
 // One kzg::verify_batch over the powers of the domain's generator (they are derived on the device): n draws from `rng`, one device call.
 bool vec_verify(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs);
 bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs);
+// kzg::verify_each over the same items: out[i] = 0 iff proof i opens `com` to v[i] at omega^i. No draws.
+std::vector<uint8_t> vec_verify_each(const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs);
+size_t vec_verify_each_flat(const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs, uint8_t* status_out);
 // src/vec.rs:52-69: one Fr::rand per item in index order, then ONE batched GPU call for all items
 std::vector<enc::Ciphertext> vec_encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points,
                                          const std::vector<Fr>& values, const std::vector<std::vector<uint8_t>>& messages);

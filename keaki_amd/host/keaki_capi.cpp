@@ -264,6 +264,32 @@ int keaki_host_verify_batch(void* rng, void* s, const uint64_t* coms, size_t n_c
     return 0;
   });
 }
+// one verdict per item: status_out[i] = 0 valid / 1 invalid, *out_bad = the number of ones
+int keaki_host_verify_each(void* s, const uint64_t* coms, size_t n_coms, const uint64_t* points, int point_mode, const uint64_t* values, const uint64_t* proofs,
+                           size_t n, uint8_t* status_out, uint64_t* out_bad) {
+  return guard([&] {
+    *out_bad = kzg::verify_each_flat(((Setup*)s)->s, coms, n_coms, reinterpret_cast<const Fr*>(points), point_mode != 0, reinterpret_cast<const Fr*>(values), proofs,
+                                     n, status_out);
+    return 0;
+  });
+}
+// verify_batch, then verify_each if it rejects: idx_out (room for n) receives the invalid indices, *out_count how many
+int keaki_host_locate_invalid(void* rng, void* s, const uint64_t* coms, size_t n_coms, const uint64_t* points, int point_mode, const uint64_t* values,
+                              const uint64_t* proofs, size_t n, uint64_t* idx_out, uint64_t* out_count) {
+  return guard([&] {
+    const std::vector<size_t> bad = kzg::locate_invalid_flat(*(Rng*)rng, ((Setup*)s)->s, coms, n_coms, reinterpret_cast<const Fr*>(points), point_mode != 0,
+                                                             reinterpret_cast<const Fr*>(values), proofs, n);
+    for (size_t i = 0; i < bad.size(); i++) idx_out[i] = bad[i];
+    *out_count = bad.size();
+    return 0;
+  });
+}
+int keaki_host_vec_verify_each(void* s, const uint64_t* com, const uint64_t* v, size_t n, const uint64_t* proofs, uint8_t* status_out, uint64_t* out_bad) {
+  return guard([&] {
+    *out_bad = vec::vec_verify_each_flat(((Setup*)s)->s, g1_of(com), reinterpret_cast<const Fr*>(v), n, proofs, status_out);
+    return 0;
+  });
+}
 int keaki_host_vec_verify(void* rng, void* s, const uint64_t* com, const uint64_t* v, size_t n, const uint64_t* proofs, int* out_ok) {
   return guard([&] {
     *out_ok = vec::vec_verify_flat(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), reinterpret_cast<const Fr*>(v), n, proofs) ? 1 : 0;

@@ -365,17 +365,54 @@ def verify(setup: KZGSetup, commitment, point, value, proof) -> bool:
     return bool(ok.value)
 
 
-def verify_batch(rng: "Rng", setup: "KZGSetup", commitments, points, values, proofs, roots_of_unity: bool = False) -> bool:
-    """kzg::verify_batch: n openings in one device call. One gamma per item is drawn from `rng` in index order. commitments: one G1 (shared) or n;
-    points: n Fr -- or, with roots_of_unity, the ONE Fr omega (item i is opened at omega^i)."""
+def _opening_args(what, commitments, points, values, proofs, roots_of_unity):
+    """n openings as contiguous arrays: commitments (1 or n), points (n, or the ONE omega with roots_of_unity), values, the first n proofs"""
     vals = np.ascontiguousarray(_u64(values, 4)); n = vals.shape[0]
     coms = np.ascontiguousarray(_u64(commitments, 8)); pts = np.ascontiguousarray(_u64(points, 4)); pr = np.ascontiguousarray(_u64(proofs, 8)[:n])
     if coms.shape[0] not in (1, n) or pts.shape[0] != (1 if roots_of_unity else n) or pr.shape[0] != n:
-        raise ValueError("verify_batch: array lengths disagree")
+        raise ValueError("%s: array lengths disagree" % what)
+    return coms, pts, vals, pr, n
+
+
+def verify_batch(rng: "Rng", setup: "KZGSetup", commitments, points, values, proofs, roots_of_unity: bool = False) -> bool:
+    """kzg::verify_batch: n openings in one device call. One gamma per item is drawn from `rng` in index order. commitments: one G1 (shared) or n;
+    points: n Fr -- or, with roots_of_unity, the ONE Fr omega (item i is opened at omega^i)."""
+    coms, pts, vals, pr, n = _opening_args("verify_batch", commitments, points, values, proofs, roots_of_unity)
     ok = C.c_int(0)
     _ck(_lib().keaki_host_verify_batch(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(pts), C.c_int(1 if roots_of_unity else 0), _p(vals), _p(pr),
                                        C.c_size_t(n), C.byref(ok)))
     return bool(ok.value)
+
+
+def verify_each(setup: "KZGSetup", commitments, points, values, proofs, roots_of_unity: bool = False) -> np.ndarray:
+    """kzg::verify_each: one verdict per opening in one device call -> uint8[n], 0 = valid, 1 = invalid. Exact: nothing is drawn. Arguments as
+    verify_batch."""
+    coms, pts, vals, pr, n = _opening_args("verify_each", commitments, points, values, proofs, roots_of_unity)
+    status = np.zeros(n, np.uint8); bad = C.c_uint64(0)
+    _ck(_lib().keaki_host_verify_each(setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(pts), C.c_int(1 if roots_of_unity else 0), _p(vals), _p(pr), C.c_size_t(n),
+                                      _p(status), C.byref(bad)))
+    return status
+
+
+def locate_invalid(rng: "Rng", setup: "KZGSetup", commitments, points, values, proofs, roots_of_unity: bool = False) -> list:
+    """kzg::locate_invalid: verify_batch (drawing from `rng` what verify_batch draws), and verify_each only if it rejects -> the indices of the
+    invalid items, [] for a clean batch"""
+    coms, pts, vals, pr, n = _opening_args("locate_invalid", commitments, points, values, proofs, roots_of_unity)
+    idx = np.zeros(max(n, 1), np.uint64); count = C.c_uint64(0)
+    _ck(_lib().keaki_host_locate_invalid(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(pts), C.c_int(1 if roots_of_unity else 0), _p(vals), _p(pr),
+                                         C.c_size_t(n), _p(idx), C.byref(count)))
+    return [int(i) for i in idx[:count.value]]
+
+
+def vec_verify_each(setup: "KZGSetup", com, v, proofs) -> np.ndarray:
+    """vec::vec_verify_each: uint8[len(v)], 0 where proof i opens `com` to v[i] over the domain of len(v) + PADDING_LEN evaluations"""
+    vals = np.ascontiguousarray(_u64(v, 4)); n = vals.shape[0]
+    pr = np.ascontiguousarray(_u64(proofs, 8)[:n])
+    if pr.shape[0] != n:
+        raise ValueError("vec_verify_each: fewer proofs than values")
+    status = np.zeros(n, np.uint8); bad = C.c_uint64(0)
+    _ck(_lib().keaki_host_vec_verify_each(setup.h, _p(_u64(com)), _p(vals), C.c_size_t(n), _p(pr), _p(status), C.byref(bad)))
+    return status
 
 
 def vec_verify(rng: "Rng", setup: "KZGSetup", com, v, proofs) -> bool:

@@ -144,6 +144,13 @@ extern "C" {
     pub fn keaki_hip_kzg_verify_batch_dev(ctx: *mut keaki_hip_ctx, d_com_aff: *const c_void, com_stride: i32, d_tau_g2_aff: *const c_void,
                                           d_points: *const c_void, point_mode: i32, d_values: *const c_void, d_proofs_aff: *const c_void,
                                           d_gammas: *const c_void, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
+    // one verdict per opening: status[i] = 0 <=> e(C_i - y_i g1 + z_i proof_i, g2) e(-proof_i, [tau]_2) == 1; lhs_out_aff: n x u64[8] or null
+    pub fn keaki_hip_kzg_verify_each(ctx: *mut keaki_hip_ctx, com_aff: *const u64, com_stride: i32, tau_g2_aff: *const u64, points: *const u64,
+                                     point_mode: i32, values: *const u64, proofs_aff: *const u64, n: usize, status: *mut u8, n_bad: *mut u64,
+                                     first_bad: *mut u64, lhs_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_each_dev(ctx: *mut keaki_hip_ctx, d_com_aff: *const c_void, com_stride: i32, d_tau_g2_aff: *const c_void,
+                                         d_points: *const c_void, point_mode: i32, d_values: *const c_void, d_proofs_aff: *const c_void, n: usize,
+                                         d_status: *mut c_void, n_bad: *mut u64, first_bad: *mut u64, d_lhs_out_aff: *mut c_void) -> keaki_status;
 
     // ---- SRS ingest checks (src/kzg/ptau.rs:266,314 read unchecked)
     pub fn keaki_hip_srs_g1_check(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, n_off_curve: *mut u64, first_off_curve: *mut u64) -> keaki_status;

@@ -434,6 +434,27 @@ pub fn verify_batch(commitments: &[G1Projective], tau_g2: &G2Projective, points:
     ok != 0
 }
 
+/// One verdict per opening (`keaki_hip_kzg_verify_each`): item i is valid iff `e(C_i - y_i g1 + z_i proof_i, g2) * e(-proof_i, [tau]_2) == 1`,
+/// the predicate of `verify` with `z_i proof_i` moved across the pairing. Arguments as [`verify_batch`], without gammas: the verdict is exact.
+/// Returns `true` for every valid item.
+pub fn verify_each(commitments: &[G1Projective], tau_g2: &G2Projective, points: &[Fr], roots_of_unity: bool, values: &[Fr], proofs: &[G1Projective]) -> Vec<bool> {
+    let dev = Device::global();
+    let n = values.len();
+    assert!(proofs.len() == n && (commitments.len() == 1 || commitments.len() == n));
+    assert!(points.len() == if roots_of_unity { 1 } else { n });
+    let flat = |v: &[G1Projective]| -> Vec<u64> { G1Projective::normalize_batch(v).iter().flat_map(|p| g1_words(p)).collect() };
+    let (c, p, t) = (flat(commitments), flat(proofs), g2_words(&tau_g2.into_affine()));
+    let mut status = vec![0u8; n];
+    let mut n_bad = 0u64;
+    dev.check(
+        unsafe {
+            sys::keaki_hip_kzg_verify_each(dev.ctx, c.as_ptr(), if commitments.len() == 1 { 0 } else { 1 }, t.as_ptr(), fr_ptr(points), if roots_of_unity { 1 } else { 0 }, fr_ptr(values), p.as_ptr(), n, status.as_mut_ptr(), &mut n_bad, core::ptr::null_mut(), core::ptr::null_mut())
+        },
+        "kzg_verify_each",
+    );
+    status.iter().map(|&s| s == 0).collect()
+}
+
 /// `serialize_compressed` of n G2 points on the device (`keaki_hip_g2_compress`): n x 64 bytes, what a `Ciphertext`'s point costs on the wire.
 pub fn g2_compress(points: &[G2Projective]) -> Vec<u8> {
     let dev = Device::global();
