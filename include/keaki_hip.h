@@ -605,6 +605,91 @@ keaki_status keaki_hip_final_exp_batch(keaki_hip_ctx* ctx, const uint64_t* f_mon
  * inputs; *mismatches_out must come back 0. */
 keaki_status keaki_hip_selftest_field(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, uint64_t* mismatches_out);
 
+/* Field probe: ONE shipped field function on operands the HOST chose, raw result limbs back (tests/test_gpu_field_ops.py compares them
+ * with Python integers, exactly). Record layout:
+ *   operands: n records of 12 slots x 9 uint32_t. A lazy operand (9 x 29-bit limbs, any u32 per limb) fills its slot; a saturated operand
+ *             (8 x 32-bit words) uses words 0..7 of its slot. Operand k of an op is slot k; unused slots are ignored.
+ *   out:      n records of 9 uint32_t: the raw result. Saturated results use words 0..7, predicates word 0 (0 / 1); the rest is 0.
+ * One record per lane, 64 lanes per workgroup. The lane-pair ops (KEAKI_FOP_FQ2_MUL and above) take records 2r and 2r + 1 as the c0 and c1
+ * lanes of one Fq2 element: n must be even (the library pads the launch to whole waves with copies of record 0; only the first n records
+ * are stored). 1 <= n <= 65536; an unknown op, n out of range, an odd n of a lane-pair op or a null pointer is KEAKI_ERR_BAD_ARG and
+ * launches nothing. KEAKI_FOP_FQ_INV_XGCD answers a non-canonical operand (>= p) with all-ones words instead of running (its loop would
+ * not end). Operand bounds are the callee's own (fq29_core.hip.h, fq29_asm.hip.h, pair261.hip.h); the probe does not check them. */
+#define KEAKI_FOP_FIRST_PAIR KEAKI_FOP_FQ2_MUL
+#define KEAKI_FOP_SLOTS 12
+#define KEAKI_FOP_SLOT_WORDS 9
+#define KEAKI_FOP_MAX_RECORDS 65536
+typedef enum {
+  /* 9 x 29-bit lazy streams (fq29_core.hip.h, fq29_asm.hip.h, fq29_dot_asm.hip.h) */
+  KEAKI_FOP_U29_MUL = 0,             /* u29_mul(s0, s1): s0 is the wide side */
+  KEAKI_FOP_U29_MUL_REF = 1,
+  KEAKI_FOP_U29_SQR = 2,
+  KEAKI_FOP_U29_SQR_REF = 3,
+  KEAKI_FOP_U29_MUL2 = 4,            /* u29_mul2(s0, s1, s2, s3) = s0 s1 + s2 s3 */
+  KEAKI_FOP_U29_DOT3 = 5,            /* sum of s(2k) s(2k+1), k < 3 */
+  KEAKI_FOP_U29_DOT4 = 6,
+  KEAKI_FOP_U29_DOT6 = 7,
+  KEAKI_FOP_U29_CARRY = 8,
+  KEAKI_FOP_U29_SUB_K2 = 9,          /* u29_sub(s0, s1, Q29::K2) ... */
+  KEAKI_FOP_U29_SUB_K4 = 10,
+  KEAKI_FOP_U29_SUB_K4W = 11,
+  KEAKI_FOP_U29_SUB_K8 = 12,
+  KEAKI_FOP_U29_SUB_K16 = 13,
+  KEAKI_FOP_U29_SUB_K16W = 14,
+  KEAKI_FOP_U29_SUB_K32 = 15,
+  KEAKI_FOP_U29_SUB_K64 = 16,
+  KEAKI_FOP_U29_SUB_K128 = 17,
+  KEAKI_FOP_U29_SUB_RAW_K16 = 18,    /* u29_sub_raw(s0, s1, K) */
+  KEAKI_FOP_U29_SUB_RAW_K32 = 19,
+  KEAKI_FOP_U29_SUB3 = 20,           /* u29_sub3(s0, s1, s2) */
+  KEAKI_FOP_U29_MAYBE_ZERO = 21,
+  KEAKI_FOP_U29_MAYBE_ZERO34 = 22,
+  KEAKI_FOP_U29_IS_ZERO = 23,
+  KEAKI_FOP_U29_PACK_CANONICAL = 24, /* limbs -> 8 words */
+  KEAKI_FOP_U29_FROM_SAT_SHIFT5 = 25,/* 8 words -> limbs */
+  KEAKI_FOP_U29_FROM_SAT_PLAIN = 26,
+  KEAKI_FOP_U29_FROM_FQ = 27,
+  KEAKI_FOP_U29_TO_FQ = 28,
+  KEAKI_FOP_U29_TO_SAT = 29,
+  /* saturated 8 x 32 streams (bn254_field.hip.h, bn254_field_asm.hip.h), Montgomery radix 2^256 */
+  KEAKI_FOP_FQ_MUL = 30,
+  KEAKI_FOP_FQ_SQR = 31,
+  KEAKI_FOP_FQ_ADD = 32,
+  KEAKI_FOP_FQ_SUB = 33,
+  KEAKI_FOP_FQ_NEG = 34,
+  KEAKI_FOP_FQ_DBL = 35,
+  KEAKI_FOP_FQ_HALF = 36,
+  KEAKI_FOP_FQ_REDUCE_ONCE = 37,     /* fp_reduce_once<FqParamsRef> */
+  KEAKI_FOP_FQ_INV_XGCD = 38,
+  KEAKI_FOP_FQ_INV_SAFEGCD = 39,
+  KEAKI_FOP_FQ_INV_FERMAT = 40,
+  KEAKI_FOP_FQ_INV = 41,             /* fq_inv: the inverse the kernels call */
+  KEAKI_FOP_FR_FROM_MONT = 42,       /* fp_from_mont<FrParams> */
+  KEAKI_FOP_FR_MUL = 43,
+  KEAKI_FOP_FR_ADD = 44,
+  KEAKI_FOP_FR_SUB = 45,
+  /* 2^261 form of the pairing tower (pair261.hip.h), one lane per record */
+  KEAKI_FOP_TO261 = 46,
+  KEAKI_FOP_TO256 = 47,
+  KEAKI_FOP_CANON_WORDS = 48,
+  KEAKI_FOP_FQ_INV261 = 49,
+  /* lane-pair ops: every op from here on */
+  KEAKI_FOP_FQ2_MUL = 50,
+  KEAKI_FOP_FQ2_SQR = 51,
+  KEAKI_FOP_FQ2_MUL_XI = 52,
+  KEAKI_FOP_FQ2_MUL_FQ = 53,         /* s1: this lane's Fq factor */
+  KEAKI_FOP_FQ2_INV = 54,
+  KEAKI_FOP_FQ2_CONJ = 55,
+  KEAKI_FOP_FQ2_NEG = 56,
+  KEAKI_FOP_FQ4_SQR_T0 = 57,         /* fq4_sqr(&t0, &t1, s0, s1) */
+  KEAKI_FOP_FQ4_SQR_T1 = 58,
+  KEAKI_FOP_FQ6_MUL_C0 = 59,         /* fq6_mul of (s0, s1, s2) by (s3, s4, s5) */
+  KEAKI_FOP_FQ6_MUL_C1 = 60,
+  KEAKI_FOP_FQ6_MUL_C2 = 61,
+  KEAKI_FOP_COUNT = 62
+} keaki_field_op;
+keaki_status keaki_hip_selftest_field_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

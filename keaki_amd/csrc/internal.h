@@ -344,5 +344,10 @@ keaki_status fkb_pass_run(keaki_hip_ctx* ctx, const void* d_hat_s, uint32_t log2
                           const uint64_t* inv_d_or_null, const uint64_t* inv_2d, void* d_proofs, const void** d_coeffs_out);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
+// field probe (field_probe.hip): op `op` of keaki_field_op on n records at d_operands (field_probe_padded(op, n) records: lane-pair ops run whole
+// waves), raw results to d_out (n records). Checks op and n itself (KEAKI_ERR_BAD_ARG, nothing launched).
+bool field_probe_is_pair(uint32_t op);
+size_t field_probe_padded(uint32_t op, size_t n);
+keaki_status field_probe_run(keaki_hip_ctx* ctx, uint32_t op, const void* d_operands, size_t n, void* d_out);
 
 }  // namespace keaki_internal
