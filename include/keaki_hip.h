@@ -104,7 +104,8 @@ const char* keaki_hip_version(void);
  * fused route with a pairing per item; 0 = never the single path; default 16,384, measured -- see keaki_hip_encap_multi),
  * "pair_wide_max" (pairing batches up to this size run the twelve-lanes-per-pairing kernel; -1 = automatic (4096), 0 = never), "pair_two_waves"
  * (up to 1,024 pairings: the line side of the Miller loop on a second wave; 0 = one wave), "msm_short_tables" (an MSM over less than half of an SRS
- * with window tables: 0 = the generic path as before round 4, 1 / -1 = the tables).
+ * with window tables: 0 = the generic path as before round 4, 1 / -1 = the tables), "vec_update_k_pass" (entries of the change list per pass of
+ * keaki_hip_vec_update's proof kernel: 1 .. 8, 0 = the built-in 8; any other value is refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
  * What the library does with HOST memory of the caller, and its off switches (round 5):
  *   "host_prefault" (default 1): while the kernels of a host-array call run, the library first-touches the caller's OUTPUT arrays (writes a zero
  *       into one byte per 4 KB page, the whole range being overwritten by the download that follows; outputs >= 1 MB only) and asks for transparent
@@ -127,7 +128,7 @@ keaki_status keaki_hip_ctx_set_option(keaki_hip_ctx* ctx, const char* name, int6
 /* Test hook: every single device allocation of this ctx above `bytes` fails with KEAKI_ERR_OOM (0 = no limit). This is how the tests
  * exercise the optional-memory fallbacks (SRS window tables, the wide GT table); nothing in the library sets it. */
 keaki_status keaki_hip_debug_set_alloc_limit(keaki_hip_ctx* ctx, size_t bytes);
-/* Device memory this ctx holds right now, bytes: out4[0] = window tables + FK23 transforms of SRS handles built through this ctx (the
+/* Device memory this ctx holds right now, bytes: out4[0] = window tables + FK23 transforms + vec_update tables of SRS handles built through this ctx (the
  * points themselves belong to the caller's upload), [1] = grow-only workspaces, [2] = fixed-base / GT tables of encapsulate, [3] = total. */
 keaki_status keaki_hip_ctx_memory(keaki_hip_ctx* ctx, size_t* out4);
 /* Gives back every workspace and every fixed-base / GT table of the context (out4[1] and out4[2] drop to 0): for a long-lived process after
@@ -227,6 +228,45 @@ keaki_status keaki_hip_fr_fft(keaki_hip_ctx* ctx, uint64_t* data, uint32_t log2n
 keaki_status keaki_hip_vec_commit(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const uint64_t* values, size_t n, const uint64_t* pad, uint32_t log2d,
                                   const uint64_t* omega_d_inv, const uint64_t* inv_d, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
                                   const uint64_t* inv_2d, uint64_t* com_out_jac, uint64_t* proofs_out_aff);
+
+/* ---- vec_update: change k evaluations of a committed vector, the commitment and all d proofs follow ---------------------------------------------
+ * The holder of (com, proofs) of keaki_hip_vec_commit changes evaluation idx[t] by deltas[t] (t < k) WITHOUT the vector: afterwards com and
+ * proofs are byte for byte what keaki_hip_vec_commit returns for the changed vector (proofs are affine, the commitment a normalised Jacobian:
+ * both forms are unique). With w = omega_d, c_i = w^i / d and two tables of d G1 points that depend on (srs, d) only,
+ *   a_i = w^-i sum_k w^(-ik) srs[k] = [(tau^d - 1) / (tau - w^i)]_1,   u_i = (w^-i / d) sum_k (d-1-k) w^(-ik) srs[k] = [(L_i(tau) - 1) / (tau - w^i)]_1,
+ *   com'  = com  + sum_t (delta_t c_(i_t)) a_(i_t)
+ *   pi_j' = pi_j + sum_{t: i_t != j} s_tj (a_(i_t) - a_j) + sum_{t: i_t = j} delta_t u_j,   s_tj = delta_t c_(i_t) / (w^(i_t) - w^j)
+ * (identities in tau: any SRS, tau = 0 and tau on the domain included): (k + 1) d scalar multiples instead of the d (log2 d + 3) of FK23.
+ *   indices    address the evaluations over the whole domain (the padding slot of vec_commit is an ordinary index); duplicates add; delta = 0
+ *              is an ordinary entry. k = 0, or both outputs NULL, writes nothing and returns KEAKI_OK. Either output may be NULL.
+ *   routes     the list runs in passes of 8 entries (option "vec_update_k_pass": 1 .. 8, 0 = 8): one kernel per pass, one lane per proof,
+ *              every pass a complete update of its own entries. The commitment is k scalar multiples and a sum.
+ *   tables     192 B x d (a, u, w^-i, 1 / (w^t - 1)), built on first use or by keaki_hip_srs_g1_precompute_update, cached in the SRS handle for ONE d
+ *              (another d replaces them) beside the FK23 transform, which they never evict; built under the handle's lock, counted in
+ *              keaki_hip_ctx_memory out4[0], freed with the handle.
+ *   errors     a null required pointer, an index >= d, log2d > 27, k >= 2^31 -> KEAKI_ERR_BAD_ARG; d > len(srs) -> KEAKI_ERR_TOO_LARGE; tables (or
+ *              workspace) the device or keaki_hip_debug_set_alloc_limit refuses -> KEAKI_ERR_OOM. Nothing is written in any of these cases and
+ *              the context stays usable.
+ *   host form  one upload (indices, deltas, com, proofs), the kernels, one download; returns only when nothing reads or writes caller memory.
+ *   _dev       idx (u32), deltas, com, proofs are device pointers (16-byte aligned; idx 4-byte), the domain constants stay host pointers;
+ *              asynchronous on the ctx stream. The indices cannot be checked without a round trip: an entry with an index >= d does nothing.
+ *   numbers    (MI355X, medians, one process, alternating rounds: profiles/vec_update_times.txt, bench_tools/bench_vec_update.py) against
+ *              keaki_hip_vec_commit at the same d on a handle with window tables, resident / from host arrays:
+ *                d = 2^12: commit 19 ms;  update k = 1: 3.1 / 3.2 ms, k = 4: 4.2 / 4.3, k = 16: 10 / 10, k = 64: 38 / 38, k = 256: 147 / 147
+ *                d = 2^16: commit 31 ms;  update k = 1: 3.3 / 3.5 ms, k = 4: 4.4 / 4.6, k = 16: 11 / 11, k = 64: 39 / 39, k = 256: 150 / 150
+ *                d = 2^20: commit 238 ms (207 resident);  update k = 1: 23 / 26 ms, k = 4: 36 / 39, k = 16: 102 / 105, k = 64: 401 / 405, k = 256: 1,598 / 1,601
+ *              so one changed entry costs a ninth of a fresh commitment at 2^16 and 2^20 (a sixth at 2^12). A pass of 8 entries costs about 5 ms up
+ *              to d = 2^16 (one chain per lane: latency) and 50 ms at 2^20. Crossover, where the update stops winning and the caller should call
+ *              keaki_hip_vec_commit instead: k = 16 still wins and k = 64 loses at every measured d; by the pass cost the break-even lies near
+ *              k = 32 at 2^12 and 2^20 and near k = 48 at 2^16 (not measured between 16 and 64). Table build: 35 / 30 / 198 ms, 0.75 / 12 / 192 MB. */
+keaki_status keaki_hip_srs_g1_precompute_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
+                                                const uint64_t* inv_d);     /* setup-time, optional: vec_update builds the tables on first use anyway */
+keaki_status keaki_hip_vec_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
+                                  const uint64_t* inv_d, const uint32_t* idx, const uint64_t* deltas, size_t k, uint64_t* com_inout_jac,
+                                  uint64_t* proofs_inout_aff);
+keaki_status keaki_hip_vec_update_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
+                                      const uint64_t* inv_d, const void* d_idx, const void* d_deltas, size_t k, void* d_com_inout_jac,
+                                      void* d_proofs_inout_aff);
 
 /* ---- KZG `open` in one call (scope row f-4) -------------------------------------------------------------------------
  * Replaces the body of `open` (reference src/kzg.rs:104-124): value = p(point) and proof = commit(q), q = (p - p(point)) / (x - point),

@@ -32,7 +32,10 @@ struct SrsHandle {
 // FK23: hat_s = DFT_2d(reversed SRS) for the last requested d (2d Jacobian points), reused by later FK23 calls on the handle. Owned by
 // fk_cache_ensure: log2d names a transform only when its build was enqueued in full, bytes is what hat_s holds (and `acct` counts).
 struct FkCache { void* hat_s = nullptr; int log2d = -1; size_t bytes = 0; };
-struct keaki_hip_srs_g1 : SrsHandle { FkCache fk; };
+// vec_update: the update tables of the last requested d (vec_update.hip: a | u | omega_d^-i | 1 / (omega_d^t - 1)), beside the FK23 transform and
+// independent of it. Owned by upd_cache_ensure under the same rules as FkCache.
+struct UpdCache { void* tab = nullptr; int log2d = -1; size_t bytes = 0; };
+struct keaki_hip_srs_g1 : SrsHandle { FkCache fk; UpdCache upd; };
 struct keaki_hip_srs_g2 : SrsHandle {};
 
 #include <dlfcn.h>
@@ -491,7 +494,8 @@ void srs_free(keaki_hip_ctx* ctx, H* srs) {
   size_t held = srs->table_bytes;          // booked on the context that built them, whichever context (or NULL) frees the handle
   if constexpr (std::is_same_v<H, keaki_hip_srs_g1>) {
     if (srs->fk.hat_s) (void)hipFree(srs->fk.hat_s);
-    held += srs->fk.bytes;
+    if (srs->upd.tab) (void)hipFree(srs->upd.tab);
+    held += srs->fk.bytes + srs->upd.bytes;
   }
   with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, held); });
   delete srs;
@@ -606,6 +610,11 @@ bool gt_wb_b_refuses(keaki_hip_ctx* ctx, const char*, long long v) {          //
   fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: gt_wb_b = %lld out of range", v);
   return true;
 }
+bool vec_update_k_pass_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= (long long)UPD_K_PASS) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: vec_update_k_pass = %lld out of range (1 .. %u; 0 = %u)", v, UPD_K_PASS, UPD_K_PASS);
+  return true;
+}
 #define TUNE_OPTION(member, ...) TuneOption{#member, assign_member<&Tuning::member>, __VA_ARGS__}
 const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(msm_c, msm_c_refuses<MSM_C_MAX>), TUNE_OPTION(msm_c_shared, msm_c_refuses<MSM_C_SHARED_MAX>), TUNE_OPTION(msm_short_tables),
@@ -614,7 +623,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(fb_occ1), TUNE_OPTION(pair_wide_max), TUNE_OPTION(pair_two_waves),
     TUNE_OPTION(gt_wb_b, gt_wb_b_refuses, [](keaki_hip_ctx* ctx) { ctx->kem.gt_b_ready = ctx->kem.gt_b_fallback = false; }),   // B's table: rebuilt at the new width on next use
     TUNE_OPTION(encap_gt), TUNE_OPTION(encap_multi_single_min), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
-    TUNE_OPTION(msm_pipe_growth),
+    TUNE_OPTION(msm_pipe_growth), TUNE_OPTION(vec_update_k_pass, vec_update_k_pass_refuses),
 #ifdef KEAKI_DIAG
     TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
 #endif
@@ -637,7 +646,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
+                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->vu_io, &ctx->vu_work, &ctx->vu_pass, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
     v.push_back({b, 1});
   ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
@@ -1467,6 +1476,84 @@ keaki_status keaki_hip_vec_commit(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, con
   ST_TRY(download(feed, proofs_out_aff, b + o_out, d * 64));
   resolve_timing(ctx);
   return KEAKI_OK;
+}
+
+// ---- vec_update: k evaluations of a committed vector change, the commitment and all d proofs follow (vec_update.hip) -------------------------
+namespace {
+// The ONE owner of a G1 handle's update tables, as fk_cache_ensure is of its FK23 transform: afterwards srs->upd.tab holds the tables of d = 2^log2d.
+// The caller holds srs->mu. Tables of another d are dropped first, the new ones are named only once their build is enqueued in full.
+keaki_status upd_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d_inv, const uint64_t* inv_d) {
+  UpdCache& c = srs->upd;
+  if (c.log2d == (int)log2d) return KEAKI_OK;
+  auto book = [&](size_t now) {
+    const size_t before = c.bytes;
+    with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
+    c.bytes = now;
+  };
+  c.log2d = -1;
+  if (c.tab) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.tab); c.tab = nullptr; book(0); }
+  const size_t bytes = upd_table_bytes(log2d);
+  ST_TRY(dev_alloc(ctx, &c.tab, bytes));
+  book(bytes);
+  ST_TRY(upd_tables_run(ctx, srs->d, log2d, omega_d_inv, inv_d, c.tab));
+  c.log2d = (int)log2d;
+  return KEAKI_OK;
+}
+constexpr const char* SRS_SHORT_UPD = "vec_update: a domain of %zu but the SRS holds %zu points";
+// how the three entries start: pointers, log2d and k in range, the handle on this device with d points, its lock taken
+keaki_status upd_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, size_t k, const char* what, std::unique_lock<std::recursive_mutex>& hl) {
+  if (!srs || !args_ok || log2d > 27 || k >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", what);
+  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, SRS_SHORT_UPD));
+  hl = std::unique_lock<std::recursive_mutex>(srs->mu);
+  return KEAKI_OK;
+}
+}  // namespace
+keaki_status keaki_hip_srs_g1_precompute_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
+                                                const uint64_t* inv_d) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.vec_update_tables");
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(upd_enter(ctx, srs, log2d, omega_d && omega_d_inv && inv_d, 0, "srs_g1_precompute_update", hl));
+  ST_TRY(upd_cache_ensure(ctx, srs, log2d, omega_d_inv, inv_d));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // setup-time call: return when the tables exist
+  return KEAKI_OK;
+}
+keaki_status keaki_hip_vec_update_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
+                                      const uint64_t* inv_d, const void* d_idx, const void* d_deltas, size_t k, void* d_com_inout_jac, void* d_proofs_inout_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.vec_update");
+  std::unique_lock<std::recursive_mutex> hl;
+  const bool aligned = !(((uintptr_t)d_idx & 3) | (((uintptr_t)d_deltas | (uintptr_t)d_com_inout_jac | (uintptr_t)d_proofs_inout_aff) & 15));
+  ST_TRY(upd_enter(ctx, srs, log2d, omega_d && omega_d_inv && inv_d && (!k || (d_idx && d_deltas)) && aligned, k, "vec_update_dev", hl));
+  if (k == 0 || (!d_com_inout_jac && !d_proofs_inout_aff)) return KEAKI_OK;
+  ST_TRY(upd_cache_ensure(ctx, srs, log2d, omega_d_inv, inv_d));
+  return upd_apply_run(ctx, srs->upd.tab, log2d, inv_d, d_idx, d_deltas, k, d_com_inout_jac, d_proofs_inout_aff);
+}
+keaki_status keaki_hip_vec_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
+                                  const uint64_t* inv_d, const uint32_t* idx, const uint64_t* deltas, size_t k, uint64_t* com_inout_jac, uint64_t* proofs_inout_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.vec_update");
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(upd_enter(ctx, srs, log2d, omega_d && omega_d_inv && inv_d && (!k || (idx && deltas)), k, "vec_update", hl));
+  const size_t d = (size_t)1 << log2d;
+  for (size_t t = 0; t < k; t++)
+    if (idx[t] >= d) return fail(ctx, KEAKI_ERR_BAD_ARG, "vec_update: index %u (entry %zu) is outside the domain of %zu", idx[t], t, d);
+  if (k == 0 || (!com_inout_jac && !proofs_inout_aff)) return KEAKI_OK;
+  // one staging block: deltas (k Fr) | commitment | proofs (d affine) | indices (k u32)
+  const size_t o_dl = 0, o_com = o_dl + k * 32, o_pr = o_com + 96, o_ix = o_pr + (proofs_inout_aff ? d * 64 : 0), total = o_ix + k * 4;
+  ST_TRY(reserve(ctx, ctx->vu_io, total));
+  ST_TRY(upd_cache_ensure(ctx, srs, log2d, omega_d_inv, inv_d));       // before the first copy: a refused table leaves nothing behind
+  char* b = (char*)ctx->vu_io.p;
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, b + o_dl, deltas, k * 32));
+  ST_TRY(feed.put(0, b + o_ix, idx, k * 4));
+  if (com_inout_jac) ST_TRY(feed.put(0, b + o_com, com_inout_jac, 96));
+  if (proofs_inout_aff) ST_TRY(feed.put(0, b + o_pr, proofs_inout_aff, d * 64));
+  ST_TRY(upd_apply_run(ctx, srs->upd.tab, log2d, inv_d, b + o_ix, b + o_dl, k, com_inout_jac ? b + o_com : nullptr, proofs_inout_aff ? b + o_pr : nullptr));
+  // both outputs in one download when both are asked for (they are neighbours in the block)
+  if (com_inout_jac && !proofs_inout_aff) return download(feed, com_inout_jac, b + o_com, 96);
+  if (com_inout_jac) HIP_TRY(ctx, hipMemcpyAsync(com_inout_jac, b + o_com, 96, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, proofs_inout_aff, b + o_pr, d * 64);
 }
 
 // ---- FK23 sharded over `world` = 2^k ranks: one handle per rank, the caller runs the exchanges between the steps -----------------

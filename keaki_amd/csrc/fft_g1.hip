@@ -561,6 +561,19 @@ keaki_status fk_hat_s_run(keaki_hip_ctx* ctx, const void* d_srs, u32 log2d, cons
   run_stages(ctx, false, s, (const Fr*)d_tw2d, N, d, 1u, 1, 0, [&](u32 half) { return N / (2 * half); });
   return launch_check(ctx, "fk_hat_s");
 }
+// In-place size-n transform of n = 2^log2n Jacobian points, decimation in frequency: natural order in, position q out holds
+// X[brev(q)] = sum_k root^(brev(q) k) a[k]. d_tw: root^k, k < n / 2 (vec_update.hip: the two update tables of an SRS, root = omega_d^-1).
+keaki_status g1_dif_run(keaki_hip_ctx* ctx, void* d_pts_jac, u32 log2n, const void* d_tw) {
+  const u32 n = 1u << log2n;
+  if (n >= 2) run_stages(ctx, false, (G1Jac*)d_pts_jac, (const Fr*)d_tw, n, n / 2, 1u, 1, 0, [&](u32 half) { return n / (2 * half); });
+  return launch_check(ctx, "g1_dif");
+}
+// the window-table workspace of the per-lane-scalar ladders for a job of `lanes` lanes (null: private memory, one launch); a launch covers at most
+// *lanes_per_launch lanes
+void* ladder_workspace(keaki_hip_ctx* ctx, u32 lanes, u32* lanes_per_launch) {
+  *lanes_per_launch = FK_TAB_LANES;
+  return fk_table(ctx, lanes);
+}
 // d = 2^log2d openings from the cached hat_s. d_work: 2d Jacobian points. d_hat_a: 2d Fr, natural order, already divided by 2d.
 // d_tw2d: omega_2d^k, d_tw2d_inv: omega_2d^-k (k < d). Output: d affine proofs, natural order.
 keaki_status open_fk_run(keaki_hip_ctx* ctx, const void* d_hat_s, u32 log2d, const void* d_hat_a, const void* d_tw2d, const void* d_tw2d_inv,

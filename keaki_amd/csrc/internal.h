@@ -27,6 +27,8 @@ struct DevBuf {
 // could never run. msm_g2.hip checks both limits against the plans. keaki_hip_ctx_set_option refuses the widths between a limit and 24,
 // tune_from_env ignores them; any other value outside 3 .. 24 means automatic, as it always did.
 constexpr int MSM_C_MAX = 19, MSM_C_SHARED_MAX = 23;
+// vec_update (vec_update.hip): entries of the change list a pass of the proof kernel takes (8 scalar words per entry and lane in LDS: 16 KB a wave)
+constexpr uint32_t UPD_K_PASS = 8;
 inline bool msm_c_too_wide(long long v, int max) { return v > max && v <= 24; }
 // Tuning / diagnostic switches of a context: every member but alloc_limit is an option of keaki_hip_ctx_set_option by its own name, with an
 // entry in TUNE_OPTIONS (api.hip). The environment is read ONCE, in keaki_hip_ctx_create (tune_from_env); afterwards only
@@ -59,6 +61,7 @@ struct Tuning {
   int msm_pipe_chunks = -1;      // KEAKI_MSM_PIPE_CHUNKS / "msm_pipe_chunks": chunks of a host-pointer MSM (upload under the kernels); -1 = automatic, 0 / 1 = one copy in front, k = k chunks at any length
   long long msm_pipe_min = 1 << 20;   // KEAKI_MSM_PIPE_MIN / "msm_pipe_min": automatic chunking from this many scalars on
   int msm_pipe_growth = 160;     // KEAKI_MSM_PIPE_GROWTH / "msm_pipe_growth": size of chunk j + 1 in percent of chunk j (100 = equal chunks; round 6: 160, measured best or tied at 2^20 .. 2^24, profiles/r06_msm_pipe_growth.txt; 140 until round 5)
+  int vec_update_k_pass = 0;     // KEAKI_VEC_UPDATE_K_PASS / "vec_update_k_pass": entries of the change list per pass of vec_update's proof kernel, 1 .. UPD_K_PASS; 0 = UPD_K_PASS
 #ifdef KEAKI_DIAG
   unsigned diag_row_mask = 0;    // "diag_row_mask" (ONLY in the diagnostic build, `make -C keaki_amd/csrc diag`; never in libkeaki_hip.so): the table-row index of every (row, sign) entry of the bucket-ordered stream is ANDed with this mask before the bucket kernel runs, so its gathers hit a table of (mask + 1) x 64 B -- the arithmetic, the instruction stream and the kernel binary stay the shipped ones, the RESULT IS WRONG by construction (bench_tools/r6_bucket_clock_diag.py)
 #endif
@@ -166,6 +169,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf em_offsets;                // encap_multi / encrypt_multi, _dev forms: the device copy of the caller's group offsets (8 B per group)
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
   keaki_internal::DevBuf ve_io, ve_pts, ve_out;     // kzg verify_each: the small in/out block (counters, commitment, [tau]_2, omega) | L and -proof of a launch chunk (128 B per item) | host form: the status bytes and L of the whole call
+  keaki_internal::DevBuf vu_io, vu_work, vu_pass;   // vec_update: host form: indices, deltas, commitment and proofs of the call | the 2d Jacobian points of a table build, the terms of the commitment | header and window tables of a pass
   // instrumentation
   bool timing = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -342,6 +346,16 @@ keaki_status fkb_reserve(keaki_hip_ctx* ctx, uint32_t log2d, size_t rows);
 const void* fkb_tables_run(keaki_hip_ctx* ctx, uint32_t log2d, size_t rows, const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* omega_d_inv_or_null);
 keaki_status fkb_pass_run(keaki_hip_ctx* ctx, const void* d_hat_s, uint32_t log2d, size_t cap, const void* d_rows, size_t n, uint32_t rows, size_t stride,
                           const uint64_t* inv_d_or_null, const uint64_t* inv_2d, void* d_proofs, const void** d_coeffs_out);
+// the stage machinery of FK23 for other callers (fft_g1.hip): an in-place size-2^log2n transform, decimation in frequency (d_tw: root^k, k < n / 2;
+// position q out holds X[brev(q)]) | the window-table workspace of the per-lane-scalar ladders (null: private memory) and the lanes one launch may cover
+keaki_status g1_dif_run(keaki_hip_ctx* ctx, void* d_pts_jac, uint32_t log2n, const void* d_tw);
+void* ladder_workspace(keaki_hip_ctx* ctx, uint32_t lanes, uint32_t* lanes_per_launch);
+// vec_update (vec_update.hip). The tables of (srs, d = 2^log2d): a (d affine) | u (d affine) | omega_d^-i (d Fr) | 1 / (omega_d^t - 1) (d Fr). upd_apply_run: k >= 1
+// entries (d_idx: u32, d_deltas: Fr) onto d_com (normalised Jacobian, or null) and d_proofs (d affine, or null); an index >= d does nothing. Asynchronous on ctx->stream.
+size_t upd_table_bytes(uint32_t log2d);
+keaki_status upd_tables_run(keaki_hip_ctx* ctx, const void* d_srs, uint32_t log2d, const uint64_t* omega_d_inv, const uint64_t* inv_d, void* d_tab);
+keaki_status upd_apply_run(keaki_hip_ctx* ctx, const void* d_tab, uint32_t log2d, const uint64_t* inv_d, const void* d_idx, const void* d_deltas, size_t k,
+                           void* d_com, void* d_proofs);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 // field probe (field_probe.hip): op `op` of keaki_field_op on n records at d_operands (field_probe_padded(op, n) records: lane-pair ops run whole

@@ -30,6 +30,7 @@ EXPORTS = [
     "keaki_hip_encap_multi", "keaki_hip_encap_multi_dev", "keaki_hip_encrypt_multi", "keaki_hip_encrypt_multi_dev",
     "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
+    "keaki_hip_srs_g1_precompute_update", "keaki_hip_vec_update", "keaki_hip_vec_update_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
     "keaki_hip_group_kzg_open", "keaki_hip_group_encap_batch", "keaki_hip_group_decap_batch",
@@ -183,6 +184,9 @@ def load_library():
         lib.keaki_hip_vec_commit_batch_dev.argtypes = [vp, vp, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         lib.keaki_hip_encap_prepare.argtypes = [vp, vp, sz]
         lib.keaki_hip_vec_commit.argtypes = [vp, vp, vp, sz, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+        lib.keaki_hip_srs_g1_precompute_update.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
+        lib.keaki_hip_vec_update.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, sz, vp, vp]
+        lib.keaki_hip_vec_update_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, sz, vp, vp]
         lib.keaki_hip_group_create.argtypes = [C.POINTER(i32), sz, C.POINTER(vp)]
         lib.keaki_hip_group_destroy.argtypes = [vp]
         lib.keaki_hip_group_destroy.restype = None
@@ -334,6 +338,32 @@ class KeakiHip:
                                                _ptr(_np(omega_d_inv)), _ptr(_np(inv_d)), _ptr(_np(omega_2d)), _ptr(_np(omega_2d_inv)), _ptr(_np(inv_2d)),
                                                _ptr(com), _ptr(proofs)))
         return com, proofs
+
+    def srs_g1_precompute_update(self, srs: "SrsG1", log2d: int, omega_d, omega_d_inv, inv_d):
+        """setup-time build of the handle's vec_update tables for d = 2^log2d (192 B x d; vec_update builds them on first use anyway)"""
+        self._ck(self.lib.keaki_hip_srs_g1_precompute_update(self.ctx, srs.handle, log2d, _ptr(_np(omega_d)), _ptr(_np(omega_d_inv)), _ptr(_np(inv_d))))
+
+    def vec_update(self, srs: "SrsG1", log2d: int, omega_d, omega_d_inv, inv_d, idx, deltas, com=None, proofs=None):
+        """evaluation idx[t] += deltas[t] (t < k) of a committed vector: `com` (u64[12] normalised Jacobian) and `proofs` ((d, 8) affine), either
+        may be None, are updated IN PLACE to the bytes vec_commit returns for the changed vector (keaki_hip_vec_update) -> (com, proofs).
+        Measured crossover (profiles/vec_update_times.txt): the update wins up to k = 16 and loses at k = 64 at d = 2^12, 2^16 and 2^20 (break-even near
+        k = 32, near 48 at 2^16): above it a fresh vec_commit is cheaper."""
+        ix = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        dl = _np(deltas, 4)
+        if dl.shape[0] != ix.shape[0]:
+            raise ValueError("vec_update: %d indices but %d deltas" % (ix.shape[0], dl.shape[0]))
+        for name, a, shape in (("com", com, (12,)), ("proofs", proofs, (1 << log2d, 8))):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags.c_contiguous and a.flags.writeable and a.shape == shape):
+                raise ValueError("vec_update: %s must be a writable contiguous uint64 array of shape %s (it is updated in place)" % (name, shape))
+        self._ck(self.lib.keaki_hip_vec_update(self.ctx, srs.handle, log2d, _ptr(_np(omega_d)), _ptr(_np(omega_d_inv)), _ptr(_np(inv_d)),
+                                               _ptr(ix) if ix.shape[0] else None, _ptr(dl) if ix.shape[0] else None, ix.shape[0], _ptr(com), _ptr(proofs)))
+        return com, proofs
+
+    def vec_update_dev(self, srs: "SrsG1", log2d: int, omega_d, omega_d_inv, inv_d, d_idx: int, d_deltas: int, k: int, d_com: int, d_proofs: int):
+        """the same on device-resident arrays (u32 indices, Fr deltas, 96-byte commitment, d x 64-byte proofs; 0 = absent), asynchronous on the ctx stream"""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._ck(self.lib.keaki_hip_vec_update_dev(self.ctx, srs.handle, log2d, _ptr(_np(omega_d)), _ptr(_np(omega_d_inv)), _ptr(_np(inv_d)),
+                                                   vp(d_idx), vp(d_deltas), k, vp(d_com), vp(d_proofs)))
 
     def set_timing(self, on: bool):
         self._ck(self.lib.keaki_hip_set_timing(self.ctx, 1 if on else 0))

@@ -700,6 +700,48 @@ std::vector<std::pair<G1, std::vector<G1>>> vec_commit_batch(Rng& rng, const kzg
   return out;
 }
 
+namespace {
+// (domain, log2 of its size) of an update over `domain_size` evaluations: a power of two, on a single device
+std::pair<Radix2Domain, unsigned> update_domain(const kzg::KZGSetup& setup, size_t domain_size, const char* what) {
+  if (setup.device()->group()) throw std::invalid_argument(std::string(what) + ": a group device has no update tables (single device only)");
+  if (domain_size < 1 || (domain_size & (domain_size - 1)) != 0) throw std::invalid_argument(std::string(what) + ": the domain size is not a power of two");
+  unsigned log_size = 0;
+  while ((size_t(1) << log_size) < domain_size) log_size++;
+  return {Radix2Domain::create(domain_size), log_size};
+}
+}  // namespace
+void precompute_vec_update(const kzg::KZGSetup& setup, size_t domain_size) {
+  const auto dl = update_domain(setup, domain_size, "precompute_vec_update");
+  const Device& dev = *setup.device();
+  dev.check(keaki_hip_srs_g1_precompute_update(dev.ctx(), setup.srs(), dl.second, dl.first.group_gen.l, dl.first.group_gen_inv.l, dl.first.size_inv.l));
+}
+void vec_update_flat(const kzg::KZGSetup& setup, size_t domain_size, const uint32_t* idx, const Fr* deltas, size_t k, uint64_t* com_inout, uint64_t* proofs_inout) {
+  const auto dl = update_domain(setup, domain_size, "vec_update");
+  const Device& dev = *setup.device();
+  uint64_t jac[12];
+  if (com_inout) {                               // affine -> normalised Jacobian (x, y, 1 | 1, 1, 0)
+    G1 c; memcpy(c.w.data(), com_inout, 64);
+    const bool inf = c.is_zero();
+    for (int i = 0; i < 3; i++) memcpy(jac + 4 * i, G1_GEN_W, 32);      // G1_GEN_W[0..4) is x = 1: the Montgomery one of Fq
+    if (inf) memset(jac + 8, 0, 32); else memcpy(jac, com_inout, 64);
+  }
+  dev.check(keaki_hip_vec_update(dev.ctx(), setup.srs(), dl.second, dl.first.group_gen.l, dl.first.group_gen_inv.l, dl.first.size_inv.l, idx, k ? deltas[0].l : nullptr, k,
+                                 com_inout ? jac : nullptr, proofs_inout));
+  if (com_inout && k) { const G1 c = jac_to_g1(jac); memcpy(com_inout, c.w.data(), 64); }
+}
+void vec_update(const kzg::KZGSetup& setup, G1& com, std::vector<G1>& proofs, const std::vector<size_t>& idx, const std::vector<Fr>& old_values,
+                const std::vector<Fr>& new_values) {
+  if (idx.size() != old_values.size() || idx.size() != new_values.size()) throw std::invalid_argument("vec_update: idx, old_values and new_values differ in length");
+  std::vector<uint32_t> ix(idx.size());
+  std::vector<Fr> deltas(idx.size());
+  for (size_t t = 0; t < idx.size(); t++) {
+    if (idx[t] >= proofs.size()) throw std::invalid_argument("vec_update: index " + std::to_string(idx[t]) + " is outside the domain of " + std::to_string(proofs.size()));
+    ix[t] = (uint32_t)idx[t];
+    deltas[t] = new_values[t] - old_values[t];
+  }
+  vec_update_flat(setup, proofs.size(), ix.data(), deltas.data(), ix.size(), com.w.data(), proofs.empty() ? nullptr : proofs[0].w.data());
+}
+
 bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs) {
   const Radix2Domain domain = Radix2Domain::create(n + PADDING_LEN);      // the domain vec_commit interpolated over (src/vec.rs:36)
   return kzg::verify_batch_flat(rng, setup, com.w.data(), 1, &domain.group_gen, true, v, proofs, n);

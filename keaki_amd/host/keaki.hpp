@@ -255,6 +255,18 @@ G1 vec_commit_flat(Rng& rng, const kzg::KZGSetup& setup, const Fr* v, size_t n, 
 // same power of two -- in one device call (keaki_hip_vec_commit_batch; domains up to 2^12 run its batch kernels). One padding scalar per vector,
 // drawn in index order, the rule vec_commit follows; (commitment, proofs) per vector as vec_commit returns them over that domain. Single device only.
 std::vector<std::pair<G1, std::vector<G1>>> vec_commit_batch(Rng& rng, const kzg::KZGSetup& setup, const std::vector<std::vector<Fr>>& vecs);
+// What src/vec.rs lacks and vector commitments are chosen for: the holder of (com, proofs) changes positions idx[t] from old_values[t] to
+// new_values[t] WITHOUT the vector; afterwards com and proofs are what vec_commit returns for the changed vector with the same padding scalar. The
+// domain is Radix2Domain::create(proofs.size()); indices address its evaluations (index v.size() is the padding slot), duplicates add. One device
+// call (keaki_hip_vec_update): (k + 1) d scalar multiples against FK23's d (log2 d + 3). Measured (profiles/vec_update_times.txt): one entry costs a
+// ninth of vec_commit at d = 2^16 and 2^20; the update wins up to k = 16 and loses at k = 64 at every measured d (break-even near k = 32, near 48
+// at 2^16): above that commit afresh. Single device only.
+void vec_update(const kzg::KZGSetup& setup, G1& com, std::vector<G1>& proofs, const std::vector<size_t>& idx, const std::vector<Fr>& old_values,
+                const std::vector<Fr>& new_values);
+// the same on contiguous buffers, taking the differences: com = 8 words (affine) in / out or null, proofs = domain_size x 8 words in / out or null
+void vec_update_flat(const kzg::KZGSetup& setup, size_t domain_size, const uint32_t* idx, const Fr* deltas, size_t k, uint64_t* com_inout, uint64_t* proofs_inout);
+// setup-time, optional: the update tables of (setup, domain_size) (192 bytes per evaluation; vec_update builds them on first use anyway)
+void precompute_vec_update(const kzg::KZGSetup& setup, size_t domain_size);
 // lines :27-37 of it (padding draw, iFFT): the coefficient vector over the whole domain, not trimmed
 std::vector<Fr> vec_commit_coeffs(Rng& rng, const kzg::KZGSetup& setup, const std::vector<Fr>& v);
 // lines :27-44 of it (padding draw, iFFT, open_fk): the dense coefficient vector and the proofs, without the final commit

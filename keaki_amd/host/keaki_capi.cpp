@@ -381,6 +381,30 @@ int keaki_host_vec_commit_batch(void* rng, void* s, const uint64_t* v, const siz
     return 0;
   });
 }
+// vec_update: positions idx[t] (t < k) of a committed vector go from old_values[t] to new_values[t]; com (8 words) and proofs (domain_size x 8 words) in place
+int keaki_host_vec_update(void* s, const uint64_t* idx, const uint64_t* old_values, const uint64_t* new_values, size_t k, size_t domain_size, uint64_t* com_inout,
+                          uint64_t* proofs_inout) {
+  return guard([&] {
+    G1 com = g1_of(com_inout);
+    std::vector<G1> proofs(domain_size);
+    if (domain_size) memcpy(proofs[0].w.data(), proofs_inout, 64 * domain_size);
+    vec::vec_update(((Setup*)s)->s, com, proofs, std::vector<size_t>(idx, idx + k), frs_of(old_values, k), frs_of(new_values, k));
+    memcpy(com_inout, com.w.data(), 64);
+    if (domain_size) memcpy(proofs_inout, proofs[0].w.data(), 64 * domain_size);
+    return 0;
+  });
+}
+// the same from the differences, on the caller's arrays (either of com / proofs may be null)
+int keaki_host_vec_update_flat(void* s, size_t domain_size, const uint32_t* idx, const uint64_t* deltas, size_t k, uint64_t* com_inout, uint64_t* proofs_inout) {
+  return guard([&] {
+    static_assert(sizeof(Fr) == 32, "Fr is four u64 limbs");
+    vec::vec_update_flat(((Setup*)s)->s, domain_size, idx, reinterpret_cast<const Fr*>(deltas), k, com_inout, proofs_inout);
+    return 0;
+  });
+}
+int keaki_host_precompute_vec_update(void* s, size_t domain_size) {
+  return guard([&] { vec::precompute_vec_update(((Setup*)s)->s, domain_size); return 0; });
+}
 // vec_encrypt with equal-length messages (msg_len each, concatenated)
 int keaki_host_vec_encrypt(void* rng, void* s, const uint64_t* com, const uint64_t* points, const uint64_t* values, const uint8_t* msgs,
                            size_t n, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {

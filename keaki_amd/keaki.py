@@ -526,6 +526,33 @@ def vec_commit(rng: Rng, setup: KZGSetup, v):
     return com, proofs
 
 
+def vec_update(setup: KZGSetup, com, proofs, idx, old_values, new_values):
+    """vec::vec_update: positions idx[t] of a committed vector go from old_values[t] to new_values[t] -> (com, proofs) of the changed vector with
+    the same padding scalar, without the vector. The domain is len(proofs); index len(v) is the padding slot; duplicates add."""
+    pr = np.array(_u64(proofs, 8)); c = np.array(_u64(com)).reshape(8)
+    ix = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1); k = ix.shape[0]
+    ov = np.ascontiguousarray(_u64(old_values, 4)); nv = np.ascontiguousarray(_u64(new_values, 4))
+    if ov.shape[0] != k or nv.shape[0] != k:
+        raise ValueError("vec_update: idx, old_values and new_values differ in length")
+    _ck(_lib().keaki_host_vec_update(setup.h, _p(ix), _p(ov), _p(nv), C.c_size_t(k), C.c_size_t(pr.shape[0]), _p(c), _p(pr)))
+    return c, pr
+
+
+def vec_update_flat(setup: KZGSetup, domain_size: int, idx, deltas, com=None, proofs=None):
+    """vec::vec_update_flat: the same from the differences, IN PLACE on `com` (u64[8]) and `proofs` (u64[domain_size, 8]); either may be None"""
+    ix = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1); dl = np.ascontiguousarray(_u64(deltas, 4))
+    if dl.shape[0] != ix.shape[0]:
+        raise ValueError("vec_update_flat: idx and deltas differ in length")
+    _ck(_lib().keaki_host_vec_update_flat(setup.h, C.c_size_t(domain_size), _p(ix), _p(dl), C.c_size_t(ix.shape[0]),
+                                          _p(com) if com is not None else None, _p(proofs) if proofs is not None else None))
+    return com, proofs
+
+
+def precompute_vec_update(setup: KZGSetup, domain_size: int) -> None:
+    """setup-time: the update tables of this domain size (192 bytes per evaluation)"""
+    _ck(_lib().keaki_host_precompute_vec_update(setup.h, C.c_size_t(domain_size)))
+
+
 def vec_commit_batch(rng: Rng, setup: KZGSetup, vecs):
     """m vectors over one domain (that of the longest + PADDING_LEN) in one device call -> (commitments (m, 8), proofs (m, size, 8)); one
     padding scalar per vector, drawn in index order; see keaki::vec::vec_commit_batch"""

@@ -109,6 +109,15 @@ extern "C" {
     pub fn keaki_hip_vec_commit(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, values: *const u64, n: usize, pad: *const u64, log2d: u32,
                                 omega_d_inv: *const u64, inv_d: *const u64, omega_2d: *const u64, omega_2d_inv: *const u64, inv_2d: *const u64,
                                 com_out_jac: *mut u64, proofs_out_aff: *mut u64) -> keaki_status;
+    // vec_update: evaluation idx[t] += deltas[t] (t < k), the commitment and all d proofs follow in place; either output may be null
+    pub fn keaki_hip_srs_g1_precompute_update(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, omega_d: *const u64,
+                                              omega_d_inv: *const u64, inv_d: *const u64) -> keaki_status;
+    pub fn keaki_hip_vec_update(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, omega_d: *const u64, omega_d_inv: *const u64,
+                                inv_d: *const u64, idx: *const u32, deltas: *const u64, k: usize, com_inout_jac: *mut u64,
+                                proofs_inout_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_vec_update_dev(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, omega_d: *const u64, omega_d_inv: *const u64,
+                                    inv_d: *const u64, d_idx: *const c_void, d_deltas: *const c_void, k: usize, d_com_inout_jac: *mut c_void,
+                                    d_proofs_inout_aff: *mut c_void) -> keaki_status;
 
     // ---- KZG open / verify in one call (src/kzg.rs:104-124, :127-151)
     pub fn keaki_hip_kzg_open(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, coeffs: *const u64, n: usize, point: *const u64,
