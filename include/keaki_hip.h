@@ -730,6 +730,73 @@ typedef enum {
 } keaki_field_op;
 keaki_status keaki_hip_selftest_field_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out);
 
+/* Tower probe: ONE shipped function of the pairing's Fq12 tower (pair261.hip.h, pairing.hip.h) or of its twelve-lane form
+ * (pairing_wide.hip.h) on operands the HOST chose, all twelve result words back (tests/test_gpu_tower_ops.py compares them with Python
+ * integers, exactly). The field probe above stops at fq6_mul; this one starts there. Record layout (uint32_t words):
+ *   operands: n records of KEAKI_TOP_REC_WORDS words
+ *     A    [  0,  96)  Fq12 operand a: 12 Fq in the tower's memory order c0.c0.c0, c0.c0.c1, c0.c1.c0 ... c1.c2.c1 (Fq2 coefficient m = 3 h + j
+ *                      of c_h.c_j, component e at Fq index 2 m + e), 8 canonical words each (< p), residue x 2^261 mod p
+ *     B    [ 96, 192)  Fq12 operand b, the same form
+ *     LINE [192, 246)  a line c0 + (d0 + d1 v) w as LIMBS: c0.c0, c0.c1, d0.c0, d0.c1, d1.c0, d1.c1, nine 29-bit limbs each; exact limbs,
+ *                      value < 2p (c0, d0) | < p (d1), what fq12_mul_by_034_limbs and w12_mul_034 take
+ *     T    [246, 294)  running point (X, Y, Z), homogeneous projective on the twist: 3 Fq2 = 6 Fq of 8 canonical words (2^261 form).
+ *                      KEAKI_TOP_ELL reads its Line (c0, c1, c2 as Fq2 words) here
+ *     Q    [294, 326)  affine point (x, y): 2 Fq2 = 4 Fq of 8 canonical words
+ *     P    [326, 344)  P.x, P.y as nine exact limbs each, value < p (KEAKI_TOP_ELL)
+ *   out:      n records of KEAKI_TOP_OUT_WORDS words: 12 Fq of 8 canonical words, 2^261 form. Fq12 results in the tower's memory order;
+ *             the line functions give T' = (X, Y, Z) in Fq 0..5 and the line (c0, c1, c2) in Fq 6..11; KEAKI_TOP_FQ6_INV inverts c0 of A
+ *             into Fq 0..5 and leaves 6..11 zero. An op reads the areas its function takes and ignores the rest.
+ * Geometry. Lane-pair ops (below KEAKI_TOP_FIRST_WIDE): one record per lane pair, 32 per wave, the even lane holds component 0; 18 Fq of LDS
+ * parking per lane as k_pairing. Wide ops: one record per 16-lane row, 4 per wave; lane pair k of a row holds the flat coefficient of w^k
+ * (k = 2 j + e for c_e.c_j), lanes 12..15 shadow pairs 0 and 1 and store nothing; the exchange area is k_pairing_wide's. The wide line
+ * functions keep T in every pair: pair k stores Fq2 number k of the six results. All 64 lanes run: the library pads the launch to whole waves
+ * with copies of record 0 and only the first n records are stored. 1 <= n <= KEAKI_TOP_MAX_RECORDS; an unknown op, n out of range or a
+ * null pointer is KEAKI_ERR_BAD_ARG and launches nothing. Operand bounds are the callee's own; the probe does not check them.
+ * Every op is one call with the template arguments of a shipped call site (k_pairing, k_pairing2, k_gt_table_fill, k_gt_encap_exp,
+ * k_pairing_wide and its kin). Not probed: fq12_sqr<false>, fq12_cyc_sqr<false> and fq12_mul_by_034_limbs<false> (only the on-device
+ * self-test instantiates them); w12_mul_forms apart from line_forms (w12_mul_034 is exactly that pair of calls); the addition operand of the
+ * st = 3, 4, 5 Miller steps (Fq2 ops of the field probe, applied before the call); the two-wave choreography of k_pairing_wide2 (its
+ * functions are the ones probed here, its scheduling stays with the end-to-end tests); the GT window tables (tests/test_gpu_fb_digit_edges.py). */
+#define KEAKI_TOP_REC_WORDS 344
+#define KEAKI_TOP_OUT_WORDS 96
+#define KEAKI_TOP_MAX_RECORDS 4096
+#define KEAKI_TOP_FIRST_WIDE KEAKI_TOP_W12_MUL
+typedef enum {
+  /* lane-pair form (pair261.hip.h, pairing.hip.h) */
+  KEAKI_TOP_FQ12_MUL = 0,            /* fq12_mul(&a, &a, &b) */
+  KEAKI_TOP_FQ12_MUL_LD = 1,         /* fq12_mul_ld<true>(&a, &a, halves of B from memory, park) */
+  KEAKI_TOP_FQ12_SQR = 2,            /* fq12_sqr<true>(&a, &a, park, 3) */
+  KEAKI_TOP_FQ12_INV = 3,            /* fq12_inv<false>: 0 -> 0 */
+  KEAKI_TOP_FQ12_INV_PARKED = 4,     /* fq12_inv<true>(&a, &a, park) */
+  KEAKI_TOP_FQ12_CONJ = 5,
+  KEAKI_TOP_FQ12_CYC_SQR = 6,        /* fq12_cyc_sqr<true>(&a, &a, park): total, the square on unitary elements */
+  KEAKI_TOP_FQ12_FROB1 = 7,          /* fq12_frob(&a, &a, k), k = 1, 2, 3 (k is a run-time value, as in the kernels) */
+  KEAKI_TOP_FQ12_FROB2 = 8,
+  KEAKI_TOP_FQ12_FROB3 = 9,
+  KEAKI_TOP_FQ12_FROB_PARKED1 = 10,  /* fq12_frob_parked(&a, &a, k, park) */
+  KEAKI_TOP_FQ12_FROB_PARKED2 = 11,
+  KEAKI_TOP_FQ12_FROB_PARKED3 = 12,
+  KEAKI_TOP_FQ12_MUL_BY_034 = 13,    /* fq12_mul_by_034_limbs<true>(&a, c0, d0, d1, true, park, 3) on LINE */
+  KEAKI_TOP_ELL = 14,                /* ell(&a, line words in T, P.x, P.y, park, 3) */
+  KEAKI_TOP_FQ6_INV = 15,            /* fq6_inv of a.c0: 0 -> 0 */
+  KEAKI_TOP_LINE_DOUBLE = 16,        /* line_double(&T, &l) */
+  KEAKI_TOP_LINE_ADD = 17,           /* line_add(&T, &Q.x, &Q.y, &l) */
+  /* twelve-lane form (pairing_wide.hip.h): every op from here on */
+  KEAKI_TOP_W12_MUL = 18,
+  KEAKI_TOP_W12_MUL_034 = 19,        /* w12_mul_034 = w12_mul_forms(a, line_forms(c0, d0, d1)) on LINE */
+  KEAKI_TOP_W12_CYC_SQR = 20,
+  KEAKI_TOP_W12_FROB1 = 21,
+  KEAKI_TOP_W12_FROB2 = 22,
+  KEAKI_TOP_W12_FROB3 = 23,
+  KEAKI_TOP_W12_CONJ = 24,
+  KEAKI_TOP_W12_INV = 25,            /* w12_gather, fq12_inv<false>, w12_own */
+  KEAKI_TOP_W12_GATHER_OWN = 26,     /* w12_own(w12_gather(a)): the element itself */
+  KEAKI_TOP_W_LINE_DOUBLE = 27,
+  KEAKI_TOP_W_LINE_ADD = 28,
+  KEAKI_TOP_COUNT = 29
+} keaki_tower_op;
+keaki_status keaki_hip_selftest_tower_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

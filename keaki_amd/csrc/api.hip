@@ -2472,5 +2472,18 @@ keaki_status keaki_hip_selftest_field_ops(keaki_hip_ctx* ctx, uint32_t op, const
   ST_TRY(field_probe_run(ctx, op, ctx->io_a.p, n, ctx->io_b.p));
   return download(feed, out, ctx->io_b.p, n * KEAKI_FOP_SLOT_WORDS * 4);
 }
+keaki_status keaki_hip_selftest_tower_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out) {
+  CTX_GUARD(ctx);
+  if (!operands || !out || op >= KEAKI_TOP_COUNT || n == 0 || n > KEAKI_TOP_MAX_RECORDS)
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "selftest_tower_ops: bad argument");
+  const size_t rec = (size_t)KEAKI_TOP_REC_WORDS * 4, padded = tower_probe_padded(op, n);
+  CopyFeed feed(ctx);
+  ST_TRY(reserve(ctx, ctx->io_a, padded * rec));
+  ST_TRY(reserve(ctx, ctx->io_b, n * KEAKI_TOP_OUT_WORDS * 4));
+  ST_TRY(feed.put(0, ctx->io_a.p, operands, n * rec));
+  for (size_t i = n; i < padded; i++) ST_TRY(feed.put(0, (char*)ctx->io_a.p + i * rec, operands, rec));     // the tail lanes of a wave run record 0
+  ST_TRY(tower_probe_run(ctx, op, ctx->io_a.p, n, ctx->io_b.p));
+  return download(feed, out, ctx->io_b.p, n * KEAKI_TOP_OUT_WORDS * 4);
+}
 
 }  // extern "C"

@@ -363,5 +363,10 @@ keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t it
 bool field_probe_is_pair(uint32_t op);
 size_t field_probe_padded(uint32_t op, size_t n);
 keaki_status field_probe_run(keaki_hip_ctx* ctx, uint32_t op, const void* d_operands, size_t n, void* d_out);
+// tower probe (tower_probe.hip, tower_probe_wide.hip): op `op` of keaki_tower_op on n records at d_operands (tower_probe_padded(op, n) records: whole
+// waves of 32 lane pairs or of 4 rows), twelve Fq per record to d_out (n records). Checks op and n itself (KEAKI_ERR_BAD_ARG, nothing launched).
+bool tower_probe_is_wide(uint32_t op);
+size_t tower_probe_padded(uint32_t op, size_t n);
+keaki_status tower_probe_run(keaki_hip_ctx* ctx, uint32_t op, const void* d_operands, size_t n, void* d_out);
 
 }  // namespace keaki_internal

@@ -508,13 +508,16 @@ static KTOWER void fq12_cyc_sqr(Fq12* r, const Fq12* a, uint4* park = nullptr) {
 //   r1.c0 = e0 c0 + a0 d0 + a2 (xi d1)          r1.c1 = e1 c0 + a0 d1 + a1 d0          r1.c2 = e2 c0 + a1 d1 + a2 d0
 // six streams of six Fq products; the multiplications by xi sit on the line's side (two per line instead of one per product).
 // The line's coefficients arrive as LIMBS of this lane's component: c0, d0 exact and < 2p (outputs of the products by P's coordinates),
-// d1 exact and < p. Bounds: f's coefficients 1; terms c0: 2 + 2, d0: 2 + 2, d1: 1 + 2, xi d1 (< 11p, negated 16p): 27, xi d0 (< 22p, 32p): 54.
+// d1 exact and < p. Bounds: f's coefficients 1; terms c0: 2 + 4, d0: 2 + 4, d1: 1 + 2, xi d1 (< 11p, negated 16p): 27, xi d0 (< 22p, 32p): 54.
+// c0 and d0 are negated against 4p, not 2p: the carried difference K - y keeps up to 2^232 + 2^207 in its limbs 0..7, so K must exceed the bound
+// of y by 2^233, and 2p - y falls short of that for y within 2^233 of 2p (limb 8 came out as -1: tests/test_gpu_tower_ops.py, c0 = 2p - 1). The
+// products by P's coordinates stay below 1.006 p, so no pairing ever got there; the stated bound now holds to its end. At most 6 + 27 + 54 = 87 < 169.
 template <bool PARK = false>
 static KTOWER void fq12_mul_by_034_limbs(Fq12* f, U29 c0, U29 d0, const U29& d1, bool fence_c0_d0, uint4* park = nullptr, int pidx = 0) {
   if (fence_c0_d0) { fence9(c0); fence9(d0); }
   const U29 c0o = quad<0xB1>(c0), d0o = quad<0xB1>(d0), d1o = quad<0xB1>(d1);
   (void)c0o;
-  const YF yc0 = y_of(c0, Q29::K2), yd0 = y_of(d0, Q29::K2), yd1 = y_of(d1, Q29::K2);
+  const YF yc0 = y_of(c0, Q29::K4), yd0 = y_of(d0, Q29::K4), yd1 = y_of(d1, Q29::K2);
   const YF yxd0 = y_of(xi_limbs(d0, d0o, Q29::K4), Q29::K32), yxd1 = y_of(xi_limbs(d1, d1o, Q29::K2), Q29::K16);
   const XF a0 = x_of(cut(f->c0.c0.v)), a1 = x_of(cut(f->c0.c1.v)), a2 = x_of(cut(f->c0.c2.v));
   const XF e0 = x_of(cut(f->c1.c0.v)), e1 = x_of(cut(f->c1.c1.v)), e2 = x_of(cut(f->c1.c2.v));

@@ -110,14 +110,15 @@ static KNOINLINE Fq w12_mul(const Fq a, const Fq b, uint4* ex) {
 //   c_k = a_k c0 + a_(k-1) d0 + a_(k-3) d1, indices mod 6, xi on the line's side where they wrap (k = 0; k < 3)
 // The line's coefficients are known to every pair as LIMBS of this lane's component: c0, d0 exact and < 2p, d1 exact and < p.
 // The line's side of it, for THIS lane's pair: the product forms of c0, of d0 or xi d0 (k = 0 wraps), of d1 or xi d1 (k < 3 wraps). The choice is
-// made on the limbs, before the forms: bounds c0 4 | d0 with the xi-sized bias 2 + 32 = 34, xi d0 54 | d1 1 + 16 = 17, xi d1 27: at most 85.
+// made on the limbs, before the forms: bounds c0 2 + 4 = 6 (negated against 4p: 2p leaves no room for the carried limbs when c0 is within 2^233
+// of 2p, see fq12_mul_by_034_limbs) | d0 with the xi-sized bias 2 + 32 = 34, xi d0 54 | d1 1 + 16 = 17, xi d1 27: at most 87.
 struct LineForms { YF c0, y1, y3; };
 KDEV LineForms line_forms(U29 c0, U29 d0, const U29& d1) {
   fence9(c0); fence9(d0);
   const u32 k = my_pair();
   const U29 xd0 = xi_limbs(d0, quad<0xB1>(d0), Q29::K4), xd1 = xi_limbs(d1, quad<0xB1>(d1), Q29::K2);
   LineForms r;
-  r.c0 = y_of(c0, Q29::K2);
+  r.c0 = y_of(c0, Q29::K4);
   r.y1 = y_of(sel9(k >= 1u, d0, xd0), Q29::K32);
   r.y3 = y_of(sel9(k >= 3u, d1, xd1), Q29::K16);
   return r;

@@ -28,7 +28,7 @@ EXPORTS = [
     "keaki_hip_encrypt_batch", "keaki_hip_encrypt_batch_dev", "keaki_hip_decrypt_batch", "keaki_hip_decrypt_batch_dev",
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
     "keaki_hip_encap_multi", "keaki_hip_encap_multi_dev", "keaki_hip_encrypt_multi", "keaki_hip_encrypt_multi_dev",
-    "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
+    "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_selftest_tower_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_srs_g1_precompute_update", "keaki_hip_vec_update", "keaki_hip_vec_update_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
@@ -52,6 +52,18 @@ def field_op_codes() -> dict:
     for m in re.finditer(r"#define\s+KEAKI_FOP_([A-Z_]+)\s+(\w+)", hdr):
         v = m.group(2)
         codes[m.group(1)] = int(v) if v.isdigit() else codes[v[len("KEAKI_FOP_"):]]
+    return codes
+
+
+def tower_op_codes() -> dict:
+    """{'FQ12_MUL': 0, ...}: the op codes of keaki_hip_selftest_tower_ops with the record geometry ('REC_WORDS', 'OUT_WORDS', 'MAX_RECORDS',
+    'FIRST_WIDE'), read from include/keaki_hip.h so that no second list exists"""
+    import re
+    hdr = open(os.path.join(os.path.dirname(_HERE), "include", "keaki_hip.h")).read()
+    codes = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bKEAKI_TOP_([A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    for m in re.finditer(r"#define\s+KEAKI_TOP_([A-Z_]+)\s+(\w+)", hdr):
+        v = m.group(2)
+        codes[m.group(1)] = int(v) if v.isdigit() else codes[v[len("KEAKI_TOP_"):]]
     return codes
 
 
@@ -134,6 +146,7 @@ def load_library():
         lib.keaki_hip_decap_batch_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz]
         lib.keaki_hip_selftest_field.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.keaki_hip_selftest_field_ops.argtypes = [vp, C.c_uint32, vp, sz, vp]
+        lib.keaki_hip_selftest_tower_ops.argtypes = [vp, C.c_uint32, vp, sz, vp]
         lib.keaki_hip_open_fk.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
         lib.keaki_hip_open_fk_poly.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
         lib.keaki_hip_fr_fft.argtypes = [vp, vp, C.c_uint32, vp, vp]
@@ -389,6 +402,14 @@ class KeakiHip:
         a = np.ascontiguousarray(operands, dtype=np.uint32).reshape(-1, 12, 9)
         out = np.zeros((a.shape[0], 9), np.uint32)
         self._ck(self.lib.keaki_hip_selftest_field_ops(self.ctx, op, _ptr(a), a.shape[0], _ptr(out)))
+        return out
+
+    def tower_ops(self, op: int, operands) -> np.ndarray:
+        """one shipped function of the Fq12 tower on host-chosen operands (keaki_hip_selftest_tower_ops): operands n x 344 uint32 -> the twelve result
+        words n x 12 x 8 uint32"""
+        a = np.ascontiguousarray(operands, dtype=np.uint32).reshape(-1, 344)
+        out = np.zeros((a.shape[0], 12, 8), np.uint32)
+        self._ck(self.lib.keaki_hip_selftest_tower_ops(self.ctx, op, _ptr(a), a.shape[0], _ptr(out)))
         return out
 
     # ---- SRS
