@@ -67,6 +67,7 @@ enum {
   KEAKI_ERR_NO_DEVICE = -4,    /* no gfx950 device visible                                    */
   KEAKI_ERR_TOO_LARGE = -5     /* polynomial longer than the SRS: KZGError::PolynomialTooLarge */
 };
+enum { KEAKI_SET_MAX = 1024 };  /* most points of a KZG set opening (keaki_hip_kzg_set_polys and the calls built on it) */
 
 typedef struct keaki_hip_ctx keaki_hip_ctx;
 typedef struct keaki_hip_srs_g1 keaki_hip_srs_g1; /* device-resident [tau^i]_1, affine */
@@ -281,6 +282,53 @@ keaki_status keaki_hip_kzg_open(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs,
  * n <= 1), value_out = p(point) (u64[4] or NULL). Same recurrence as keaki_hip_kzg_open, host pointers in and out. */
 keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, size_t n, const uint64_t* point, uint64_t* quotient_out,
                                     uint64_t* value_out);
+
+/* ---- KZG set openings: ONE proof for k points ----------------------------------------------------------------------------------------------
+ * Beyond the reference (whose open / verify, src/kzg.rs:104-148, take one point): the batch opening of the original KZG paper. For the set
+ * S = {z_0 .. z_(k-1)} of DISTINCT points, Z(x) = prod (x - z_j), I = the interpolant of (z_j, y_j) (deg < k) and the weights
+ * c_j = 1 / Z'(z_j) = 1 / prod_(t != j) (z_j - z_t):
+ *     pi_S = [((p - I) / Z)(tau)]_1 = sum_j c_j pi_j           e(C - [I(tau)]_1, g2) == e(pi_S, [Z(tau)]_2)
+ * (pi_j the single openings: partial fractions of 1 / Z). One 64-byte proof and two pairings whatever k is.
+ *   distinct   The library does NOT look for repeated points: a repeated z_j makes a weight 0 and every result meaningless. Distinct points
+ *              are the caller's contract; the host layers (host/keaki.cpp, rust/keaki/src/hip.rs) sort a copy and refuse a repeat.
+ *   layout     points, values, weights: k Fr; z_coeffs_out: k + 1 Fr, low degree first (monic); i_coeffs_out: k Fr, low degree first; proofs_aff:
+ *              k x u64[8] affine; proof_out_jac: u64[12] normalised Jacobian (a unique form: equal group elements give equal bytes).
+ *   set_polys  Z, the weights and, when values is given, I (values NULL: i_coeffs_out must be NULL): one workgroup, O(k^2) Fr products.
+ *   open_multi proof and values_out[j] = p(z_j) (values_out may be NULL) from the n coefficients: the quotient (p - I) / Z is computed on the device
+ *              as sum_j c_j (p - p(z_j)) / (x - z_j), the blockwise recurrence of keaki_hip_kzg_open for 8 points side by side (every coefficient is
+ *              read once per pass of 8 points: ceil(k / 8) passes), in front of ONE MSM over n - 1 terms (the top k - 1 are zero in Fr), which
+ *              uses the handle's window tables exactly as keaki_hip_kzg_open does. k = 1 is byte for byte keaki_hip_kzg_open. n <= k: the proof
+ *              is the identity (R, R, 0), the values are still written; n = 0: zero values.
+ *   aggregate  pi_S = sum_j c_j pi_j from the k single proofs, without the polynomial: the weights, then one MSM over the proofs as an ad-hoc
+ *              base vector. Byte for byte open_multi's proof for the same set.
+ *   verify_multi  [Z(tau)]_2 by an MSM over the first k + 1 points of srs_g2 ([tau^i]_2), [I(tau)]_1 by an MSM over the first k points of srs_g1,
+ *              then the predicate through keaki_hip_kzg_verify itself with com := C - [I]_1, value := 0, point := 0, tau_g2 := [Z]_2.
+ *              *ok_out = 1 / 0. pair_out_aff (or NULL): C - [I]_1 (u64[8]) then [Z]_2 (u64[16]), affine. Host arrays only.
+ *   errors     k = 0 or k > KEAKI_SET_MAX, a null required pointer, i_coeffs_out without values -> KEAKI_ERR_BAD_ARG; n - 1 > len(srs), k + 1 >
+ *              len(srs_g2), k > len(srs_g1) -> KEAKI_ERR_TOO_LARGE; a refused workspace -> KEAKI_ERR_OOM. Nothing is written in any of these cases
+ *              and the context stays usable.
+ *   host form  one upload in front of the kernels (open_multi does NOT run the chunk pipeline of keaki_hip_kzg_open: the coefficients are
+ *              uploaded whole, whatever n is), the kernels, one download; returns only when nothing reads or writes caller memory.
+ *   _dev       every array is a device pointer (16-byte aligned); asynchronous on the ctx stream. Workspace grow-only, counted in
+ *              keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim.
+ *   numbers    (MI355X, medians, one process, alternating rounds, resident: profiles/open_multi_times.txt, bench_tools/bench_open_multi.py) open_multi at
+ *              k = 2 / 8 / 64: 2^24 coefficients 18.3 / 24.5 / 80.6 ms (one MSM of that size 15.8; k calls of keaki_hip_kzg_open from host arrays 41 / 159 /
+ *              1,224), 2^20: 3.0 / 4.9 / 23 ms (8.5 / 26 / 188), 2^12: 1.6 / 2.8 / 14 ms -- where k = 64 LOSES to keaki_hip_kzg_open_batch_dev + aggregate
+ *              (7.0 ms): short polynomials with many points belong there. The fused quotient beats k single-point quotients at every size measured
+ *              (2^24, k = 64: 65 against 105 ms). verify_multi: 8 - 9 ms whatever k is (k single verifications: 3.4 ms at k = 2, 13.4 at 8, 108 at 64). */
+keaki_status keaki_hip_kzg_set_polys(keaki_hip_ctx* ctx, const uint64_t* points, const uint64_t* values, size_t k, uint64_t* z_coeffs_out,
+                                     uint64_t* weights_out, uint64_t* i_coeffs_out);
+keaki_status keaki_hip_kzg_set_polys_dev(keaki_hip_ctx* ctx, const void* d_points, const void* d_values, size_t k, void* d_z_coeffs_out,
+                                         void* d_weights_out, void* d_i_coeffs_out);
+keaki_status keaki_hip_kzg_open_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, const uint64_t* points, size_t k,
+                                      uint64_t* proof_out_jac, uint64_t* values_out);
+keaki_status keaki_hip_kzg_open_multi_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, const void* d_points, size_t k,
+                                          void* d_proof_out_jac, void* d_values_out);
+keaki_status keaki_hip_kzg_aggregate(keaki_hip_ctx* ctx, const uint64_t* points, const uint64_t* proofs_aff, size_t k, uint64_t* proof_out_jac);
+keaki_status keaki_hip_kzg_aggregate_dev(keaki_hip_ctx* ctx, const void* d_points, const void* d_proofs_aff, size_t k, void* d_proof_out_jac);
+keaki_status keaki_hip_kzg_verify_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                        const uint64_t* points, const uint64_t* values, size_t k, const uint64_t* proof_aff, int32_t* ok_out,
+                                        uint64_t* pair_out_aff);
 
 /* ---- batched commit and open: m polynomials over ONE SRS in one call ---------------------------------------------------------------------
  * Generalises `commit` (reference src/kzg.rs:89-101) and `open` (src/kzg.rs:104-124) from one polynomial to m rows. A single MSM costs

@@ -646,7 +646,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->vu_io, &ctx->vu_work, &ctx->vu_pass, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
+                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->vu_io, &ctx->vu_work, &ctx->vu_pass, &ctx->ks_io, &ctx->ks_q, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
     v.push_back({b, 1});
   ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
@@ -1785,6 +1785,117 @@ keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, 
   return download(feed, value_out, b + L.o_v, value_out ? 32 : 0);
 }
 
+// ---- KZG set openings: one proof for k points (kzg_multi.hip) -------------------------------------------------------------------------------
+// ks_io: [points | values | Z | weights | I], a slot of KEAKI_SET_MAX + 1 Fr each, then [proof 96 | I1 96 | Z2 192 | com 64 | C - I1 64 | Z2 affine 128]
+// ks_q:  [quotient: n Fr | work of multi_quotient_run]
+extern "C++" {
+namespace {
+struct KsLayout {
+  static constexpr size_t SLOT = ((size_t)KEAKI_SET_MAX + 1) * 32;
+  static constexpr size_t O_PTS = 0, O_VAL = SLOT, O_ZC = 2 * SLOT, O_W = 3 * SLOT, O_IC = 4 * SLOT, O_PROOF = 5 * SLOT, O_I1 = O_PROOF + 96, O_Z2 = O_I1 + 96,
+                          O_COM = O_Z2 + 192, O_PAIR = O_COM + 64, TOTAL = O_PAIR + 192;
+};
+keaki_status set_args(keaki_hip_ctx* ctx, const char* what, size_t k, bool pointers_ok) {
+  if (k == 0 || k > KEAKI_SET_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: k = %zu must be in 1 .. %d", what, k, (int)KEAKI_SET_MAX);
+  if (!pointers_ok) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
+  return KEAKI_OK;
+}
+// the arguments are checked and ks_io is reserved; d_values may be null
+keaki_status open_multi_core(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, const void* d_points, size_t k, void* d_proof_out_jac,
+                             void* d_values) {
+  using S = KsLayout;
+  char* io = (char*)ctx->ks_io.p;
+  ST_TRY(reserve(ctx, ctx->ks_q, n * 32 + multi_quotient_work_bytes(n)));
+  char* q = (char*)ctx->ks_q.p;
+  if (!d_values) d_values = io + S::O_VAL;
+  ST_TRY(set_polys_run(ctx, d_points, nullptr, k, nullptr, io + S::O_W, nullptr));
+  if (n == 0) HIP_TRY(ctx, hipMemsetAsync(d_values, 0, k * 32, ctx->stream));                   // the zero polynomial evaluates to 0
+  // n <= k: only the values are wanted (p = I, the MSM below takes no terms); the passes still write their n - 1 quotient words, which are zero
+  // and never read -- an edge case not worth a second kernel form
+  else ST_TRY(multi_quotient_run(ctx, d_coeffs, n, d_points, io + S::O_W, k, q, d_values, q + n * 32));
+  const auto tb = srs_tables(srs);
+  return msm_g1_run(ctx, srs->d, srs->n, q, n > k ? n - 1 : 0, d_proof_out_jac, tb.first, tb.second);     // n <= k: p = I, the quotient is zero
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_kzg_set_polys_dev(keaki_hip_ctx* ctx, const void* d_points, const void* d_values, size_t k, void* d_z_coeffs_out, void* d_weights_out,
+                                         void* d_i_coeffs_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_set_polys");
+  ST_TRY(set_args(ctx, "kzg_set_polys", k, d_points && d_z_coeffs_out && d_weights_out && (!d_i_coeffs_out || d_values)));
+  return set_polys_run(ctx, d_points, d_values, k, d_z_coeffs_out, d_weights_out, d_i_coeffs_out);
+}
+keaki_status keaki_hip_kzg_set_polys(keaki_hip_ctx* ctx, const uint64_t* points, const uint64_t* values, size_t k, uint64_t* z_coeffs_out, uint64_t* weights_out,
+                                     uint64_t* i_coeffs_out) {
+  CTX_GUARD(ctx);
+  using S = KsLayout;
+  ST_TRY(set_args(ctx, "kzg_set_polys", k, points && z_coeffs_out && weights_out && (!i_coeffs_out || values)));
+  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
+  char* io = (char*)ctx->ks_io.p;
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, io + S::O_PTS, points, k * 32));
+  if (i_coeffs_out) ST_TRY(feed.put(0, io + S::O_VAL, values, k * 32));
+  ST_TRY(keaki_hip_kzg_set_polys_dev(ctx, io + S::O_PTS, i_coeffs_out ? io + S::O_VAL : nullptr, k, io + S::O_ZC, io + S::O_W, i_coeffs_out ? io + S::O_IC : nullptr));
+  HIP_TRY(ctx, hipMemcpyAsync(z_coeffs_out, io + S::O_ZC, (k + 1) * 32, hipMemcpyDeviceToHost, ctx->stream));
+  if (i_coeffs_out) HIP_TRY(ctx, hipMemcpyAsync(i_coeffs_out, io + S::O_IC, k * 32, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, weights_out, io + S::O_W, k * 32);
+}
+keaki_status keaki_hip_kzg_open_multi_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_coeffs, size_t n, const void* d_points, size_t k,
+                                          void* d_proof_out_jac, void* d_values_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_open_multi");
+  ST_TRY(set_args(ctx, "kzg_open_multi", k, srs && d_points && d_proof_out_jac && (!n || d_coeffs)));
+  ST_TRY(srs_holds(ctx, srs, "kzg_open_multi", n ? n - 1 : 0, SRS_SHORT_MSM));
+  ST_TRY(reserve(ctx, ctx->ks_io, KsLayout::TOTAL));
+  return open_multi_core(ctx, srs, d_coeffs, n, d_points, k, d_proof_out_jac, d_values_out);
+}
+keaki_status keaki_hip_kzg_open_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const uint64_t* coeffs, size_t n, const uint64_t* points, size_t k,
+                                      uint64_t* proof_out_jac, uint64_t* values_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_open_multi");
+  using S = KsLayout;
+  ST_TRY(set_args(ctx, "kzg_open_multi", k, srs && points && proof_out_jac && (!n || coeffs)));
+  ST_TRY(srs_holds(ctx, srs, "kzg_open_multi", n ? n - 1 : 0, SRS_SHORT_MSM));
+  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
+  ST_TRY(reserve(ctx, ctx->io_a, n ? n * 32 : 16));
+  char* io = (char*)ctx->ks_io.p;
+  // one upload in front of the kernels: the chunk pipeline of keaki_hip_kzg_open is not used here
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, ctx->io_a.p, coeffs, n * 32));
+  ST_TRY(feed.put(0, io + S::O_PTS, points, k * 32));
+  ST_TRY(open_multi_core(ctx, srs, ctx->io_a.p, n, io + S::O_PTS, k, io + S::O_PROOF, io + S::O_VAL));
+  if (values_out) HIP_TRY(ctx, hipMemcpyAsync(values_out, io + S::O_VAL, k * 32, hipMemcpyDeviceToHost, ctx->stream));
+  ST_TRY(download(feed, proof_out_jac, io + S::O_PROOF, 96));
+  resolve_timing(ctx);
+  return KEAKI_OK;
+}
+keaki_status keaki_hip_kzg_aggregate_dev(keaki_hip_ctx* ctx, const void* d_points, const void* d_proofs_aff, size_t k, void* d_proof_out_jac) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_aggregate");
+  using S = KsLayout;
+  ST_TRY(set_args(ctx, "kzg_aggregate", k, d_points && d_proofs_aff && d_proof_out_jac));
+  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
+  char* io = (char*)ctx->ks_io.p;
+  ST_TRY(set_polys_run(ctx, d_points, nullptr, k, nullptr, io + S::O_W, nullptr));
+  return msm_g1_run(ctx, d_proofs_aff, k, io + S::O_W, k, d_proof_out_jac);          // the proofs as an ad-hoc base vector: no tables
+}
+keaki_status keaki_hip_kzg_aggregate(keaki_hip_ctx* ctx, const uint64_t* points, const uint64_t* proofs_aff, size_t k, uint64_t* proof_out_jac) {
+  CTX_GUARD(ctx);
+  using S = KsLayout;
+  ST_TRY(set_args(ctx, "kzg_aggregate", k, points && proofs_aff && proof_out_jac));
+  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
+  ST_TRY(reserve(ctx, ctx->io_a, k * G1_AFF_BYTES));
+  char* io = (char*)ctx->ks_io.p;
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, io + S::O_PTS, points, k * 32));
+  ST_TRY(feed.put(0, ctx->io_a.p, proofs_aff, k * G1_AFF_BYTES));
+  ST_TRY(keaki_hip_kzg_aggregate_dev(ctx, io + S::O_PTS, ctx->io_a.p, k, io + S::O_PROOF));
+  ST_TRY(download(feed, proof_out_jac, io + S::O_PROOF, 96));
+  resolve_timing(ctx);
+  return KEAKI_OK;
+}
+
 // ---- batched commit / open: m rows over one SRS in one call (msm_batch.hip) ---------------------------------------------------------------
 extern "C++" {
 namespace {
@@ -2055,6 +2166,40 @@ keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, c
   uint8_t gt[768];
   ST_TRY(download(ctx, gt, io + O_GT, 768));                                       // synchronises: `in` stays alive until here
   *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
+  return KEAKI_OK;
+}
+
+// The set predicate e(C - [I(tau)]_1, g2) == e(proof, [Z(tau)]_2): the two set polynomials (kzg_multi.hip), [Z]_2 and [I]_1 by the library's MSMs over
+// the powers, then keaki_hip_kzg_verify ITSELF with com := C - [I]_1, value := 0, point := 0, tau_g2 := [Z]_2 (the two points cross the host once:
+// 192 bytes, which pair_out hands to the tests).
+keaki_status keaki_hip_kzg_verify_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                        const uint64_t* points, const uint64_t* values, size_t k, const uint64_t* proof_aff, int32_t* ok_out,
+                                        uint64_t* pair_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_multi");
+  using S = KsLayout;
+  ST_TRY(set_args(ctx, "kzg_verify_multi", k, srs_g1 && srs_g2 && com_aff && points && values && proof_aff && ok_out));
+  ST_TRY(srs_holds(ctx, srs_g2, "kzg_verify_multi", k + 1, "kzg_verify_multi: Z has %zu coefficients but the G2 SRS holds %zu points"));
+  ST_TRY(srs_holds(ctx, srs_g1, "kzg_verify_multi", k, "kzg_verify_multi: I has %zu coefficients but the G1 SRS holds %zu points"));
+  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
+  char* io = (char*)ctx->ks_io.p;
+  uint64_t pair[24];
+  {
+    CopyFeed feed(ctx);
+    ST_TRY(feed.put(0, io + S::O_PTS, points, k * 32));
+    ST_TRY(feed.put(0, io + S::O_VAL, values, k * 32));
+    ST_TRY(feed.put(0, io + S::O_COM, com_aff, 64));
+    ST_TRY(set_polys_run(ctx, io + S::O_PTS, io + S::O_VAL, k, io + S::O_ZC, io + S::O_W, io + S::O_IC));
+    const auto t2 = srs_tables(srs_g2);
+    ST_TRY(msm_g2_run(ctx, srs_g2->d, srs_g2->n, io + S::O_ZC, k + 1, io + S::O_Z2, t2.first, t2.second));
+    const auto t1 = srs_tables(srs_g1);
+    ST_TRY(msm_g1_run(ctx, srs_g1->d, srs_g1->n, io + S::O_IC, k, io + S::O_I1, t1.first, t1.second));
+    ST_TRY(set_pair_points_run(ctx, io + S::O_COM, io + S::O_I1, io + S::O_Z2, io + S::O_PAIR, io + S::O_PAIR + 64));
+    ST_TRY(download(feed, pair, io + S::O_PAIR, 192));
+  }
+  const uint64_t zero[4] = {0, 0, 0, 0};
+  ST_TRY(keaki_hip_kzg_verify(ctx, pair, pair + 8, zero, zero, proof_aff, ok_out));
+  if (pair_out_aff) memcpy(pair_out_aff, pair, 192);
   return KEAKI_OK;
 }
 

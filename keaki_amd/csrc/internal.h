@@ -170,6 +170,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf vb_io, vb_s;               // kzg verify_batch: the small in/out block with the reduction's partials | the scalars gamma_i z_i of the second MSM (32 B per item)
   keaki_internal::DevBuf ve_io, ve_pts, ve_out;     // kzg verify_each: the small in/out block (counters, commitment, [tau]_2, omega) | L and -proof of a launch chunk (128 B per item) | host form: the status bytes and L of the whole call
   keaki_internal::DevBuf vu_io, vu_work, vu_pass;   // vec_update: host form: indices, deltas, commitment and proofs of the call | the 2d Jacobian points of a table build, the terms of the commitment | header and window tables of a pass
+  keaki_internal::DevBuf ks_io, ks_q;               // KZG set openings: points, values, Z, weights, I and the small results of a call | the quotient and the work of its passes (kzg_multi.hip)
   // instrumentation
   bool timing = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -356,6 +357,15 @@ size_t upd_table_bytes(uint32_t log2d);
 keaki_status upd_tables_run(keaki_hip_ctx* ctx, const void* d_srs, uint32_t log2d, const uint64_t* omega_d_inv, const uint64_t* inv_d, void* d_tab);
 keaki_status upd_apply_run(keaki_hip_ctx* ctx, const void* d_tab, uint32_t log2d, const uint64_t* inv_d, const void* d_idx, const void* d_deltas, size_t k,
                            void* d_com, void* d_proofs);
+// KZG set openings (kzg_multi.hip). set_polys_run: Z (k + 1 Fr; d_zc may be null when d_ic is), the weights 1 / Z'(z_j) (k Fr) and, with values, the
+// interpolant (k Fr) of 1 <= k <= KEAKI_SET_MAX DISTINCT points, one workgroup. multi_quotient_run: d_q = the n - 1 coefficients of
+// sum_j weight_j (p - p(z_j)) / (x - z_j) = (p - I) / Z and d_values[j] = p(z_j), for n >= 1 coefficients, in passes of 8 points. All on ctx->stream.
+keaki_status set_polys_run(keaki_hip_ctx* ctx, const void* d_points, const void* d_values, size_t k, void* d_zc, void* d_weights, void* d_ic);
+size_t multi_quotient_work_bytes(size_t n);
+keaki_status multi_quotient_run(keaki_hip_ctx* ctx, const void* d_c, size_t n, const void* d_points, const void* d_weights, size_t k, void* d_q, void* d_values,
+                                void* d_work);
+// verify_multi: d_out_a_aff = C - I1, d_out_z_aff = Z2 (affine) from the commitment and the two MSM results (normalised or not)
+keaki_status set_pair_points_run(keaki_hip_ctx* ctx, const void* d_com_aff, const void* d_i1_jac, const void* d_z2_jac, void* d_out_a_aff, void* d_out_z_aff);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 // field probe (field_probe.hip): op `op` of keaki_field_op on n records at d_operands (field_probe_padded(op, n) records: lane-pair ops run whole

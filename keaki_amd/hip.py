@@ -31,6 +31,8 @@ EXPORTS = [
     "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_selftest_tower_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_srs_g1_precompute_update", "keaki_hip_vec_update", "keaki_hip_vec_update_dev",
+    "keaki_hip_kzg_set_polys", "keaki_hip_kzg_set_polys_dev", "keaki_hip_kzg_open_multi", "keaki_hip_kzg_open_multi_dev",
+    "keaki_hip_kzg_aggregate", "keaki_hip_kzg_aggregate_dev", "keaki_hip_kzg_verify_multi",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
     "keaki_hip_group_kzg_open", "keaki_hip_group_encap_batch", "keaki_hip_group_decap_batch",
@@ -200,6 +202,13 @@ def load_library():
         lib.keaki_hip_srs_g1_precompute_update.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
         lib.keaki_hip_vec_update.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, sz, vp, vp]
         lib.keaki_hip_vec_update_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, sz, vp, vp]
+        lib.keaki_hip_kzg_set_polys.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+        lib.keaki_hip_kzg_set_polys_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+        lib.keaki_hip_kzg_open_multi.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
+        lib.keaki_hip_kzg_open_multi_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
+        lib.keaki_hip_kzg_aggregate.argtypes = [vp, vp, vp, sz, vp]
+        lib.keaki_hip_kzg_aggregate_dev.argtypes = [vp, vp, vp, sz, vp]
+        lib.keaki_hip_kzg_verify_multi.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_group_create.argtypes = [C.POINTER(i32), sz, C.POINTER(vp)]
         lib.keaki_hip_group_destroy.argtypes = [vp]
         lib.keaki_hip_group_destroy.restype = None
@@ -600,6 +609,59 @@ class KeakiHip:
         out = np.zeros(12, np.uint64); val = np.zeros(4, np.uint64)
         self._ck(self.lib.keaki_hip_kzg_open(self.ctx, srs.handle, _ptr(c) if c.shape[0] else None, c.shape[0], _ptr(_np(point)), _ptr(out), _ptr(val)))
         return out, val
+
+    # ---- KZG set openings: one proof for k DISTINCT points (the library does not look for repeated points: the caller's contract) ----
+    SET_MAX = 1024
+
+    def kzg_set_polys(self, points, values=None):
+        """-> (Z: k + 1 Fr, monic, low degree first; weights 1 / Z'(z_j): k Fr; I: k Fr, the interpolant of (points, values), or None without values)"""
+        z = _np(points, 4); k = z.shape[0]
+        y = _np(values, 4) if values is not None else None
+        if y is not None and y.shape[0] != k:
+            raise ValueError("kzg_set_polys: %d points but %d values" % (k, y.shape[0]))
+        zc = np.zeros((k + 1, 4), np.uint64); w = np.zeros((k, 4), np.uint64)
+        ic = np.zeros((k, 4), np.uint64) if y is not None else None
+        self._ck(self.lib.keaki_hip_kzg_set_polys(self.ctx, _ptr(z) if k else None, _ptr(y), k, _ptr(zc), _ptr(w), _ptr(ic)))
+        return zc, w, ic
+
+    def kzg_set_polys_dev(self, d_points: int, d_values: int, k: int, d_z_coeffs: int, d_weights: int, d_i_coeffs: int):
+        self._ck(self.lib.keaki_hip_kzg_set_polys_dev(self.ctx, C.c_void_p(d_points), C.c_void_p(d_values), k, C.c_void_p(d_z_coeffs), C.c_void_p(d_weights),
+                                                      C.c_void_p(d_i_coeffs)))
+
+    def kzg_open_multi(self, srs: "SrsG1", coeffs, points):
+        """ONE proof for the k points (keaki_hip_kzg_open_multi) -> (proof as normalised Jacobian u64[12], the k values p(z_j))"""
+        c = _np(coeffs, 4); z = _np(points, 4); k = z.shape[0]
+        out = np.zeros(12, np.uint64); val = np.zeros((k, 4), np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_open_multi(self.ctx, srs.handle, _ptr(c) if c.shape[0] else None, c.shape[0], _ptr(z) if k else None, k, _ptr(out),
+                                                   _ptr(val)))
+        return out, val
+
+    def kzg_open_multi_dev(self, srs: "SrsG1", d_coeffs: int, n: int, d_points: int, k: int, d_proof: int, d_values: int):
+        self._ck(self.lib.keaki_hip_kzg_open_multi_dev(self.ctx, srs.handle, C.c_void_p(d_coeffs), n, C.c_void_p(d_points), k, C.c_void_p(d_proof),
+                                                       C.c_void_p(d_values)))
+
+    def kzg_aggregate(self, points, proofs_aff) -> np.ndarray:
+        """the set proof from the k single proofs at the k points, without the polynomial -> normalised Jacobian u64[12]"""
+        z = _np(points, 4); pr = _np(proofs_aff, 8); k = z.shape[0]
+        if pr.shape[0] != k:
+            raise ValueError("kzg_aggregate: %d points but %d proofs" % (k, pr.shape[0]))
+        out = np.zeros(12, np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_aggregate(self.ctx, _ptr(z) if k else None, _ptr(pr) if k else None, k, _ptr(out)))
+        return out
+
+    def kzg_aggregate_dev(self, d_points: int, d_proofs_aff: int, k: int, d_proof: int):
+        self._ck(self.lib.keaki_hip_kzg_aggregate_dev(self.ctx, C.c_void_p(d_points), C.c_void_p(d_proofs_aff), k, C.c_void_p(d_proof)))
+
+    def kzg_verify_multi(self, srs_g1: "SrsG1", srs_g2: "SrsG2", com_aff, points, values, proof_aff, want_pair: bool = False):
+        """e(C - [I(tau)]_1, g2) == e(proof, [Z(tau)]_2) (keaki_hip_kzg_verify_multi; srs_g2 holds [tau^i]_2) -> ok, or (ok, C - [I]_1 u64[8],
+        [Z]_2 u64[16]) with want_pair"""
+        z = _np(points, 4); y = _np(values, 4); k = z.shape[0]
+        if y.shape[0] != k:
+            raise ValueError("kzg_verify_multi: %d points but %d values" % (k, y.shape[0]))
+        ok = C.c_int32(0); pair = np.zeros(24, np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_multi(self.ctx, srs_g1.handle, srs_g2.handle, _ptr(_np(com_aff)), _ptr(z) if k else None, _ptr(y) if k else None,
+                                                     k, _ptr(_np(proof_aff)), C.byref(ok), _ptr(pair) if want_pair else None))
+        return (bool(ok.value), pair[:8].copy(), pair[8:].copy()) if want_pair else bool(ok.value)
 
     def kzg_verify(self, com_aff, tau_g2_aff, point, value, proof_aff) -> bool:
         """src/kzg.rs:127-146 on the device (affine Montgomery points, Montgomery Fr)"""

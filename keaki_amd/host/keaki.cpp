@@ -1,6 +1,7 @@
 // Host mirror of keaki's public API (see keaki.hpp). Group arithmetic = C-ABI calls into libkeaki_hip.so.
 #include "keaki.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -138,12 +139,14 @@ std::string KZGError::to_string() const {
 KZGSetup::~KZGSetup() {
   if (chunk_ && dev_) keaki_hip_srs_g1_free(dev_->ctx(), chunk_);
   if (srs_ && dev_) keaki_hip_srs_g1_free(dev_->ctx(), srs_);
+  if (srs_g2_ && dev_) keaki_hip_srs_g2_free(dev_->ctx(), srs_g2_);
   if (gsrs_ && dev_) keaki_hip_group_srs_g1_free(dev_->group(), gsrs_);
   if (gfk_ && dev_) keaki_hip_group_fk_free(dev_->group(), gfk_);
 }
 KZGSetup::KZGSetup(KZGSetup&& o) noexcept
     : dev_(std::move(o.dev_)), g1_aff_(std::move(o.g1_aff_)), tau_g2_(o.tau_g2_), srs_(o.srs_), gsrs_(o.gsrs_), gfk_(o.gfk_), gfk_log2d_(o.gfk_log2d_),
-      tables_(o.tables_), chunk_(o.chunk_), chunk_lo_(o.chunk_lo_), chunk_hi_(o.chunk_hi_) {
+      tables_(o.tables_), g2_pow_(std::move(o.g2_pow_)), srs_g2_(o.srs_g2_), chunk_(o.chunk_), chunk_lo_(o.chunk_lo_), chunk_hi_(o.chunk_hi_) {
+  o.srs_g2_ = nullptr;
   o.srs_ = nullptr; o.chunk_ = nullptr; o.gsrs_ = nullptr; o.gfk_ = nullptr;
 }
 keaki_hip_group_fk* KZGSetup::group_fk(unsigned log2d) const {
@@ -209,6 +212,83 @@ KZGSetup KZGSetup::setup(std::shared_ptr<Device> dev, const Fr& secret, size_t m
   G2 g2 = g2_generator(*dev), tau;
   dev->check(keaki_hip_g2_mul_batch(dev->ctx(), g2.w.data(), 0, secret.l, 1, tau.w.data()));
   return from_powers(std::move(dev), std::move(pts), tau);
+}
+
+static void trim(DensePolynomial& p);
+KZGSetup KZGSetup::from_powers_g2(std::shared_ptr<Device> dev, std::vector<G1> g1_aff, std::vector<G2> g2_pow) {
+  if (g2_pow.size() < 2) throw SetError("from_powers_g2: needs at least g2 and [tau]_2");
+  KZGSetup s = from_powers(std::move(dev), std::move(g1_aff), g2_pow[1]);
+  s.g2_pow_ = std::move(g2_pow);
+  return s;
+}
+KZGSetup KZGSetup::setup_with_g2(std::shared_ptr<Device> dev, const Fr& secret, size_t max_d, size_t max_set) {
+  // g2_pow[i] = g2 * secret^i, i <= max_set (at least g2 and [tau]_2), batched on the GPU like the G1 powers of `setup`
+  const size_t n2 = std::max<size_t>(max_set, 1) + 1;
+  std::vector<Fr> pw(n2);
+  Fr acc = Fr::one();
+  for (size_t i = 0; i < n2; i++) { pw[i] = acc; acc = acc * secret; }
+  std::vector<G2> g2s(n2);
+  G2 g2 = g2_generator(*dev);
+  dev->check(keaki_hip_g2_mul_batch(dev->ctx(), g2.w.data(), 0, pw[0].l, n2, g2s[0].w.data()));
+  KZGSetup s = setup(std::move(dev), secret, max_d);
+  s.g2_pow_ = std::move(g2s);
+  return s;
+}
+keaki_hip_srs_g2* KZGSetup::srs_g2() const {
+  if (g2_pow_.empty()) throw SetError("this KZGSetup holds no G2 powers: build it with setup_with_g2, from_powers_g2 or new_from_file_g2");
+  if (!srs_g2_) dev_->check(keaki_hip_srs_g2_upload(dev_->ctx(), g2_pow_[0].w.data(), g2_pow_.size(), &srs_g2_));
+  return srs_g2_;
+}
+
+// ---- set openings ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+// the device library does not look for repeated points: this layer does (sort a copy, compare neighbours)
+void check_set(const char* what, const std::vector<Fr>& points, size_t n_values) {
+  if (points.empty() || points.size() > (size_t)KEAKI_SET_MAX) throw SetError(std::string(what) + ": a set holds 1 .. " + std::to_string((int)KEAKI_SET_MAX) + " points");
+  if (n_values != points.size()) throw SetError(std::string(what) + ": one value (or proof) per point");
+  std::vector<std::array<uint64_t, 4>> z(points.size());
+  for (size_t i = 0; i < z.size(); i++) z[i] = {points[i].l[3], points[i].l[2], points[i].l[1], points[i].l[0]};
+  std::sort(z.begin(), z.end());
+  if (std::adjacent_find(z.begin(), z.end()) != z.end()) throw SetError(std::string(what) + ": repeated point in the set");
+}
+}  // namespace
+Result<std::pair<G1, std::vector<Fr>>> open_set(const KZGSetup& setup, const DensePolynomial& p_in, const std::vector<Fr>& points) {
+  typedef Result<std::pair<G1, std::vector<Fr>>> Res;
+  check_set("open_set", points, points.size());
+  DensePolynomial p = p_in;
+  trim(p);
+  const size_t qlen = p.size() > 1 ? p.size() - 1 : 0;
+  if (qlen > setup.g1_pow().size()) return Res::Err(KZGError{KZGError::PolynomialTooLarge, qlen, setup.g1_pow().size()});
+  uint64_t jac[12];
+  std::vector<Fr> values(points.size());
+  setup.device()->check(keaki_hip_kzg_open_multi(setup.device()->ctx(), setup.srs(), p.empty() ? nullptr : p[0].l, p.size(), points[0].l, points.size(), jac, values[0].l));
+  return Res::Ok({jac_to_g1(jac), std::move(values)});
+}
+bool verify_set(const KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points, const std::vector<Fr>& values, const G1& proof) {
+  check_set("verify_set", points, values.size());
+  const Device& dev = *setup.device();
+  int32_t ok = 0;
+  dev.check(keaki_hip_kzg_verify_multi(dev.ctx(), setup.srs(), setup.srs_g2(), commitment.w.data(), points[0].l, values[0].l, points.size(), proof.w.data(), &ok, nullptr));
+  return ok != 0;
+}
+G1 aggregate_proofs(const KZGSetup& setup, const std::vector<Fr>& points, const std::vector<G1>& proofs) {
+  check_set("aggregate_proofs", points, proofs.size());
+  uint64_t jac[12];
+  setup.device()->check(keaki_hip_kzg_aggregate(setup.device()->ctx(), points[0].l, proofs[0].w.data(), points.size(), jac));
+  return jac_to_g1(jac);
+}
+std::pair<G1, G2> set_pair(const KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points, const std::vector<Fr>& values) {
+  check_set("set_pair", points, values.size());
+  // keaki_hip_kzg_verify_multi hands out the two points its predicate is evaluated on; the proof slot takes any curve point (the verdict is not used)
+  const Device& dev = *setup.device();
+  int32_t ok = 0;
+  uint64_t pair[24];
+  G1 any = g1_generator();
+  dev.check(keaki_hip_kzg_verify_multi(dev.ctx(), setup.srs(), setup.srs_g2(), commitment.w.data(), points[0].l, values[0].l, points.size(), any.w.data(), &ok, pair));
+  std::pair<G1, G2> out;
+  memcpy(out.first.w.data(), pair, 64);
+  memcpy(out.second.w.data(), pair + 8, 128);
+  return out;
 }
 
 Result<G1> commit(const KZGSetup& setup, const DensePolynomial& p) {
@@ -470,6 +550,23 @@ std::vector<uint8_t> decapsulate(const kzg::KZGSetup& setup, const G1& proof, co
   return key;
 }
 
+namespace {
+// (ct, key) for the pair (A, Zq) = (C - [I]_1, [Z]_2) and the scalar r: ct = r Zq, key = KDF(e(r A, g2)), from the library's existing entries
+std::pair<G2, std::vector<uint8_t>> encap_pair(const kzg::KZGSetup& setup, const std::pair<G1, G2>& az, const Fr& r, size_t msg_len) {
+  const Device& dev = *setup.device();
+  G2 ct; G1 pt;
+  dev.check(keaki_hip_g2_mul_batch(dev.ctx(), az.second.w.data(), 0, r.l, 1, ct.w.data()));
+  dev.check(keaki_hip_g1_mul_batch(dev.ctx(), az.first.w.data(), 0, r.l, 1, pt.w.data()));
+  return {ct, decapsulate(setup, pt, g2_generator(dev), msg_len)};
+}
+}  // namespace
+std::pair<G2, std::vector<uint8_t>> encapsulate_set(Rng& rng, const kzg::KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points,
+                                                    const std::vector<Fr>& values, size_t msg_len) {
+  const std::pair<G1, G2> az = kzg::set_pair(setup, commitment, points, values);      // throws before the draw: a refused call leaves `rng` alone
+  const Fr r = fr_rand(rng);
+  return encap_pair(setup, az, r, msg_len);
+}
+
 void prepare(const kzg::KZGSetup& setup, size_t batch_hint) {
   const Device& dev = *setup.device();
   if (dev.group() && batch_hint >= GROUP_MIN_ITEMS) {
@@ -488,6 +585,13 @@ void prepare(const kzg::KZGSetup& setup, size_t batch_hint) {
 namespace enc {
 Ciphertext encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr& point, const Fr& value, const std::vector<uint8_t>& msg) {
   auto kc = kem::encapsulate(rng, setup, com, point, value, msg.size());
+  std::vector<uint8_t> ct(msg.size());
+  for (size_t i = 0; i < msg.size(); i++) ct[i] = kc.second[i] ^ msg[i];
+  return {kc.first, ct};
+}
+Ciphertext encrypt_set(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points, const std::vector<Fr>& values,
+                       const std::vector<uint8_t>& msg) {
+  auto kc = kem::encapsulate_set(rng, setup, com, points, values, msg.size());
   std::vector<uint8_t> ct(msg.size());
   for (size_t i = 0; i < msg.size(); i++) ct[i] = kc.second[i] ^ msg[i];
   return {kc.first, ct};
@@ -859,6 +963,75 @@ void vec_encrypt_batch(Rng& rng, const kzg::KZGSetup& setup, const G1* coms, con
     std::vector<uint8_t> gt_unused(n * 384);       // the ABI wants at least one of gt / key
     dev.check(keaki_hip_encap_multi(dev.ctx(), cw.data(), offsets.data(), m, setup.tau_g2().w.data(), points[0].l, values[0].l, rs[0].l, n, ct_g2_out,
                                     gt_unused.data(), nullptr, 0));
+  }
+}
+namespace {
+std::vector<Fr> subset_points(size_t domain_size, const std::vector<size_t>& idx, const char* what) {
+  const Radix2Domain dom = Radix2Domain::create(domain_size);
+  std::vector<Fr> z(idx.size());
+  for (size_t j = 0; j < idx.size(); j++) {
+    if (idx[j] >= dom.size) throw kzg::SetError(std::string(what) + ": index outside the domain");
+    z[j] = dom.group_gen.pow(idx[j]);
+  }
+  return z;            // a repeated index is a repeated point: the kzg layer refuses it
+}
+}  // namespace
+G1 vec_open_subset(const kzg::KZGSetup& setup, size_t domain_size, const std::vector<size_t>& idx, const std::vector<G1>& proofs) {
+  const std::vector<Fr> z = subset_points(domain_size, idx, "vec_open_subset");
+  std::vector<G1> sel(idx.size());
+  for (size_t j = 0; j < idx.size(); j++) {
+    if (idx[j] >= proofs.size()) throw kzg::SetError("vec_open_subset: no proof for an index");
+    sel[j] = proofs[idx[j]];
+  }
+  return kzg::aggregate_proofs(setup, z, sel);
+}
+bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const std::vector<Fr>& values, const G1& proof) {
+  return kzg::verify_set(setup, com, subset_points(domain_size, idx, "vec_verify_subset"), values, proof);
+}
+void vec_encrypt_subset_batch(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const Fr* values,
+                              size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  const Device& dev = *setup.device();
+  const size_t k = idx.size();
+  const std::vector<Fr> z = subset_points(domain_size, idx, "vec_encrypt_subset_batch");
+  if (!n) return;
+  // [Z]_2 (and the argument checks: set size, repeated index, G2 powers) from the first tuple's pair
+  const std::pair<G1, G2> az0 = kzg::set_pair(setup, com, z, std::vector<Fr>(values, values + k));
+  if (dev.group()) throw kzg::SetError("vec_encrypt_subset_batch: single device only");
+  // Z and the weights once; q_j = Z / (x - z_j) on the host; row i = -I_i = -sum_j (y_ij c_j) q_j
+  std::vector<Fr> zc(k + 1), w(k);
+  dev.check(keaki_hip_kzg_set_polys(dev.ctx(), z[0].l, nullptr, k, zc[0].l, w[0].l, nullptr));
+  std::vector<Fr> q(k * k);
+  for (size_t j = 0; j < k; j++) {
+    Fr carry = Fr::one();                                  // q_(k-1) = Z_k = 1, q_(t-1) = Z_t + z_j q_t
+    for (size_t t = k; t-- > 0;) { q[j * k + t] = carry; carry = zc[t] + z[j] * carry; }
+  }
+  std::vector<Fr> rows(n * k);
+  for (size_t i = 0; i < n; i++)
+    for (size_t j = 0; j < k; j++) {
+      const Fr sj = -(values[i * k + j] * w[j]);
+      for (size_t t = 0; t < k; t++) rows[i * k + t] = rows[i * k + t] + sj * q[j * k + t];
+    }
+  std::vector<uint64_t> jac(n * 12), coms(n * 8);
+  dev.check(keaki_hip_msm_g1_batch(dev.ctx(), setup.srs(), rows[0].l, k, n, k, jac.data()));
+  uint64_t two[24], sum[12];
+  const G1 one = g1_generator();                            // its x is the Montgomery form of 1
+  if (com.is_zero()) { memcpy(two, one.w.data(), 32); memcpy(two + 4, one.w.data(), 32); memset(two + 8, 0, 32); }
+  else { memcpy(two, com.w.data(), 64); memcpy(two + 8, one.w.data(), 32); }
+  for (size_t i = 0; i < n; i++) {
+    memcpy(two + 12, &jac[12 * i], 96);
+    dev.check(keaki_hip_g1_sum(dev.ctx(), two, 2, sum));
+    const G1 ci = jac_to_g1(sum);
+    memcpy(&coms[8 * i], ci.w.data(), 64);
+  }
+  std::vector<Fr> rs(n), zeros(n);
+  for (size_t i = 0; i < n; i++) rs[i] = fr_rand(rng);      // one r per item in index order, as everywhere else
+  std::vector<uint64_t> offsets(n + 1);
+  for (size_t i = 0; i <= n; i++) offsets[i] = i;
+  if (msg_len) {
+    dev.check(keaki_hip_encrypt_multi(dev.ctx(), coms.data(), offsets.data(), n, az0.second.w.data(), zeros[0].l, zeros[0].l, rs[0].l, msgs, n, ct_g2_out, ct_msg_out, msg_len));
+  } else {
+    std::vector<uint8_t> gt_unused(n * 384);
+    dev.check(keaki_hip_encap_multi(dev.ctx(), coms.data(), offsets.data(), n, az0.second.w.data(), zeros[0].l, zeros[0].l, rs[0].l, n, ct_g2_out, gt_unused.data(), nullptr, 0));
   }
 }
 void vec_decrypt_flat(const kzg::KZGSetup& setup, const uint64_t* proofs, const uint64_t* ct_g2, const uint8_t* ct_msgs, size_t n, size_t msg_len,

@@ -127,6 +127,15 @@ class KZGSetup {
   static KZGSetup setup(std::shared_ptr<Device> dev, const Fr& secret, size_t max_d);
   // from already-known powers (what new_from_file produces after parsing; the .ptau parser itself is out of scope)
   static KZGSetup from_powers(std::shared_ptr<Device> dev, std::vector<G1> g1_aff, const G2& tau_g2);
+  // The same with the OPTIONAL G2 powers the set openings need (open_set .. vec_encrypt_subset_batch below): g2_pow[i] = [tau^i]_2, so
+  // g2_pow[0] = g2, g2_pow[1] = tau_g2, and a set of k points needs k + 1 of them. setup_with_g2 produces [secret^i]_2 for i <= max_set on the
+  // device (one g2_mul_batch); from_powers_g2 takes what a ceremony file holds (new_from_file_g2, ptau.hpp, keeps all of its section 3).
+  // setup, from_powers and new_from_file are unchanged and carry no G2 powers: a set call on such a setup throws, it never falls back.
+  static KZGSetup setup_with_g2(std::shared_ptr<Device> dev, const Fr& secret, size_t max_d, size_t max_set);
+  static KZGSetup from_powers_g2(std::shared_ptr<Device> dev, std::vector<G1> g1_aff, std::vector<G2> g2_pow);
+  bool has_g2_powers() const { return !g2_pow_.empty(); }
+  const std::vector<G2>& g2_pow() const { return g2_pow_; }
+  keaki_hip_srs_g2* srs_g2() const;          // device handle of g2_pow on (member 0 of) the device, uploaded on first use; throws without G2 powers
   ~KZGSetup();
   KZGSetup(KZGSetup&&) noexcept;
   KZGSetup(const KZGSetup&) = delete;
@@ -155,6 +164,8 @@ class KZGSetup {
   mutable keaki_hip_group_fk* gfk_ = nullptr;
   mutable unsigned gfk_log2d_ = 0;
   bool tables_ = false;
+  std::vector<G2> g2_pow_;                      // empty: no set openings on this setup
+  mutable keaki_hip_srs_g2* srs_g2_ = nullptr;
   mutable keaki_hip_srs_g1* chunk_ = nullptr;
   mutable size_t chunk_lo_ = 0, chunk_hi_ = 0;
 };
@@ -202,6 +213,19 @@ std::vector<uint8_t> proofs_to_bytes(const KZGSetup& setup, const std::vector<G1
 std::vector<G1> proofs_from_bytes(const KZGSetup& setup, const std::vector<uint8_t>& bytes);
 void proofs_to_bytes_flat(const KZGSetup& setup, const uint64_t* proofs, size_t n, uint8_t* wire_out);
 void proofs_from_bytes_flat(const KZGSetup& setup, const uint8_t* wire, size_t n, uint64_t* proofs_out);
+// ---- set openings (no counterpart in the reference: its open / verify take one point; the batch opening of the KZG paper) -----------------
+// ONE proof pi_S = [((p - I) / Z)(tau)]_1 for the k <= KEAKI_SET_MAX points, Z = prod (x - z_j), I the interpolant of the values; checked by
+// e(C - [I(tau)]_1, g2) == e(pi_S, [Z(tau)]_2). The device library does not look for repeated points (a repeat makes the weights meaningless):
+// THIS layer refuses them -- every function below sorts a copy of the points and throws SetError when two are equal -- and it throws SetError
+// on a setup without G2 powers (verify_set and everything that encrypts; open_set and aggregate_proofs need none). Single device or member 0.
+struct SetError : std::invalid_argument { using std::invalid_argument::invalid_argument; };
+// (proof, the k values p(z_j)) in one device call (keaki_hip_kzg_open_multi). PolynomialTooLarge as `open` raises it.
+Result<std::pair<G1, std::vector<Fr>>> open_set(const KZGSetup& setup, const DensePolynomial& p, const std::vector<Fr>& points);
+bool verify_set(const KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points, const std::vector<Fr>& values, const G1& proof);
+// pi_S = sum_j c_j pi_j from the k single proofs, without the polynomial (keaki_hip_kzg_aggregate): byte for byte open_set's proof
+G1 aggregate_proofs(const KZGSetup& setup, const std::vector<Fr>& points, const std::vector<G1>& proofs);
+// what the set ciphertexts are made of: (C - [I(tau)]_1, [Z(tau)]_2) for the tuple (points, values); two small MSMs and one sum on the device
+std::pair<G1, G2> set_pair(const KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points, const std::vector<Fr>& values);
 // all openings at the roots of unity of a size-d domain (src/kzg.rs:157-203): FK23 -- three G1 FFTs + 2d scalar-mults on
 // the GPU (keaki_hip_open_fk) when p.size() == domain_size is a power of two; per-point `open` otherwise.
 Result<std::vector<G1>> open_fk(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size);
@@ -218,12 +242,20 @@ std::vector<uint8_t> decapsulate(const kzg::KZGSetup& setup, const G1& proof, co
 // setup-time (optional): the tables of encapsulation that depend on the setup only (generators, [tau]_2, e(g1, g2)), for batches of
 // `batch_hint` items per call -- on every member of a group device for its share. Like the SRS window tables: results never depend on it.
 void prepare(const kzg::KZGSetup& setup, size_t batch_hint);
+// Witness encryption to a SET claim: readable by whoever holds the set proof of `commitment` for (points, values). Draws ONE Fr::rand for r;
+// ct = r [Z(tau)]_2 (g2_mul_batch), key = KDF(e(r (C - [I(tau)]_1), g2)) (g1_mul_batch, then decap_batch against g2). One G2 point whatever k is.
+// Decapsulation is the UNCHANGED decapsulate(setup, pi_S, ct, msg_len) above: e(pi_S, r [Z]_2) is the same GT element; there is no second function.
+std::pair<G2, std::vector<uint8_t>> encapsulate_set(Rng& rng, const kzg::KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points,
+                                                    const std::vector<Fr>& values, size_t msg_len);
 }  // namespace kem
 
 namespace enc {
 using Ciphertext = std::pair<G2, std::vector<uint8_t>>;  // src/enc.rs:13
 Ciphertext encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr& point, const Fr& value, const std::vector<uint8_t>& msg);
 std::vector<uint8_t> decrypt(const kzg::KZGSetup& setup, const G1& proof, const Ciphertext& ct);
+// encapsulate_set plus the XOR; decryption is the unchanged decrypt(setup, pi_S, ct)
+Ciphertext encrypt_set(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points, const std::vector<Fr>& values,
+                       const std::vector<uint8_t>& msg);
 // Ciphertexts on the wire: n x (64 B compressed G2 point + body), the point as ark-serialize `serialize_compressed` writes it
 // (include/keaki_hip.h: compressed point wire format), all bodies of one length. The points are compressed / decompressed on the device in one
 // call. `ciphertexts_from_bytes` VALIDATES like `deserialize_compressed`: canonical encoding, on the twist, in the order-r subgroup (the points
@@ -279,6 +311,16 @@ bool vec_verify_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const 
 // kzg::verify_each over the same items: out[i] = 0 iff proof i opens `com` to v[i] at omega^i. No draws.
 std::vector<uint8_t> vec_verify_each(const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& v, const std::vector<G1>& proofs);
 size_t vec_verify_each_flat(const kzg::KZGSetup& setup, const G1& com, const Fr* v, size_t n, const uint64_t* proofs, uint8_t* status_out);
+// ---- subsets of a committed vector: the set openings at the points omega^idx of Radix2Domain::create(domain_size) ---------------------------
+// The holder of vec_commit's d proofs aggregates the k of them at idx (distinct, < domain_size) into one set proof, without the vector.
+G1 vec_open_subset(const kzg::KZGSetup& setup, size_t domain_size, const std::vector<size_t>& idx, const std::vector<G1>& proofs);
+bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const std::vector<Fr>& values, const G1& proof);
+// n items over ONE index set with different value tuples (the 1-of-2^k string-OT shape): item i is readable by the holder of a vector with
+// values[i * k + j] at idx[j] for all j. One r per item in index order. The rows -I_i come from ONE set_polys call and O(n k^2) host scalar
+// work, [-I_i(tau)]_1 from ONE msm_g1_batch (n rows of k coefficients), C is added by one g1_sum per item, then ONE encrypt_multi call with n
+// groups of one item, tau_g2 := [Z(tau)]_2, points = values = 0. Every item equals enc::encrypt_set alone with the same r. msgs: n x msg_len.
+void vec_encrypt_subset_batch(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const Fr* values,
+                              size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out);
 // src/vec.rs:52-69: one Fr::rand per item in index order, then ONE batched GPU call for all items
 std::vector<enc::Ciphertext> vec_encrypt(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points,
                                          const std::vector<Fr>& values, const std::vector<std::vector<uint8_t>>& messages);

@@ -33,6 +33,7 @@ template <class F>
 int guard(F&& f) {
   try { return f(); }
   catch (const HipError& e) { g_err = e.what(); return e.status; }
+  catch (const kzg::SetError& e) { g_err = e.what(); return 3; }          // a set call refused: repeated point, no G2 powers, bad sizes
   catch (const std::exception& e) { g_err = e.what(); return -1000; }
 }
 // bytes that do not decode (WireError): status 2, the index of the first rejected item and the reason in bad_out[0], [1]
@@ -197,6 +198,104 @@ int keaki_host_setup_from_file(int device, const char* path, void** out, uint64_
     auto r = kzg::new_from_file(dev, path);
     if (!r.ok) return file_err(r.error, err_out);
     *out = new Setup{dev, std::move(*r.setup)};
+    return 0;
+  });
+}
+// ---- set openings: setups with G2 powers (dev: a Device handle, or NULL for a context of its own on `device`) ----
+static std::shared_ptr<Device> dev_of(void* dev, int device) { return dev ? *(std::shared_ptr<Device>*)dev : std::make_shared<Device>(device); }
+int keaki_host_setup_with_g2(void* dev, int device, const uint64_t* secret, size_t max_d, size_t max_set, void** out) {
+  return guard([&] {
+    auto d = dev_of(dev, device);
+    *out = new Setup{d, kzg::KZGSetup::setup_with_g2(d, fr_of(secret), max_d, max_set)};
+    return 0;
+  });
+}
+int keaki_host_setup_from_powers_g2(void* dev, int device, const uint64_t* g1_aff, size_t n, const uint64_t* g2_pow, size_t n2, void** out) {
+  return guard([&] {
+    auto d = dev_of(dev, device);
+    std::vector<G1> pts(n);
+    for (size_t i = 0; i < n; i++) pts[i] = g1_of(g1_aff + 8 * i);
+    std::vector<G2> g2s(n2);
+    for (size_t i = 0; i < n2; i++) g2s[i] = g2_of(g2_pow + 16 * i);
+    *out = new Setup{d, kzg::KZGSetup::from_powers_g2(d, std::move(pts), std::move(g2s))};
+    return 0;
+  });
+}
+int keaki_host_setup_from_file_g2(int device, const char* path, void** out, uint64_t* err_out) {
+  return guard([&] {
+    auto dev = std::make_shared<Device>(device);
+    auto r = kzg::new_from_file_g2(dev, path);
+    if (!r.ok) return file_err(r.error, err_out);
+    *out = new Setup{dev, std::move(*r.setup)};
+    return 0;
+  });
+}
+size_t keaki_host_setup_g2_len(void* s) { return ((Setup*)s)->s.g2_pow().size(); }
+void keaki_host_setup_g2_all(void* s, uint64_t* out) {
+  const auto& v = ((Setup*)s)->s.g2_pow();
+  for (size_t i = 0; i < v.size(); i++) memcpy(out + 16 * i, v[i].w.data(), 128);
+}
+static std::vector<size_t> idx_of(const uint64_t* idx, size_t k) { return std::vector<size_t>(idx, idx + k); }
+int keaki_host_open_set(void* s, const uint64_t* coeffs, size_t n, const uint64_t* points, size_t k, uint64_t* out_g1, uint64_t* values_out, uint64_t* err_out) {
+  return guard([&] {
+    auto r = kzg::open_set(((Setup*)s)->s, frs_of(coeffs, n), frs_of(points, k));
+    if (!r.ok) return kzg_err(r.error, err_out);
+    memcpy(out_g1, r.value.first.w.data(), 64);
+    for (size_t j = 0; j < k; j++) memcpy(values_out + 4 * j, r.value.second[j].l, 32);
+    return 0;
+  });
+}
+int keaki_host_verify_set(void* s, const uint64_t* com, const uint64_t* points, const uint64_t* values, size_t k, const uint64_t* proof, int* out_ok) {
+  return guard([&] { *out_ok = kzg::verify_set(((Setup*)s)->s, g1_of(com), frs_of(points, k), frs_of(values, k), g1_of(proof)) ? 1 : 0; return 0; });
+}
+int keaki_host_aggregate_proofs(void* s, const uint64_t* points, const uint64_t* proofs, size_t k, uint64_t* out_g1) {
+  return guard([&] {
+    std::vector<G1> pr(k);
+    for (size_t j = 0; j < k; j++) pr[j] = g1_of(proofs + 8 * j);
+    G1 r = kzg::aggregate_proofs(((Setup*)s)->s, frs_of(points, k), pr);
+    memcpy(out_g1, r.w.data(), 64);
+    return 0;
+  });
+}
+int keaki_host_encapsulate_set(void* rng, void* s, const uint64_t* com, const uint64_t* points, const uint64_t* values, size_t k, size_t msg_len,
+                               uint64_t* ct_out, uint8_t* key_out) {
+  return guard([&] {
+    auto r = kem::encapsulate_set(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), frs_of(points, k), frs_of(values, k), msg_len);
+    memcpy(ct_out, r.first.w.data(), 128);
+    if (msg_len) memcpy(key_out, r.second.data(), msg_len);
+    return 0;
+  });
+}
+int keaki_host_encrypt_set(void* rng, void* s, const uint64_t* com, const uint64_t* points, const uint64_t* values, size_t k, const uint8_t* msg, size_t len,
+                           uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  return guard([&] {
+    auto c = enc::encrypt_set(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), frs_of(points, k), frs_of(values, k), std::vector<uint8_t>(msg, msg + len));
+    memcpy(ct_g2_out, c.first.w.data(), 128);
+    if (len) memcpy(ct_msg_out, c.second.data(), len);
+    return 0;
+  });
+}
+int keaki_host_vec_open_subset(void* s, size_t domain_size, const uint64_t* idx, size_t k, const uint64_t* proofs, size_t n_proofs, uint64_t* out_g1) {
+  return guard([&] {
+    std::vector<G1> pr(n_proofs);
+    for (size_t j = 0; j < n_proofs; j++) pr[j] = g1_of(proofs + 8 * j);
+    G1 r = vec::vec_open_subset(((Setup*)s)->s, domain_size, idx_of(idx, k), pr);
+    memcpy(out_g1, r.w.data(), 64);
+    return 0;
+  });
+}
+int keaki_host_vec_verify_subset(void* s, const uint64_t* com, size_t domain_size, const uint64_t* idx, const uint64_t* values, size_t k, const uint64_t* proof,
+                                 int* out_ok) {
+  return guard([&] {
+    *out_ok = vec::vec_verify_subset(((Setup*)s)->s, g1_of(com), domain_size, idx_of(idx, k), frs_of(values, k), g1_of(proof)) ? 1 : 0;
+    return 0;
+  });
+}
+int keaki_host_vec_encrypt_subset_batch(void* rng, void* s, const uint64_t* com, size_t domain_size, const uint64_t* idx, size_t k, const uint64_t* values, size_t n,
+                                        const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  return guard([&] {
+    const std::vector<Fr> v = frs_of(values, n * k);
+    vec::vec_encrypt_subset_batch(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), domain_size, idx_of(idx, k), v.data(), n, msgs, msg_len, ct_g2_out, ct_msg_out);
     return 0;
   });
 }

@@ -135,7 +135,7 @@ FileResult<PowersOfTau> get_powers_from_file(const std::string& path) {
 
 #ifndef KEAKI_PTAU_PARSE_ONLY          /* the sanitizer harness (ptau_fuzz_main.cpp) builds the parser alone: no GPU library behind it */
 namespace kzg {
-FileSetup new_from_file(std::shared_ptr<Device> dev, const std::string& path) {
+static FileSetup from_file(std::shared_ptr<Device> dev, const std::string& path, bool keep_g2) {
   auto fail = [](ptau::SetupFileError e) { return FileSetup{false, nullptr, std::move(e)}; };
   auto pw = ptau::get_powers_from_file(path);
   if (!pw.ok) return fail(pw.error);
@@ -144,11 +144,14 @@ FileSetup new_from_file(std::shared_ptr<Device> dev, const std::string& path) {
   uint64_t bad = 0, first = 0;
   dev->check(keaki_hip_g2_check(dev->ctx(), pw.value.g2[0].w.data(), pw.value.g2.size(), &bad, &first));
   if (bad) return fail(ptau::SetupFileError{ptau::SetupFileError::OffCurve, bad, first, "3 (tauG2)"});
-  auto s = std::make_unique<KZGSetup>(KZGSetup::from_powers(dev, std::move(pw.value.g1), pw.value.g2[1]));
+  auto s = std::make_unique<KZGSetup>(keep_g2 ? KZGSetup::from_powers_g2(dev, std::move(pw.value.g1), std::move(pw.value.g2))
+                                                  : KZGSetup::from_powers(dev, std::move(pw.value.g1), pw.value.g2[1]));
   dev->check(keaki_hip_srs_g1_check(dev->ctx(), s->srs(), &bad, &first));
   if (bad) return fail(ptau::SetupFileError{ptau::SetupFileError::OffCurve, bad, first, "2 (tauG1)"});
   return FileSetup{true, std::move(s), ptau::SetupFileError{ptau::SetupFileError::FileError, 0, 0, ""}};
 }
+FileSetup new_from_file(std::shared_ptr<Device> dev, const std::string& path) { return from_file(std::move(dev), path, false); }
+FileSetup new_from_file_g2(std::shared_ptr<Device> dev, const std::string& path) { return from_file(std::move(dev), path, true); }
 }  // namespace kzg
 #endif
 }  // namespace keaki

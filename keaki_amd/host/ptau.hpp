@@ -66,5 +66,7 @@ struct FileSetup {          // Result<KZGSetup, SetupFileError>
   ptau::SetupFileError error;
 };
 FileSetup new_from_file(std::shared_ptr<Device> dev, const std::string& path);
+// the same, keeping ALL of section 3 ([tau^i]_2, 2^power points) as the setup's G2 powers: what the set openings need (KZGSetup::from_powers_g2)
+FileSetup new_from_file_g2(std::shared_ptr<Device> dev, const std::string& path);
 }  // namespace kzg
 }  // namespace keaki

@@ -27,6 +27,10 @@ class KZGError(Exception):
         return isinstance(other, KZGError) and self.args_tuple == other.args_tuple
 
 
+class SetError(ValueError):
+    """a set call refused by the host layer: a repeated point (or index), a setup without G2 powers, 0 or more than 1,024 points, mismatched lengths"""
+
+
 class KeakiHostError(RuntimeError):
     pass
 
@@ -70,6 +74,8 @@ def _lib():
         lib.keaki_host_domain.argtypes = [C.c_size_t, C.c_void_p]
         lib.keaki_host_setup_len.restype = C.c_size_t
         lib.keaki_host_setup_len.argtypes = [C.c_void_p]
+        lib.keaki_host_setup_g2_len.restype = C.c_size_t
+        lib.keaki_host_setup_g2_len.argtypes = [C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -88,6 +94,8 @@ def _ck(st, err=None):
         return
     if st == 1 and err is not None:
         raise KZGError(int(err[0]), int(err[1]))
+    if st == 3:
+        raise SetError(_lib().keaki_host_last_error().decode())
     if st == 2 and err is not None:
         raise SetupFileError(int(err[0]), int(err[1]), int(err[2]), _lib().keaki_host_last_error().decode())
     raise KeakiHostError(f"status {st}: {_lib().keaki_host_last_error().decode()}")
@@ -280,6 +288,36 @@ class KZGSetup:
         _ck(_lib().keaki_host_setup_from_file(device, os.fsencode(path), C.byref(h), _p(err)), err)
         return KZGSetup(h)
 
+    @staticmethod
+    def setup_with_g2(secret, max_d: int, max_set: int, device=0) -> "KZGSetup":
+        """`setup` plus the G2 powers [secret^i]_2, i <= max_set, which the set openings need (open_set .. vec_encrypt_subset_batch)"""
+        h = C.c_void_p(); on = isinstance(device, Device)
+        _ck(_lib().keaki_host_setup_with_g2(device.h if on else None, 0 if on else device, _p(_u64(secret)), C.c_size_t(max_d), C.c_size_t(max_set), C.byref(h)))
+        return KZGSetup(h)
+
+    @staticmethod
+    def from_powers_g2(g1_aff, g2_pow, device=0) -> "KZGSetup":
+        """g2_pow[i] = [tau^i]_2 (g2_pow[0] = g2, g2_pow[1] = tau_g2): a set of k points needs k + 1 of them"""
+        pts = _u64(g1_aff, 8); g2s = _u64(g2_pow, 16); h = C.c_void_p(); on = isinstance(device, Device)
+        _ck(_lib().keaki_host_setup_from_powers_g2(device.h if on else None, 0 if on else device, _p(pts), C.c_size_t(pts.shape[0]), _p(g2s),
+                                                   C.c_size_t(g2s.shape[0]), C.byref(h)))
+        return KZGSetup(h)
+
+    @staticmethod
+    def new_from_file_g2(path: str, device: int = 0) -> "KZGSetup":
+        """new_from_file that keeps ALL of section 3 of the .ptau ([tau^i]_2) as the setup's G2 powers"""
+        h = C.c_void_p(); err = np.zeros(3, np.uint64)
+        _ck(_lib().keaki_host_setup_from_file_g2(device, os.fsencode(path), C.byref(h), _p(err)), err)
+        return KZGSetup(h)
+
+    def g2_pow(self) -> np.ndarray:
+        """the G2 powers (n, 16); empty for a setup made by setup / from_powers / new_from_file"""
+        n = _lib().keaki_host_setup_g2_len(self.h)
+        out = np.zeros((n, 16), np.uint64)
+        if n:
+            _lib().keaki_host_setup_g2_all(self.h, _p(out))
+        return out
+
     def g1_pow(self) -> np.ndarray:
         n = _lib().keaki_host_setup_len(self.h)
         out = np.zeros((n, 8), np.uint64)
@@ -363,6 +401,78 @@ def verify(setup: KZGSetup, commitment, point, value, proof) -> bool:
     ok = C.c_int(0)
     _ck(_lib().keaki_host_verify(setup.h, _p(_u64(commitment)), _p(_u64(point)), _p(_u64(value)), _p(_u64(proof)), C.byref(ok)))
     return bool(ok.value)
+
+
+# ---- set openings: ONE proof, one check, one ciphertext for k <= 1,024 DISTINCT points (this layer refuses repeats: SetError) ----
+def open_set(setup: KZGSetup, p, points):
+    """-> (proof u64[8], the k values p(z_j) (k, 4)) in one device call (kzg::open_set)"""
+    c = _u64(p, 4); z = _u64(points, 4); k = z.shape[0]
+    out = np.zeros(8, np.uint64); vals = np.zeros((max(k, 1), 4), np.uint64); err = np.zeros(2, np.uint64)
+    _ck(_lib().keaki_host_open_set(setup.h, _p(c), C.c_size_t(c.shape[0]), _p(z), C.c_size_t(k), _p(out), _p(vals), _p(err)), err)
+    return out, vals[:k]
+
+
+def verify_set(setup: KZGSetup, commitment, points, values, proof) -> bool:
+    z = _u64(points, 4); y = _u64(values, 4); ok = C.c_int(0)
+    if y.shape[0] != z.shape[0]:
+        raise SetError("verify_set: one value per point")
+    _ck(_lib().keaki_host_verify_set(setup.h, _p(_u64(commitment)), _p(z), _p(y), C.c_size_t(z.shape[0]), _p(_u64(proof)), C.byref(ok)))
+    return bool(ok.value)
+
+
+def aggregate_proofs(setup: KZGSetup, points, proofs) -> np.ndarray:
+    """the set proof from the k single proofs at the k points, without the polynomial: byte for byte open_set's"""
+    z = _u64(points, 4); pr = _u64(proofs, 8); out = np.zeros(8, np.uint64)
+    if pr.shape[0] != z.shape[0]:
+        raise SetError("aggregate_proofs: one proof per point")
+    _ck(_lib().keaki_host_aggregate_proofs(setup.h, _p(z), _p(pr), C.c_size_t(z.shape[0]), _p(out)))
+    return out
+
+
+def encapsulate_set(rng: "Rng", setup: KZGSetup, commitment, points, values, msg_len: int):
+    """(ct, key) readable by the holder of the set proof for (points, values); ONE draw from rng. Decapsulation: decapsulate(setup, set_proof, ct, msg_len)"""
+    z = _u64(points, 4); y = _u64(values, 4); ct = np.zeros(16, np.uint64); key = np.zeros(max(msg_len, 1), np.uint8)
+    if y.shape[0] != z.shape[0]:
+        raise SetError("encapsulate_set: one value per point")
+    _ck(_lib().keaki_host_encapsulate_set(rng.h, setup.h, _p(_u64(commitment)), _p(z), _p(y), C.c_size_t(z.shape[0]), C.c_size_t(msg_len), _p(ct), _p(key)))
+    return ct, key[:msg_len].tobytes()
+
+
+def encrypt_set(rng: "Rng", setup: KZGSetup, com, points, values, msg: bytes):
+    """encapsulate_set plus the XOR; decryption: decrypt(setup, set_proof, ct)"""
+    z = _u64(points, 4); y = _u64(values, 4)
+    if y.shape[0] != z.shape[0]:
+        raise SetError("encrypt_set: one value per point")
+    m = np.frombuffer(msg or b"\0", np.uint8).copy(); ct = np.zeros(16, np.uint64); out = np.zeros(max(len(msg), 1), np.uint8)
+    _ck(_lib().keaki_host_encrypt_set(rng.h, setup.h, _p(_u64(com)), _p(z), _p(y), C.c_size_t(z.shape[0]), _p(m), C.c_size_t(len(msg)), _p(ct), _p(out)))
+    return ct, out[:len(msg)].tobytes()
+
+
+def vec_open_subset(setup: KZGSetup, domain_size: int, idx, proofs) -> np.ndarray:
+    """one set proof for the positions idx of a committed vector, from the d proofs of vec_commit (points omega^idx)"""
+    ix = np.ascontiguousarray(idx, np.uint64); pr = _u64(proofs, 8); out = np.zeros(8, np.uint64)
+    _ck(_lib().keaki_host_vec_open_subset(setup.h, C.c_size_t(domain_size), _p(ix), C.c_size_t(ix.shape[0]), _p(pr), C.c_size_t(pr.shape[0]), _p(out)))
+    return out
+
+
+def vec_verify_subset(setup: KZGSetup, com, domain_size: int, idx, values, proof) -> bool:
+    ix = np.ascontiguousarray(idx, np.uint64); y = _u64(values, 4); ok = C.c_int(0)
+    if y.shape[0] != ix.shape[0]:
+        raise SetError("vec_verify_subset: one value per index")
+    _ck(_lib().keaki_host_vec_verify_subset(setup.h, _p(_u64(com)), C.c_size_t(domain_size), _p(ix), _p(y), C.c_size_t(ix.shape[0]), _p(_u64(proof)), C.byref(ok)))
+    return bool(ok.value)
+
+
+def vec_encrypt_subset_batch(rng: "Rng", setup: KZGSetup, com, domain_size: int, idx, values, messages: np.ndarray):
+    """n items over ONE index set with different value tuples: values (n, k, 4), messages (n, msg_len) uint8 -> (ct_g2 (n, 16), bodies (n, msg_len)).
+    Item i is readable by the holder of a vector with values[i, j] at idx[j] for every j; one r per item in index order."""
+    ix = np.ascontiguousarray(idx, np.uint64); k = ix.shape[0]
+    y = np.ascontiguousarray(values, np.uint64).reshape(-1, max(k, 1), 4); n = y.shape[0]
+    msgs = np.ascontiguousarray(messages, np.uint8).reshape(n, -1); ml = msgs.shape[1]
+    ct = np.zeros((n, 16), np.uint64); body = np.zeros((n, max(ml, 1)), np.uint8)
+    _ck(_lib().keaki_host_vec_encrypt_subset_batch(rng.h, setup.h, _p(_u64(com)), C.c_size_t(domain_size), _p(ix), C.c_size_t(k), _p(y), C.c_size_t(n),
+                                                   _p(msgs if ml else body), C.c_size_t(ml), _p(ct), _p(body)))
+    return ct, body[:, :ml]
 
 
 def _opening_args(what, commitments, points, values, proofs, roots_of_unity):

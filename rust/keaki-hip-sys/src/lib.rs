@@ -124,6 +124,22 @@ extern "C" {
                               proof_out_jac: *mut u64, value_out: *mut u64) -> keaki_status;
     pub fn keaki_hip_kzg_quotient(ctx: *mut keaki_hip_ctx, coeffs: *const u64, n: usize, point: *const u64, quotient_out: *mut u64,
                                   value_out: *mut u64) -> keaki_status;
+    // KZG set openings: one proof for k <= 1,024 DISTINCT points (the caller's contract). Z (k + 1 Fr), weights 1 / Z'(z_j), interpolant I |
+    // pi_S = [((p - I) / Z)(tau)]_1 and the k values | the same proof from the k single proofs | e(C - [I]_1, g2) == e(pi_S, [Z]_2)
+    pub fn keaki_hip_kzg_set_polys(ctx: *mut keaki_hip_ctx, points: *const u64, values: *const u64, k: usize, z_coeffs_out: *mut u64,
+                                   weights_out: *mut u64, i_coeffs_out: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_set_polys_dev(ctx: *mut keaki_hip_ctx, d_points: *const c_void, d_values: *const c_void, k: usize, d_z_coeffs_out: *mut c_void,
+                                       d_weights_out: *mut c_void, d_i_coeffs_out: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_kzg_open_multi(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, coeffs: *const u64, n: usize, points: *const u64, k: usize,
+                                    proof_out_jac: *mut u64, values_out: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_open_multi_dev(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, d_coeffs: *const c_void, n: usize, d_points: *const c_void,
+                                        k: usize, d_proof_out_jac: *mut c_void, d_values_out: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_kzg_aggregate(ctx: *mut keaki_hip_ctx, points: *const u64, proofs_aff: *const u64, k: usize, proof_out_jac: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_aggregate_dev(ctx: *mut keaki_hip_ctx, d_points: *const c_void, d_proofs_aff: *const c_void, k: usize,
+                                       d_proof_out_jac: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_multi(ctx: *mut keaki_hip_ctx, srs_g1: *const keaki_hip_srs_g1, srs_g2: *const keaki_hip_srs_g2, com_aff: *const u64,
+                                      points: *const u64, values: *const u64, k: usize, proof_aff: *const u64, ok_out: *mut i32,
+                                      pair_out_aff: *mut u64) -> keaki_status;
     // m rows over one SRS in one call (generalises commit, src/kzg.rs:89-101, and open, src/kzg.rs:104-124): row j = n Fr at + 4 * stride * j words
     pub fn keaki_hip_msm_g1_batch(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, scalars: *const u64, n: usize, m: usize, stride: usize,
                                   out_jac: *mut u64) -> keaki_status;

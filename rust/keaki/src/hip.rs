@@ -399,6 +399,39 @@ pub fn open(srs: &HipSrs, coeffs: &[Fr], point: &Fr) -> G1Projective {
 }
 const OPEN_HOST_QUOTIENT_MAX: usize = 8192;
 
+/// ONE proof for the k points (`keaki_hip_kzg_open_multi`): `[((p - I) / Z)(tau)]_1` and the k values `p(z_j)`. The points must be DISTINCT
+/// (1 ..= 1,024 of them): the device library does not look, so this function does (sort and compare), as the C++ host layer does.
+pub fn open_set(srs: &HipSrs, coeffs: &[Fr], points: &[Fr]) -> (G1Projective, Vec<Fr>) {
+    assert_distinct(points);
+    let dev = Device::global();
+    let mut out = [0u64; 12];
+    let mut values = vec![Fr::from(0u64); points.len()];
+    dev.check(
+        unsafe {
+            sys::keaki_hip_kzg_open_multi(dev.ctx, srs.srs(), fr_ptr(coeffs), coeffs.len(), fr_ptr(points), points.len(), out.as_mut_ptr(), values.as_mut_ptr() as *mut u64)
+        },
+        "kzg_open_multi",
+    );
+    (g1_from_jac(&out), values)
+}
+
+/// The same proof from the k single proofs at the k points, without the polynomial (`keaki_hip_kzg_aggregate`).
+pub fn aggregate_proofs(points: &[Fr], proofs: &[G1Projective]) -> G1Projective {
+    assert_eq!(points.len(), proofs.len());
+    assert_distinct(points);
+    let dev = Device::global();
+    let words: Vec<u64> = proofs.iter().flat_map(|p| g1_words(&p.into_affine())).collect();
+    let mut out = [0u64; 12];
+    dev.check(unsafe { sys::keaki_hip_kzg_aggregate(dev.ctx, fr_ptr(points), words.as_ptr(), points.len(), out.as_mut_ptr()) }, "kzg_aggregate");
+    g1_from_jac(&out)
+}
+
+fn assert_distinct(points: &[Fr]) {
+    let mut z: Vec<Fr> = points.to_vec();
+    z.sort();
+    assert!(!z.is_empty() && z.windows(2).all(|w| w[0] != w[1]), "a set opening needs 1 or more DISTINCT points");
+}
+
 pub fn verify(commitment: &G1Projective, tau_g2: &G2Projective, point: &Fr, value: &Fr, proof: &G1Projective) -> bool {
     let dev = Device::global();
     let (c, t, p) = (g1_words(&commitment.into_affine()), g2_words(&tau_g2.into_affine()), g1_words(&proof.into_affine()));
