@@ -106,7 +106,10 @@ const char* keaki_hip_version(void);
  * "pair_wide_max" (pairing batches up to this size run the twelve-lanes-per-pairing kernel; -1 = automatic (4096), 0 = never), "pair_two_waves"
  * (up to 1,024 pairings: the line side of the Miller loop on a second wave; 0 = one wave), "msm_short_tables" (an MSM over less than half of an SRS
  * with window tables: 0 = the generic path as before round 4, 1 / -1 = the tables), "vec_update_k_pass" (entries of the change list per pass of
- * keaki_hip_vec_update's proof kernel: 1 .. 8, 0 = the built-in 8; any other value is refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
+ * keaki_hip_vec_update's proof kernel: 1 .. 8, 0 = the built-in 8; any other value is refused with KEAKI_ERR_BAD_ARG, in the environment ignored),
+ * "fk_coset_group" (terms per Straus group of the FK23 coset openings' pointwise kernel: 1, 2 or 4, 0 = the built-in 4; 1 = one ladder per term, the A/B
+ * form), "fk_coset_min_lanes" (that kernel splits the terms of a position over lanes while its launch has fewer lanes than this: 1 .. 2^31, 0 = the
+ * built-in 131,072; other values of the two are refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
  * What the library does with HOST memory of the caller, and its off switches (round 5):
  *   "host_prefault" (default 1): while the kernels of a host-array call run, the library first-touches the caller's OUTPUT arrays (writes a zero
  *       into one byte per 4 KB page, the whole range being overwritten by the download that follows; outputs >= 1 MB only) and asks for transparent
@@ -129,7 +132,7 @@ keaki_status keaki_hip_ctx_set_option(keaki_hip_ctx* ctx, const char* name, int6
 /* Test hook: every single device allocation of this ctx above `bytes` fails with KEAKI_ERR_OOM (0 = no limit). This is how the tests
  * exercise the optional-memory fallbacks (SRS window tables, the wide GT table); nothing in the library sets it. */
 keaki_status keaki_hip_debug_set_alloc_limit(keaki_hip_ctx* ctx, size_t bytes);
-/* Device memory this ctx holds right now, bytes: out4[0] = window tables + FK23 transforms + vec_update tables of SRS handles built through this ctx (the
+/* Device memory this ctx holds right now, bytes: out4[0] = window tables + FK23 transforms + coset transforms + vec_update tables of SRS handles built through this ctx (the
  * points themselves belong to the caller's upload), [1] = grow-only workspaces, [2] = fixed-base / GT tables of encapsulate, [3] = total. */
 keaki_status keaki_hip_ctx_memory(keaki_hip_ctx* ctx, size_t* out4);
 /* Gives back every workspace and every fixed-base / GT table of the context (out4[1] and out4[2] drop to 0): for a long-lived process after
@@ -329,6 +332,45 @@ keaki_status keaki_hip_kzg_aggregate_dev(keaki_hip_ctx* ctx, const void* d_point
 keaki_status keaki_hip_kzg_verify_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
                                         const uint64_t* points, const uint64_t* values, size_t k, const uint64_t* proof_aff, int32_t* ok_out,
                                         uint64_t* pair_out_aff);
+
+/* ---- FK23 coset openings: all d / l set proofs of a vector in one call (FK20 / FK23 "multi-reveal") ------------------------------------------
+ * The set-opening counterpart of keaki_hip_open_fk_poly. p has d = 2^log2d coefficients, l = 2^log2l <= d, r = d / l. Coset i < r is the index set
+ * {i + t r : t < l} of the size-d evaluation domain: the l solutions of x^l = c_i, c_i = omega_r^i. Its proof is pi_i = [floor(p / (x^l - c_i))(tau)]_1,
+ * which is what keaki_hip_kzg_open_multi returns for those l points. All r proofs come out of one pass: the 2d scalar multiples that FK23 pays,
+ * summed l at a time into 2r points, then group transforms of size 2r and r instead of 2d and d (derivation: csrc/fk_coset.hip).
+ *   arguments  omega_2r: the generator of ark-poly's Radix2EvaluationDomain of size 2r (= omega_2d^l), omega_2r_inv its inverse, inv_2r = (2r)^-1; the
+ *              library derives omega_r and every twiddle on the device. coeffs: d Fr (a shorter polynomial is zero-padded by the caller). hat_a (the
+ *              raw form, for tests that choose the scalars): l rows of 2r Fr, row j at hat_a + 4 * 2r * j words in natural order, row j =
+ *              DFT_2r(r zeros, then f_(u l + j), u < r) with the (2r)^-1 folded in -- as keaki_hip_open_fk takes its hat_a.
+ *   results    proofs_out_aff: r affine points in natural order, (0, 0) for the identity; proof i belongs to c_i = omega_r^i and is byte for byte the
+ *              affine form of keaki_hip_kzg_open_multi on coset i. log2l = 0: the bytes of keaki_hip_open_fk_poly. r = 1: one identity, no transform runs.
+ *   errors     a null required pointer, log2l > log2d, log2d > 27, l > KEAKI_SET_MAX (so every proof can be checked by keaki_hip_kzg_verify_multi) ->
+ *              KEAKI_ERR_BAD_ARG; d > len(srs) -> KEAKI_ERR_TOO_LARGE; a refused cache or workspace -> KEAKI_ERR_OOM. Nothing is written in any of
+ *              these cases and the context stays usable.
+ *   cache      the l transforms of the SRS rows depend on (srs, d, l) only: 2d JACOBIAN points (192 B x d; the form the group transform leaves, the
+ *              ladder's table build reads any Z), built on first use or by keaki_hip_srs_g1_precompute_fk_cosets, cached in the SRS handle for ONE
+ *              (log2d, log2l) beside -- and never evicting -- the FK23 transform and the vec_update tables; another pair replaces them. Counted in
+ *              keaki_hip_ctx_memory out4[0], freed with the handle.
+ *   kernel     one lane per position q < 2r (or per slice of its l terms: below "fk_coset_min_lanes" lanes -- default 131,072: two resident waves per SIMD,
+ *              set from the threshold sweep of profiles/fk_coset_times.txt -- the terms of a position are split over S lanes and the partial sums added). A lane runs its terms in groups of G = 4 (option
+ *              "fk_coset_group": 1, 2, 4): GLV halves in signed 4-bit windows, G window tables of 1 KB in a lane-contiguous workspace on ONE working
+ *              curve, ONE chain of 129 doublings per group with 66 G mixed additions.
+ *   host form  one upload, the kernels, one download; returns only when nothing reads or writes caller memory.
+ *   _dev       d_coeffs and d_proofs_out_aff are device pointers (16-byte aligned), the domain constants stay host pointers (read before the call
+ *              returns); asynchronous on the ctx stream. Workspace grow-only, counted in keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim.
+ *   numbers    (MI355X, medians, one process, alternating rounds, cache warm: profiles/fk_coset_times.txt, bench_tools/bench_fk_coset.py) resident, l = 4 / 16 /
+ *              64: d = 2^20 82 / 48 / 42 ms against 200 for keaki_hip_open_fk_poly at the same d; 2^16 26 / 21 / 16 against 30; 2^12 16 / 12 / 10
+ *              against 67 (19 from host arrays); host arrays cost at most 1 ms more. The parent's routes for the same r proofs, extrapolated from 64
+ *              cosets: open_fk_poly + r aggregations 37 s and r open_multi calls 371 s at d = 2^20, l = 64. Cache build 32 - 835 ms (one transform per
+ *              row). At d = 2^20 the pointwise kernel takes 15 / 17 / 18 ms with G = 4 and 21 / 24 / 24 with one ladder per term; at d <= 2^16 its launch
+ *              is too small to fill the device and G = 1 is the faster form (1.5 against 2.1 ms of 16 - 26): the tail of small transforms dominates there. */
+keaki_status keaki_hip_srs_g1_precompute_fk_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* omega_2r);
+keaki_status keaki_hip_open_fk_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* hat_a, const uint64_t* omega_2r,
+                                      const uint64_t* omega_2r_inv, uint64_t* proofs_out_aff);
+keaki_status keaki_hip_open_fk_cosets_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* coeffs,
+                                           const uint64_t* omega_2r, const uint64_t* omega_2r_inv, const uint64_t* inv_2r, uint64_t* proofs_out_aff);
+keaki_status keaki_hip_open_fk_cosets_poly_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const void* d_coeffs,
+                                               const uint64_t* omega_2r, const uint64_t* omega_2r_inv, const uint64_t* inv_2r, void* d_proofs_out_aff);
 
 /* ---- batched commit and open: m polynomials over ONE SRS in one call ---------------------------------------------------------------------
  * Generalises `commit` (reference src/kzg.rs:89-101) and `open` (src/kzg.rs:104-124) from one polynomial to m rows. A single MSM costs

@@ -4,6 +4,7 @@
 #include "internal.h"
 #include "host_plan.h"
 #include "encap_multi_plan.h"
+#include "fk_coset_plan.h"
 
 #include <algorithm>
 #include <cctype>
@@ -35,7 +36,10 @@ struct FkCache { void* hat_s = nullptr; int log2d = -1; size_t bytes = 0; };
 // vec_update: the update tables of the last requested d (vec_update.hip: a | u | omega_d^-i | 1 / (omega_d^t - 1)), beside the FK23 transform and
 // independent of it. Owned by upd_cache_ensure under the same rules as FkCache.
 struct UpdCache { void* tab = nullptr; int log2d = -1; size_t bytes = 0; };
-struct keaki_hip_srs_g1 : SrsHandle { FkCache fk; UpdCache upd; };
+// FK23 coset openings: the l transforms hat_s_j = DFT_2r(row j of the SRS, reversed) of the last requested (d, l), 2d Jacobian points (fk_coset.hip), beside
+// the other two and independent of them. Owned by fkc_cache_ensure under the same rules as FkCache; (log2d, log2l) is the key.
+struct FkcCache { void* hat_s = nullptr; int log2d = -1, log2l = -1; size_t bytes = 0; };
+struct keaki_hip_srs_g1 : SrsHandle { FkCache fk; UpdCache upd; FkcCache fkc; };
 struct keaki_hip_srs_g2 : SrsHandle {};
 
 #include <dlfcn.h>
@@ -262,6 +266,73 @@ keaki_status open_fk_from_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32
   ST_TRY(open_fk_poly_scalars_run(ctx, log2d, d_p, omega_2d, omega_2d_inv, inv_2d, d_fr_work, &s));
   ST_TRY(fk_cache_ensure(ctx, srs, log2d, s.tw));
   return open_fk_run(ctx, srs->fk.hat_s, log2d, s.hat_a, s.tw, s.twi, d_g_work, d_proofs_aff);
+}
+// The ONE owner of a G1 handle's coset transforms (fk_coset.hip), as fk_cache_ensure is of its FK23 transform: afterwards srs->fkc.hat_s holds the l rows
+// for (d, l) = (2^log2d, 2^log2l), r = d / l >= 2. d_tw: omega_2r^k, k < r, ready in stream order; the caller holds srs->mu. Rows of another (d, l) are
+// dropped first, the new ones are named only once their build is enqueued in full. It touches neither srs->fk nor srs->upd.
+keaki_status fkc_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const void* d_tw) {
+  FkcCache& c = srs->fkc;
+  if (c.log2d == (int)log2d && c.log2l == (int)log2l) return KEAKI_OK;
+  auto book = [&](size_t now) {
+    const size_t before = c.bytes;
+    with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
+    c.bytes = now;
+  };
+  c.log2d = c.log2l = -1;
+  if (c.hat_s) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.hat_s); c.hat_s = nullptr; book(0); }
+  const size_t bytes = ((size_t)2 << log2d) * G1_JAC_BYTES;
+  ST_TRY(dev_alloc(ctx, &c.hat_s, bytes));
+  book(bytes);
+  ST_TRY(fkc_hat_s_run(ctx, srs->d, log2d, log2l, d_tw, c.hat_s));
+  c.log2d = (int)log2d; c.log2l = (int)log2l;
+  return KEAKI_OK;
+}
+// One call of the coset openings on device data. Exactly one of d_coeffs (d Fr) and d_hat_a (l rows of 2r Fr) is given; `host` stages it from the caller's
+// array and downloads the r proofs to proofs_out, else d_out receives them in stream order. Every allocation that can be refused (workspaces, the
+// handle's transforms) comes before the first copy and before any kernel that writes an output.
+void prefault_out(const keaki_hip_ctx* ctx, void* p, size_t bytes);
+struct FkcCall {
+  uint32_t log2d, log2l;
+  const uint64_t *omega_2r, *omega_2r_inv, *inv_2r;      // inv_2r: null for the raw hat_a form
+};
+keaki_status fkc_call(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const FkcCall& k, const void* coeffs, const void* hat_a, bool host, void* out) {
+  const uint32_t log2r = k.log2d - k.log2l, l = 1u << k.log2l;
+  const size_t d = (size_t)1 << k.log2d, r = (size_t)1 << log2r;
+  if (r == 1) {                                           // deg p < d = l: the one quotient is zero
+    if (host) { memset(out, 0, G1_AFF_BYTES); return KEAKI_OK; }
+    HIP_TRY(ctx, hipMemsetAsync(out, 0, G1_AFF_BYTES, ctx->stream));
+    return KEAKI_OK;
+  }
+  const FkcPlan plan = fkc_plan(2 * r, l, (uint32_t)ctx->tune.fk_coset_group, (uint64_t)ctx->tune.fk_coset_min_lanes);
+  // one block: scalar work | point work | host forms: coefficients (d Fr) and proofs (r affine)
+  const size_t o_fr = 0, o_g = o_fr + fkc_fr_bytes(k.log2d, k.log2l), o_in = o_g + fkc_g_bytes(k.log2d, k.log2l, plan), o_out = o_in + (host && coeffs ? d * 32 : 0),
+               total = o_out + (host ? r * G1_AFF_BYTES : 0);
+  ST_TRY(reserve(ctx, ctx->fc_work, total));
+  uint32_t per_launch = 0;
+  ST_TRY(fkc_reserve_tab(ctx, (size_t)plan.S * 2 * r, plan.G, &per_launch));
+  char* b = (char*)ctx->fc_work.p;
+  const FkcScalars s = fkc_layout(k.log2d, k.log2l, b + o_fr);
+  ST_TRY(fkc_tables_run(ctx, log2r, k.omega_2r, k.omega_2r_inv, s));
+  ST_TRY(fkc_cache_ensure(ctx, srs, k.log2d, k.log2l, s.tw));
+  CopyFeed feed(ctx);
+  const void* d_p = coeffs;
+  if (host && coeffs) { ST_TRY(feed.put(0, b + o_in, coeffs, d * 32)); d_p = b + o_in; }
+  if (hat_a) {
+    if (host) ST_TRY(feed.put(0, s.hat_a, hat_a, 2 * d * 32));
+    else HIP_TRY(ctx, hipMemcpyAsync(s.hat_a, hat_a, 2 * d * 32, hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    ST_TRY(fkc_scalars_run(ctx, k.log2d, k.log2l, d_p, k.inv_2r, s));
+  }
+  ST_TRY(fkc_open_run(ctx, srs->fkc.hat_s, k.log2d, k.log2l, s, plan, per_launch, b + o_g, host ? (void*)(b + o_out) : out));
+  if (!host) return KEAKI_OK;
+  prefault_out(ctx, out, r * G1_AFF_BYTES);
+  return download(feed, out, b + o_out, r * G1_AFF_BYTES);
+}
+// how the coset entries start: fk_enter's checks, and l = 2^log2l <= min(d, KEAKI_SET_MAX)
+keaki_status fkc_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, bool args_ok, const char* what,
+                       std::unique_lock<std::recursive_mutex>& hl) {
+  const bool l_ok = log2l <= log2d && log2l < 32 && ((uint64_t)1 << log2l) <= (uint64_t)KEAKI_SET_MAX;
+  return fk_enter(ctx, srs, log2d, args_ok && l_ok, what, hl);
 }
 
 // The caller's OUTPUT buffer is usually fresh memory (calloc / vec![0; n] / numpy.zeros): its pages do not exist until first touched, and a
@@ -495,7 +566,8 @@ void srs_free(keaki_hip_ctx* ctx, H* srs) {
   if constexpr (std::is_same_v<H, keaki_hip_srs_g1>) {
     if (srs->fk.hat_s) (void)hipFree(srs->fk.hat_s);
     if (srs->upd.tab) (void)hipFree(srs->upd.tab);
-    held += srs->fk.bytes + srs->upd.bytes;
+    if (srs->fkc.hat_s) (void)hipFree(srs->fkc.hat_s);
+    held += srs->fk.bytes + srs->upd.bytes + srs->fkc.bytes;
   }
   with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, held); });
   delete srs;
@@ -610,6 +682,16 @@ bool gt_wb_b_refuses(keaki_hip_ctx* ctx, const char*, long long v) {          //
   fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: gt_wb_b = %lld out of range", v);
   return true;
 }
+bool fk_coset_group_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v == 0 || v == 1 || v == 2 || v == 4) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: fk_coset_group = %lld must be 1, 2 or 4 (0 = %u)", v, FKC_G);
+  return true;
+}
+bool fk_coset_min_lanes_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= ((long long)1 << 31)) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: fk_coset_min_lanes = %lld out of range (1 .. 2^31; 0 = %u)", v, FKC_SPLIT_MIN_LANES);
+  return true;
+}
 bool vec_update_k_pass_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
   if (v >= 0 && v <= (long long)UPD_K_PASS) return false;
   if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: vec_update_k_pass = %lld out of range (1 .. %u; 0 = %u)", v, UPD_K_PASS, UPD_K_PASS);
@@ -624,6 +706,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(gt_wb_b, gt_wb_b_refuses, [](keaki_hip_ctx* ctx) { ctx->kem.gt_b_ready = ctx->kem.gt_b_fallback = false; }),   // B's table: rebuilt at the new width on next use
     TUNE_OPTION(encap_gt), TUNE_OPTION(encap_multi_single_min), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
     TUNE_OPTION(msm_pipe_growth), TUNE_OPTION(vec_update_k_pass, vec_update_k_pass_refuses),
+    TUNE_OPTION(fk_coset_group, fk_coset_group_refuses), TUNE_OPTION(fk_coset_min_lanes, fk_coset_min_lanes_refuses),
 #ifdef KEAKI_DIAG
     TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
 #endif
@@ -646,7 +729,7 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
   std::vector<BufClass> v{{&ctx->fb_bases, 2}};
   for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
                     &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->vu_io, &ctx->vu_work, &ctx->vu_pass, &ctx->ks_io, &ctx->ks_q, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr})
+                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->vu_io, &ctx->vu_work, &ctx->vu_pass, &ctx->ks_io, &ctx->ks_q, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr, &ctx->fc_work})
     v.push_back({b, 1});
   ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
@@ -1432,6 +1515,46 @@ keaki_status keaki_hip_srs_g1_precompute_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // setup-time call: return when the table exists
   return KEAKI_OK;
+}
+// ---- FK23 coset openings: all d / l set proofs of the l-point cosets in one call (fk_coset.hip) ------------------------------------------------
+keaki_status keaki_hip_srs_g1_precompute_fk_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* omega_2r) {
+  CTX_GUARD(ctx);
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fkc_enter(ctx, srs, log2d, log2l, omega_2r != nullptr, "srs_g1_precompute_fk_cosets", hl));
+  if (log2d == log2l) return KEAKI_OK;                    // r = 1: the call needs no transform
+  const uint32_t r = 1u << (log2d - log2l);
+  ST_TRY(reserve(ctx, ctx->io_d, (size_t)r * 32));
+  if (srs->fkc.log2d != (int)log2d || srs->fkc.log2l != (int)log2l) {
+    fr_powers_run(ctx, omega_2r, r, ctx->io_d.p);
+    ST_TRY(fkc_cache_ensure(ctx, srs, log2d, log2l, ctx->io_d.p));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // setup-time call: return when the rows exist
+  return KEAKI_OK;
+}
+keaki_status keaki_hip_open_fk_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* hat_a, const uint64_t* omega_2r,
+                                      const uint64_t* omega_2r_inv, uint64_t* proofs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.open_fk_cosets");
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fkc_enter(ctx, srs, log2d, log2l, hat_a && omega_2r && omega_2r_inv && proofs_out_aff, "open_fk_cosets", hl));
+  return fkc_call(ctx, srs, {log2d, log2l, omega_2r, omega_2r_inv, nullptr}, nullptr, hat_a, true, proofs_out_aff);
+}
+keaki_status keaki_hip_open_fk_cosets_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* coeffs,
+                                           const uint64_t* omega_2r, const uint64_t* omega_2r_inv, const uint64_t* inv_2r, uint64_t* proofs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.open_fk_cosets");
+  std::unique_lock<std::recursive_mutex> hl;
+  ST_TRY(fkc_enter(ctx, srs, log2d, log2l, coeffs && omega_2r && omega_2r_inv && inv_2r && proofs_out_aff, "open_fk_cosets_poly", hl));
+  return fkc_call(ctx, srs, {log2d, log2l, omega_2r, omega_2r_inv, inv_2r}, coeffs, nullptr, true, proofs_out_aff);
+}
+keaki_status keaki_hip_open_fk_cosets_poly_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const void* d_coeffs,
+                                               const uint64_t* omega_2r, const uint64_t* omega_2r_inv, const uint64_t* inv_2r, void* d_proofs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.open_fk_cosets");
+  std::unique_lock<std::recursive_mutex> hl;
+  const bool aligned = !(((uintptr_t)d_coeffs | (uintptr_t)d_proofs_out_aff) & 15);
+  ST_TRY(fkc_enter(ctx, srs, log2d, log2l, d_coeffs && omega_2r && omega_2r_inv && inv_2r && d_proofs_out_aff && aligned, "open_fk_cosets_poly_dev", hl));
+  return fkc_call(ctx, srs, {log2d, log2l, omega_2r, omega_2r_inv, inv_2r}, d_coeffs, nullptr, false, d_proofs_out_aff);
 }
 // In-place scalar-field DFT of n = 2^log2n elements with the order-n root `omega`, then an optional scaling (the 1/n of an inverse transform).
 keaki_status keaki_hip_fr_fft(keaki_hip_ctx* ctx, uint64_t* data, uint32_t log2n, const uint64_t* omega, const uint64_t* scale_or_null) {

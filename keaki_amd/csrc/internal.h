@@ -61,6 +61,8 @@ struct Tuning {
   int msm_pipe_chunks = -1;      // KEAKI_MSM_PIPE_CHUNKS / "msm_pipe_chunks": chunks of a host-pointer MSM (upload under the kernels); -1 = automatic, 0 / 1 = one copy in front, k = k chunks at any length
   long long msm_pipe_min = 1 << 20;   // KEAKI_MSM_PIPE_MIN / "msm_pipe_min": automatic chunking from this many scalars on
   int msm_pipe_growth = 160;     // KEAKI_MSM_PIPE_GROWTH / "msm_pipe_growth": size of chunk j + 1 in percent of chunk j (100 = equal chunks; round 6: 160, measured best or tied at 2^20 .. 2^24, profiles/r06_msm_pipe_growth.txt; 140 until round 5)
+  int fk_coset_group = 0;        // KEAKI_FK_COSET_GROUP / "fk_coset_group": terms per Straus group of the FK23 coset openings' pointwise kernel, 1, 2 or 4; 0 = FKC_G (fk_coset_plan.h); 1 = one ladder per term (A/B switch)
+  long long fk_coset_min_lanes = 0;   // KEAKI_FK_COSET_MIN_LANES / "fk_coset_min_lanes": the pointwise launch of the FK23 coset openings splits a position's terms over lanes while it has fewer lanes than this; 0 = FKC_SPLIT_MIN_LANES
   int vec_update_k_pass = 0;     // KEAKI_VEC_UPDATE_K_PASS / "vec_update_k_pass": entries of the change list per pass of vec_update's proof kernel, 1 .. UPD_K_PASS; 0 = UPD_K_PASS
 #ifdef KEAKI_DIAG
   unsigned diag_row_mask = 0;    // "diag_row_mask" (ONLY in the diagnostic build, `make -C keaki_amd/csrc diag`; never in libkeaki_hip.so): the table-row index of every (row, sign) entry of the bucket-ordered stream is ANDed with this mask before the bucket kernel runs, so its gathers hit a table of (mask + 1) x 64 B -- the arithmetic, the instruction stream and the kernel binary stay the shipped ones, the RESULT IS WRONG by construction (bench_tools/r6_bucket_clock_diag.py)
@@ -171,6 +173,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf ve_io, ve_pts, ve_out;     // kzg verify_each: the small in/out block (counters, commitment, [tau]_2, omega) | L and -proof of a launch chunk (128 B per item) | host form: the status bytes and L of the whole call
   keaki_internal::DevBuf vu_io, vu_work, vu_pass;   // vec_update: host form: indices, deltas, commitment and proofs of the call | the 2d Jacobian points of a table build, the terms of the commitment | header and window tables of a pass
   keaki_internal::DevBuf ks_io, ks_q;               // KZG set openings: points, values, Z, weights, I and the small results of a call | the quotient and the work of its passes (kzg_multi.hip)
+  keaki_internal::DevBuf fc_work;                   // FK23 coset openings (fk_coset.hip): twiddles, hat_a, the partial sums and the two transforms of a call; host forms: + coefficients and proofs
   // instrumentation
   bool timing = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -366,6 +369,19 @@ keaki_status multi_quotient_run(keaki_hip_ctx* ctx, const void* d_c, size_t n, c
                                 void* d_work);
 // verify_multi: d_out_a_aff = C - I1, d_out_z_aff = Z2 (affine) from the commitment and the two MSM results (normalised or not)
 keaki_status set_pair_points_run(keaki_hip_ctx* ctx, const void* d_com_aff, const void* d_i1_jac, const void* d_z2_jac, void* d_out_a_aff, void* d_out_z_aff);
+// FK23 coset openings (fk_coset.hip; the split of a position's terms: fk_coset_plan.h). r = 2^(log2d - log2l) >= 2 everywhere. The scalar workspace
+// (fkc_fr_bytes) holds tw = omega_2r^k, twi = omega_2r^-k (k < r), twr = omega_r^k (k < r / 2) and hat_a (l rows of 2r Fr, natural order, divided by 2r).
+struct FkcPlan;
+struct FkcScalars { void *tw, *twi, *twr, *hat_a; };
+size_t fkc_fr_bytes(uint32_t log2d, uint32_t log2l);
+size_t fkc_g_bytes(uint32_t log2d, uint32_t log2l, const FkcPlan& plan);
+FkcScalars fkc_layout(uint32_t log2d, uint32_t log2l, void* d_fr_work);
+keaki_status fkc_reserve_tab(keaki_hip_ctx* ctx, size_t lanes, uint32_t G, uint32_t* lanes_per_launch);
+keaki_status fkc_tables_run(keaki_hip_ctx* ctx, uint32_t log2r, const uint64_t* omega_2r, const uint64_t* omega_2r_inv, const FkcScalars& s);
+keaki_status fkc_hat_s_run(keaki_hip_ctx* ctx, const void* d_srs, uint32_t log2d, uint32_t log2l, const void* d_tw, void* d_hat_s);
+keaki_status fkc_scalars_run(keaki_hip_ctx* ctx, uint32_t log2d, uint32_t log2l, const void* d_p, const uint64_t* inv_2r, const FkcScalars& s);
+keaki_status fkc_open_run(keaki_hip_ctx* ctx, const void* d_hat_s, uint32_t log2d, uint32_t log2l, const FkcScalars& s, const FkcPlan& plan,
+                          uint32_t lanes_per_launch, void* d_g_work, void* d_proofs_aff);
 keaki_status selftest_u29_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 keaki_status selftest_field_run(keaki_hip_ctx* ctx, uint32_t blocks, uint32_t iters, uint32_t seed, void* d_mismatches);
 // field probe (field_probe.hip): op `op` of keaki_field_op on n records at d_operands (field_probe_padded(op, n) records: lane-pair ops run whole

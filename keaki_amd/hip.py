@@ -33,6 +33,7 @@ EXPORTS = [
     "keaki_hip_srs_g1_precompute_update", "keaki_hip_vec_update", "keaki_hip_vec_update_dev",
     "keaki_hip_kzg_set_polys", "keaki_hip_kzg_set_polys_dev", "keaki_hip_kzg_open_multi", "keaki_hip_kzg_open_multi_dev",
     "keaki_hip_kzg_aggregate", "keaki_hip_kzg_aggregate_dev", "keaki_hip_kzg_verify_multi",
+    "keaki_hip_srs_g1_precompute_fk_cosets", "keaki_hip_open_fk_cosets", "keaki_hip_open_fk_cosets_poly", "keaki_hip_open_fk_cosets_poly_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
     "keaki_hip_group_kzg_open", "keaki_hip_group_encap_batch", "keaki_hip_group_decap_batch",
@@ -209,6 +210,10 @@ def load_library():
         lib.keaki_hip_kzg_aggregate.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_kzg_aggregate_dev.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_kzg_verify_multi.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_srs_g1_precompute_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
+        lib.keaki_hip_open_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        lib.keaki_hip_open_fk_cosets_poly.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+        lib.keaki_hip_open_fk_cosets_poly_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
         lib.keaki_hip_group_create.argtypes = [C.POINTER(i32), sz, C.POINTER(vp)]
         lib.keaki_hip_group_destroy.argtypes = [vp]
         lib.keaki_hip_group_destroy.restype = None
@@ -811,6 +816,32 @@ class KeakiHip:
     def srs_g1_precompute_fk(self, srs: "SrsG1", log2d: int, omega_2d):
         """setup-time build of the handle's cached FK23 transform for d = 2^log2d (later open_fk / open_fk_poly / vec_commit calls at this d reuse it)"""
         self._ck(self.lib.keaki_hip_srs_g1_precompute_fk(self.ctx, srs.handle, log2d, _ptr(_np(omega_2d))))
+
+    # FK23 coset openings: all r = d / l set proofs of the l-point cosets {i + t r} in one call (keaki_hip_open_fk_cosets*). omega_2r: the generator
+    # of the size-2r domain (= omega_2d^l); proof i belongs to c_i = omega_r^i and equals the affine form of kzg_open_multi on coset i
+    def open_fk_cosets_poly(self, srs: "SrsG1", log2d: int, log2l: int, coeffs, omega_2r, omega_2r_inv, inv_2r) -> np.ndarray:
+        p = _np(coeffs, 4)
+        assert p.shape[0] == 1 << log2d and log2l <= log2d
+        out = np.zeros((1 << (log2d - log2l), 8), np.uint64)
+        self._ck(self.lib.keaki_hip_open_fk_cosets_poly(self.ctx, srs.handle, log2d, log2l, _ptr(p), _ptr(_np(omega_2r)), _ptr(_np(omega_2r_inv)),
+                                                        _ptr(_np(inv_2r)), _ptr(out)))
+        return out
+
+    def open_fk_cosets_poly_dev(self, srs: "SrsG1", log2d: int, log2l: int, d_coeffs: int, omega_2r, omega_2r_inv, inv_2r, d_proofs: int):
+        self._ck(self.lib.keaki_hip_open_fk_cosets_poly_dev(self.ctx, srs.handle, log2d, log2l, C.c_void_p(d_coeffs), _ptr(_np(omega_2r)),
+                                                            _ptr(_np(omega_2r_inv)), _ptr(_np(inv_2r)), C.c_void_p(d_proofs)))
+
+    def open_fk_cosets(self, srs: "SrsG1", log2d: int, log2l: int, hat_a, omega_2r, omega_2r_inv) -> np.ndarray:
+        """the raw form: hat_a = l rows of 2r Fr (natural order, divided by 2r), row j = DFT_2r(r zeros, then the coefficients u l + j)"""
+        ha = _np(hat_a, 4)
+        assert ha.shape[0] == 2 << log2d and log2l <= log2d
+        out = np.zeros((1 << (log2d - log2l), 8), np.uint64)
+        self._ck(self.lib.keaki_hip_open_fk_cosets(self.ctx, srs.handle, log2d, log2l, _ptr(ha), _ptr(_np(omega_2r)), _ptr(_np(omega_2r_inv)), _ptr(out)))
+        return out
+
+    def srs_g1_precompute_fk_cosets(self, srs: "SrsG1", log2d: int, log2l: int, omega_2r):
+        """setup-time build of the handle's cached coset transforms for (d, l) = (2^log2d, 2^log2l)"""
+        self._ck(self.lib.keaki_hip_srs_g1_precompute_fk_cosets(self.ctx, srs.handle, log2d, log2l, _ptr(_np(omega_2r))))
 
     # ---- KEM composites
     # FK23 sharded over `world` ranks: the steps between the caller's exchanges (keaki_amd/dist.py::ShardedFk drives them)

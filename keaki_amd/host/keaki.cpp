@@ -530,6 +530,24 @@ Result<std::vector<G1>> open_fk(const KZGSetup& setup, const std::vector<Fr>& p,
   return Result<std::vector<G1>>::Ok(std::move(out));
 }
 
+std::vector<G1> open_fk_cosets(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size, size_t l) {
+  const size_t d = domain_size;
+  if (d < 1 || (d & (d - 1)) != 0 || l < 1 || (l & (l - 1)) != 0 || l > d) throw SetError("open_fk_cosets: the domain and the coset size are powers of two, l <= d");
+  if (l > (size_t)KEAKI_SET_MAX) throw SetError("open_fk_cosets: more than KEAKI_SET_MAX points in a coset");
+  if (p.size() > d) throw SetError("open_fk_cosets: more coefficients than the domain holds");
+  if (d > setup.g1_pow().size()) throw SetError("open_fk_cosets: the domain is larger than the SRS");
+  unsigned log2d = 0, log2l = 0;
+  while ((size_t(1) << log2d) < d) log2d++;
+  while ((size_t(1) << log2l) < l) log2l++;
+  std::vector<Fr> c(p);
+  c.resize(d, Fr::zero());
+  const vec::Radix2Domain d2 = vec::Radix2Domain::create(2 * (d / l));     // omega_2r = omega_2d^l
+  std::vector<G1> out(d / l);
+  const Device& dev = *setup.device();
+  dev.check(keaki_hip_open_fk_cosets_poly(dev.ctx(), setup.srs(), log2d, log2l, c[0].l, d2.group_gen.l, d2.group_gen_inv.l, d2.size_inv.l, out[0].w.data()));
+  return out;
+}
+
 }  // namespace kzg
 
 // ------------------------------------------------------------------------------------------------ kem / enc
@@ -987,6 +1005,18 @@ G1 vec_open_subset(const kzg::KZGSetup& setup, size_t domain_size, const std::ve
 }
 bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const std::vector<Fr>& values, const G1& proof) {
   return kzg::verify_set(setup, com, subset_points(domain_size, idx, "vec_verify_subset"), values, proof);
+}
+std::vector<G1> vec_open_cosets(const kzg::KZGSetup& setup, const std::vector<Fr>& evals, size_t l) {
+  if (evals.empty()) throw kzg::SetError("vec_open_cosets: no evaluations");
+  const Radix2Domain dom = Radix2Domain::create(evals.size());
+  return kzg::open_fk_cosets(setup, dom.ifft(evals), dom.size, l);
+}
+std::vector<size_t> vec_coset_indices(size_t domain_size, size_t l, size_t i) {
+  const size_t d = Radix2Domain::create(domain_size).size;
+  if (l < 1 || (l & (l - 1)) != 0 || l > d || i >= d / l) throw kzg::SetError("vec_coset_indices: l is a power of two <= the domain, i < domain / l");
+  std::vector<size_t> idx(l);
+  for (size_t t = 0; t < l; t++) idx[t] = i + t * (d / l);
+  return idx;
 }
 void vec_encrypt_subset_batch(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const Fr* values,
                               size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {

@@ -231,6 +231,11 @@ std::pair<G1, G2> set_pair(const KZGSetup& setup, const G1& commitment, const st
 Result<std::vector<G1>> open_fk(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size);
 // setup-time: tabulate the SRS-only part of open_fk (hat_s) for power-of-two domain size d, so the first open_fk does not pay for it
 void precompute_open_fk(const KZGSetup& setup, size_t domain_size);
+// The set-opening counterpart of open_fk (no counterpart in the reference): the r = domain_size / l set proofs of the l-point cosets
+// {i + t r : t < l} of the size-domain_size domain, in one device call (keaki_hip_open_fk_cosets_poly). Proof i is byte for byte
+// open_set(p, the coset's points).first and is checked by verify_set / vec_verify_subset. p.size() <= domain_size (zero-padded); domain_size and l
+// powers of two, l <= min(domain_size, KEAKI_SET_MAX), domain_size <= the SRS: anything else throws SetError. Single device or member 0.
+std::vector<G1> open_fk_cosets(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size, size_t l);
 
 }  // namespace kzg
 
@@ -315,6 +320,11 @@ size_t vec_verify_each_flat(const kzg::KZGSetup& setup, const G1& com, const Fr*
 // The holder of vec_commit's d proofs aggregates the k of them at idx (distinct, < domain_size) into one set proof, without the vector.
 G1 vec_open_subset(const kzg::KZGSetup& setup, size_t domain_size, const std::vector<size_t>& idx, const std::vector<G1>& proofs);
 bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const std::vector<Fr>& values, const G1& proof);
+// For the holder of the vector who wants EVERY block proof: evals are the evaluations over Radix2Domain::create(evals.size()) (what vec_commit
+// commits to: the vector, its padding scalar, zeros); the inverse transform, then kzg::open_fk_cosets: r = size / l proofs, proof i for the
+// positions vec_coset_indices(size, l, i) = {i + t r : t < l} -- the index list vec_verify_subset and vec_encrypt_subset_batch take.
+std::vector<G1> vec_open_cosets(const kzg::KZGSetup& setup, const std::vector<Fr>& evals, size_t l);
+std::vector<size_t> vec_coset_indices(size_t domain_size, size_t l, size_t i);
 // n items over ONE index set with different value tuples (the 1-of-2^k string-OT shape): item i is readable by the holder of a vector with
 // values[i * k + j] at idx[j] for all j. One r per item in index order. The rows -I_i come from ONE set_polys call and O(n k^2) host scalar
 // work, [-I_i(tau)]_1 from ONE msm_g1_batch (n rows of k coefficients), C is added by one g1_sum per item, then ONE encrypt_multi call with n

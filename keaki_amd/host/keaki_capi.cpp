@@ -275,6 +275,28 @@ int keaki_host_encrypt_set(void* rng, void* s, const uint64_t* com, const uint64
     return 0;
   });
 }
+// FK23 coset openings: out_proofs holds domain_size / l (vec_open_cosets: next power of two >= n, / l) affine points; out_idx holds l indices
+int keaki_host_open_fk_cosets(void* s, const uint64_t* coeffs, size_t n, size_t domain_size, size_t l, uint64_t* out_proofs) {
+  return guard([&] {
+    std::vector<G1> r = kzg::open_fk_cosets(((Setup*)s)->s, frs_of(coeffs, n), domain_size, l);
+    for (size_t i = 0; i < r.size(); i++) memcpy(out_proofs + 8 * i, r[i].w.data(), 64);
+    return 0;
+  });
+}
+int keaki_host_vec_open_cosets(void* s, const uint64_t* evals, size_t n, size_t l, uint64_t* out_proofs) {
+  return guard([&] {
+    std::vector<G1> r = vec::vec_open_cosets(((Setup*)s)->s, frs_of(evals, n), l);
+    for (size_t i = 0; i < r.size(); i++) memcpy(out_proofs + 8 * i, r[i].w.data(), 64);
+    return 0;
+  });
+}
+int keaki_host_vec_coset_indices(size_t domain_size, size_t l, size_t i, uint64_t* out_idx) {
+  return guard([&] {
+    const std::vector<size_t> r = vec::vec_coset_indices(domain_size, l, i);
+    for (size_t t = 0; t < r.size(); t++) out_idx[t] = r[t];
+    return 0;
+  });
+}
 int keaki_host_vec_open_subset(void* s, size_t domain_size, const uint64_t* idx, size_t k, const uint64_t* proofs, size_t n_proofs, uint64_t* out_g1) {
   return guard([&] {
     std::vector<G1> pr(n_proofs);

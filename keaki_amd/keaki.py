@@ -455,6 +455,42 @@ def vec_open_subset(setup: KZGSetup, domain_size: int, idx, proofs) -> np.ndarra
     return out
 
 
+def _next_pow2(n: int) -> int:
+    return 1 << max(n - 1, 0).bit_length()
+
+
+def open_fk_cosets(setup: KZGSetup, coeffs, domain_size: int, l: int) -> np.ndarray:
+    """the r = domain_size / l set proofs of the l-point cosets {i + t r} of the size-domain_size domain, in one device call (kzg::open_fk_cosets)
+    -> (r, 8) affine; proof i is open_set's proof for the coset's points. Bad shapes: SetError"""
+    c = _u64(coeffs, 4)
+    if domain_size < 1 or l < 1 or domain_size % l:
+        raise SetError("open_fk_cosets: l divides the domain size")
+    out = np.zeros((domain_size // l, 8), np.uint64)
+    _ck(_lib().keaki_host_open_fk_cosets(setup.h, _p(c), C.c_size_t(c.shape[0]), C.c_size_t(domain_size), C.c_size_t(l), _p(out)))
+    return out
+
+
+def vec_open_cosets(setup: KZGSetup, evals, l: int) -> np.ndarray:
+    """every block proof of a vector from its evaluations over the domain (vec::vec_open_cosets): the inverse transform, then open_fk_cosets;
+    proof i belongs to the positions vec_coset_indices(size, l, i)"""
+    e = _u64(evals, 4)
+    size = _next_pow2(e.shape[0])
+    if e.shape[0] < 1 or l < 1 or size % l:
+        raise SetError("vec_open_cosets: l divides the domain size")
+    out = np.zeros((size // l, 8), np.uint64)
+    _ck(_lib().keaki_host_vec_open_cosets(setup.h, _p(e), C.c_size_t(e.shape[0]), C.c_size_t(l), _p(out)))
+    return out
+
+
+def vec_coset_indices(domain_size: int, l: int, i: int) -> np.ndarray:
+    """{i + t r : t < l}, r = size / l: the index list vec_verify_subset and vec_encrypt_subset_batch take"""
+    if l < 1 or i < 0 or domain_size < 1:
+        raise SetError("vec_coset_indices: bad argument")
+    out = np.zeros(l, np.uint64)
+    _ck(_lib().keaki_host_vec_coset_indices(C.c_size_t(domain_size), C.c_size_t(l), C.c_size_t(i), _p(out)))
+    return out
+
+
 def vec_verify_subset(setup: KZGSetup, com, domain_size: int, idx, values, proof) -> bool:
     ix = np.ascontiguousarray(idx, np.uint64); y = _u64(values, 4); ok = C.c_int(0)
     if y.shape[0] != ix.shape[0]:

@@ -140,6 +140,15 @@ extern "C" {
     pub fn keaki_hip_kzg_verify_multi(ctx: *mut keaki_hip_ctx, srs_g1: *const keaki_hip_srs_g1, srs_g2: *const keaki_hip_srs_g2, com_aff: *const u64,
                                       points: *const u64, values: *const u64, k: usize, proof_aff: *const u64, ok_out: *mut i32,
                                       pair_out_aff: *mut u64) -> keaki_status;
+    // FK23 coset openings: all r = d / l set proofs of the l-point cosets {i + t r} of the size-d domain in one call; omega_2r generates the size-2r
+    // domain. proofs_out_aff: r affine points, proof i = the affine form of keaki_hip_kzg_open_multi on coset i. hat_a (raw form): l rows of 2r Fr
+    pub fn keaki_hip_srs_g1_precompute_fk_cosets(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, log2l: u32, omega_2r: *const u64) -> keaki_status;
+    pub fn keaki_hip_open_fk_cosets(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, log2l: u32, hat_a: *const u64, omega_2r: *const u64,
+                                    omega_2r_inv: *const u64, proofs_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_open_fk_cosets_poly(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, log2l: u32, coeffs: *const u64, omega_2r: *const u64,
+                                         omega_2r_inv: *const u64, inv_2r: *const u64, proofs_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_open_fk_cosets_poly_dev(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2d: u32, log2l: u32, d_coeffs: *const c_void,
+                                             omega_2r: *const u64, omega_2r_inv: *const u64, inv_2r: *const u64, d_proofs_out_aff: *mut c_void) -> keaki_status;
     // m rows over one SRS in one call (generalises commit, src/kzg.rs:89-101, and open, src/kzg.rs:104-124): row j = n Fr at + 4 * stride * j words
     pub fn keaki_hip_msm_g1_batch(ctx: *mut keaki_hip_ctx, srs: *const keaki_hip_srs_g1, scalars: *const u64, n: usize, m: usize, stride: usize,
                                   out_jac: *mut u64) -> keaki_status;

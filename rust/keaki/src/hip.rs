@@ -592,6 +592,46 @@ pub fn open_fk(srs: &HipSrs, coeffs: &[Fr], omega_2d: &Fr, omega_2d_inv: &Fr, in
     out.chunks_exact(8).map(|w| g1_from_words(w).into()).collect()
 }
 
+/// The set-opening counterpart of `open_fk` (`keaki_hip_open_fk_cosets_poly`): the `r = d / l` set proofs of the l-point cosets `{i + t r : t < l}`
+/// of the size-d domain (`d = coeffs.len()`, `d` and `l` powers of two, `l <= min(d, 1024)`, `d <= srs.len()`), in one device call. Proof `i` is
+/// `open_set`'s proof for the coset's points. Single-GPU device.
+pub fn open_fk_cosets(srs: &HipSrs, coeffs: &[Fr], l: usize) -> Vec<G1Projective> {
+    use ark_poly::{EvaluationDomain, Radix2EvaluationDomain};
+    let dev = Device::global();
+    let d = coeffs.len();
+    assert!(dev.group.is_null() && d.is_power_of_two() && l.is_power_of_two() && l <= d && l <= 1024 && d <= srs.len());
+    let r = d / l;
+    let dom2 = Radix2EvaluationDomain::<Fr>::new(2 * r).unwrap();
+    let one = |x: &Fr| fr_ptr(core::slice::from_ref(x));
+    let mut out = vec![0u64; 8 * r];
+    dev.check(
+        unsafe {
+            sys::keaki_hip_open_fk_cosets_poly(
+                dev.ctx, srs.srs(), d.trailing_zeros(), l.trailing_zeros(), fr_ptr(coeffs), one(&dom2.group_gen), one(&dom2.group_gen_inv), one(&dom2.size_inv),
+                out.as_mut_ptr(),
+            )
+        },
+        "open_fk_cosets_poly",
+    );
+    out.chunks_exact(8).map(|w| g1_from_words(w).into()).collect()
+}
+
+/// The positions of coset `i`: the index list of a block proof of `vec_open_cosets`.
+pub fn vec_coset_indices(domain_size: usize, l: usize, i: usize) -> Vec<usize> {
+    let d = domain_size.next_power_of_two();
+    assert!(l.is_power_of_two() && l <= d && i < d / l);
+    (0..l).map(|t| i + t * (d / l)).collect()
+}
+
+/// Every block proof of a vector from its evaluations over the domain: the inverse transform, then `open_fk_cosets`.
+pub fn vec_open_cosets(srs: &HipSrs, evals: &[Fr], l: usize) -> Vec<G1Projective> {
+    use ark_poly::{EvaluationDomain, Radix2EvaluationDomain};
+    let dom = Radix2EvaluationDomain::<Fr>::new(evals.len()).unwrap();
+    let mut coeffs = dom.ifft(evals);
+    coeffs.resize(dom.size(), Fr::from(0u64));
+    open_fk_cosets(srs, &coeffs, l)
+}
+
 /// Whether `vec_commit` takes the one-call device path: a domain of at least 2^12 evaluations that the SRS covers, on a single-GPU device
 /// (a device group runs the steps one by one: its FK23 openings and its commit are sharded over the members).
 pub fn fused_vec_commit(domain_size: usize, srs_len: usize) -> bool {
