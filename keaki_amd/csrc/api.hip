@@ -30,17 +30,24 @@ struct SrsHandle {
   size_t table_bytes = 0;
   int c_table = 0;
 };
-// FK23: hat_s = DFT_2d(reversed SRS) for the last requested d (2d Jacobian points), reused by later FK23 calls on the handle. Owned by
-// fk_cache_ensure: log2d names a transform only when its build was enqueued in full, bytes is what hat_s holds (and `acct` counts).
-struct FkCache { void* hat_s = nullptr; int log2d = -1; size_t bytes = 0; };
-// vec_update: the update tables of the last requested d (vec_update.hip: a | u | omega_d^-i | 1 / (omega_d^t - 1)), beside the FK23 transform and
-// independent of it. Owned by upd_cache_ensure under the same rules as FkCache.
-struct UpdCache { void* tab = nullptr; int log2d = -1; size_t bytes = 0; };
-// FK23 coset openings: the l transforms hat_s_j = DFT_2r(row j of the SRS, reversed) of the last requested (d, l), 2d Jacobian points (fk_coset.hip), beside
-// the other two and independent of them. Owned by fkc_cache_ensure under the same rules as FkCache; (log2d, log2l) is the key.
-struct FkcCache { void* hat_s = nullptr; int log2d = -1, log2l = -1; size_t bytes = 0; };
-struct keaki_hip_srs_g1 : SrsHandle { FkCache fk; UpdCache upd; FkcCache fkc; };
-struct keaki_hip_srs_g2 : SrsHandle {};
+// A device table derived from the points of a G1 handle for the LAST requested shape, reused by later calls on the handle. Owned by
+// srs_cache_ensure: the key names a table only when its build was enqueued in full (an unused part stays -1), bytes is what p holds (and `acct` counts).
+struct SrsCache {
+  void* p = nullptr;
+  int key[2] = {-1, -1};
+  size_t bytes = 0;
+  bool holds(int k0, int k1 = -1) const { return key[0] == k0 && key[1] == k1; }
+};
+// fk: FK23, hat_s = DFT_2d(reversed SRS), 2d Jacobian points, key log2d | upd: vec_update, the update tables of d (vec_update.hip: a | u | omega_d^-i |
+// 1 / (omega_d^t - 1)), key log2d | fkc: FK23 coset openings, the l transforms hat_s_j = DFT_2r(row j of the SRS, reversed), 2d Jacobian points
+// (fk_coset.hip), key (log2d, log2l). The three are independent of each other; a new cache is added HERE (srs_free walks them).
+struct keaki_hip_srs_g1 : SrsHandle {
+  SrsCache fk, upd, fkc;
+  template <class F> void for_each_cache(F&& f) { for (SrsCache* c : {&fk, &upd, &fkc}) f(*c); }
+};
+struct keaki_hip_srs_g2 : SrsHandle {
+  template <class F> void for_each_cache(F&&) {}
+};
 
 #include <dlfcn.h>
 #include <sys/mman.h>
@@ -230,32 +237,38 @@ keaki_status srs_holds(keaki_hip_ctx* ctx, const SrsHandle* srs, const char* wha
   if (k > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, too_short, k, srs->n);
   return KEAKI_OK;
 }
-// The ONE owner of a G1 handle's cached FK23 transform: afterwards srs->fk.hat_s is the transform for d = 2^log2d. d_tw: omega_2d^k, k < d,
-// ready in stream order; the caller holds srs->mu. A transform for another d is dropped first (after the stream's work that may read it), the
-// new one is allocated through dev_alloc and named (log2d) only once its build is enqueued; on every exit -- a refused allocation
-// included -- fk.bytes and the `tables` count of the handle's accounting context (srs->acct, as for the window tables) say what hat_s holds.
-keaki_status fk_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_tw) {
-  FkCache& c = srs->fk;
-  if (c.log2d == (int)log2d) return KEAKI_OK;
+// The ONE owner of every cache of a G1 handle: afterwards c.p is the table of key (k0, k1), `bytes` long, that `build(c.p)` enqueues on the
+// context's stream; the caller holds srs->mu. A table of another key is dropped first (after the stream's work that may read it), the new
+// one is allocated through dev_alloc and named only once its build is enqueued in full; on every exit -- a refused allocation
+// included -- c.bytes and the `tables` count of the handle's accounting context (srs->acct, as for the window tables) say what c.p holds.
+template <class Build>
+keaki_status srs_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, SrsCache& c, int k0, int k1, size_t bytes, Build build) {
+  if (c.holds(k0, k1)) return KEAKI_OK;
   auto book = [&](size_t now) {
     const size_t before = c.bytes;
     with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
     c.bytes = now;
   };
-  c.log2d = -1;
-  if (c.hat_s) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.hat_s); c.hat_s = nullptr; book(0); }
-  const size_t bytes = ((size_t)2 << log2d) * G1_JAC_BYTES;
-  ST_TRY(dev_alloc(ctx, &c.hat_s, bytes));
+  c.key[0] = c.key[1] = -1;
+  if (c.p) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.p); c.p = nullptr; book(0); }
+  ST_TRY(dev_alloc(ctx, &c.p, bytes));
   book(bytes);
-  ST_TRY(fk_hat_s_run(ctx, srs->d, log2d, d_tw, c.hat_s));
-  c.log2d = (int)log2d;
+  ST_TRY(build(c.p));
+  c.key[0] = k0; c.key[1] = k1;
   return KEAKI_OK;
 }
+// the FK23 transform of d = 2^log2d into srs->fk. d_tw: omega_2d^k, k < d, ready in stream order
+keaki_status fk_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_tw) {
+  return srs_cache_ensure(ctx, srs, srs->fk, (int)log2d, -1, ((size_t)2 << log2d) * G1_JAC_BYTES,
+                          [&](void* hat_s) { return fk_hat_s_run(ctx, srs->d, log2d, d_tw, hat_s); });
+}
 // How every FK23 entry starts: its pointers are there (`args_ok`) and log2d is in range, the handle lives on this device and holds the
-// d = 2^log2d points, and `hl` takes the handle's lock: the cached transform belongs to the handle, one FK23 call per handle at a time.
-keaki_status fk_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, const char* what, std::unique_lock<std::recursive_mutex>& hl) {
+// d = 2^log2d points (`too_short`: the family's message when it does not), and `hl` takes the handle's lock: the caches belong to the
+// handle, one call per handle at a time.
+keaki_status fk_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, const char* what, std::unique_lock<std::recursive_mutex>& hl,
+                      const char* too_short = SRS_SHORT_FK) {
   if (!srs || !args_ok || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", what);
-  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, SRS_SHORT_FK));
+  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, too_short));
   hl = std::unique_lock<std::recursive_mutex>(srs->mu);
   return KEAKI_OK;
 }
@@ -265,74 +278,7 @@ keaki_status open_fk_from_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32
   FkPolyScalars s;
   ST_TRY(open_fk_poly_scalars_run(ctx, log2d, d_p, omega_2d, omega_2d_inv, inv_2d, d_fr_work, &s));
   ST_TRY(fk_cache_ensure(ctx, srs, log2d, s.tw));
-  return open_fk_run(ctx, srs->fk.hat_s, log2d, s.hat_a, s.tw, s.twi, d_g_work, d_proofs_aff);
-}
-// The ONE owner of a G1 handle's coset transforms (fk_coset.hip), as fk_cache_ensure is of its FK23 transform: afterwards srs->fkc.hat_s holds the l rows
-// for (d, l) = (2^log2d, 2^log2l), r = d / l >= 2. d_tw: omega_2r^k, k < r, ready in stream order; the caller holds srs->mu. Rows of another (d, l) are
-// dropped first, the new ones are named only once their build is enqueued in full. It touches neither srs->fk nor srs->upd.
-keaki_status fkc_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const void* d_tw) {
-  FkcCache& c = srs->fkc;
-  if (c.log2d == (int)log2d && c.log2l == (int)log2l) return KEAKI_OK;
-  auto book = [&](size_t now) {
-    const size_t before = c.bytes;
-    with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
-    c.bytes = now;
-  };
-  c.log2d = c.log2l = -1;
-  if (c.hat_s) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.hat_s); c.hat_s = nullptr; book(0); }
-  const size_t bytes = ((size_t)2 << log2d) * G1_JAC_BYTES;
-  ST_TRY(dev_alloc(ctx, &c.hat_s, bytes));
-  book(bytes);
-  ST_TRY(fkc_hat_s_run(ctx, srs->d, log2d, log2l, d_tw, c.hat_s));
-  c.log2d = (int)log2d; c.log2l = (int)log2l;
-  return KEAKI_OK;
-}
-// One call of the coset openings on device data. Exactly one of d_coeffs (d Fr) and d_hat_a (l rows of 2r Fr) is given; `host` stages it from the caller's
-// array and downloads the r proofs to proofs_out, else d_out receives them in stream order. Every allocation that can be refused (workspaces, the
-// handle's transforms) comes before the first copy and before any kernel that writes an output.
-void prefault_out(const keaki_hip_ctx* ctx, void* p, size_t bytes);
-struct FkcCall {
-  uint32_t log2d, log2l;
-  const uint64_t *omega_2r, *omega_2r_inv, *inv_2r;      // inv_2r: null for the raw hat_a form
-};
-keaki_status fkc_call(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const FkcCall& k, const void* coeffs, const void* hat_a, bool host, void* out) {
-  const uint32_t log2r = k.log2d - k.log2l, l = 1u << k.log2l;
-  const size_t d = (size_t)1 << k.log2d, r = (size_t)1 << log2r;
-  if (r == 1) {                                           // deg p < d = l: the one quotient is zero
-    if (host) { memset(out, 0, G1_AFF_BYTES); return KEAKI_OK; }
-    HIP_TRY(ctx, hipMemsetAsync(out, 0, G1_AFF_BYTES, ctx->stream));
-    return KEAKI_OK;
-  }
-  const FkcPlan plan = fkc_plan(2 * r, l, (uint32_t)ctx->tune.fk_coset_group, (uint64_t)ctx->tune.fk_coset_min_lanes);
-  // one block: scalar work | point work | host forms: coefficients (d Fr) and proofs (r affine)
-  const size_t o_fr = 0, o_g = o_fr + fkc_fr_bytes(k.log2d, k.log2l), o_in = o_g + fkc_g_bytes(k.log2d, k.log2l, plan), o_out = o_in + (host && coeffs ? d * 32 : 0),
-               total = o_out + (host ? r * G1_AFF_BYTES : 0);
-  ST_TRY(reserve(ctx, ctx->fc_work, total));
-  uint32_t per_launch = 0;
-  ST_TRY(fkc_reserve_tab(ctx, (size_t)plan.S * 2 * r, plan.G, &per_launch));
-  char* b = (char*)ctx->fc_work.p;
-  const FkcScalars s = fkc_layout(k.log2d, k.log2l, b + o_fr);
-  ST_TRY(fkc_tables_run(ctx, log2r, k.omega_2r, k.omega_2r_inv, s));
-  ST_TRY(fkc_cache_ensure(ctx, srs, k.log2d, k.log2l, s.tw));
-  CopyFeed feed(ctx);
-  const void* d_p = coeffs;
-  if (host && coeffs) { ST_TRY(feed.put(0, b + o_in, coeffs, d * 32)); d_p = b + o_in; }
-  if (hat_a) {
-    if (host) ST_TRY(feed.put(0, s.hat_a, hat_a, 2 * d * 32));
-    else HIP_TRY(ctx, hipMemcpyAsync(s.hat_a, hat_a, 2 * d * 32, hipMemcpyDeviceToDevice, ctx->stream));
-  } else {
-    ST_TRY(fkc_scalars_run(ctx, k.log2d, k.log2l, d_p, k.inv_2r, s));
-  }
-  ST_TRY(fkc_open_run(ctx, srs->fkc.hat_s, k.log2d, k.log2l, s, plan, per_launch, b + o_g, host ? (void*)(b + o_out) : out));
-  if (!host) return KEAKI_OK;
-  prefault_out(ctx, out, r * G1_AFF_BYTES);
-  return download(feed, out, b + o_out, r * G1_AFF_BYTES);
-}
-// how the coset entries start: fk_enter's checks, and l = 2^log2l <= min(d, KEAKI_SET_MAX)
-keaki_status fkc_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, bool args_ok, const char* what,
-                       std::unique_lock<std::recursive_mutex>& hl) {
-  const bool l_ok = log2l <= log2d && log2l < 32 && ((uint64_t)1 << log2l) <= (uint64_t)KEAKI_SET_MAX;
-  return fk_enter(ctx, srs, log2d, args_ok && l_ok, what, hl);
+  return open_fk_run(ctx, srs->fk.p, log2d, s.hat_a, s.tw, s.twi, d_g_work, d_proofs_aff);
 }
 
 // The caller's OUTPUT buffer is usually fresh memory (calloc / vec![0; n] / numpy.zeros): its pages do not exist until first touched, and a
@@ -563,12 +509,7 @@ void srs_free(keaki_hip_ctx* ctx, H* srs) {
   if (srs->owned && srs->d) (void)hipFree((void*)srs->d);
   if (srs->table) (void)hipFree(srs->table);
   size_t held = srs->table_bytes;          // booked on the context that built them, whichever context (or NULL) frees the handle
-  if constexpr (std::is_same_v<H, keaki_hip_srs_g1>) {
-    if (srs->fk.hat_s) (void)hipFree(srs->fk.hat_s);
-    if (srs->upd.tab) (void)hipFree(srs->upd.tab);
-    if (srs->fkc.hat_s) (void)hipFree(srs->fkc.hat_s);
-    held += srs->fk.bytes + srs->upd.bytes + srs->fkc.bytes;
-  }
+  srs->for_each_cache([&](SrsCache& c) { if (c.p) (void)hipFree(c.p); held += c.bytes; });
   with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, held); });
   delete srs;
 }
@@ -725,13 +666,9 @@ void tune_from_env(Tuning& t) {
   }
 }
 struct BufClass { DevBuf* b; int cls; };   // cls: 1 = workspace, 2 = GT / fixed-base tables of encapsulate
-std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {
-  std::vector<BufClass> v{{&ctx->fb_bases, 2}};
-  for (DevBuf* b : {&ctx->digits, &ctx->hist, &ctx->offsets, &ctx->cursor, &ctx->sorted, &ctx->buckets, &ctx->acc29, &ctx->partials, &ctx->wsums,
-                    &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->io_a, &ctx->io_b, &ctx->io_c, &ctx->io_d, &ctx->io_e, &ctx->perm, &ctx->heavy,
-                    &ctx->pair_ws, &ctx->em_offsets, &ctx->vb_io, &ctx->vb_s, &ctx->ve_io, &ctx->ve_pts, &ctx->ve_out, &ctx->vu_io, &ctx->vu_work, &ctx->vu_pass, &ctx->ks_io, &ctx->ks_q, &ctx->mb_canon, &ctx->mb_wsums, &ctx->mb_q, &ctx->fk_tab, &ctx->fkb_pts, &ctx->fkb_fr, &ctx->fc_work})
-    v.push_back({b, 1});
-  ctx->kem.for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
+std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {      // the list is keaki_hip_ctx::for_each_buf (internal.h), beside the declarations
+  std::vector<BufClass> v;
+  ctx->for_each_buf([&](DevBuf* b, int cls) { v.push_back({b, cls}); });
   return v;
 }
 }  // namespace
@@ -1479,7 +1416,7 @@ keaki_status keaki_hip_open_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32
   ST_TRY(feed.put(0, b + o_t2, tw_2d_inv, d * 32));
   (void)tw_d;                       // the size-d transforms take every second entry of the 2d tables
   ST_TRY(fk_cache_ensure(ctx, srs, log2d, b + o_t1));
-  ST_TRY(open_fk_run(ctx, srs->fk.hat_s, log2d, b + o_ha, b + o_t1, b + o_t2, b + o_w, b + o_p));
+  ST_TRY(open_fk_run(ctx, srs->fk.p, log2d, b + o_ha, b + o_t1, b + o_t2, b + o_w, b + o_p));
   prefault_out(ctx, proofs_out_aff, d * 64);
   return download(feed, proofs_out_aff, b + o_p, d * 64);
 }
@@ -1509,7 +1446,7 @@ keaki_status keaki_hip_srs_g1_precompute_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1
   ST_TRY(fk_enter(ctx, srs, log2d, omega_2d != nullptr, "srs_g1_precompute_fk", hl));
   const uint32_t d = 1u << log2d;
   ST_TRY(reserve(ctx, ctx->io_d, (size_t)d * 32));
-  if (srs->fk.log2d != (int)log2d) {
+  if (!srs->fk.holds((int)log2d)) {
     fr_powers_run(ctx, omega_2d, d, ctx->io_d.p);
     ST_TRY(fk_cache_ensure(ctx, srs, log2d, ctx->io_d.p));
   }
@@ -1517,6 +1454,59 @@ keaki_status keaki_hip_srs_g1_precompute_fk(keaki_hip_ctx* ctx, keaki_hip_srs_g1
   return KEAKI_OK;
 }
 // ---- FK23 coset openings: all d / l set proofs of the l-point cosets in one call (fk_coset.hip) ------------------------------------------------
+namespace {
+// the l coset transforms of (d, l) = (2^log2d, 2^log2l), r = d / l >= 2, into srs->fkc. d_tw: omega_2r^k, k < r, ready in stream order
+keaki_status fkc_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const void* d_tw) {
+  return srs_cache_ensure(ctx, srs, srs->fkc, (int)log2d, (int)log2l, ((size_t)2 << log2d) * G1_JAC_BYTES,
+                          [&](void* hat_s) { return fkc_hat_s_run(ctx, srs->d, log2d, log2l, d_tw, hat_s); });
+}
+// One call of the coset openings on device data. Exactly one of d_coeffs (d Fr) and d_hat_a (l rows of 2r Fr) is given; `host` stages it from the caller's
+// array and downloads the r proofs to proofs_out, else d_out receives them in stream order. Every allocation that can be refused (workspaces, the
+// handle's transforms) comes before the first copy and before any kernel that writes an output.
+struct FkcCall {
+  uint32_t log2d, log2l;
+  const uint64_t *omega_2r, *omega_2r_inv, *inv_2r;      // inv_2r: null for the raw hat_a form
+};
+keaki_status fkc_call(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const FkcCall& k, const void* coeffs, const void* hat_a, bool host, void* out) {
+  const uint32_t log2r = k.log2d - k.log2l, l = 1u << k.log2l;
+  const size_t d = (size_t)1 << k.log2d, r = (size_t)1 << log2r;
+  if (r == 1) {                                           // deg p < d = l: the one quotient is zero
+    if (host) { memset(out, 0, G1_AFF_BYTES); return KEAKI_OK; }
+    HIP_TRY(ctx, hipMemsetAsync(out, 0, G1_AFF_BYTES, ctx->stream));
+    return KEAKI_OK;
+  }
+  const FkcPlan plan = fkc_plan(2 * r, l, (uint32_t)ctx->tune.fk_coset_group, (uint64_t)ctx->tune.fk_coset_min_lanes);
+  // one block: scalar work | point work | host forms: coefficients (d Fr) and proofs (r affine)
+  const size_t o_fr = 0, o_g = o_fr + fkc_fr_bytes(k.log2d, k.log2l), o_in = o_g + fkc_g_bytes(k.log2d, k.log2l, plan), o_out = o_in + (host && coeffs ? d * 32 : 0),
+               total = o_out + (host ? r * G1_AFF_BYTES : 0);
+  ST_TRY(reserve(ctx, ctx->fc_work, total));
+  uint32_t per_launch = 0;
+  ST_TRY(fkc_reserve_tab(ctx, (size_t)plan.S * 2 * r, plan.G, &per_launch));
+  char* b = (char*)ctx->fc_work.p;
+  const FkcScalars s = fkc_layout(k.log2d, k.log2l, b + o_fr);
+  ST_TRY(fkc_tables_run(ctx, log2r, k.omega_2r, k.omega_2r_inv, s));
+  ST_TRY(fkc_cache_ensure(ctx, srs, k.log2d, k.log2l, s.tw));
+  CopyFeed feed(ctx);
+  const void* d_p = coeffs;
+  if (host && coeffs) { ST_TRY(feed.put(0, b + o_in, coeffs, d * 32)); d_p = b + o_in; }
+  if (hat_a) {
+    if (host) ST_TRY(feed.put(0, s.hat_a, hat_a, 2 * d * 32));
+    else HIP_TRY(ctx, hipMemcpyAsync(s.hat_a, hat_a, 2 * d * 32, hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    ST_TRY(fkc_scalars_run(ctx, k.log2d, k.log2l, d_p, k.inv_2r, s));
+  }
+  ST_TRY(fkc_open_run(ctx, srs->fkc.p, k.log2d, k.log2l, s, plan, per_launch, b + o_g, host ? (void*)(b + o_out) : out));
+  if (!host) return KEAKI_OK;
+  prefault_out(ctx, out, r * G1_AFF_BYTES);
+  return download(feed, out, b + o_out, r * G1_AFF_BYTES);
+}
+// how the coset entries start: fk_enter's checks, and l = 2^log2l <= min(d, KEAKI_SET_MAX)
+keaki_status fkc_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, bool args_ok, const char* what,
+                       std::unique_lock<std::recursive_mutex>& hl) {
+  const bool l_ok = log2l <= log2d && log2l < 32 && ((uint64_t)1 << log2l) <= (uint64_t)KEAKI_SET_MAX;
+  return fk_enter(ctx, srs, log2d, args_ok && l_ok, what, hl);
+}
+}  // namespace
 keaki_status keaki_hip_srs_g1_precompute_fk_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, uint32_t log2l, const uint64_t* omega_2r) {
   CTX_GUARD(ctx);
   std::unique_lock<std::recursive_mutex> hl;
@@ -1524,7 +1514,7 @@ keaki_status keaki_hip_srs_g1_precompute_fk_cosets(keaki_hip_ctx* ctx, keaki_hip
   if (log2d == log2l) return KEAKI_OK;                    // r = 1: the call needs no transform
   const uint32_t r = 1u << (log2d - log2l);
   ST_TRY(reserve(ctx, ctx->io_d, (size_t)r * 32));
-  if (srs->fkc.log2d != (int)log2d || srs->fkc.log2l != (int)log2l) {
+  if (!srs->fkc.holds((int)log2d, (int)log2l)) {
     fr_powers_run(ctx, omega_2r, r, ctx->io_d.p);
     ST_TRY(fkc_cache_ensure(ctx, srs, log2d, log2l, ctx->io_d.p));
   }
@@ -1603,32 +1593,15 @@ keaki_status keaki_hip_vec_commit(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, con
 
 // ---- vec_update: k evaluations of a committed vector change, the commitment and all d proofs follow (vec_update.hip) -------------------------
 namespace {
-// The ONE owner of a G1 handle's update tables, as fk_cache_ensure is of its FK23 transform: afterwards srs->upd.tab holds the tables of d = 2^log2d.
-// The caller holds srs->mu. Tables of another d are dropped first, the new ones are named only once their build is enqueued in full.
+// the update tables of d = 2^log2d into srs->upd
 keaki_status upd_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d_inv, const uint64_t* inv_d) {
-  UpdCache& c = srs->upd;
-  if (c.log2d == (int)log2d) return KEAKI_OK;
-  auto book = [&](size_t now) {
-    const size_t before = c.bytes;
-    with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
-    c.bytes = now;
-  };
-  c.log2d = -1;
-  if (c.tab) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.tab); c.tab = nullptr; book(0); }
-  const size_t bytes = upd_table_bytes(log2d);
-  ST_TRY(dev_alloc(ctx, &c.tab, bytes));
-  book(bytes);
-  ST_TRY(upd_tables_run(ctx, srs->d, log2d, omega_d_inv, inv_d, c.tab));
-  c.log2d = (int)log2d;
-  return KEAKI_OK;
+  return srs_cache_ensure(ctx, srs, srs->upd, (int)log2d, -1, upd_table_bytes(log2d),
+                          [&](void* tab) { return upd_tables_run(ctx, srs->d, log2d, omega_d_inv, inv_d, tab); });
 }
 constexpr const char* SRS_SHORT_UPD = "vec_update: a domain of %zu but the SRS holds %zu points";
-// how the three entries start: pointers, log2d and k in range, the handle on this device with d points, its lock taken
+// how the three entries start: fk_enter's checks with vec_update's message, and k < 2^31
 keaki_status upd_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, size_t k, const char* what, std::unique_lock<std::recursive_mutex>& hl) {
-  if (!srs || !args_ok || log2d > 27 || k >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", what);
-  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, SRS_SHORT_UPD));
-  hl = std::unique_lock<std::recursive_mutex>(srs->mu);
-  return KEAKI_OK;
+  return fk_enter(ctx, srs, log2d, args_ok && k < ((size_t)1 << 31), what, hl, SRS_SHORT_UPD);
 }
 }  // namespace
 keaki_status keaki_hip_srs_g1_precompute_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
@@ -1650,7 +1623,7 @@ keaki_status keaki_hip_vec_update_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs,
   ST_TRY(upd_enter(ctx, srs, log2d, omega_d && omega_d_inv && inv_d && (!k || (d_idx && d_deltas)) && aligned, k, "vec_update_dev", hl));
   if (k == 0 || (!d_com_inout_jac && !d_proofs_inout_aff)) return KEAKI_OK;
   ST_TRY(upd_cache_ensure(ctx, srs, log2d, omega_d_inv, inv_d));
-  return upd_apply_run(ctx, srs->upd.tab, log2d, inv_d, d_idx, d_deltas, k, d_com_inout_jac, d_proofs_inout_aff);
+  return upd_apply_run(ctx, srs->upd.p, log2d, inv_d, d_idx, d_deltas, k, d_com_inout_jac, d_proofs_inout_aff);
 }
 keaki_status keaki_hip_vec_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const uint64_t* omega_d, const uint64_t* omega_d_inv,
                                   const uint64_t* inv_d, const uint32_t* idx, const uint64_t* deltas, size_t k, uint64_t* com_inout_jac, uint64_t* proofs_inout_aff) {
@@ -1672,7 +1645,7 @@ keaki_status keaki_hip_vec_update(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uin
   ST_TRY(feed.put(0, b + o_ix, idx, k * 4));
   if (com_inout_jac) ST_TRY(feed.put(0, b + o_com, com_inout_jac, 96));
   if (proofs_inout_aff) ST_TRY(feed.put(0, b + o_pr, proofs_inout_aff, d * 64));
-  ST_TRY(upd_apply_run(ctx, srs->upd.tab, log2d, inv_d, b + o_ix, b + o_dl, k, com_inout_jac ? b + o_com : nullptr, proofs_inout_aff ? b + o_pr : nullptr));
+  ST_TRY(upd_apply_run(ctx, srs->upd.p, log2d, inv_d, b + o_ix, b + o_dl, k, com_inout_jac ? b + o_com : nullptr, proofs_inout_aff ? b + o_pr : nullptr));
   // both outputs in one download when both are asked for (they are neighbours in the block)
   if (com_inout_jac && !proofs_inout_aff) return download(feed, com_inout_jac, b + o_com, 96);
   if (com_inout_jac) HIP_TRY(ctx, hipMemcpyAsync(com_inout_jac, b + o_com, 96, hipMemcpyDeviceToHost, ctx->stream));
@@ -2183,7 +2156,7 @@ keaki_status fkb_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d,
   for (size_t r0 = 0; r0 < m; r0 += rows) {
     const size_t cnt = std::min(rows, m - r0);
     const void* coeffs = nullptr;
-    ST_TRY(fkb_pass_run(ctx, srs->fk.hat_s, log2d, rows, (const char*)d_rows + r0 * stride * 32, n, (uint32_t)cnt, stride, d_com ? k.inv_d : nullptr, k.inv_2d,
+    ST_TRY(fkb_pass_run(ctx, srs->fk.p, log2d, rows, (const char*)d_rows + r0 * stride * 32, n, (uint32_t)cnt, stride, d_com ? k.inv_d : nullptr, k.inv_2d,
                         (char*)d_proofs + r0 * d * G1_AFF_BYTES, &coeffs));
     if (d_com) ST_TRY(msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, coeffs, d, cnt, d, (char*)d_com + r0 * G1_JAC_BYTES));
   }
