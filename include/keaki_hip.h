@@ -109,7 +109,8 @@ const char* keaki_hip_version(void);
  * keaki_hip_vec_update's proof kernel: 1 .. 8, 0 = the built-in 8; any other value is refused with KEAKI_ERR_BAD_ARG, in the environment ignored),
  * "fk_coset_group" (terms per Straus group of the FK23 coset openings' pointwise kernel: 1, 2 or 4, 0 = the built-in 4; 1 = one ladder per term, the A/B
  * form), "fk_coset_min_lanes" (that kernel splits the terms of a position over lanes while its launch has fewer lanes than this: 1 .. 2^31, 0 = the
- * built-in 131,072; other values of the two are refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
+ * built-in 131,072; other values of the two are refused with KEAKI_ERR_BAD_ARG, in the environment ignored), "verify_cosets_blocks" (workgroups of
+ * keaki_hip_kzg_verify_cosets' transform kernel: 1 .. 1,024, 0 = automatic, three per compute unit; results do not depend on it; other values refused).
  * What the library does with HOST memory of the caller, and its off switches (round 5):
  *   "host_prefault" (default 1): while the kernels of a host-array call run, the library first-touches the caller's OUTPUT arrays (writes a zero
  *       into one byte per 4 KB page, the whole range being overwritten by the download that follows; outputs >= 1 MB only) and asks for transparent
@@ -477,6 +478,67 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
 keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff,
                                             const void* d_points, int32_t point_mode, const void* d_values, const void* d_proofs_aff,
                                             const void* d_gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff);
+
+/* ---- KZG coset batch verification: n set proofs over cosets of one size in one call ----------------------------------------------------------
+ * The verifier's counterpart of keaki_hip_open_fk_cosets: what keaki_hip_kzg_verify_multi checks one proof at a time, for n items at once. l =
+ * 2^log2l, omega_l the generator of ark-poly's Radix2EvaluationDomain of size l. Item k < n: a commitment C_k, a shift h_k != 0, the l claimed
+ * values y_(k,t) = p_k(h_k omega_l^t), a proof pi_k, the caller's coefficient gamma_k. Every coset of size l has Z(X) = X^l - c, c_k = h_k^l, so all
+ * items share ONE G2 point [tau^l]_2 and the per-item part of Z crosses the pairing as a G1 scalar. The single check (verify_multi's on those l points):
+ *     e(C_k - [I_k(tau)]_1, g2) == e(pi_k, [tau^l]_2 - c_k g2)      I_k(X) = sum_j a_(k,j) X^j,   a_(k,j) = h_k^-j l^-1 sum_t y_(k,t) omega_l^(-j t)
+ * The call evaluates EXACTLY this combination:
+ *     J_j = sum_k gamma_k a_(k,j)  (j < l)       L = sum_k gamma_k C_k - sum_j J_j [tau^j]_1 + sum_k (gamma_k c_k) pi_k       R = sum_k gamma_k pi_k
+ *     *ok_out = 1  <=>  e(L, g2) == e(R, [tau^l]_2)
+ * for the gammas it is given; that is a deterministic contract. If all n items are valid it always accepts. If one is invalid it rejects except
+ * with probability <= 1/r -- PROVIDED the gamma_k are independent, uniform in Fr and unknown to whoever produced the proofs. Badly chosen gammas
+ * void the bound: with all gamma_k equal, two errors can cancel (y_(0,t) + d and y_(1,t) - d at equal shifts are accepted together), and gamma = 0
+ * accepts anything. gammas are drawn by the caller, one Fr::rand per item in index order (the rule encap_batch follows for r), so the randomness
+ * stream stays the caller's and every result is reproducible. At l = 1 the equation is keaki_hip_kzg_verify_batch's with z_k = h_k (and
+ * [tau^0]_1 = g1 = the first point of srs_g1): sums_out_aff is byte for byte what that call returns.
+ *   srs_g1       the handle whose first l points [tau^j]_1 the MSM with -J reads
+ *   com_aff      com_stride = 0: ONE affine G1 point u64[8], the commitment of all items (a vector's cosets); 1: n points
+ *   tau_l_g2_aff u64[16]: [tau^l]_2, passed by the caller as verify_batch takes [tau]_2 (point l of a G2 SRS)
+ *   points       point_mode = 0: n Fr, h_k; 1: ONE Fr omega, item k has h_k = omega^k (derived on the device). Coset i of keaki_hip_open_fk_cosets is
+ *                {i + t r}: h = omega_d^i, so all r cosets of a vector are point_mode 1 with omega_d.
+ *   values       value (k, t) is the Fr at values + 4 (k item_stride + t t_stride) words. Rows: (item_stride, t_stride) = (l, 1). A vector of d = r l
+ *                evaluations in domain order, all r cosets: (1, r) with n = r.
+ *   omega_l_inv, inv_l   u64[4] each: omega_l^-1 and l^-1 (the library derives every h_k^-1 itself: one Fermat inversion per 16 items)
+ *   proofs_aff, gammas   n affine G1 points, n Fr;   sums_out_aff u64[16] = L then R, affine ((0,0) = identity), or NULL
+ *   zero shift   h_k = 0 is no coset. The library does NOT look: the inverses of the 16 items that share its inversion come out 0 and the results
+ *                are meaningless. Non-zero shifts are the caller's contract; the host layers (host/keaki.cpp, rust/keaki/src/hip.rs) refuse a zero.
+ * Identity commitments and proofs, zero values and gammas are ordinary inputs. n = 0: *ok_out = 1, the sums are the identity.
+ *   errors     a null required pointer, com_stride or point_mode outside {0, 1}, l > KEAKI_SET_MAX, n l >= 2^31, strides under which two values of the
+ *              call would share an address (a item_stride = b t_stride for some 0 <= a < n, 0 <= b < l, not both zero: rows (l, 1) and domain order
+ *              (1, n) never do), (n - 1) item_stride or (l - 1) t_stride of 2^47 or more -> KEAKI_ERR_BAD_ARG; l > len(srs_g1) -> KEAKI_ERR_TOO_LARGE; a refused workspace ->
+ *              KEAKI_ERR_OOM. Nothing is written in any of these cases, nothing is launched, and the context stays usable.
+ *   kernels    csrc/kzg_cosets.hip: one launch derives 1 / h_k, s_k = gamma_k c_k and sum gamma; one launch runs the size-l inverse transforms of ALL
+ *              items in LDS (tiles of 1024 / l items, (l / 2) log2 l butterflies per item, twist and gamma applied before the sum over items), a
+ *              third folds the per-workgroup rows into -J. Then: MSM of gamma over the proofs (R), MSM of s over the proofs, MSM of -J over
+ *              [tau^j]_1, MSM of gamma over the commitments (or (sum gamma) C), one sum, ONE launch of two pairings.
+ *   host form  one upload in front of the kernels (the span of the values the strides name; no chunk pipeline), the kernels, 896 bytes back;
+ *              returns only when nothing reads or writes caller memory, also on failure.
+ *   _dev       every array is a device pointer (16-byte aligned; the commitment, [tau^l]_2 and omega too); omega_l_inv, inv_l (read before the call
+ *              returns), ok_out and sums_out_aff stay HOST pointers, so this form synchronises as well. Workspace: 64 B per item + 32 B per value
+ *              of at most 1,024 tiles, grow-only, counted in keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim.
+ *   out of scope  a per-coset verdict (a verify_each for cosets): a rejected batch falls back to keaki_hip_kzg_verify_multi per coset. The multi-GPU
+ *              form: the host layers refuse a device group.
+ *   numbers    (MI355X, medians of alternating rounds in one process: profiles/verify_cosets_times.txt, bench_tools/bench_verify_cosets.py) all r cosets of a
+ *              vector, resident / from host arrays, l = 4 / 16 / 64: d = 2^20 7.8 / 7.4 / 7.2 ms (host 8.7 / 8.2 / 8.0), 2^16 7.0 / 6.9 / 7.1, 2^12 6.9 / 7.2 /
+ *              7.1; l = 1,024 at d = 2^20 7.6 ms (8.2). Against (a) the only route before, r calls of keaki_hip_kzg_verify_multi (7.7 - 8.8 ms each at l <=
+ *              64, 23 at l = 1,024; 64 calls timed, EXTRAPOLATED to r): 126 s at d = 2^20, l = 64 (1/17,600), 2,275 s at l = 4; at r = 2, measured, 7.7 ms
+ *              against 15.6 - 47: the call wins from r = 2 on at every shape. Against (b) keaki_hip_kzg_verify_batch_dev on the same d values as d single
+ *              openings (which needs d proofs, not r): 9.1 - 9.2 ms at d = 2^20 (the call takes 0.78 - 0.86 of it), 6.4 - 6.5 at 2^16 and 6.2 - 6.3 at 2^12, where
+ *              the call LOSES by 0.4 - 0.9 ms (1.05 - 1.15 x): both are floors of launches there, and this call has one MSM and the inversion chain more.
+ *              The Fr kernels at d = 2^20, l = 4 / 64 / 1,024: k_vc_prepare 0.52 / 0.56 / 0.61 ms (ONE Fermat chain's latency, whatever n is), k_vc_transform
+ *              0.06 / 0.12 / 0.23 ms, k_vc_finish 0.10 / 0.08 / 0.08 ms: a tenth of the call; the rest is the MSMs' and the pairings' (1.46 ms). */
+keaki_status keaki_hip_kzg_verify_cosets(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride,
+                                         const uint64_t* tau_l_g2_aff, const uint64_t* points, int32_t point_mode, const uint64_t* values,
+                                         size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
+                                         const uint64_t* proofs_aff, const uint64_t* gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff);
+keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride,
+                                             const void* d_tau_l_g2_aff, const void* d_points, int32_t point_mode, const void* d_values,
+                                             size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
+                                             const uint64_t* inv_l, const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out,
+                                             uint64_t* sums_out_aff);
 
 /* ---- KZG verify_each: one verdict per opening, n openings in one call ---------------------------------------------------
  * verify_batch answers "are all n openings valid?"; this call says WHICH are not. Per item, by bilinearity (z_i proof_i moved across the

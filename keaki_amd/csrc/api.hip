@@ -638,6 +638,11 @@ bool vec_update_k_pass_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
   if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: vec_update_k_pass = %lld out of range (1 .. %u; 0 = %u)", v, UPD_K_PASS, UPD_K_PASS);
   return true;
 }
+bool verify_cosets_blocks_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= (long long)VC_MAX_BLOCKS) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: verify_cosets_blocks = %lld out of range (1 .. %u; 0 = automatic)", v, VC_MAX_BLOCKS);
+  return true;
+}
 #define TUNE_OPTION(member, ...) TuneOption{#member, assign_member<&Tuning::member>, __VA_ARGS__}
 const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(msm_c, msm_c_refuses<MSM_C_MAX>), TUNE_OPTION(msm_c_shared, msm_c_refuses<MSM_C_SHARED_MAX>), TUNE_OPTION(msm_short_tables),
@@ -648,6 +653,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(encap_gt), TUNE_OPTION(encap_multi_single_min), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
     TUNE_OPTION(msm_pipe_growth), TUNE_OPTION(vec_update_k_pass, vec_update_k_pass_refuses),
     TUNE_OPTION(fk_coset_group, fk_coset_group_refuses), TUNE_OPTION(fk_coset_min_lanes, fk_coset_min_lanes_refuses),
+    TUNE_OPTION(verify_cosets_blocks, verify_cosets_blocks_refuses),
 #ifdef KEAKI_DIAG
     TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
 #endif
@@ -2418,6 +2424,137 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
   };
   ST_TRY(verify_batch_core(ctx, ctx->io_e.p, com_stride, ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, ctx->io_a.p, n, stage, ok_out, sums_out_aff));
   feed.settled();                 // verify_batch_core has downloaded the result
+  return KEAKI_OK;
+}
+
+// ---- KZG coset batch verification: n set proofs over cosets of size l, one linear combination, two pairings ----------------------------------
+// L = sum gamma_k C_k - sum_j J_j [tau^j]_1 + sum (gamma_k c_k) proof_k, R = sum gamma_k proof_k, accept <=> e(L, g2) == e(R, [tau^l]_2): sum gamma_k x
+// (verify_multi's predicate on the coset h_k <omega_l>, whose Z is X^l - c_k, with c_k proof_k moved across the pairing). Kernel sequence, all on
+// ctx->stream, modelled on verify_batch_core: MSM R (gammas over the proofs) | k_vc_prepare + k_vc_transform + k_vc_finish (kzg_cosets.hip: s_k = gamma_k c_k,
+// -J, g) | MSM M (s over the proofs) | MSM T (-J over the first l points of the SRS, with the handle's window tables) | K: MSM (gammas over the
+// commitments) or g C | g1_sum of K, M, T | the two pairings in ONE launch | 768 GT bytes + the two sums back.
+// vc_io block: [pts: C 64] [mul: g C 64] [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64] [qs: g2 128 | tau^l 128] [omega 32] [gt 768]
+extern "C++" {
+namespace {
+struct VcLayout {
+  static constexpr size_t O_PTS = 0, O_MUL = 64, O_SUM = 128, O_L = 416, O_R = 512, O_PS = 608, O_QS = 736, O_OMEGA = 992, O_GT = 1024, TOTAL = 1792;
+};
+struct VcArgs {
+  const keaki_hip_srs_g1* srs;
+  const void *com, *tau_l, *points, *values, *proofs, *gammas;
+  int32_t com_stride, point_mode;
+  size_t item_stride, t_stride, n;
+  uint32_t log2l;
+  const uint64_t *omega_l_inv, *inv_l;
+};
+// The commitment (com_stride 0) and [tau^l]_2 are already in their vc_io slots; a.* are device pointers.
+keaki_status verify_cosets_core(keaki_hip_ctx* ctx, const VcArgs& a, const VcWork& w, int32_t* ok_out, uint64_t* sums_out_aff) {
+  using V = VcLayout;
+  char* io = (char*)ctx->vc_io.p;
+  const size_t n = a.n, l = (size_t)1 << a.log2l;
+  ST_TRY(g2_generator_to(ctx, io + V::O_QS));
+  ST_TRY(msm_g1_run(ctx, a.proofs, n, a.gammas, n, io + V::O_R));
+  ST_TRY(verify_cosets_scalars_run(ctx, a.gammas, a.points, a.point_mode, a.values, a.item_stride, a.t_stride, a.log2l, a.omega_l_inv, a.inv_l, n, w));
+  ST_TRY(msm_g1_run(ctx, a.proofs, n, w.s, n, io + V::O_SUM + 96));
+  const auto t1 = srs_tables(a.srs);
+  ST_TRY(msm_g1_run(ctx, a.srs->d, a.srs->n, w.neg_j, l, io + V::O_SUM + 192, t1.first, t1.second));
+  if (a.com_stride) {
+    ST_TRY(msm_g1_run(ctx, a.com, n, a.gammas, n, io + V::O_SUM));
+  } else {
+    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, w.g, 1, io + V::O_MUL));                                   // g C
+    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
+  }
+  ST_TRY(g1_sum_run(ctx, io + V::O_SUM, 3, io + V::O_L));
+  ST_TRY(verify_batch_jac_to_aff_run(ctx, io + V::O_L, io + V::O_R, io + V::O_PS));
+  ST_TRY(pairing_run(ctx, io + V::O_PS, io + V::O_QS, 1, 2, io + V::O_GT));
+  uint8_t gt[768];
+  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, io + V::O_PS, 128, hipMemcpyDeviceToHost, ctx->stream));
+  ST_TRY(download(ctx, gt, io + V::O_GT, 768));
+  *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
+  return KEAKI_OK;
+}
+// Two values (k, t) != (k', t') of the call share an address iff a item_stride = b t_stride for some 0 <= a < n, 0 <= b < l, not both zero; the
+// smallest such pair is (t_stride / g, item_stride / g), g = gcd.
+bool verify_cosets_strides_overlap(size_t n, size_t l, size_t item_stride, size_t t_stride) {
+  if ((n > 1 && item_stride == 0) || (l > 1 && t_stride == 0)) return true;
+  if (n <= 1 || l <= 1) return false;
+  size_t g = item_stride, b = t_stride;
+  while (b) { const size_t r = g % b; g = b; b = r; }
+  return t_stride / g < n && item_stride / g < l;
+}
+keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const int32_t* ok_out) {
+  if ((a.com_stride != 0 && a.com_stride != 1) || (a.point_mode != 0 && a.point_mode != 1))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: com_stride = %d, point_mode = %d: both must be 0 or 1", (int)a.com_stride, (int)a.point_mode);
+  if (!ok_out || !a.srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: %s is null", ok_out ? "srs_g1" : "ok_out");
+  if (a.log2l > 31 || ((size_t)1 << a.log2l) > KEAKI_SET_MAX)
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: l = 2^%u exceeds KEAKI_SET_MAX = %d", a.log2l, (int)KEAKI_SET_MAX);
+  const size_t l = (size_t)1 << a.log2l;
+  if (a.n && (!a.com || !a.tau_l || !a.points || !a.values || !a.proofs || !a.gammas || !a.omega_l_inv || !a.inv_l))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: null pointer");
+  if (a.n >= ((size_t)1 << 31) || a.n * l >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: n * l = %zu * %zu must be < 2^31", a.n, l);
+  if (a.n && verify_cosets_strides_overlap(a.n, l, a.item_stride, a.t_stride))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: under item_stride = %zu, t_stride = %zu two of the %zu x %zu values share an address", a.item_stride,
+                a.t_stride, a.n, l);
+  // the extent (n - 1) item_stride + (l - 1) t_stride stays below 2^48 values (each term below 2^47, checked without forming a product that could wrap): 32 x the
+  // extent, the bytes the host form uploads and the kernels' address arithmetic, fits 64 bits with room to spare
+  constexpr size_t HALF = (size_t)1 << 47;
+  if (a.n && ((a.n > 1 && a.item_stride >= HALF / (a.n - 1)) || (l > 1 && a.t_stride >= HALF / (l - 1))))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: item_stride = %zu, t_stride = %zu put the last of the %zu x %zu values 2^48 or more values behind the first",
+                a.item_stride, a.t_stride, a.n, l);
+  return srs_holds(ctx, a.srs, "kzg_verify_cosets", l, "kzg_verify_cosets: I has %zu coefficients but the G1 SRS holds %zu points");
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride,
+                                             const void* d_tau_l_g2_aff, const void* d_points, int32_t point_mode, const void* d_values,
+                                             size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
+                                             const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_cosets");
+  const VcArgs a = {srs_g1, d_com_aff, d_tau_l_g2_aff, d_points, d_values, d_proofs_aff, d_gammas, com_stride, point_mode, item_stride, t_stride, n, log2l,
+                    omega_l_inv, inv_l};
+  ST_TRY(verify_cosets_args(ctx, a, ok_out));
+  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
+  ST_TRY(reserve(ctx, ctx->vc_io, VcLayout::TOTAL));
+  ST_TRY(reserve(ctx, ctx->vc_work, verify_cosets_work_bytes(n, log2l)));
+  char* io = (char*)ctx->vc_io.p;
+  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VcLayout::O_PTS, d_com_aff, 64, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(io + VcLayout::O_QS + 128, d_tau_l_g2_aff, 128, hipMemcpyDeviceToDevice, ctx->stream));
+  return verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff);
+}
+
+keaki_status keaki_hip_kzg_verify_cosets(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride,
+                                         const uint64_t* tau_l_g2_aff, const uint64_t* points, int32_t point_mode, const uint64_t* values,
+                                         size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
+                                         const uint64_t* proofs_aff, const uint64_t* gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_verify_cosets");
+  VcArgs a = {srs_g1, com_aff, tau_l_g2_aff, points, values, proofs_aff, gammas, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
+  ST_TRY(verify_cosets_args(ctx, a, ok_out));
+  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
+  // the values go up as the one span the strides name, behind the kernels' own workspace; every buffer is reserved before the first copy
+  const size_t l = (size_t)1 << log2l, span = (n - 1) * item_stride + (l - 1) * t_stride + 1, work = (verify_cosets_work_bytes(n, log2l) + 255) & ~(size_t)255;
+  ST_TRY(reserve(ctx, ctx->vc_io, VcLayout::TOTAL));
+  ST_TRY(reserve(ctx, ctx->vc_work, work + span * 32));
+  ST_TRY(reserve(ctx, ctx->io_a, n * 32));
+  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
+  if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
+  if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
+  char* io = (char*)ctx->vc_io.p;
+  char* d_values = (char*)ctx->vc_work.p + work;
+  CopyFeed feed(ctx);
+  if (com_stride) ST_TRY(feed.put(0, ctx->io_e.p, com_aff, n * G1_AFF_BYTES));
+  else ST_TRY(feed.put(0, io + VcLayout::O_PTS, com_aff, 64));
+  ST_TRY(feed.put(0, io + VcLayout::O_QS + 128, tau_l_g2_aff, 128));
+  if (point_mode) ST_TRY(feed.put(0, io + VcLayout::O_OMEGA, points, 32));
+  else ST_TRY(feed.put(0, ctx->io_c.p, points, n * 32));
+  ST_TRY(feed.put(0, ctx->io_a.p, gammas, n * 32));
+  ST_TRY(feed.put(0, ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES));
+  ST_TRY(feed.put(0, d_values, values, span * 32));
+  a.com = ctx->io_e.p; a.points = point_mode ? (const void*)(io + VcLayout::O_OMEGA) : ctx->io_c.p; a.values = d_values; a.proofs = ctx->io_b.p; a.gammas = ctx->io_a.p;
+  ST_TRY(verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff));
+  feed.settled();                 // verify_cosets_core has downloaded the result
   return KEAKI_OK;
 }
 

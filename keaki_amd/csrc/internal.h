@@ -29,6 +29,8 @@ struct DevBuf {
 constexpr int MSM_C_MAX = 19, MSM_C_SHARED_MAX = 23;
 // vec_update (vec_update.hip): entries of the change list a pass of the proof kernel takes (8 scalar words per entry and lane in LDS: 16 KB a wave)
 constexpr uint32_t UPD_K_PASS = 8;
+// kzg verify_cosets (kzg_cosets.hip): Fr elements of one LDS tile (VC_TILE_ELEMS / l items) | most workgroups of the transform kernel (= partial rows the finish kernel folds)
+constexpr uint32_t VC_TILE_ELEMS = 1024, VC_MAX_BLOCKS = 1024;
 inline bool msm_c_too_wide(long long v, int max) { return v > max && v <= 24; }
 // Tuning / diagnostic switches of a context: every member but alloc_limit is an option of keaki_hip_ctx_set_option by its own name, with an
 // entry in TUNE_OPTIONS (api.hip). The environment is read ONCE, in keaki_hip_ctx_create (tune_from_env); afterwards only
@@ -63,6 +65,7 @@ struct Tuning {
   int msm_pipe_growth = 160;     // KEAKI_MSM_PIPE_GROWTH / "msm_pipe_growth": size of chunk j + 1 in percent of chunk j (100 = equal chunks; round 6: 160, measured best or tied at 2^20 .. 2^24, profiles/r06_msm_pipe_growth.txt; 140 until round 5)
   int fk_coset_group = 0;        // KEAKI_FK_COSET_GROUP / "fk_coset_group": terms per Straus group of the FK23 coset openings' pointwise kernel, 1, 2 or 4; 0 = FKC_G (fk_coset_plan.h); 1 = one ladder per term (A/B switch)
   long long fk_coset_min_lanes = 0;   // KEAKI_FK_COSET_MIN_LANES / "fk_coset_min_lanes": the pointwise launch of the FK23 coset openings splits a position's terms over lanes while it has fewer lanes than this; 0 = FKC_SPLIT_MIN_LANES
+  int verify_cosets_blocks = 0;  // KEAKI_VERIFY_COSETS_BLOCKS / "verify_cosets_blocks": workgroups of verify_cosets' transform kernel, 1 .. VC_MAX_BLOCKS; 0 = automatic (three per compute unit, what its LDS holds; a test sets 2 to make a workgroup run several tiles)
   int vec_update_k_pass = 0;     // KEAKI_VEC_UPDATE_K_PASS / "vec_update_k_pass": entries of the change list per pass of vec_update's proof kernel, 1 .. UPD_K_PASS; 0 = UPD_K_PASS
 #ifdef KEAKI_DIAG
   unsigned diag_row_mask = 0;    // "diag_row_mask" (ONLY in the diagnostic build, `make -C keaki_amd/csrc diag`; never in libkeaki_hip.so): the table-row index of every (row, sign) entry of the bucket-ordered stream is ANDed with this mask before the bucket kernel runs, so its gathers hit a table of (mask + 1) x 64 B -- the arithmetic, the instruction stream and the kernel binary stay the shipped ones, the RESULT IS WRONG by construction (bench_tools/r6_bucket_clock_diag.py)
@@ -173,6 +176,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf ve_io, ve_pts, ve_out;     // kzg verify_each: the small in/out block (counters, commitment, [tau]_2, omega) | L and -proof of a launch chunk (128 B per item) | host form: the status bytes and L of the whole call
   keaki_internal::DevBuf vu_io, vu_work, vu_pass;   // vec_update: host form: indices, deltas, commitment and proofs of the call | the 2d Jacobian points of a table build, the terms of the commitment | header and window tables of a pass
   keaki_internal::DevBuf ks_io, ks_q;               // KZG set openings: points, values, Z, weights, I and the small results of a call | the quotient and the work of its passes (kzg_multi.hip)
+  keaki_internal::DevBuf vc_io, vc_work;            // kzg verify_cosets: the small in/out block (VcLayout, api.hip) | s, 1 / h, -J, g and the partial rows of a call (kzg_cosets.hip: verify_cosets_layout)
   keaki_internal::DevBuf fc_work;                   // FK23 coset openings (fk_coset.hip): twiddles, hat_a, the partial sums and the two transforms of a call; host forms: + coefficients and proofs
   // every DevBuf above with its memory class, kem's included (KemState::for_each_buf): what keaki_hip_ctx_destroy and _trim free and
   // keaki_hip_ctx_memory counts. A new workspace is added HERE.
@@ -180,7 +184,7 @@ struct keaki_hip_ctx {
     f(&fb_bases, 2);
     for (keaki_internal::DevBuf* b : {&digits, &hist, &offsets, &cursor, &sorted, &buckets, &acc29, &partials, &wsums, &tmp_a, &tmp_b, &tmp_c, &io_a, &io_b, &io_c,
                                       &io_d, &io_e, &perm, &heavy, &pair_ws, &fk_tab, &mb_canon, &mb_wsums, &mb_q, &fkb_pts, &fkb_fr, &em_offsets, &vb_io, &vb_s,
-                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work})
+                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work})
       f(b, 1);
     kem.for_each_buf(f);
   }
@@ -317,6 +321,15 @@ constexpr uint32_t VB_MAX_BLOCKS = 1024;
 size_t verify_batch_partials_bytes();
 keaki_status verify_batch_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const void* d_values, size_t n,
                                       void* d_s_out, void* d_partials, void* d_gt_out);
+// kzg verify_cosets (kzg_cosets.hip), n items of l = 2^log2l values each, 1 <= n, n * l < 2^31, l <= KEAKI_SET_MAX. The workspace of a call
+// (verify_cosets_work_bytes) holds s_k = gamma_k h_k^l (n Fr: the second MSM's scalars) | 1 / h_k (n Fr) | -J_j (l Fr: the scalars of the MSM over
+// [tau^j]_1) | g = sum gamma_k (1 Fr) | the partial rows. point_mode 0: h_k = d_points[k]; 1: h_k = d_points[0]^k. Value (k, t) is the Fr at
+// d_values + 32 (k item_stride + t t_stride) bytes. omega_l_inv, inv_l: host pointers, read before the call returns.
+struct VcWork { void *s, *hinv, *neg_j, *g, *part_g, *part_j; };
+size_t verify_cosets_work_bytes(size_t n, uint32_t log2l);
+VcWork verify_cosets_layout(size_t n, uint32_t log2l, void* d_work);
+keaki_status verify_cosets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const void* d_values, size_t item_stride,
+                                       size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, const VcWork& w);
 // layout moves around the final sum (no arithmetic): n <= 64 affine points -> normalised Jacobian | the normalised Jacobian sums L, R -> d_out_lr_aff[0], [1] affine
 keaki_status verify_batch_aff_to_jac_run(keaki_hip_ctx* ctx, const void* d_in_aff, uint32_t n, void* d_out_jac);
 keaki_status verify_batch_jac_to_aff_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_r_jac, void* d_out_lr_aff);

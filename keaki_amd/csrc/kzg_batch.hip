@@ -15,18 +15,6 @@ namespace bn254 {
 
 constexpr u32 VB_THREADS = 256, VB_WAVES = VB_THREADS / 64;
 
-// sum over the 64 lanes of a wave by cross-lane moves; every lane ends up with the total
-KDEV Fr fr_wave_sum(Fr a) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Fr o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o.l[j] = (u32)__shfl_xor((int)a.l[j], off, 64);
-    a = fp_add<FrParams>(a, o);
-  }
-  return a;
-}
-
 // (g, t) of the workgroup -> out2[0], out2[1]: one partial per wave through LDS, thread 0 adds the VB_WAVES of them
 KDEV void fr_block_sum2(Fr g, Fr t, Fr* __restrict__ out2) {
   __shared__ Fr sh[2 * VB_WAVES];

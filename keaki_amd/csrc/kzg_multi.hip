@@ -32,6 +32,7 @@
 #include <type_traits>
 #include "internal.h"
 #include "bn254_curve.hip.h"
+#include "kzg_fr.hip.h"
 
 namespace bn254 {
 
@@ -49,19 +50,6 @@ KDEV void mq_each(F&& f) {
 }
 KDEV Fr mq_mul(const Fr& a, const Fr& b) { return fp_mul<FrParams>(a, b); }
 KDEV Fr mq_add(const Fr& a, const Fr& b) { return fp_add<FrParams>(a, b); }
-KDEV Fr mq_fr_inv(const Fr& x) {                      // x^(r - 2); 0 -> 0
-  Fr acc = fp_one<FrParams>();
-#pragma unroll 1
-  for (int wi = 7; wi >= 0; wi--) {
-    const u32 word = wi ? FrParams::MOD[wi] : FrParams::MOD[0] - 2u;
-#pragma unroll 1
-    for (int b = 31; b >= 0; b--) {
-      acc = mq_mul(acc, acc);
-      if ((word >> b) & 1u) acc = mq_mul(acc, x);
-    }
-  }
-  return acc;
-}
 
 // The wave-uniform data of a pass: w[lev * K + j] = z_j^(MQ_L^lev), cw[j] = c_j; entries j >= kk are zero (padding).
 template <int K>
@@ -185,7 +173,7 @@ static __global__ void __launch_bounds__(1024) k_set_polys(const Fr* __restrict_
 #pragma unroll 1
     for (u32 t = 0; t < k; t++)
       if (t != i) prod = mq_mul(prod, fp_sub<FrParams>(zi, z[t]));
-    c = mq_fr_inv(prod);
+    c = fr_inv(prod);
     wts[i] = c;
   }
   if (!ic) return;                       // uniform: no barrier below is skipped by a part of the block

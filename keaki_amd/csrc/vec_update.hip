@@ -21,6 +21,7 @@
 // equal / opposite operands, the four results meet in jac_add.
 #include "jac29.hip.h"
 #include "internal.h"
+#include "kzg_fr.hip.h"
 
 namespace bn254 {
 
@@ -33,24 +34,11 @@ struct UpdHdr {
 };
 constexpr u32 UPD_ROW_WORDS = 32, UPD_ROWS = 16;      // window table of one base: row m - 1 = m a, 15 rows used
 
-KDEV Fr upd_fr_inv(const Fr& x) {                     // x^(r - 2); 0 -> 0
-  Fr acc = fp_one<FrParams>();
-#pragma unroll
-  for (int wi = 7; wi >= 0; wi--) {
-    const u32 word = wi ? FrParams::MOD[wi] : FrParams::MOD[0] - 2u;
-#pragma unroll 1
-    for (int b = 31; b >= 0; b--) {
-      acc = fp_mul<FrParams>(acc, acc);
-      if ((word >> b) & 1u) acc = fp_mul<FrParams>(acc, x);
-    }
-  }
-  return acc;
-}
 // e[t] = 1 / (w^t - 1), t >= 1; e[0] = 0 (never read). pw[i] = w^-i, so w^t = pw[d - t].
 static __global__ void __launch_bounds__(64) k_upd_etab(const Fr* __restrict__ pw, u32 d, Fr* __restrict__ e) {
   const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= d) return;
-  e[t] = t ? upd_fr_inv(fp_sub<FrParams>(pw[d - t], fp_one<FrParams>())) : fp_zero<FrParams>();
+  e[t] = t ? fr_inv(fp_sub<FrParams>(pw[d - t], fp_one<FrParams>())) : fp_zero<FrParams>();
 }
 // s[k] = P_k, w[k] = (d - 1 - k) P_k  (the weights are below 2^27: plain double-and-add)
 static __global__ void __launch_bounds__(64) k_upd_load(const G1Aff* __restrict__ srs, u32 d, G1Jac* __restrict__ s, G1Jac* __restrict__ w) {

@@ -34,6 +34,7 @@ EXPORTS = [
     "keaki_hip_kzg_set_polys", "keaki_hip_kzg_set_polys_dev", "keaki_hip_kzg_open_multi", "keaki_hip_kzg_open_multi_dev",
     "keaki_hip_kzg_aggregate", "keaki_hip_kzg_aggregate_dev", "keaki_hip_kzg_verify_multi",
     "keaki_hip_srs_g1_precompute_fk_cosets", "keaki_hip_open_fk_cosets", "keaki_hip_open_fk_cosets_poly", "keaki_hip_open_fk_cosets_poly_dev",
+    "keaki_hip_kzg_verify_cosets", "keaki_hip_kzg_verify_cosets_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
     "keaki_hip_group_kzg_open", "keaki_hip_group_encap_batch", "keaki_hip_group_decap_batch",
@@ -209,6 +210,8 @@ def load_library():
         lib.keaki_hip_kzg_open_multi_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
         lib.keaki_hip_kzg_aggregate.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_kzg_aggregate_dev.argtypes = [vp, vp, vp, sz, vp]
+        lib.keaki_hip_kzg_verify_cosets.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_kzg_verify_cosets_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_kzg_verify_multi.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_srs_g1_precompute_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
         lib.keaki_hip_open_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -694,6 +697,36 @@ class KeakiHip:
         ok = C.c_int32(0); sums = np.zeros(16, np.uint64)
         self._ck(self.lib.keaki_hip_kzg_verify_batch_dev(self.ctx, dp(d_com), int(com_stride), dp(d_tau_g2), dp(d_points), int(point_mode), dp(d_values),
                                                          dp(d_proofs), dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
+        return bool(ok.value), sums[:8].copy(), sums[8:].copy()
+
+    def kzg_verify_cosets(self, srs_g1: "SrsG1", com_aff, tau_l_g2_aff, points, values, item_stride: int, t_stride: int, log2l: int, omega_l_inv, inv_l,
+                          proofs_aff, gammas, point_mode: int = 0):
+        """n set proofs over cosets of size l = 2^log2l in one call (keaki_hip_kzg_verify_cosets) -> (ok, L u64[8], R u64[8]). com_aff: one affine
+        point or n of them; points: the n shifts h_k, or with point_mode = 1 the ONE Fr omega (h_k = omega^k); values: a flat Fr array in which value
+        (k, t) is entry k * item_stride + t * t_stride -- rows: (l, 1); a vector in domain order: (1, n); tau_l_g2_aff: [tau^l]_2; gammas: n Fr
+        the CALLER drew"""
+        pr, g, c, z, v = _np(proofs_aff, 8), _np(gammas, 4), _np(com_aff, 8), _np(points, 4), _np(values, 4)
+        n = g.shape[0]
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if pr.shape[0] != n or (com_stride and c.shape[0] != n) or z.shape[0] != (1 if point_mode else n):
+            raise ValueError("kzg_verify_cosets: array lengths disagree")
+        if n and 0 <= log2l < 32 and v.shape[0] < (n - 1) * int(item_stride) + ((1 << log2l) - 1) * int(t_stride) + 1:
+            raise ValueError("kzg_verify_cosets: the strides reach past the %d values given" % v.shape[0])
+        ok = C.c_int32(0); sums = np.zeros(16, np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_cosets(self.ctx, srs_g1.handle, _ptr(c), com_stride, _ptr(_np(tau_l_g2_aff)), _ptr(z), int(point_mode), _ptr(v),
+                                                      int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)), _ptr(pr), _ptr(g), n,
+                                                      C.byref(ok), _ptr(sums)))
+        return bool(ok.value), sums[:8].copy(), sums[8:].copy()
+
+    def kzg_verify_cosets_dev(self, srs_g1: "SrsG1", d_com, com_stride: int, d_tau_l_g2, d_points, point_mode: int, d_values, item_stride: int, t_stride: int,
+                              log2l: int, omega_l_inv, inv_l, d_proofs, d_gammas, n: int):
+        """the same with every array resident: device pointers (ints) or torch tensors; omega_l_inv and inv_l stay host arrays -> (ok, L, R) on the
+        host (the call synchronises). The caller answers for the extent of d_values under the strides"""
+        dp = lambda x: C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+        ok = C.c_int32(0); sums = np.zeros(16, np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_cosets_dev(self.ctx, srs_g1.handle, dp(d_com), int(com_stride), dp(d_tau_l_g2), dp(d_points), int(point_mode),
+                                                          dp(d_values), int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)),
+                                                          dp(d_proofs), dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
         return bool(ok.value), sums[:8].copy(), sums[8:].copy()
 
     def kzg_verify_each(self, com_aff, tau_g2_aff, points, values, proofs_aff, point_mode: int = 0, want_lhs: bool = False):

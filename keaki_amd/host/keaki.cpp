@@ -548,6 +548,37 @@ std::vector<G1> open_fk_cosets(const KZGSetup& setup, const std::vector<Fr>& p, 
   return out;
 }
 
+bool verify_cosets_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values,
+                        size_t item_stride, size_t t_stride, size_t l, const uint64_t* proofs, size_t n) {
+  if (l < 1 || (l & (l - 1)) != 0) throw SetError("verify_cosets: the coset size is a power of two");
+  if (l > (size_t)KEAKI_SET_MAX) throw SetError("verify_cosets: more than KEAKI_SET_MAX points in a coset");
+  if (l > setup.g1_pow().size()) throw SetError("verify_cosets: the coset is larger than the SRS");
+  if (n_coms != 1 && n_coms != n) throw SetError("verify_cosets: one commitment, or one per item");
+  if (setup.g2_pow().size() <= l) throw SetError("verify_cosets: this KZGSetup holds no [tau^l]_2: build it with G2 powers beyond l (setup_with_g2, from_powers_g2)");
+  const Device& dev = *setup.device();
+  if (dev.group()) throw SetError("verify_cosets: single device only");
+  if (!roots_of_unity)
+    for (size_t k = 0; k < n; k++)
+      if (shifts[k] == Fr::zero()) throw SetError("verify_cosets: a zero shift is no coset");
+  std::vector<Fr> gammas(n);
+  for (size_t k = 0; k < n; k++) gammas[k] = fr_rand(rng);       // one draw per item in index order
+  if (n == 0) return true;
+  unsigned log2l = 0;
+  while ((size_t(1) << log2l) < l) log2l++;
+  const vec::Radix2Domain dl = vec::Radix2Domain::create(l);
+  int32_t ok = 0;
+  dev.check(keaki_hip_kzg_verify_cosets(dev.ctx(), setup.srs(), coms, n_coms == 1 ? 0 : 1, setup.g2_pow()[l].w.data(), shifts[0].l, roots_of_unity ? 1 : 0,
+                                        values[0].l, item_stride, t_stride, log2l, dl.group_gen_inv.l, dl.size_inv.l, proofs, gammas[0].l, n, &ok, nullptr));
+  return ok != 0;
+}
+bool verify_cosets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& shifts, size_t l, const std::vector<Fr>& values,
+                   const std::vector<G1>& proofs) {
+  const size_t n = shifts.size();
+  if (l == 0 || values.size() != n * l || proofs.size() != n || (commitments.size() != 1 && commitments.size() != n))
+    throw SetError("verify_cosets: l values and one proof per item, commitments one or n");
+  return verify_cosets_flat(rng, setup, commitments.empty() ? nullptr : commitments[0].w.data(), commitments.size(), shifts.data(), false, values.data(), l, 1, l, n ? proofs[0].w.data() : nullptr, n);
+}
+
 }  // namespace kzg
 
 // ------------------------------------------------------------------------------------------------ kem / enc
@@ -1017,6 +1048,32 @@ std::vector<size_t> vec_coset_indices(size_t domain_size, size_t l, size_t i) {
   std::vector<size_t> idx(l);
   for (size_t t = 0; t < l; t++) idx[t] = i + t * (d / l);
   return idx;
+}
+bool vec_verify_cosets_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* evals, size_t domain_size, size_t l, const uint64_t* proofs) {
+  const size_t d = domain_size;
+  if (d < 1 || (d & (d - 1)) != 0 || l < 1 || (l & (l - 1)) != 0 || l > d) throw kzg::SetError("vec_verify_cosets: the domain and the coset size are powers of two, l <= d");
+  const Radix2Domain dom = Radix2Domain::create(d);
+  return kzg::verify_cosets_flat(rng, setup, com.w.data(), 1, &dom.group_gen, true, evals, 1, d / l, l, proofs, d / l);
+}
+bool vec_verify_cosets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& evals, size_t l, const std::vector<G1>& proofs) {
+  if (evals.empty()) throw kzg::SetError("vec_verify_cosets: no evaluations");
+  const size_t d = Radix2Domain::create(evals.size()).size;
+  if (l < 1 || (l & (l - 1)) != 0 || l > d || proofs.size() != d / l) throw kzg::SetError("vec_verify_cosets: l is a power of two <= the domain, one proof per coset");
+  std::vector<Fr> e(evals);
+  e.resize(d, Fr::zero());
+  return vec_verify_cosets_flat(rng, setup, com, e.data(), d, l, proofs[0].w.data());
+}
+bool vec_verify_cosets_subset(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets,
+                              const std::vector<Fr>& values, const std::vector<G1>& proofs) {
+  const Radix2Domain dom = Radix2Domain::create(domain_size);
+  if (l < 1 || (l & (l - 1)) != 0 || l > dom.size) throw kzg::SetError("vec_verify_cosets_subset: l is a power of two <= the domain");
+  if (values.size() != cosets.size() * l || proofs.size() != cosets.size()) throw kzg::SetError("vec_verify_cosets_subset: l values and one proof per listed coset");
+  std::vector<Fr> h(cosets.size());
+  for (size_t k = 0; k < cosets.size(); k++) {
+    if (cosets[k] >= dom.size / l) throw kzg::SetError("vec_verify_cosets_subset: coset index outside domain / l");
+    h[k] = dom.group_gen.pow(cosets[k]);
+  }
+  return kzg::verify_cosets_flat(rng, setup, com.w.data(), 1, h.data(), false, values.data(), l, 1, l, proofs.empty() ? nullptr : proofs[0].w.data(), cosets.size());
 }
 void vec_encrypt_subset_batch(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const Fr* values,
                               size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {

@@ -236,6 +236,19 @@ void precompute_open_fk(const KZGSetup& setup, size_t domain_size);
 // open_set(p, the coset's points).first and is checked by verify_set / vec_verify_subset. p.size() <= domain_size (zero-padded); domain_size and l
 // powers of two, l <= min(domain_size, KEAKI_SET_MAX), domain_size <= the SRS: anything else throws SetError. Single device or member 0.
 std::vector<G1> open_fk_cosets(const KZGSetup& setup, const std::vector<Fr>& p, size_t domain_size, size_t l);
+// The verifier's counterpart (no counterpart in the reference): n set proofs over cosets of ONE size l in one device call
+// (keaki_hip_kzg_verify_cosets: three or four MSMs and two pairings whatever n is, against n x verify_set). Item k: commitments[k] (or the one
+// commitment of all items), the coset shifts[k] <omega_l> (omega_l: the generator of Radix2Domain::create(l)), its l values values[k * l + t] =
+// p_k(shifts[k] omega_l^t), proofs[k]. Draws one Fr::rand per item in index order (the gammas of the combination, as verify_batch). All items
+// valid: always true; one invalid: false except with probability <= 1 / r. Needs a setup whose G2 powers reach [tau^l]_2 (g2_pow().size() > l);
+// refuses (SetError) a zero shift -- the device library does not look --, an l that is not a power of two or exceeds KEAKI_SET_MAX or the SRS,
+// array sizes that disagree, and a device group (single device only). A rejected batch says nothing about WHICH item: verify_set per coset does.
+bool verify_cosets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& shifts, size_t l, const std::vector<Fr>& values,
+                   const std::vector<G1>& proofs);
+// the same on contiguous buffers, with the value addressing of the device call: value (k, t) is values[k * item_stride + t * t_stride]; roots_of_unity:
+// `shifts` is ONE Fr omega and item k has the shift omega^k (nothing to refuse: a power of a root of unity is not zero)
+bool verify_cosets_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values,
+                        size_t item_stride, size_t t_stride, size_t l, const uint64_t* proofs, size_t n);
 
 }  // namespace kzg
 
@@ -325,6 +338,16 @@ bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_
 // positions vec_coset_indices(size, l, i) = {i + t r : t < l} -- the index list vec_verify_subset and vec_encrypt_subset_batch take.
 std::vector<G1> vec_open_cosets(const kzg::KZGSetup& setup, const std::vector<Fr>& evals, size_t l);
 std::vector<size_t> vec_coset_indices(size_t domain_size, size_t l, size_t i);
+// The counterpart of vec_open_cosets for whoever holds the evaluations: are the r = size / l proofs the block proofs of `com` for evals? ONE
+// kzg::verify_cosets_flat over the vector in domain order (value (i, t) is evals[i + t r]; the shifts omega_d^i are derived on the device): r
+// draws from `rng`, one device call. evals.size() <= the domain (zero-padded, as vec_open_cosets reads them), proofs.size() == r.
+bool vec_verify_cosets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& evals, size_t l, const std::vector<G1>& proofs);
+// evals: domain_size (a power of two) Fr; proofs: domain_size / l affine points
+bool vec_verify_cosets_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const Fr* evals, size_t domain_size, size_t l, const uint64_t* proofs);
+// some of the cosets: cosets[k] < size / l names the positions vec_coset_indices(domain_size, l, cosets[k]), values[k * l + t] is the value at position
+// cosets[k] + t r, proofs[k] its block proof. One draw per listed coset in list order, one device call.
+bool vec_verify_cosets_subset(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets,
+                              const std::vector<Fr>& values, const std::vector<G1>& proofs);
 // n items over ONE index set with different value tuples (the 1-of-2^k string-OT shape): item i is readable by the holder of a vector with
 // values[i * k + j] at idx[j] for all j. One r per item in index order. The rows -I_i come from ONE set_polys call and O(n k^2) host scalar
 // work, [-I_i(tau)]_1 from ONE msm_g1_batch (n rows of k coefficients), C is added by one g1_sum per item, then ONE encrypt_multi call with n

@@ -306,6 +306,36 @@ int keaki_host_vec_open_subset(void* s, size_t domain_size, const uint64_t* idx,
     return 0;
   });
 }
+// coset batch verification (include/keaki_hip.h: keaki_hip_kzg_verify_cosets). n_coms: 1 or n; values: n rows of l; the gammas are drawn from rng
+int keaki_host_verify_cosets(void* rng, void* s, const uint64_t* coms, size_t n_coms, const uint64_t* shifts, size_t l, const uint64_t* values, const uint64_t* proofs,
+                             size_t n, int* out_ok) {
+  return guard([&] {
+    std::vector<G1> c(n_coms), pr(n);
+    for (size_t i = 0; i < n_coms; i++) c[i] = g1_of(coms + 8 * i);
+    for (size_t i = 0; i < n; i++) pr[i] = g1_of(proofs + 8 * i);
+    *out_ok = kzg::verify_cosets(*(Rng*)rng, ((Setup*)s)->s, c, frs_of(shifts, n), l, frs_of(values, n * l), pr) ? 1 : 0;
+    return 0;
+  });
+}
+// all cosets of a vector: evals n <= domain Fr (zero-padded to the next power of two d), proofs d / l affine points
+int keaki_host_vec_verify_cosets(void* rng, void* s, const uint64_t* com, const uint64_t* evals, size_t n, size_t l, const uint64_t* proofs, size_t n_proofs,
+                                 int* out_ok) {
+  return guard([&] {
+    std::vector<G1> pr(n_proofs);
+    for (size_t i = 0; i < n_proofs; i++) pr[i] = g1_of(proofs + 8 * i);
+    *out_ok = vec::vec_verify_cosets(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), frs_of(evals, n), l, pr) ? 1 : 0;
+    return 0;
+  });
+}
+int keaki_host_vec_verify_cosets_subset(void* rng, void* s, const uint64_t* com, size_t domain_size, size_t l, const uint64_t* cosets, size_t k, const uint64_t* values,
+                                        const uint64_t* proofs, int* out_ok) {
+  return guard([&] {
+    std::vector<G1> pr(k);
+    for (size_t i = 0; i < k; i++) pr[i] = g1_of(proofs + 8 * i);
+    *out_ok = vec::vec_verify_cosets_subset(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), domain_size, l, idx_of(cosets, k), frs_of(values, k * l), pr) ? 1 : 0;
+    return 0;
+  });
+}
 int keaki_host_vec_verify_subset(void* s, const uint64_t* com, size_t domain_size, const uint64_t* idx, const uint64_t* values, size_t k, const uint64_t* proof,
                                  int* out_ok) {
   return guard([&] {

@@ -499,6 +499,41 @@ def vec_verify_subset(setup: KZGSetup, com, domain_size: int, idx, values, proof
     return bool(ok.value)
 
 
+def verify_cosets(rng: "Rng", setup: KZGSetup, commitments, shifts, l: int, values, proofs) -> bool:
+    """kzg::verify_cosets: n set proofs over cosets shifts[k] <omega_l> of ONE size l in one device call. values (n, l, 4): value t of item k belongs to
+    shifts[k] omega_l^t. One gamma per item is drawn from `rng` in index order. commitments: one G1 (shared) or n. The setup needs G2 powers beyond l.
+    A zero shift, an l that is not a power of two, a setup without [tau^l]_2, a device group: SetError"""
+    h = np.ascontiguousarray(_u64(shifts, 4)); n = h.shape[0]
+    coms = np.ascontiguousarray(_u64(commitments, 8)); pr = np.ascontiguousarray(_u64(proofs, 8)); y = np.ascontiguousarray(_u64(values, 4))
+    if l < 1 or y.shape[0] != n * l or pr.shape[0] != n or coms.shape[0] not in (1, n):
+        raise SetError("verify_cosets: l values and one proof per item, commitments one or n")
+    ok = C.c_int(0)
+    _ck(_lib().keaki_host_verify_cosets(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(h), C.c_size_t(l), _p(y), _p(pr), C.c_size_t(n), C.byref(ok)))
+    return bool(ok.value)
+
+
+def vec_verify_cosets(rng: "Rng", setup: KZGSetup, com, evals, l: int, proofs) -> bool:
+    """vec::vec_verify_cosets: are the size / l proofs of vec_open_cosets(evals, l) the block proofs of `com`? One device call over the evaluations
+    in domain order; one gamma per coset is drawn from `rng`"""
+    e = np.ascontiguousarray(_u64(evals, 4)); pr = np.ascontiguousarray(_u64(proofs, 8)); ok = C.c_int(0)
+    if e.shape[0] < 1 or l < 1:
+        raise SetError("vec_verify_cosets: no evaluations")
+    _ck(_lib().keaki_host_vec_verify_cosets(rng.h, setup.h, _p(_u64(com)), _p(e), C.c_size_t(e.shape[0]), C.c_size_t(l), _p(pr), C.c_size_t(pr.shape[0]), C.byref(ok)))
+    return bool(ok.value)
+
+
+def vec_verify_cosets_subset(rng: "Rng", setup: KZGSetup, com, domain_size: int, l: int, cosets, values, proofs) -> bool:
+    """vec::vec_verify_cosets_subset: the listed cosets only. cosets[k] < size / l names the positions vec_coset_indices(size, l, cosets[k]); values
+    (k, l, 4) in the order of those positions; proofs (k, 8)"""
+    ix = np.ascontiguousarray(cosets, np.uint64); k = ix.shape[0]
+    y = np.ascontiguousarray(_u64(values, 4)); pr = np.ascontiguousarray(_u64(proofs, 8)); ok = C.c_int(0)
+    if l < 1 or y.shape[0] != k * l or pr.shape[0] != k:
+        raise SetError("vec_verify_cosets_subset: l values and one proof per listed coset")
+    _ck(_lib().keaki_host_vec_verify_cosets_subset(rng.h, setup.h, _p(_u64(com)), C.c_size_t(domain_size), C.c_size_t(l), _p(ix), C.c_size_t(k), _p(y), _p(pr),
+                                                   C.byref(ok)))
+    return bool(ok.value)
+
+
 def vec_encrypt_subset_batch(rng: "Rng", setup: KZGSetup, com, domain_size: int, idx, values, messages: np.ndarray):
     """n items over ONE index set with different value tuples: values (n, k, 4), messages (n, msg_len) uint8 -> (ct_g2 (n, 16), bodies (n, msg_len)).
     Item i is readable by the holder of a vector with values[i, j] at idx[j] for every j; one r per item in index order."""

@@ -178,6 +178,15 @@ extern "C" {
     pub fn keaki_hip_kzg_verify_batch_dev(ctx: *mut keaki_hip_ctx, d_com_aff: *const c_void, com_stride: i32, d_tau_g2_aff: *const c_void,
                                           d_points: *const c_void, point_mode: i32, d_values: *const c_void, d_proofs_aff: *const c_void,
                                           d_gammas: *const c_void, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
+    // n set proofs over cosets h_k <omega_l> of size l = 2^log2l: e(L, g2) == e(R, [tau^l]_2); value (k, t) at values + 4 (k item_stride + t t_stride) words
+    pub fn keaki_hip_kzg_verify_cosets(ctx: *mut keaki_hip_ctx, srs_g1: *const keaki_hip_srs_g1, com_aff: *const u64, com_stride: i32, tau_l_g2_aff: *const u64,
+                                       points: *const u64, point_mode: i32, values: *const u64, item_stride: usize, t_stride: usize, log2l: u32,
+                                       omega_l_inv: *const u64, inv_l: *const u64, proofs_aff: *const u64, gammas: *const u64, n: usize, ok_out: *mut i32,
+                                       sums_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_cosets_dev(ctx: *mut keaki_hip_ctx, srs_g1: *const keaki_hip_srs_g1, d_com_aff: *const c_void, com_stride: i32,
+                                           d_tau_l_g2_aff: *const c_void, d_points: *const c_void, point_mode: i32, d_values: *const c_void,
+                                           item_stride: usize, t_stride: usize, log2l: u32, omega_l_inv: *const u64, inv_l: *const u64,
+                                           d_proofs_aff: *const c_void, d_gammas: *const c_void, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
     // one verdict per opening: status[i] = 0 <=> e(C_i - y_i g1 + z_i proof_i, g2) e(-proof_i, [tau]_2) == 1; lhs_out_aff: n x u64[8] or null
     pub fn keaki_hip_kzg_verify_each(ctx: *mut keaki_hip_ctx, com_aff: *const u64, com_stride: i32, tau_g2_aff: *const u64, points: *const u64,
                                      point_mode: i32, values: *const u64, proofs_aff: *const u64, n: usize, status: *mut u8, n_bad: *mut u64,

@@ -467,6 +467,36 @@ pub fn verify_batch(commitments: &[G1Projective], tau_g2: &G2Projective, points:
     ok != 0
 }
 
+/// n set proofs over cosets of one size in one call (`keaki_hip_kzg_verify_cosets`): item k is the coset `shifts[k] * <omega_l>` of size `l` (a
+/// power of two, at most 1024) with its `l` values `values[k * l ..]` (value t belongs to `shifts[k] * omega_l^t`), `e(L, g2) == e(R, [tau^l]_2)` with
+/// L = sum gamma_k C_k - sum_j J_j [tau^j]_1 + sum (gamma_k shifts[k]^l) proof_k and R = sum gamma_k proof_k. `commitments`: one for all items or
+/// one per item. `tau_l_g2`: `[tau^l]_2`. `gammas`: drawn by the CALLER, one `Fr::rand` per item in index order; the soundness bound 1/r needs
+/// them independent, uniform and unknown to whoever made the proofs. A zero shift is refused here (the library does not look). Single-GPU device.
+pub fn verify_cosets(srs: &HipSrs, commitments: &[G1Projective], tau_l_g2: &G2Projective, shifts: &[Fr], l: usize, values: &[Fr], proofs: &[G1Projective],
+                     gammas: &[Fr]) -> bool {
+    use ark_poly::{EvaluationDomain, Radix2EvaluationDomain};
+    let dev = Device::global();
+    let n = shifts.len();
+    assert!(dev.group.is_null() && l.is_power_of_two() && l <= 1024 && l <= srs.len());
+    assert!(values.len() == n * l && proofs.len() == n && gammas.len() == n && (commitments.len() == 1 || commitments.len() == n));
+    assert!(shifts.iter().all(|h| *h != Fr::from(0u64)), "verify_cosets: a zero shift is no coset");
+    let dom = Radix2EvaluationDomain::<Fr>::new(l).unwrap();
+    let one = |x: &Fr| fr_ptr(core::slice::from_ref(x));
+    let flat = |v: &[G1Projective]| -> Vec<u64> { G1Projective::normalize_batch(v).iter().flat_map(|p| g1_words(p)).collect() };
+    let (c, p, t) = (flat(commitments), flat(proofs), g2_words(&tau_l_g2.into_affine()));
+    let mut ok = 0i32;
+    dev.check(
+        unsafe {
+            sys::keaki_hip_kzg_verify_cosets(
+                dev.ctx, srs.srs(), c.as_ptr(), if commitments.len() == 1 { 0 } else { 1 }, t.as_ptr(), fr_ptr(shifts), 0, fr_ptr(values), l, 1, l.trailing_zeros(),
+                one(&dom.group_gen_inv), one(&dom.size_inv), p.as_ptr(), fr_ptr(gammas), n, &mut ok, core::ptr::null_mut(),
+            )
+        },
+        "kzg_verify_cosets",
+    );
+    ok != 0
+}
+
 /// One verdict per opening (`keaki_hip_kzg_verify_each`): item i is valid iff `e(C_i - y_i g1 + z_i proof_i, g2) * e(-proof_i, [tau]_2) == 1`,
 /// the predicate of `verify` with `z_i proof_i` moved across the pairing. Arguments as [`verify_batch`], without gammas: the verdict is exact.
 /// Returns `true` for every valid item.
