@@ -110,7 +110,11 @@ const char* keaki_hip_version(void);
  * "fk_coset_group" (terms per Straus group of the FK23 coset openings' pointwise kernel: 1, 2 or 4, 0 = the built-in 4; 1 = one ladder per term, the A/B
  * form), "fk_coset_min_lanes" (that kernel splits the terms of a position over lanes while its launch has fewer lanes than this: 1 .. 2^31, 0 = the
  * built-in 131,072; other values of the two are refused with KEAKI_ERR_BAD_ARG, in the environment ignored), "verify_cosets_blocks" (workgroups of
- * keaki_hip_kzg_verify_cosets' transform kernel: 1 .. 1,024, 0 = automatic, three per compute unit; results do not depend on it; other values refused).
+ * keaki_hip_kzg_verify_cosets' transform kernel: 1 .. 1,024, 0 = automatic, three per compute unit; results do not depend on it; other values refused),
+ * "coset_rows_min_lanes" (keaki_hip_kzg_coset_pairs: the row kernel splits an item's l bases over lanes while a launch has fewer lanes than this: 1 .. 2^31,
+ * 0 = the built-in 131,072), "coset_rows_route" (how that call sums its rows: 1 = the handle's window table over the first l SRS points, 2 = the batched
+ * MSM, 0 = by plan), "coset_rows_wb" (window bits of that table: 8, 10 or 13, 0 = by plan -- the switch of the width sweep; a table the allocator refuses
+ * means route 2); results do not depend on any of the three; other values are refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
  * What the library does with HOST memory of the caller, and its off switches (round 5):
  *   "host_prefault" (default 1): while the kernels of a host-array call run, the library first-touches the caller's OUTPUT arrays (writes a zero
  *       into one byte per 4 KB page, the whole range being overwritten by the download that follows; outputs >= 1 MB only) and asks for transparent
@@ -519,8 +523,7 @@ keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_co
  *   _dev       every array is a device pointer (16-byte aligned; the commitment, [tau^l]_2 and omega too); omega_l_inv, inv_l (read before the call
  *              returns), ok_out and sums_out_aff stay HOST pointers, so this form synchronises as well. Workspace: 64 B per item + 32 B per value
  *              of at most 1,024 tiles, grow-only, counted in keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim.
- *   out of scope  a per-coset verdict (a verify_each for cosets): a rejected batch falls back to keaki_hip_kzg_verify_multi per coset. The multi-GPU
- *              form: the host layers refuse a device group.
+ *   out of scope  The multi-GPU form: the host layers refuse a device group. (The per-coset verdict is keaki_hip_kzg_verify_cosets_each, below.)
  *   numbers    (MI355X, medians of alternating rounds in one process: profiles/verify_cosets_times.txt, bench_tools/bench_verify_cosets.py) all r cosets of a
  *              vector, resident / from host arrays, l = 4 / 16 / 64: d = 2^20 7.8 / 7.4 / 7.2 ms (host 8.7 / 8.2 / 8.0), 2^16 7.0 / 6.9 / 7.1, 2^12 6.9 / 7.2 /
  *              7.1; l = 1,024 at d = 2^20 7.6 ms (8.2). Against (a) the only route before, r calls of keaki_hip_kzg_verify_multi (7.7 - 8.8 ms each at l <=
@@ -539,6 +542,79 @@ keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip
                                              size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
                                              const uint64_t* inv_l, const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out,
                                              uint64_t* sums_out_aff);
+
+/* ---- KZG coset pairs and per-coset verdicts: the per-item side of the coset check, all n cosets in one call -----------------
+ * verify_cosets answers "are all n set proofs valid?" in two pairings. Two things need the PER-ITEM points of the same check
+ *     e(A_k, g2) == e(pi_k, [tau^l]_2 - c_k g2)        A_k = C_k - [I_k(tau)]_1        c_k = h_k^l
+ * (I_k the coset interpolant defined above): a verdict per coset, and encryption to the claimed values of every coset (ct_k = r_k ([tau^l]_2 - c_k g2),
+ * key_k = KDF(e(r_k A_k, g2)): keaki_hip_encap_multi / _encrypt_multi with n groups of one item, coms := A, points := c, values := 0 and [tau^l]_2).
+ *
+ * keaki_hip_kzg_coset_pairs: lhs_out_aff[k] = A_k (affine G1, (0,0) = identity), c_out[k] = c_k (Fr, Montgomery).
+ *   srs_g1, com_aff, com_stride, points, point_mode, values, item_stride, t_stride, log2l, omega_l_inv, inv_l, n, the zero-shift rule
+ *              exactly as in keaki_hip_kzg_verify_cosets. The handle is not const: its coset table is built on first use (below).
+ *   equalities lhs_out_aff[k] followed by [tau^l]_2 - c_k g2 is pair_out_aff of keaki_hip_kzg_verify_multi on the l points h_k omega_l^t of coset k.
+ *              Every route, and handles with and without window tables or a precomputed coset table, give the same bytes (affine points are unique).
+ *   errors     those of keaki_hip_kzg_verify_cosets (a null required pointer, com_stride or point_mode outside {0, 1}, l > KEAKI_SET_MAX, n l >= 2^31,
+ *              overlapping strides, extents of 2^47 -> KEAKI_ERR_BAD_ARG; l > len(srs_g1) -> KEAKI_ERR_TOO_LARGE; a refused workspace -> KEAKI_ERR_OOM): nothing
+ *              is written, nothing launched, the context stays usable. n = 0: nothing is written.
+ *   kernels    csrc/kzg_cosets.hip, the instantiations without gammas of verify_cosets' kernels: 1 / h_k and c_k (one Fermat inversion per 16 items), then
+ *              per launch chunk the size-l inverse transforms in LDS with EVERY item's row -a_(k,j) stored (32 B per value). csrc/kzg_coset_pairs.hip:
+ *              route 1, k_cp_rows: all rows share the l bases [tau^j]_1, so the handle keeps T[j][w][d] = d 2^(wb w) [tau^j]_1 (signed wb-bit digits, wb =
+ *              13 / 10 / 8 bits for l <= 64 / <= 512 / 1,024: the widest whose table stays under 512 MiB, csrc/coset_rows_plan.h) and a row is l x ceil(254 / wb)
+ *              additions in the lazy 29-bit XYZZ form with no doublings (l = 64: 1,280 against about 5,300 of the batched MSM; l = 4: 80 against about
+ *              1,450). A lane owns an (item, slice of the l bases); the S slices of an item (S a power of two <= min(l, 64), doubled while the launch has
+ *              fewer than "coset_rows_min_lanes" lanes) meet by cross-lane exchange; one general addition joins C_k; k_cp_affine inverts 8 items under
+ *              one inversion. Route 2: the rows through the batched MSM (keaki_hip_msm_g1_batch's kernels) plus C_k: the fallback when the table's
+ *              allocation is refused, and the A/B partner ("coset_rows_route").
+ *   table      64 B x l x windows x (2^(wb - 1) + 1): 21 MB at l = 4, 336 MB at l = 64, 437 MB at l = 512, 270 MB at l = 1,024. Built on first use or by
+ *              keaki_hip_srs_g1_precompute_cosets, cached in the SRS handle for ONE l beside the FK23, update and FK23-coset caches (none evicts another),
+ *              counted in keaki_hip_ctx_memory out4[0], freed with the handle. Results never depend on it.
+ *   chunks     launch chunks of at most 2^20 values (32 MiB of rows + 224 B per item), grow-only, counted in out4[1]; a refused reservation halves the
+ *              chunk, and the call fails only when one item does not fit. + 32 B per item of the call (1 / h_k).
+ *   host form  one upload in front (the span of the values the strides name), the kernels, one download of 96 n bytes; returns only when nothing reads or
+ *              writes caller memory, also on failure.
+ *   _dev       every array is a device pointer (16-byte aligned; the commitment and omega too); omega_l_inv, inv_l stay HOST pointers, read before the
+ *              call returns. Asynchronous on the context's stream.
+ *
+ * keaki_hip_kzg_verify_cosets_each: status[k] = 0 <=> the coset check holds for item k. With c_k pi_k moved across the pairing:
+ *     L_k = A_k + c_k pi_k          status[k] = 0  <=>  e(L_k, g2) * e(-pi_k, [tau^l]_2) == 1
+ * which is keaki_hip_kzg_verify_each on (coms := A, points := c, values := 0, [tau]_2 := [tau^l]_2): coset_pairs into the workspace, then that call's
+ * kernels unchanged (no new pairing code). The verdict is exact and equals that of keaki_hip_kzg_verify_multi on the l points of item k; n_bad = 0 <=>
+ * keaki_hip_kzg_verify_cosets accepts (for any gammas with valid items; with the probability stated there otherwise). At log2l = 0 the status and L bytes
+ * are those of keaki_hip_kzg_verify_each with z_k = h_k.
+ *   tau_l_g2_aff, proofs_aff   as in keaki_hip_kzg_verify_cosets;   status, n_bad, first_bad, lhs_out_aff (the L_k, or NULL), identities, [tau^l]_2 = identity,
+ *              n = 0 and "a bad item never fails the call" as in keaki_hip_kzg_verify_each; errors: those of both calls, nothing written.
+ *   workspace  + 128 B per item of the call (A_k, c_k, the zero values) on top of both calls' own.
+ *   _dev       n_bad and first_bad stay HOST pointers: synchronises, like keaki_hip_kzg_verify_each_dev.
+ *   out of scope  device groups / multi-GPU (the host layers refuse a device group), and a C-ABI encap_cosets: encryption to cosets is composed from
+ *              keaki_hip_kzg_coset_pairs and keaki_hip_encap_multi / keaki_hip_encrypt_multi by the caller.
+ *   numbers    (MI355X, medians of alternating rounds in one process: profiles/coset_each_times.txt, bench_tools/bench_coset_each.py) all r cosets of a vector,
+ *              l = 4 / 16 / 64. coset_pairs resident, route 1: d = 2^20 2.8 / 3.1 / 3.2 ms (4.4 / 3.8 / 3.8 from host arrays), 2^16 0.88 / 0.87 / 1.04, 2^12 0.78 /
+ *              0.92 / 0.96; l = 1,024 at 2^20 5.1 ms. Route 2 on the same inputs: 173 / 50 / 18 ms at 2^20 (13 at l = 1,024), 11.5 / 5.0 / 3.3 at 2^16, 2.8 / 2.4 /
+ *              2.5 at 2^12: the table route wins at EVERY measured shape (2.6 - 62 x) and is the default at every l. verify_cosets_each resident: d = 2^20 43.2 /
+ *              13.7 / 9.0 ms (10.7 at l = 1,024), 2^16 and 2^12 6.4 - 6.7 ms (the latency of one pairing chunk); keaki_hip_kzg_verify_cosets on the same items,
+ *              the floor: 7.0 - 7.6 ms. Against the only route before, r calls of keaki_hip_kzg_verify_multi (64 timed at 7.7 - 8.8 ms each, 23 ms at l = 1,024,
+ *              EXTRAPOLATED to r): 125 s at d = 2^20, l = 64 (1/14,000), 2,251 s at l = 4 (1/52,000). Encryption to all cosets through the host layer
+ *              (vec_encrypt_cosets, 32-byte messages) at d = 2^16: 13.3 / 5.7 / 3.9 ms against 276 / 69 / 16 s as r encrypt_set calls (64 timed, EXTRAPOLATED).
+ *              The width and lane sweeps behind the plan are in the same file and summarised in csrc/coset_rows_plan.h. Kernel shares (rocprofv3) and the
+ *              first call's table build were not measured. */
+keaki_status keaki_hip_srs_g1_precompute_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2l);
+keaki_status keaki_hip_kzg_coset_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride, const uint64_t* points,
+                                       int32_t point_mode, const uint64_t* values, size_t item_stride, size_t t_stride, uint32_t log2l,
+                                       const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, uint64_t* lhs_out_aff, uint64_t* c_out);
+keaki_status keaki_hip_kzg_coset_pairs_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride, const void* d_points,
+                                           int32_t point_mode, const void* d_values, size_t item_stride, size_t t_stride, uint32_t log2l,
+                                           const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, void* d_lhs_out_aff, void* d_c_out);
+keaki_status keaki_hip_kzg_verify_cosets_each(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride,
+                                              const uint64_t* tau_l_g2_aff, const uint64_t* points, int32_t point_mode, const uint64_t* values,
+                                              size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
+                                              const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad, uint64_t* first_bad,
+                                              uint64_t* lhs_out_aff);
+keaki_status keaki_hip_kzg_verify_cosets_each_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride,
+                                                  const void* d_tau_l_g2_aff, const void* d_points, int32_t point_mode, const void* d_values,
+                                                  size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
+                                                  const uint64_t* inv_l, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
+                                                  uint64_t* first_bad, void* d_lhs_out_aff);
 
 /* ---- KZG verify_each: one verdict per opening, n openings in one call ---------------------------------------------------
  * verify_batch answers "are all n openings valid?"; this call says WHICH are not. Per item, by bilinearity (z_i proof_i moved across the

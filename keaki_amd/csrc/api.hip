@@ -5,6 +5,7 @@
 #include "host_plan.h"
 #include "encap_multi_plan.h"
 #include "fk_coset_plan.h"
+#include "coset_rows_plan.h"
 
 #include <algorithm>
 #include <cctype>
@@ -40,10 +41,11 @@ struct SrsCache {
 };
 // fk: FK23, hat_s = DFT_2d(reversed SRS), 2d Jacobian points, key log2d | upd: vec_update, the update tables of d (vec_update.hip: a | u | omega_d^-i |
 // 1 / (omega_d^t - 1)), key log2d | fkc: FK23 coset openings, the l transforms hat_s_j = DFT_2r(row j of the SRS, reversed), 2d Jacobian points
-// (fk_coset.hip), key (log2d, log2l). The three are independent of each other; a new cache is added HERE (srs_free walks them).
+// (fk_coset.hip), key (log2d, log2l) | cr: kzg coset_pairs, the window table over the first l points (kzg_coset_pairs.hip, coset_rows_plan.h), key (log2l, wb).
+// The four are independent of each other; a new cache is added HERE (srs_free walks them).
 struct keaki_hip_srs_g1 : SrsHandle {
-  SrsCache fk, upd, fkc;
-  template <class F> void for_each_cache(F&& f) { for (SrsCache* c : {&fk, &upd, &fkc}) f(*c); }
+  SrsCache fk, upd, fkc, cr;
+  template <class F> void for_each_cache(F&& f) { for (SrsCache* c : {&fk, &upd, &fkc, &cr}) f(*c); }
 };
 struct keaki_hip_srs_g2 : SrsHandle {
   template <class F> void for_each_cache(F&&) {}
@@ -643,6 +645,21 @@ bool verify_cosets_blocks_refuses(keaki_hip_ctx* ctx, const char*, long long v) 
   if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: verify_cosets_blocks = %lld out of range (1 .. %u; 0 = automatic)", v, VC_MAX_BLOCKS);
   return true;
 }
+bool coset_rows_min_lanes_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= ((long long)1 << 31)) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: coset_rows_min_lanes = %lld out of range (1 .. 2^31; 0 = %u)", v, CR_MIN_LANES);
+  return true;
+}
+bool coset_rows_route_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= 2) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: coset_rows_route = %lld must be 0 (by plan), 1 (window table) or 2 (batched MSM)", v);
+  return true;
+}
+bool coset_rows_wb_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v == 0 || v == 8 || v == 10 || v == 13) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: coset_rows_wb = %lld must be 8, 10 or 13 (0 = by plan)", v);
+  return true;
+}
 #define TUNE_OPTION(member, ...) TuneOption{#member, assign_member<&Tuning::member>, __VA_ARGS__}
 const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(msm_c, msm_c_refuses<MSM_C_MAX>), TUNE_OPTION(msm_c_shared, msm_c_refuses<MSM_C_SHARED_MAX>), TUNE_OPTION(msm_short_tables),
@@ -654,6 +671,8 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(msm_pipe_growth), TUNE_OPTION(vec_update_k_pass, vec_update_k_pass_refuses),
     TUNE_OPTION(fk_coset_group, fk_coset_group_refuses), TUNE_OPTION(fk_coset_min_lanes, fk_coset_min_lanes_refuses),
     TUNE_OPTION(verify_cosets_blocks, verify_cosets_blocks_refuses),
+    TUNE_OPTION(coset_rows_min_lanes, coset_rows_min_lanes_refuses), TUNE_OPTION(coset_rows_route, coset_rows_route_refuses),
+    TUNE_OPTION(coset_rows_wb, coset_rows_wb_refuses),
 #ifdef KEAKI_DIAG
     TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
 #endif
@@ -2482,26 +2501,30 @@ bool verify_cosets_strides_overlap(size_t n, size_t l, size_t item_stride, size_
   while (b) { const size_t r = g % b; g = b; b = r; }
   return t_stride / g < n && item_stride / g < l;
 }
-keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const int32_t* ok_out) {
+// The ONE argument check of the coset calls (`what`: kzg_verify_cosets, kzg_coset_pairs, kzg_verify_cosets_each). `out_ok` / `out_name`: the output that is
+// required at any n; `rest_ok`: the call's own arrays beyond the commitment, the shifts, the values and the two constants are there (asked for n > 0).
+keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const char* what, bool out_ok, const char* out_name, bool rest_ok) {
   if ((a.com_stride != 0 && a.com_stride != 1) || (a.point_mode != 0 && a.point_mode != 1))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: com_stride = %d, point_mode = %d: both must be 0 or 1", (int)a.com_stride, (int)a.point_mode);
-  if (!ok_out || !a.srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: %s is null", ok_out ? "srs_g1" : "ok_out");
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: com_stride = %d, point_mode = %d: both must be 0 or 1", what, (int)a.com_stride, (int)a.point_mode);
+  if (!out_ok || !a.srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, out_ok ? "srs_g1" : out_name);
   if (a.log2l > 31 || ((size_t)1 << a.log2l) > KEAKI_SET_MAX)
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: l = 2^%u exceeds KEAKI_SET_MAX = %d", a.log2l, (int)KEAKI_SET_MAX);
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: l = 2^%u exceeds KEAKI_SET_MAX = %d", what, a.log2l, (int)KEAKI_SET_MAX);
   const size_t l = (size_t)1 << a.log2l;
-  if (a.n && (!a.com || !a.tau_l || !a.points || !a.values || !a.proofs || !a.gammas || !a.omega_l_inv || !a.inv_l))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: null pointer");
-  if (a.n >= ((size_t)1 << 31) || a.n * l >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: n * l = %zu * %zu must be < 2^31", a.n, l);
+  if (a.n && (!a.com || !a.points || !a.values || !a.omega_l_inv || !a.inv_l || !rest_ok)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
+  if (a.n >= ((size_t)1 << 31) || a.n * l >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n * l = %zu * %zu must be < 2^31", what, a.n, l);
   if (a.n && verify_cosets_strides_overlap(a.n, l, a.item_stride, a.t_stride))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: under item_stride = %zu, t_stride = %zu two of the %zu x %zu values share an address", a.item_stride,
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: under item_stride = %zu, t_stride = %zu two of the %zu x %zu values share an address", what, a.item_stride,
                 a.t_stride, a.n, l);
   // the extent (n - 1) item_stride + (l - 1) t_stride stays below 2^48 values (each term below 2^47, checked without forming a product that could wrap): 32 x the
   // extent, the bytes the host form uploads and the kernels' address arithmetic, fits 64 bits with room to spare
   constexpr size_t HALF = (size_t)1 << 47;
   if (a.n && ((a.n > 1 && a.item_stride >= HALF / (a.n - 1)) || (l > 1 && a.t_stride >= HALF / (l - 1))))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_cosets: item_stride = %zu, t_stride = %zu put the last of the %zu x %zu values 2^48 or more values behind the first",
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu, t_stride = %zu put the last of the %zu x %zu values 2^48 or more values behind the first", what,
                 a.item_stride, a.t_stride, a.n, l);
-  return srs_holds(ctx, a.srs, "kzg_verify_cosets", l, "kzg_verify_cosets: I has %zu coefficients but the G1 SRS holds %zu points");
+  return srs_holds(ctx, a.srs, what, l, "kzg cosets: I has %zu coefficients but the G1 SRS holds %zu points");
+}
+keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const int32_t* ok_out) {
+  return verify_cosets_args(ctx, a, "kzg_verify_cosets", ok_out != nullptr, "ok_out", a.tau_l && a.proofs && a.gammas);
 }
 }  // namespace
 }  // extern "C++"
@@ -2676,6 +2699,166 @@ keaki_status keaki_hip_kzg_verify_each(keaki_hip_ctx* ctx, const uint64_t* com_a
                           point_mode ? (void*)(io + VeLayout::O_OMEGA) : ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, n, out,
                           lhs_out_aff ? out + lhs_off : nullptr, n_bad, first_bad));
   // the counters are back, so the status bytes are final: one download (status and L lie in one buffer, but go to two arrays of the caller)
+  prefault_out(ctx, lhs_out_aff, lhs_out_aff ? n * G1_AFF_BYTES : 0);
+  if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out + lhs_off, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, status, out, n);
+}
+
+// ---- KZG coset pairs and per-coset verdicts ------------------------------------------------------------------------------------------------
+// coset_pairs: A_k = C_k - [I_k(tau)]_1 and c_k = h_k^l for n cosets (kzg_coset_pairs.hip has the derivation and the kernels). Kernel sequence, all on
+// ctx->stream: k_vc_prepare<., true> over the n items (c, 1 / h) | per launch chunk (coset_rows_plan.h): k_vc_transform<., true> (the rows), then route 1
+// k_cp_rows over the handle's window table, or route 2 msm_g1_batch_run over the rows + k_cp_join; k_cp_affine. verify_cosets_each is coset_pairs into
+// cp_pairs [A: n x 64 | c: n x 32 | zeros: n x 32] and verify_each_core on (coms := A, points := c, values := 0, [tau]_2 := [tau^l]_2).
+extern "C++" {
+namespace {
+keaki_status coset_table_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2l, uint32_t wb) {
+  return srs_cache_ensure(ctx, srs, srs->cr, (int)log2l, (int)wb, cr_table_bytes(log2l, wb), [&](void* t) { return coset_table_run(ctx, srs->d, log2l, wb, t); });
+}
+// a.* are device pointers; the caller holds the context. Every allocation that can be refused (the table, the workspace) comes before the first launch.
+keaki_status coset_pairs_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const VcArgs& a, void* d_lhs, void* d_c) {
+  const size_t n = a.n, l = (size_t)1 << a.log2l;
+  std::lock_guard<std::recursive_mutex> hl(srs->mu);       // the table belongs to the handle: one call per handle at a time
+  int route = cr_route(ctx->tune.coset_rows_route, a.log2l);
+  const uint32_t wb = ctx->tune.coset_rows_wb ? (uint32_t)ctx->tune.coset_rows_wb : cr_wb(a.log2l);
+  if (route == 1) {
+    const keaki_status st = coset_table_ensure(ctx, srs, a.log2l, wb);
+    if (st == KEAKI_ERR_OOM) { ctx->err.clear(); route = 2; }      // optional memory, like the window tables of an MSM
+    else if (st != KEAKI_OK) return st;
+  }
+  const size_t hinv_bytes = (n * 32 + 255) & ~(size_t)255, per_item = l * 32 + sizeof(uint64_t) * 16 + (route == 2 ? G1_JAC_BYTES : 0);
+  size_t ch = cr_chunk_items(n, a.log2l);
+  for (;;) {
+    const keaki_status st = reserve(ctx, ctx->cp_work, hinv_bytes + ch * per_item);
+    if (st == KEAKI_OK) break;
+    if (st != KEAKI_ERR_OOM || ch <= 1) return st;
+    ctx->err.clear();
+    ch = cr_chunk_halve(ch);
+  }
+  char* hinv = (char*)ctx->cp_work.p;
+  char* rows = hinv + hinv_bytes;
+  char* xyzz = rows + ch * l * 32;
+  char* jac = xyzz + ch * 128;
+  const auto tb = srs_tables(srs);
+  ST_TRY(coset_pairs_shifts_run(ctx, a.points, a.point_mode, a.log2l, n, d_c, hinv));
+  for (size_t lo = 0; lo < n; lo += ch) {
+    const size_t m = std::min(ch, n - lo);
+    ST_TRY(coset_pairs_rows_run(ctx, a.values, a.item_stride, a.t_stride, hinv, a.log2l, a.omega_l_inv, a.inv_l, lo, m, route == 2, rows));
+    if (route == 1) {
+      ST_TRY(coset_rows_table_run(ctx, srs->cr.p, wb, rows, a.log2l, cr_slices(m, a.log2l, (uint64_t)ctx->tune.coset_rows_min_lanes), a.com, a.com_stride, lo, m, xyzz));
+    } else {
+      ST_TRY(msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, rows, l, m, l, jac));
+      ST_TRY(coset_rows_join_run(ctx, jac, a.com, a.com_stride, lo, m, xyzz));
+    }
+    ST_TRY(coset_rows_affine_run(ctx, xyzz, m, (char*)d_lhs + lo * G1_AFF_BYTES));
+  }
+  return KEAKI_OK;
+}
+struct CpPairs { char *a, *c, *zeros; };
+keaki_status coset_each_reserve(keaki_hip_ctx* ctx, size_t n, size_t extra, CpPairs* out) {
+  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
+  ST_TRY(reserve(ctx, ctx->cp_pairs, n * 128 + extra));
+  out->a = (char*)ctx->cp_pairs.p; out->c = out->a + n * G1_AFF_BYTES; out->zeros = out->c + n * 32;
+  return KEAKI_OK;
+}
+keaki_status coset_each_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const VcArgs& a, const uint64_t* tau_host, const CpPairs& w, void* d_status, void* d_lhs,
+                             uint64_t* n_bad, uint64_t* first_bad) {
+  ST_TRY(coset_pairs_core(ctx, srs, a, w.a, w.c));
+  HIP_TRY(ctx, hipMemsetAsync(w.zeros, 0, a.n * 32, ctx->stream));
+  return verify_each_core(ctx, w.a, 1, a.tau_l, tau_host, w.c, 0, w.zeros, a.proofs, a.n, d_status, d_lhs, n_bad, first_bad);
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_srs_g1_precompute_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2l) {
+  CTX_GUARD(ctx);
+  if (!srs || log2l > 31 || ((size_t)1 << log2l) > KEAKI_SET_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g1_precompute_cosets: bad argument");
+  ST_TRY(srs_holds(ctx, srs, "srs_g1_precompute_cosets", (size_t)1 << log2l, "kzg cosets: I has %zu coefficients but the G1 SRS holds %zu points"));
+  std::lock_guard<std::recursive_mutex> hl(srs->mu);
+  return coset_table_ensure(ctx, srs, log2l, cr_wb(log2l));
+}
+
+keaki_status keaki_hip_kzg_coset_pairs_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride, const void* d_points,
+                                           int32_t point_mode, const void* d_values, size_t item_stride, size_t t_stride, uint32_t log2l,
+                                           const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, void* d_lhs_out_aff, void* d_c_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_coset_pairs");
+  const VcArgs a = {srs_g1, d_com_aff, nullptr, d_points, d_values, nullptr, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
+  ST_TRY(verify_cosets_args(ctx, a, "kzg_coset_pairs", true, "", d_lhs_out_aff && d_c_out));
+  if (n == 0) return KEAKI_OK;
+  return coset_pairs_core(ctx, srs_g1, a, d_lhs_out_aff, d_c_out);
+}
+
+keaki_status keaki_hip_kzg_coset_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride, const uint64_t* points,
+                                       int32_t point_mode, const uint64_t* values, size_t item_stride, size_t t_stride, uint32_t log2l,
+                                       const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, uint64_t* lhs_out_aff, uint64_t* c_out) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_coset_pairs");
+  VcArgs a = {srs_g1, com_aff, nullptr, points, values, nullptr, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
+  ST_TRY(verify_cosets_args(ctx, a, "kzg_coset_pairs", true, "", lhs_out_aff && c_out));
+  if (n == 0) return KEAKI_OK;
+  const size_t l = (size_t)1 << log2l, span = (n - 1) * item_stride + (l - 1) * t_stride + 1;
+  ST_TRY(reserve(ctx, ctx->cp_pairs, n * 96));
+  ST_TRY(reserve(ctx, ctx->cp_in, span * 32));
+  ST_TRY(reserve(ctx, ctx->io_c, point_mode ? 32 : n * 32));
+  ST_TRY(reserve(ctx, ctx->io_e, (com_stride ? n : 1) * G1_AFF_BYTES));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, ctx->io_e.p, com_aff, (com_stride ? n : 1) * G1_AFF_BYTES));
+  ST_TRY(feed.put(0, ctx->io_c.p, points, point_mode ? 32 : n * 32));
+  ST_TRY(feed.put(0, ctx->cp_in.p, values, span * 32));
+  a.com = ctx->io_e.p; a.points = ctx->io_c.p; a.values = ctx->cp_in.p;
+  char* out = (char*)ctx->cp_pairs.p;
+  ST_TRY(coset_pairs_core(ctx, srs_g1, a, out, out + n * G1_AFF_BYTES));
+  HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, c_out, out + n * G1_AFF_BYTES, n * 32);
+}
+
+keaki_status keaki_hip_kzg_verify_cosets_each_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride,
+                                                  const void* d_tau_l_g2_aff, const void* d_points, int32_t point_mode, const void* d_values,
+                                                  size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
+                                                  const uint64_t* inv_l, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
+                                                  uint64_t* first_bad, void* d_lhs_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_cosets_each");
+  const VcArgs a = {srs_g1, d_com_aff, d_tau_l_g2_aff, d_points, d_values, d_proofs_aff, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l,
+                    omega_l_inv, inv_l};
+  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets_each", n_bad != nullptr, "n_bad", d_tau_l_g2_aff && d_proofs_aff && d_status));
+  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
+  CpPairs w;
+  ST_TRY(coset_each_reserve(ctx, n, 0, &w));
+  uint64_t tau_host[16];
+  ST_TRY(read_constants(ctx, d_tau_l_g2_aff, nullptr, tau_host, nullptr));          // the key of the line table
+  return coset_each_core(ctx, srs_g1, a, tau_host, w, d_status, d_lhs_out_aff, n_bad, first_bad);
+}
+
+keaki_status keaki_hip_kzg_verify_cosets_each(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride,
+                                              const uint64_t* tau_l_g2_aff, const uint64_t* points, int32_t point_mode, const uint64_t* values,
+                                              size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
+                                              const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad, uint64_t* first_bad,
+                                              uint64_t* lhs_out_aff) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_verify_cosets_each");
+  VcArgs a = {srs_g1, com_aff, tau_l_g2_aff, points, values, proofs_aff, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
+  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets_each", n_bad != nullptr, "n_bad", tau_l_g2_aff && proofs_aff && status));
+  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
+  // every buffer is reserved before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only
+  const size_t l = (size_t)1 << log2l, span = (n - 1) * item_stride + (l - 1) * t_stride + 1;
+  const size_t lhs_off = (n + 63) & ~(size_t)63, out_bytes = lhs_off + (lhs_out_aff ? n * G1_AFF_BYTES : 0);
+  CpPairs w;
+  ST_TRY(coset_each_reserve(ctx, n, out_bytes, &w));
+  ST_TRY(reserve(ctx, ctx->cp_in, span * 32));
+  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
+  ST_TRY(reserve(ctx, ctx->io_c, point_mode ? 32 : n * 32));
+  ST_TRY(reserve(ctx, ctx->io_e, (com_stride ? n : 1) * G1_AFF_BYTES));
+  char* io = (char*)ctx->ve_io.p;
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, io + VeLayout::O_TAU, tau_l_g2_aff, 128));
+  ST_TRY(feed.put(0, ctx->io_e.p, com_aff, (com_stride ? n : 1) * G1_AFF_BYTES));
+  ST_TRY(feed.put(0, ctx->io_c.p, points, point_mode ? 32 : n * 32));
+  ST_TRY(feed.put(0, ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES));
+  ST_TRY(feed.put(0, ctx->cp_in.p, values, span * 32));
+  a.com = ctx->io_e.p; a.tau_l = io + VeLayout::O_TAU; a.points = ctx->io_c.p; a.values = ctx->cp_in.p; a.proofs = ctx->io_b.p;
+  char* out = w.zeros + n * 32;
+  ST_TRY(coset_each_core(ctx, srs_g1, a, tau_l_g2_aff, w, out, lhs_out_aff ? out + lhs_off : nullptr, n_bad, first_bad));
   prefault_out(ctx, lhs_out_aff, lhs_out_aff ? n * G1_AFF_BYTES : 0);
   if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out + lhs_off, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
   return download(feed, status, out, n);

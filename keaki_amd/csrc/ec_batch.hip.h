@@ -79,13 +79,16 @@ __host__ __device__ inline FbShape fb_shape(u32 wb) { return {wb, (254u + wb - 1
 // Table build: T[j][d] = d * base_j with base_j = 2^(wb j) * base. Two launches: the window bases (lane j doubles wb * j times: the longest lane
 // is the only chain there is), then one lane per entry with a ladder over the BITS OF d -- at most wb - 1 doublings and additions. (Until round 4
 // an entry was a full 254-bit scalar multiplication by d 2^(wb j) mod r: 20 ms for a 16-bit G2 table, 2 x that in the first call of a context.)
+// n_bases > 1 (the coset table over the first l SRS points, g1_fb_tables_run): out[b * windows + j] for base b, and the entry kernel runs over the
+// n_bases x windows window bases as one long list (its FbShape carries windows := n_bases x windows). A base that is the identity gives identities.
 template <class F>
-__global__ void __launch_bounds__(64) k_fb_window_bases(const Aff<F>* __restrict__ base, FbShape g, Aff<F>* __restrict__ out) {
-  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= g.windows) return;
-  Jac<F> a = jac_from_aff(*base);
+__global__ void __launch_bounds__(64) k_fb_window_bases(const Aff<F>* __restrict__ base, FbShape g, Aff<F>* __restrict__ out, u32 n_bases) {
+  const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= g.windows * n_bases) return;
+  const u32 b = idx / g.windows, j = idx % g.windows;
+  Jac<F> a = jac_from_aff(base[b]);
   for (u32 t = 0; t < g.wb * j; t++) a = jac_dbl(a);
-  out[j] = jac_to_aff(a);
+  out[idx] = jac_to_aff(a);
 }
 template <class F>
 __global__ void __launch_bounds__(64) k_fb_table_entries(const Aff<F>* __restrict__ bases, FbShape g, Aff<F>* __restrict__ table) {

@@ -25,10 +25,21 @@ keaki_status g1_generator_to(keaki_hip_ctx* ctx, void* d_dst) {
 keaki_status g1_fb_table_run(keaki_hip_ctx* ctx, const void* d_base, void* d_table, uint32_t wb) {
   const FbShape g = fb_shape(wb);
   ST_TRY(reserve(ctx, ctx->fb_bases, 64 * sizeof(G2Aff)));
-  hipLaunchKernelGGL((k_fb_window_bases<Fq>), dim3(1), dim3(64), 0, ctx->stream, (const G1Aff*)d_base, g, (G1Aff*)ctx->fb_bases.p);
+  hipLaunchKernelGGL((k_fb_window_bases<Fq>), dim3(1), dim3(64), 0, ctx->stream, (const G1Aff*)d_base, g, (G1Aff*)ctx->fb_bases.p, 1u);
   hipLaunchKernelGGL((k_fb_table_entries<Fq>), dim3(cdiv((size_t)g.windows * g.entries, 64)), dim3(64), 0, ctx->stream, (const G1Aff*)ctx->fb_bases.p, g,
                      (G1Aff*)d_table);
   return launch_check(ctx, "g1_fb_table");
+}
+// the coset table (kzg_coset_pairs.hip): table[(b * windows + j) * entries + d] = d 2^(wb j) * bases[b], b < n_bases, by the same two ladders
+keaki_status g1_fb_tables_run(keaki_hip_ctx* ctx, const void* d_bases, uint32_t n_bases, void* d_table, uint32_t wb) {
+  const FbShape g = fb_shape(wb);
+  const u32 rows = n_bases * g.windows;
+  ST_TRY(reserve(ctx, ctx->fb_bases, (size_t)rows * sizeof(G1Aff)));
+  hipLaunchKernelGGL((k_fb_window_bases<Fq>), dim3(cdiv(rows, 64)), dim3(64), 0, ctx->stream, (const G1Aff*)d_bases, g, (G1Aff*)ctx->fb_bases.p, n_bases);
+  const FbShape all = {g.wb, rows, g.entries};
+  hipLaunchKernelGGL((k_fb_table_entries<Fq>), dim3(cdiv((size_t)rows * g.entries, 64)), dim3(64), 0, ctx->stream, (const G1Aff*)ctx->fb_bases.p, all,
+                     (G1Aff*)d_table);
+  return launch_check(ctx, "g1_fb_tables");
 }
 keaki_status encap_g1_fixed_run(keaki_hip_ctx* ctx, const void* d_tab_a, uint32_t wb_a, const void* d_tab_b, uint32_t wb_b, const void* d_xs,
                                 const void* d_rs, size_t n, void* d_out) {

@@ -23,7 +23,7 @@ keaki_status g2_generator_to(keaki_hip_ctx* ctx, void* d_dst) {
 keaki_status g2_fb_table_run(keaki_hip_ctx* ctx, const void* d_base, void* d_table, uint32_t wb) {
   const FbShape g = fb_shape(wb);
   ST_TRY(reserve(ctx, ctx->fb_bases, 64 * sizeof(G2Aff)));
-  hipLaunchKernelGGL((k_fb_window_bases<Fq2>), dim3(1), dim3(64), 0, ctx->stream, (const G2Aff*)d_base, g, (G2Aff*)ctx->fb_bases.p);
+  hipLaunchKernelGGL((k_fb_window_bases<Fq2>), dim3(1), dim3(64), 0, ctx->stream, (const G2Aff*)d_base, g, (G2Aff*)ctx->fb_bases.p, 1u);
   hipLaunchKernelGGL((k_fb_table_entries<Fq2>), dim3(cdiv((size_t)g.windows * g.entries, 64)), dim3(64), 0, ctx->stream, (const G2Aff*)ctx->fb_bases.p, g,
                      (G2Aff*)d_table);
   return launch_check(ctx, "g2_fb_table");
@@ -36,7 +36,7 @@ keaki_status verify_points_run(keaki_hip_ctx* ctx, const void* d_tab_g1, const v
 }
 keaki_status g2_pow2_multiples_run(keaki_hip_ctx* ctx, const void* d_base, uint32_t count, void* d_out) {
   const FbShape g = {1u, count, 0u};                 // "windows" of one bit: base_s = 2^s base
-  hipLaunchKernelGGL((k_fb_window_bases<Fq2>), dim3(cdiv(count, 64)), dim3(64), 0, ctx->stream, (const G2Aff*)d_base, g, (G2Aff*)d_out);
+  hipLaunchKernelGGL((k_fb_window_bases<Fq2>), dim3(cdiv(count, 64)), dim3(64), 0, ctx->stream, (const G2Aff*)d_base, g, (G2Aff*)d_out, 1u);
   return launch_check(ctx, "g2_pow2_multiples");
 }
 // share_simds: a latency-bound job of this context runs beside this kernel (the table of a new commitment): the 256-register form, whose waves

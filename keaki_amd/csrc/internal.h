@@ -66,6 +66,9 @@ struct Tuning {
   int fk_coset_group = 0;        // KEAKI_FK_COSET_GROUP / "fk_coset_group": terms per Straus group of the FK23 coset openings' pointwise kernel, 1, 2 or 4; 0 = FKC_G (fk_coset_plan.h); 1 = one ladder per term (A/B switch)
   long long fk_coset_min_lanes = 0;   // KEAKI_FK_COSET_MIN_LANES / "fk_coset_min_lanes": the pointwise launch of the FK23 coset openings splits a position's terms over lanes while it has fewer lanes than this; 0 = FKC_SPLIT_MIN_LANES
   int verify_cosets_blocks = 0;  // KEAKI_VERIFY_COSETS_BLOCKS / "verify_cosets_blocks": workgroups of verify_cosets' transform kernel, 1 .. VC_MAX_BLOCKS; 0 = automatic (three per compute unit, what its LDS holds; a test sets 2 to make a workgroup run several tiles)
+  long long coset_rows_min_lanes = 0;   // KEAKI_COSET_ROWS_MIN_LANES / "coset_rows_min_lanes": the row kernel of kzg coset_pairs splits an item's l bases over lanes while a launch has fewer lanes than this; 0 = CR_MIN_LANES (coset_rows_plan.h)
+  int coset_rows_route = 0;      // KEAKI_COSET_ROWS_ROUTE / "coset_rows_route": how kzg coset_pairs sums its rows: 1 = the handle's window table over the first l SRS points, 2 = the batched MSM; 0 = by plan (coset_rows_plan.h: cr_route)
+  int coset_rows_wb = 0;         // KEAKI_COSET_ROWS_WB / "coset_rows_wb": window bits of that table, 8, 10 or 13; 0 = by plan (coset_rows_plan.h: cr_wb; the switch of the width sweep)
   int vec_update_k_pass = 0;     // KEAKI_VEC_UPDATE_K_PASS / "vec_update_k_pass": entries of the change list per pass of vec_update's proof kernel, 1 .. UPD_K_PASS; 0 = UPD_K_PASS
 #ifdef KEAKI_DIAG
   unsigned diag_row_mask = 0;    // "diag_row_mask" (ONLY in the diagnostic build, `make -C keaki_amd/csrc diag`; never in libkeaki_hip.so): the table-row index of every (row, sign) entry of the bucket-ordered stream is ANDed with this mask before the bucket kernel runs, so its gathers hit a table of (mask + 1) x 64 B -- the arithmetic, the instruction stream and the kernel binary stay the shipped ones, the RESULT IS WRONG by construction (bench_tools/r6_bucket_clock_diag.py)
@@ -177,6 +180,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf vu_io, vu_work, vu_pass;   // vec_update: host form: indices, deltas, commitment and proofs of the call | the 2d Jacobian points of a table build, the terms of the commitment | header and window tables of a pass
   keaki_internal::DevBuf ks_io, ks_q;               // KZG set openings: points, values, Z, weights, I and the small results of a call | the quotient and the work of its passes (kzg_multi.hip)
   keaki_internal::DevBuf vc_io, vc_work;            // kzg verify_cosets: the small in/out block (VcLayout, api.hip) | s, 1 / h, -J, g and the partial rows of a call (kzg_cosets.hip: verify_cosets_layout)
+  keaki_internal::DevBuf cp_work, cp_pairs, cp_in;  // kzg coset_pairs: 1 / h (n Fr), then the rows, the XYZZ sums and (route 2) the Jacobian sums of a launch chunk | verify_cosets_each: A, c and the zero values of the call; host forms: + the outputs | host forms: the values
   keaki_internal::DevBuf fc_work;                   // FK23 coset openings (fk_coset.hip): twiddles, hat_a, the partial sums and the two transforms of a call; host forms: + coefficients and proofs
   // every DevBuf above with its memory class, kem's included (KemState::for_each_buf): what keaki_hip_ctx_destroy and _trim free and
   // keaki_hip_ctx_memory counts. A new workspace is added HERE.
@@ -184,7 +188,7 @@ struct keaki_hip_ctx {
     f(&fb_bases, 2);
     for (keaki_internal::DevBuf* b : {&digits, &hist, &offsets, &cursor, &sorted, &buckets, &acc29, &partials, &wsums, &tmp_a, &tmp_b, &tmp_c, &io_a, &io_b, &io_c,
                                       &io_d, &io_e, &perm, &heavy, &pair_ws, &fk_tab, &mb_canon, &mb_wsums, &mb_q, &fkb_pts, &fkb_fr, &em_offsets, &vb_io, &vb_s,
-                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work})
+                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work, &cp_work, &cp_pairs, &cp_in})
       f(b, 1);
     kem.for_each_buf(f);
   }
@@ -278,6 +282,7 @@ keaki_status g2_generator_to(keaki_hip_ctx* ctx, void* d_dst);  // writes the af
 keaki_status g1_generator_to(keaki_hip_ctx* ctx, void* d_dst);  // affine G1 generator (64 B)
 size_t fb_table_entries(uint32_t wb);                                                          // window-table entries per base at window width wb
 keaki_status g1_fb_table_run(keaki_hip_ctx* ctx, const void* d_base, void* d_table, uint32_t wb);    // table[j * entries + d] = d 2^(wb j) base
+keaki_status g1_fb_tables_run(keaki_hip_ctx* ctx, const void* d_bases, uint32_t n_bases, void* d_table, uint32_t wb);   // table[(b windows + j) entries + d] = d 2^(wb j) bases[b]
 keaki_status g2_fb_table_run(keaki_hip_ctx* ctx, const void* d_base, void* d_table, uint32_t wb);
 keaki_status g2_pow2_multiples_run(keaki_hip_ctx* ctx, const void* d_base, uint32_t count, void* d_out);   // out[s] = 2^s base (affine), lane s doubles s times
 keaki_status encap_g1_fixed_run(keaki_hip_ctx* ctx, const void* d_tab_a, uint32_t wb_a, const void* d_tab_b, uint32_t wb_b, const void* d_xs, const void* d_rs, size_t n, void* d_out);
@@ -330,6 +335,18 @@ size_t verify_cosets_work_bytes(size_t n, uint32_t log2l);
 VcWork verify_cosets_layout(size_t n, uint32_t log2l, void* d_work);
 keaki_status verify_cosets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const void* d_values, size_t item_stride,
                                        size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, const VcWork& w);
+// kzg coset_pairs. Fr side (kzg_cosets.hip, the PAIRS / ROWS instantiations of the kernels above): d_c_out[k] = h_k^l (Montgomery), d_hinv[k] = 1 / h_k for the n
+// items of a call | d_rows[(i << log2l) + j] = -a_(first + i, j) for the m items of a launch chunk (m * l < 2^31), canonical integers or (mont) Montgomery form.
+// Group side (kzg_coset_pairs.hip): the window table of the first l SRS points (coset_rows_plan.h: cr_table_bytes) | d_xyzz[i] = C_(first + i) + sum_j
+// rows[i][j] [tau^j]_1 by the table walk in S slices per item, or from the Jacobian sums of msm_g1_batch_run | m XYZZ points -> affine, (0,0) for the identity.
+keaki_status coset_pairs_shifts_run(keaki_hip_ctx* ctx, const void* d_points, int point_mode, uint32_t log2l, size_t n, void* d_c_out, void* d_hinv);
+keaki_status coset_pairs_rows_run(keaki_hip_ctx* ctx, const void* d_values, size_t item_stride, size_t t_stride, const void* d_hinv, uint32_t log2l,
+                                  const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t first, size_t m, bool mont, void* d_rows);
+keaki_status coset_table_run(keaki_hip_ctx* ctx, const void* d_srs, uint32_t log2l, uint32_t wb, void* d_table);
+keaki_status coset_rows_table_run(keaki_hip_ctx* ctx, const void* d_table, uint32_t wb, const void* d_rows, uint32_t log2l, uint32_t S, const void* d_coms,
+                                  int com_stride, size_t first, size_t m, void* d_xyzz);
+keaki_status coset_rows_join_run(keaki_hip_ctx* ctx, const void* d_sums_jac, const void* d_coms, int com_stride, size_t first, size_t m, void* d_xyzz);
+keaki_status coset_rows_affine_run(keaki_hip_ctx* ctx, const void* d_xyzz, size_t m, void* d_out_aff);
 // layout moves around the final sum (no arithmetic): n <= 64 affine points -> normalised Jacobian | the normalised Jacobian sums L, R -> d_out_lr_aff[0], [1] affine
 keaki_status verify_batch_aff_to_jac_run(keaki_hip_ctx* ctx, const void* d_in_aff, uint32_t n, void* d_out_jac);
 keaki_status verify_batch_jac_to_aff_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_r_jac, void* d_out_lr_aff);

@@ -71,7 +71,8 @@ KDEV void vc_each(F&& f) {
 }
 
 // Grid-stride over the chunks of VC_INV items. hinv_out and (point_mode 1) s_out double as the lane's own scratch on the way up.
-template <int POINT_MODE>
+// PAIRS (keaki_hip_kzg_coset_pairs: no gammas): s_out[k] = c_k itself, and nothing is summed.
+template <int POINT_MODE, bool PAIRS = false>
 static __global__ void __launch_bounds__(VC_THREADS) k_vc_prepare(const Fr* __restrict__ gammas, const Fr* __restrict__ points, u32 n, u32 log2l,
                                                                   Fr* __restrict__ s_out, Fr* __restrict__ hinv_out, Fr* __restrict__ part_g) {
   __shared__ Fr sh[VC_WAVES];
@@ -103,11 +104,16 @@ static __global__ void __launch_bounds__(VC_THREADS) k_vc_prepare(const Fr* __re
       Fr ck = h;                                    // c_k = h_k^l
 #pragma unroll 1
       for (u32 b = 0; b < log2l; b++) ck = fp_mul<FrParams>(ck, ck);
-      const Fr gamma = gammas[k];
-      s_out[k] = fp_mul<FrParams>(gamma, ck);
-      g = fp_add<FrParams>(g, gamma);
+      if constexpr (PAIRS) {
+        s_out[k] = ck;
+      } else {
+        const Fr gamma = gammas[k];
+        s_out[k] = fp_mul<FrParams>(gamma, ck);
+        g = fp_add<FrParams>(g, gamma);
+      }
     }
   }
+  if constexpr (PAIRS) return;
   g = fr_wave_sum(g);
   if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = g;
   __syncthreads();
@@ -120,10 +126,12 @@ static __global__ void __launch_bounds__(VC_THREADS) k_vc_prepare(const Fr* __re
 
 // part_j[blockIdx.x * l + j] = sum over the items k of this workgroup's tiles of gamma_k l^-1 h_k^-j b'_(k,j), b' the transform without its l^-1.
 // BY_ITEM: the lanes of a load run over the items of the tile first (item_stride < t_stride).
-template <bool BY_ITEM>
+// ROWS (keaki_hip_kzg_coset_pairs): no gammas and no sum over the items -- every item's row is stored: rows_out[k * l + j] = -a_(k,j) = -l^-1 h_k^-j b'_(k,j),
+// 32 B each, as a canonical integer (rows_mont = 0: the digits of the window-table walk) or in Montgomery form (1: the scalars of the batched MSM).
+template <bool BY_ITEM, bool ROWS = false>
 static __global__ void __launch_bounds__(VC_THREADS) k_vc_transform(const Fr* __restrict__ values, u64 item_stride, u64 t_stride, const Fr* __restrict__ gammas,
                                                                     const Fr* __restrict__ hinv, Fr omega_l_inv, Fr inv_l, u32 log2l, u32 n,
-                                                                    Fr* __restrict__ part_j) {
+                                                                    Fr* __restrict__ part_j, u32* __restrict__ rows_out = nullptr, u32 rows_mont = 0) {
   __shared__ VcTile sh;
   __shared__ Fr aux[VC_AUX];
   const u32 tid = threadIdx.x;
@@ -187,7 +195,8 @@ static __global__ void __launch_bounds__(VC_THREADS) k_vc_transform(const Fr* __
       const u32 k = k_base + slot;
       if (k < n) {
         if (i == 0 || j == 0) {
-          pw = fp_mul<FrParams>(gammas[k], inv_l);
+          if constexpr (ROWS) pw = inv_l;
+          else pw = fp_mul<FrParams>(gammas[k], inv_l);
 #pragma unroll 1
           for (u32 b = 0; b < log2l; b++)
             if ((j >> b) & 1u) pw = fp_mul<FrParams>(pw, sq[slot * log2l + b]);
@@ -195,12 +204,28 @@ static __global__ void __launch_bounds__(VC_THREADS) k_vc_transform(const Fr* __
           pw = fp_mul<FrParams>(pw, sq[slot * log2l]);
         }
         const u32 p = log2l ? (__brev(j) >> (32u - log2l)) : 0u;
-        acc[i] = fp_add<FrParams>(acc[i], fp_mul<FrParams>(vc_ld(sh, vc_phys((slot << log2l) + p, log2l)), pw));
+        const Fr term = fp_mul<FrParams>(vc_ld(sh, vc_phys((slot << log2l) + p, log2l)), pw);
+        if constexpr (ROWS) {
+          const Fr na = fp_neg<FrParams>(term);
+          u32 v[8];
+          if (rows_mont) {
+#pragma unroll
+            for (int w = 0; w < 8; w++) v[w] = na.l[w];
+          } else {
+            fp_from_mont<FrParams>(v, na);
+          }
+          uint4* dst = reinterpret_cast<uint4*>(rows_out + (((size_t)k << log2l) + j) * 8u);
+          dst[0] = make_uint4(v[0], v[1], v[2], v[3]);
+          dst[1] = make_uint4(v[4], v[5], v[6], v[7]);
+        } else {
+          acc[i] = fp_add<FrParams>(acc[i], term);
+        }
       }
     });
     __syncthreads();                                // the next tile overwrites the values and the squarings
   }
 
+  if constexpr (ROWS) return;
   // fold the T slots: value e = slot * l + j (natural order now), a tree over the slots
   vc_each<VC_RUN>([&](auto ic) { vc_st(sh, vc_phys(VC_RUN * tid + decltype(ic)::value, log2l), acc[decltype(ic)::value]); });
   __syncthreads();
@@ -305,6 +330,39 @@ keaki_status verify_cosets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas,
   hipLaunchKernelGGL(k_vc_finish, dim3(cdiv(l, 64)), dim3(VC_THREADS), 0, ctx->stream, (const Fr*)w.part_j, blocks, l, (const Fr*)w.part_g, g_blocks,
                      (Fr*)w.neg_j, (Fr*)w.g);
   return launch_check(ctx, "verify_cosets_scalars");
+}
+
+// keaki_hip_kzg_coset_pairs, Fr side. coset_pairs_shifts_run: d_c_out[k] = c_k = h_k^l (Montgomery) and d_hinv[k] = 1 / h_k for ALL n items of the call
+// (point_mode 1 steps through omega^k from k = 0). coset_pairs_rows_run: the rows -a_(k,j) of the m items from `first` on into d_rows (m x l x 32 B, in
+// (item, j) order; mont: see k_vc_transform), one launch.
+keaki_status coset_pairs_shifts_run(keaki_hip_ctx* ctx, const void* d_points, int point_mode, uint32_t log2l, size_t n, void* d_c_out, void* d_hinv) {
+  if (n == 0 || n >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_coset_pairs: n = %zu out of range on the device side", n);
+  const u32 blocks = std::min<u32>(cdiv(cdiv(n, VC_INV), VC_THREADS), VC_G_BLOCKS);
+  if (point_mode)
+    hipLaunchKernelGGL((k_vc_prepare<1, true>), dim3(blocks), dim3(VC_THREADS), 0, ctx->stream, (const Fr*)nullptr, (const Fr*)d_points, (u32)n, log2l,
+                       (Fr*)d_c_out, (Fr*)d_hinv, (Fr*)nullptr);
+  else
+    hipLaunchKernelGGL((k_vc_prepare<0, true>), dim3(blocks), dim3(VC_THREADS), 0, ctx->stream, (const Fr*)nullptr, (const Fr*)d_points, (u32)n, log2l,
+                       (Fr*)d_c_out, (Fr*)d_hinv, (Fr*)nullptr);
+  return launch_check(ctx, "coset_pairs_shifts");
+}
+keaki_status coset_pairs_rows_run(keaki_hip_ctx* ctx, const void* d_values, size_t item_stride, size_t t_stride, const void* d_hinv, uint32_t log2l,
+                                  const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t first, size_t m, bool mont, void* d_rows) {
+  if (m == 0 || log2l > 10 || ((size_t)1 << log2l) > KEAKI_SET_MAX || (m << log2l) >= ((size_t)1 << 31))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_coset_pairs: a chunk of %zu items of 2^%u values out of range on the device side", m, log2l);
+  Fr winv, linv;
+  memcpy(&winv, omega_l_inv, 32);
+  memcpy(&linv, inv_l, 32);
+  const Fr* values = (const Fr*)d_values + first * item_stride;
+  const Fr* hinv = (const Fr*)d_hinv + first;
+  const u32 blocks = std::min<u32>(vc_tiles(m, log2l), ctx->n_cu * 3u);
+  if (item_stride < t_stride)
+    hipLaunchKernelGGL((k_vc_transform<true, true>), dim3(blocks), dim3(VC_THREADS), 0, ctx->stream, values, (u64)item_stride, (u64)t_stride, (const Fr*)nullptr,
+                       hinv, winv, linv, log2l, (u32)m, (Fr*)nullptr, (u32*)d_rows, mont ? 1u : 0u);
+  else
+    hipLaunchKernelGGL((k_vc_transform<false, true>), dim3(blocks), dim3(VC_THREADS), 0, ctx->stream, values, (u64)item_stride, (u64)t_stride, (const Fr*)nullptr,
+                       hinv, winv, linv, log2l, (u32)m, (Fr*)nullptr, (u32*)d_rows, mont ? 1u : 0u);
+  return launch_check(ctx, "coset_pairs_rows");
 }
 
 }  // namespace keaki_internal

@@ -35,6 +35,8 @@ EXPORTS = [
     "keaki_hip_kzg_aggregate", "keaki_hip_kzg_aggregate_dev", "keaki_hip_kzg_verify_multi",
     "keaki_hip_srs_g1_precompute_fk_cosets", "keaki_hip_open_fk_cosets", "keaki_hip_open_fk_cosets_poly", "keaki_hip_open_fk_cosets_poly_dev",
     "keaki_hip_kzg_verify_cosets", "keaki_hip_kzg_verify_cosets_dev",
+    "keaki_hip_srs_g1_precompute_cosets", "keaki_hip_kzg_coset_pairs", "keaki_hip_kzg_coset_pairs_dev",
+    "keaki_hip_kzg_verify_cosets_each", "keaki_hip_kzg_verify_cosets_each_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
     "keaki_hip_group_kzg_open", "keaki_hip_group_encap_batch", "keaki_hip_group_decap_batch",
@@ -212,6 +214,10 @@ def load_library():
         lib.keaki_hip_kzg_aggregate_dev.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_kzg_verify_cosets.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_kzg_verify_cosets_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_srs_g1_precompute_cosets.argtypes = [vp, vp, C.c_uint32]
+        lib.keaki_hip_kzg_coset_pairs.argtypes = lib.keaki_hip_kzg_coset_pairs_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, sz, vp, vp]
+        lib.keaki_hip_kzg_verify_cosets_each.argtypes = lib.keaki_hip_kzg_verify_cosets_each_dev.argtypes = [
+            vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, sz, vp, vp, vp, vp]
         lib.keaki_hip_kzg_verify_multi.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_srs_g1_precompute_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
         lib.keaki_hip_open_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -728,6 +734,66 @@ class KeakiHip:
                                                           dp(d_values), int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)),
                                                           dp(d_proofs), dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
         return bool(ok.value), sums[:8].copy(), sums[8:].copy()
+
+    def srs_g1_precompute_cosets(self, srs: "SrsG1", log2l: int):
+        """builds the handle's window table over its first l = 2^log2l points ahead of the first kzg_coset_pairs / kzg_verify_cosets_each call
+        (keaki_hip_srs_g1_precompute_cosets); results never depend on it"""
+        self._ck(self.lib.keaki_hip_srs_g1_precompute_cosets(self.ctx, srs.handle, int(log2l)))
+
+    def kzg_coset_pairs(self, srs_g1: "SrsG1", com_aff, points, values, item_stride: int, t_stride: int, log2l: int, omega_l_inv, inv_l, n: int,
+                        point_mode: int = 0):
+        """the per-item points of the coset check (keaki_hip_kzg_coset_pairs) -> (A u64[n, 8], c u64[n, 4]): A_k = C_k - [I_k(tau)]_1 and c_k = h_k^l.
+        Arguments as kzg_verify_cosets; n is explicit because with point_mode = 1 and one commitment no array carries it"""
+        c, z, v = _np(com_aff, 8), _np(points, 4), _np(values, 4)
+        n = int(n)
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if (com_stride and c.shape[0] != n) or z.shape[0] != (1 if point_mode else n):
+            raise ValueError("kzg_coset_pairs: array lengths disagree")
+        if n and 0 <= log2l < 32 and v.shape[0] < (n - 1) * int(item_stride) + ((1 << log2l) - 1) * int(t_stride) + 1:
+            raise ValueError("kzg_coset_pairs: the strides reach past the %d values given" % v.shape[0])
+        lhs = np.zeros((n, 8), np.uint64); cs = np.zeros((n, 4), np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_coset_pairs(self.ctx, srs_g1.handle, _ptr(c), com_stride, _ptr(z), int(point_mode), _ptr(v), int(item_stride),
+                                                    int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)), n, _ptr(lhs), _ptr(cs)))
+        return lhs, cs
+
+    def kzg_coset_pairs_dev(self, srs_g1: "SrsG1", d_com, com_stride: int, d_points, point_mode: int, d_values, item_stride: int, t_stride: int, log2l: int,
+                            omega_l_inv, inv_l, n: int, d_lhs_out, d_c_out):
+        """the same with every array resident: device pointers (ints) or torch tensors; omega_l_inv and inv_l stay host arrays. Asynchronous on the
+        context's stream. The caller answers for the extent of d_values under the strides"""
+        dp = lambda x: C.c_void_p(None if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else x))
+        self._ck(self.lib.keaki_hip_kzg_coset_pairs_dev(self.ctx, srs_g1.handle, dp(d_com), int(com_stride), dp(d_points), int(point_mode), dp(d_values),
+                                                        int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)), int(n),
+                                                        dp(d_lhs_out), dp(d_c_out)))
+
+    def kzg_verify_cosets_each(self, srs_g1: "SrsG1", com_aff, tau_l_g2_aff, points, values, item_stride: int, t_stride: int, log2l: int, omega_l_inv, inv_l,
+                               proofs_aff, point_mode: int = 0, want_lhs: bool = False):
+        """one verdict per coset (keaki_hip_kzg_verify_cosets_each) -> (status uint8[n]: 0 valid / 1 invalid, n_bad, first_bad or None), and with
+        want_lhs a fourth element: the L_k = A_k + c_k proof_k (u64[n, 8]). Arguments as kzg_verify_cosets, without gammas"""
+        pr, c, z, v = _np(proofs_aff, 8), _np(com_aff, 8), _np(points, 4), _np(values, 4)
+        n = pr.shape[0]
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if (com_stride and c.shape[0] != n) or z.shape[0] != (1 if point_mode else n):
+            raise ValueError("kzg_verify_cosets_each: array lengths disagree")
+        if n and 0 <= log2l < 32 and v.shape[0] < (n - 1) * int(item_stride) + ((1 << log2l) - 1) * int(t_stride) + 1:
+            raise ValueError("kzg_verify_cosets_each: the strides reach past the %d values given" % v.shape[0])
+        status = np.zeros(n, np.uint8); lhs = np.zeros((n, 8), np.uint64) if want_lhs else None
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_kzg_verify_cosets_each(self.ctx, srs_g1.handle, _ptr(c), com_stride, _ptr(_np(tau_l_g2_aff)), _ptr(z), int(point_mode), _ptr(v),
+                                                           int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)), _ptr(pr), n,
+                                                           _ptr(status), C.byref(bad), C.byref(first), _ptr(lhs) if want_lhs else None))
+        res = (status, bad.value, (None if bad.value == 0 else first.value))
+        return res + (lhs,) if want_lhs else res
+
+    def kzg_verify_cosets_each_dev(self, srs_g1: "SrsG1", d_com, com_stride: int, d_tau_l_g2, d_points, point_mode: int, d_values, item_stride: int,
+                                   t_stride: int, log2l: int, omega_l_inv, inv_l, d_proofs, n: int, d_status, d_lhs=None):
+        """the same with every array resident; the status bytes (and the L_k) stay on the device -> (n_bad, first_bad or None) on the host (the
+        call synchronises)"""
+        dp = lambda x: C.c_void_p(None if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else x))
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_kzg_verify_cosets_each_dev(self.ctx, srs_g1.handle, dp(d_com), int(com_stride), dp(d_tau_l_g2), dp(d_points), int(point_mode),
+                                                               dp(d_values), int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)),
+                                                               _ptr(_np(inv_l)), dp(d_proofs), int(n), dp(d_status), C.byref(bad), C.byref(first), dp(d_lhs)))
+        return bad.value, (None if bad.value == 0 else first.value)
 
     def kzg_verify_each(self, com_aff, tau_g2_aff, points, values, proofs_aff, point_mode: int = 0, want_lhs: bool = False):
         """one verdict per opening (keaki_hip_kzg_verify_each) -> (status uint8[n]: 0 valid / 1 invalid, n_bad, first_bad or None), and with

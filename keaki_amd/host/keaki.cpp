@@ -571,6 +571,46 @@ bool verify_cosets_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, s
                                         values[0].l, item_stride, t_stride, log2l, dl.group_gen_inv.l, dl.size_inv.l, proofs, gammas[0].l, n, &ok, nullptr));
   return ok != 0;
 }
+namespace {
+// the refusals the three coset calls share; -> log2 l
+unsigned coset_call_check(const char* what, const KZGSetup& setup, size_t n_coms, const Fr* shifts, bool roots_of_unity, size_t l, size_t n, bool need_g2) {
+  const std::string w(what);
+  if (l < 1 || (l & (l - 1)) != 0) throw SetError(w + ": the coset size is a power of two");
+  if (l > (size_t)KEAKI_SET_MAX) throw SetError(w + ": more than KEAKI_SET_MAX points in a coset");
+  if (l > setup.g1_pow().size()) throw SetError(w + ": the coset is larger than the SRS");
+  if (n_coms != 1 && n_coms != n) throw SetError(w + ": one commitment, or one per item");
+  if (need_g2 && setup.g2_pow().size() <= l) throw SetError(w + ": this KZGSetup holds no [tau^l]_2: build it with G2 powers beyond l (setup_with_g2, from_powers_g2)");
+  if (setup.device()->group()) throw SetError(w + ": single device only");
+  if (!roots_of_unity)
+    for (size_t k = 0; k < n; k++)
+      if (shifts[k] == Fr::zero()) throw SetError(w + ": a zero shift is no coset");
+  unsigned log2l = 0;
+  while ((size_t(1) << log2l) < l) log2l++;
+  return log2l;
+}
+}  // namespace
+void coset_pairs_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values, size_t item_stride,
+                      size_t t_stride, size_t l, size_t n, uint64_t* lhs_out, Fr* c_out) {
+  const unsigned log2l = coset_call_check("coset_pairs", setup, n_coms, shifts, roots_of_unity, l, n, false);
+  if (n == 0) return;
+  const Device& dev = *setup.device();
+  const vec::Radix2Domain dl = vec::Radix2Domain::create(l);
+  dev.check(keaki_hip_kzg_coset_pairs(dev.ctx(), setup.srs(), coms, n_coms == 1 ? 0 : 1, shifts[0].l, roots_of_unity ? 1 : 0, values[0].l, item_stride, t_stride,
+                                      log2l, dl.group_gen_inv.l, dl.size_inv.l, n, lhs_out, c_out[0].l));
+}
+std::vector<uint8_t> verify_cosets_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values,
+                                             size_t item_stride, size_t t_stride, size_t l, const uint64_t* proofs, size_t n) {
+  const unsigned log2l = coset_call_check("verify_cosets_each", setup, n_coms, shifts, roots_of_unity, l, n, true);
+  std::vector<uint8_t> status(n);
+  if (n == 0) return status;
+  const Device& dev = *setup.device();
+  const vec::Radix2Domain dl = vec::Radix2Domain::create(l);
+  uint64_t n_bad = 0;
+  dev.check(keaki_hip_kzg_verify_cosets_each(dev.ctx(), setup.srs(), coms, n_coms == 1 ? 0 : 1, setup.g2_pow()[l].w.data(), shifts[0].l, roots_of_unity ? 1 : 0,
+                                             values[0].l, item_stride, t_stride, log2l, dl.group_gen_inv.l, dl.size_inv.l, proofs, n, status.data(), &n_bad, nullptr,
+                                             nullptr));
+  return status;
+}
 bool verify_cosets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<Fr>& shifts, size_t l, const std::vector<Fr>& values,
                    const std::vector<G1>& proofs) {
   const size_t n = shifts.size();
@@ -1074,6 +1114,58 @@ bool vec_verify_cosets_subset(Rng& rng, const kzg::KZGSetup& setup, const G1& co
     h[k] = dom.group_gen.pow(cosets[k]);
   }
   return kzg::verify_cosets_flat(rng, setup, com.w.data(), 1, h.data(), false, values.data(), l, 1, l, proofs.empty() ? nullptr : proofs[0].w.data(), cosets.size());
+}
+std::vector<uint8_t> vec_verify_cosets_each(const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& evals, size_t l, const std::vector<G1>& proofs) {
+  if (evals.empty()) throw kzg::SetError("vec_verify_cosets_each: no evaluations");
+  const Radix2Domain dom = Radix2Domain::create(evals.size());
+  const size_t d = dom.size;
+  if (l < 1 || (l & (l - 1)) != 0 || l > d || proofs.size() != d / l) throw kzg::SetError("vec_verify_cosets_each: l is a power of two <= the domain, one proof per coset");
+  std::vector<Fr> e(evals);
+  e.resize(d, Fr::zero());
+  return kzg::verify_cosets_each_flat(setup, com.w.data(), 1, &dom.group_gen, true, e.data(), 1, d / l, l, proofs[0].w.data(), d / l);
+}
+namespace {
+// the shifts omega_d^i of the listed cosets, with the argument checks of vec_verify_cosets_subset
+std::vector<Fr> coset_shifts(const char* what, size_t domain_size, size_t l, const std::vector<size_t>& cosets) {
+  const Radix2Domain dom = Radix2Domain::create(domain_size);
+  if (l < 1 || (l & (l - 1)) != 0 || l > dom.size) throw kzg::SetError(std::string(what) + ": l is a power of two <= the domain");
+  std::vector<Fr> h(cosets.size());
+  for (size_t k = 0; k < cosets.size(); k++) {
+    if (cosets[k] >= dom.size / l) throw kzg::SetError(std::string(what) + ": coset index outside domain / l");
+    h[k] = dom.group_gen.pow(cosets[k]);
+  }
+  return h;
+}
+}  // namespace
+std::vector<uint8_t> vec_verify_cosets_each_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets,
+                                                   const std::vector<Fr>& values, const std::vector<G1>& proofs) {
+  const std::vector<Fr> h = coset_shifts("vec_verify_cosets_each_subset", domain_size, l, cosets);
+  if (values.size() != cosets.size() * l || proofs.size() != cosets.size()) throw kzg::SetError("vec_verify_cosets_each_subset: l values and one proof per listed coset");
+  return kzg::verify_cosets_each_flat(setup, com.w.data(), 1, h.data(), false, values.data(), l, 1, l, proofs.empty() ? nullptr : proofs[0].w.data(), cosets.size());
+}
+void vec_encrypt_cosets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets, const Fr* values,
+                        const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  // every refusal comes before the first draw from rng
+  const std::vector<Fr> h = coset_shifts("vec_encrypt_cosets", domain_size, l, cosets);
+  const size_t n = cosets.size();
+  if (setup.g2_pow().size() <= l) throw kzg::SetError("vec_encrypt_cosets: this KZGSetup holds no [tau^l]_2: build it with G2 powers beyond l (setup_with_g2, from_powers_g2)");
+  std::vector<uint64_t> coms(n * 8);
+  std::vector<Fr> c(n), zeros(n);
+  kzg::coset_pairs_flat(setup, com.w.data(), 1, h.data(), false, values, l, 1, l, n, coms.data(), c.data());
+  if (!n) return;
+  const Device& dev = *setup.device();
+  std::vector<Fr> rs(n);
+  for (size_t i = 0; i < n; i++) rs[i] = fr_rand(rng);      // one r per item in index order, as everywhere else
+  std::vector<uint64_t> offsets(n + 1);
+  for (size_t i = 0; i <= n; i++) offsets[i] = i;
+  // item k: ct = r_k ([tau^l]_2 - c_k g2), key = KDF(e(r_k A_k, g2)): n groups of one item with coms := A, points := c, values := 0
+  const uint64_t* tau_l = setup.g2_pow()[l].w.data();
+  if (msg_len) {
+    dev.check(keaki_hip_encrypt_multi(dev.ctx(), coms.data(), offsets.data(), n, tau_l, c[0].l, zeros[0].l, rs[0].l, msgs, n, ct_g2_out, ct_msg_out, msg_len));
+  } else {
+    std::vector<uint8_t> gt_unused(n * 384);
+    dev.check(keaki_hip_encap_multi(dev.ctx(), coms.data(), offsets.data(), n, tau_l, c[0].l, zeros[0].l, rs[0].l, n, ct_g2_out, gt_unused.data(), nullptr, 0));
+  }
 }
 void vec_encrypt_subset_batch(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const Fr* values,
                               size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {

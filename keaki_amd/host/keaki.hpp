@@ -249,6 +249,14 @@ bool verify_cosets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commi
 // `shifts` is ONE Fr omega and item k has the shift omega^k (nothing to refuse: a power of a root of unity is not zero)
 bool verify_cosets_flat(Rng& rng, const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values,
                         size_t item_stride, size_t t_stride, size_t l, const uint64_t* proofs, size_t n);
+// The per-item points of the same check (keaki_hip_kzg_coset_pairs): lhs_out[8 k ..] = A_k = C_k - [I_k(tau)]_1 (affine words), c_out[k] = shifts[k]^l.
+// Arguments and refusals as verify_cosets_flat, but nothing is drawn and no G2 power is needed.
+void coset_pairs_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values, size_t item_stride,
+                      size_t t_stride, size_t l, size_t n, uint64_t* lhs_out, Fr* c_out);
+// WHICH items are invalid (keaki_hip_kzg_verify_cosets_each): one byte per item, 0 = the set proof holds, 1 = it does not. Exact -- nothing is
+// drawn --, and equal to verify_set on the l points of the item. Arguments and refusals as verify_cosets_flat.
+std::vector<uint8_t> verify_cosets_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values,
+                                             size_t item_stride, size_t t_stride, size_t l, const uint64_t* proofs, size_t n);
 
 }  // namespace kzg
 
@@ -348,6 +356,18 @@ bool vec_verify_cosets_flat(Rng& rng, const kzg::KZGSetup& setup, const G1& com,
 // cosets[k] + t r, proofs[k] its block proof. One draw per listed coset in list order, one device call.
 bool vec_verify_cosets_subset(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets,
                               const std::vector<Fr>& values, const std::vector<G1>& proofs);
+// WHICH block proofs are wrong: one byte per coset (0 = valid, 1 = invalid) from ONE kzg::verify_cosets_each_flat call; nothing is drawn. The first form
+// takes the vector as vec_verify_cosets does, the second the listed cosets as vec_verify_cosets_subset does; refusals as theirs.
+std::vector<uint8_t> vec_verify_cosets_each(const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& evals, size_t l, const std::vector<G1>& proofs);
+std::vector<uint8_t> vec_verify_cosets_each_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets,
+                                                   const std::vector<Fr>& values, const std::vector<G1>& proofs);
+// Message k to the l claimed values of coset cosets[k], for all listed cosets in a few device calls: values[k * l + t] is the claimed value at position
+// cosets[k] + t r, msgs n x msg_len. kzg::coset_pairs_flat gives A_k = C - [I_k(tau)]_1 and c_k; then one r per item in index order and ONE
+// encrypt_multi (encap_multi at msg_len 0) with n groups of one item, coms := A, points := c, values := 0, tau_g2 := [tau^l]_2. Item k is byte for byte
+// enc::encrypt_set on the points of coset k with the same r, and the UNCHANGED vec_decrypt with the proof of vec_open_cosets opens it. Every refusal
+// (l not a power of two, a coset index out of range, a setup without [tau^l]_2, a device group) is a SetError thrown before anything is drawn from rng.
+void vec_encrypt_cosets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, size_t l, const std::vector<size_t>& cosets, const Fr* values,
+                        const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out);
 // n items over ONE index set with different value tuples (the 1-of-2^k string-OT shape): item i is readable by the holder of a vector with
 // values[i * k + j] at idx[j] for all j. One r per item in index order. The rows -I_i come from ONE set_polys call and O(n k^2) host scalar
 // work, [-I_i(tau)]_1 from ONE msm_g1_batch (n rows of k coefficients), C is added by one g1_sum per item, then ONE encrypt_multi call with n

@@ -336,6 +336,36 @@ int keaki_host_vec_verify_cosets_subset(void* rng, void* s, const uint64_t* com,
     return 0;
   });
 }
+// one verdict per coset (include/keaki_hip.h: keaki_hip_kzg_verify_cosets_each): status_out d / l (or k) bytes, 0 = valid
+int keaki_host_vec_verify_cosets_each(void* s, const uint64_t* com, const uint64_t* evals, size_t n, size_t l, const uint64_t* proofs, size_t n_proofs,
+                                      uint8_t* status_out) {
+  return guard([&] {
+    std::vector<G1> pr(n_proofs);
+    for (size_t i = 0; i < n_proofs; i++) pr[i] = g1_of(proofs + 8 * i);
+    const std::vector<uint8_t> st = vec::vec_verify_cosets_each(((Setup*)s)->s, g1_of(com), frs_of(evals, n), l, pr);
+    memcpy(status_out, st.data(), st.size());
+    return 0;
+  });
+}
+int keaki_host_vec_verify_cosets_each_subset(void* s, const uint64_t* com, size_t domain_size, size_t l, const uint64_t* cosets, size_t k, const uint64_t* values,
+                                             const uint64_t* proofs, uint8_t* status_out) {
+  return guard([&] {
+    std::vector<G1> pr(k);
+    for (size_t i = 0; i < k; i++) pr[i] = g1_of(proofs + 8 * i);
+    const std::vector<uint8_t> st = vec::vec_verify_cosets_each_subset(((Setup*)s)->s, g1_of(com), domain_size, l, idx_of(cosets, k), frs_of(values, k * l), pr);
+    memcpy(status_out, st.data(), st.size());
+    return 0;
+  });
+}
+// message k to the l claimed values of coset cosets[k]: values k rows of l, msgs k x msg_len
+int keaki_host_vec_encrypt_cosets(void* rng, void* s, const uint64_t* com, size_t domain_size, size_t l, const uint64_t* cosets, size_t k, const uint64_t* values,
+                                  const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  return guard([&] {
+    const std::vector<Fr> v = frs_of(values, k * l);
+    vec::vec_encrypt_cosets(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), domain_size, l, idx_of(cosets, k), v.data(), msgs, msg_len, ct_g2_out, ct_msg_out);
+    return 0;
+  });
+}
 int keaki_host_vec_verify_subset(void* s, const uint64_t* com, size_t domain_size, const uint64_t* idx, const uint64_t* values, size_t k, const uint64_t* proof,
                                  int* out_ok) {
   return guard([&] {

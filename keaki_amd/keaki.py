@@ -534,6 +534,45 @@ def vec_verify_cosets_subset(rng: "Rng", setup: KZGSetup, com, domain_size: int,
     return bool(ok.value)
 
 
+def vec_verify_cosets_each(setup: KZGSetup, com, evals, l: int, proofs) -> np.ndarray:
+    """vec::vec_verify_cosets_each: WHICH of the size / l proofs of vec_open_cosets(evals, l) are wrong -> uint8[size / l], 0 = valid, 1 = invalid. One
+    device call over the evaluations in domain order; exact, nothing is drawn"""
+    e = np.ascontiguousarray(_u64(evals, 4)); pr = np.ascontiguousarray(_u64(proofs, 8))
+    if e.shape[0] < 1 or l < 1:
+        raise SetError("vec_verify_cosets_each: no evaluations")
+    status = np.zeros(max(pr.shape[0], 1), np.uint8)
+    _ck(_lib().keaki_host_vec_verify_cosets_each(setup.h, _p(_u64(com)), _p(e), C.c_size_t(e.shape[0]), C.c_size_t(l), _p(pr), C.c_size_t(pr.shape[0]), _p(status)))
+    return status[:pr.shape[0]]
+
+
+def vec_verify_cosets_each_subset(setup: KZGSetup, com, domain_size: int, l: int, cosets, values, proofs) -> np.ndarray:
+    """vec::vec_verify_cosets_each_subset: the listed cosets only, arguments as vec_verify_cosets_subset -> uint8[k]"""
+    ix = np.ascontiguousarray(cosets, np.uint64); k = ix.shape[0]
+    y = np.ascontiguousarray(_u64(values, 4)); pr = np.ascontiguousarray(_u64(proofs, 8))
+    if l < 1 or y.shape[0] != k * l or pr.shape[0] != k:
+        raise SetError("vec_verify_cosets_each_subset: l values and one proof per listed coset")
+    status = np.zeros(max(k, 1), np.uint8)
+    _ck(_lib().keaki_host_vec_verify_cosets_each_subset(setup.h, _p(_u64(com)), C.c_size_t(domain_size), C.c_size_t(l), _p(ix), C.c_size_t(k), _p(y), _p(pr),
+                                                        _p(status)))
+    return status[:k]
+
+
+def vec_encrypt_cosets(rng: "Rng", setup: KZGSetup, com, domain_size: int, l: int, cosets, values, messages: np.ndarray):
+    """vec::vec_encrypt_cosets: message k to the l claimed values of coset cosets[k]: values (k, l, 4) in the order of vec_coset_indices, messages
+    (k, msg_len) uint8 -> (ct_g2 (k, 16), bodies (k, msg_len)). One r per item in index order; item k equals encrypt_set on the coset's points with
+    the same r, and vec_decrypt with the proofs of vec_open_cosets opens it. Refusals (SetError) leave rng untouched"""
+    ix = np.ascontiguousarray(cosets, np.uint64); n = ix.shape[0]
+    y = np.ascontiguousarray(_u64(values, 4))
+    if l < 1 or y.shape[0] != n * l:
+        raise SetError("vec_encrypt_cosets: l values per listed coset")
+    msgs = np.ascontiguousarray(messages, np.uint8).reshape(n, -1) if n else np.zeros((0, 0), np.uint8)
+    ml = msgs.shape[1]
+    ct = np.zeros((max(n, 1), 16), np.uint64); body = np.zeros((max(n, 1), max(ml, 1)), np.uint8)
+    _ck(_lib().keaki_host_vec_encrypt_cosets(rng.h, setup.h, _p(_u64(com)), C.c_size_t(domain_size), C.c_size_t(l), _p(ix if n else np.zeros(1, np.uint64)),
+                                             C.c_size_t(n), _p(y if n else np.zeros((1, 4), np.uint64)), _p(msgs if ml and n else body), C.c_size_t(ml), _p(ct), _p(body)))
+    return ct[:n], body[:n, :ml]
+
+
 def vec_encrypt_subset_batch(rng: "Rng", setup: KZGSetup, com, domain_size: int, idx, values, messages: np.ndarray):
     """n items over ONE index set with different value tuples: values (n, k, 4), messages (n, msg_len) uint8 -> (ct_g2 (n, 16), bodies (n, msg_len)).
     Item i is readable by the holder of a vector with values[i, j] at idx[j] for every j; one r per item in index order."""

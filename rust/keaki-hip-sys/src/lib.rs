@@ -187,6 +187,25 @@ extern "C" {
                                            d_tau_l_g2_aff: *const c_void, d_points: *const c_void, point_mode: i32, d_values: *const c_void,
                                            item_stride: usize, t_stride: usize, log2l: u32, omega_l_inv: *const u64, inv_l: *const u64,
                                            d_proofs_aff: *const c_void, d_gammas: *const c_void, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
+    // the per-item points of the coset check, n cosets per call: lhs_out_aff[k] = C_k - [I_k(tau)]_1 (n x u64[8]), c_out[k] = h_k^l (n x u64[4], Montgomery);
+    // the handle's window table over its first l points is built on first use or by _precompute_cosets
+    pub fn keaki_hip_srs_g1_precompute_cosets(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2l: u32) -> keaki_status;
+    pub fn keaki_hip_kzg_coset_pairs(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, com_aff: *const u64, com_stride: i32, points: *const u64,
+                                     point_mode: i32, values: *const u64, item_stride: usize, t_stride: usize, log2l: u32, omega_l_inv: *const u64,
+                                     inv_l: *const u64, n: usize, lhs_out_aff: *mut u64, c_out: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_coset_pairs_dev(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, d_com_aff: *const c_void, com_stride: i32,
+                                         d_points: *const c_void, point_mode: i32, d_values: *const c_void, item_stride: usize, t_stride: usize, log2l: u32,
+                                         omega_l_inv: *const u64, inv_l: *const u64, n: usize, d_lhs_out_aff: *mut c_void, d_c_out: *mut c_void) -> keaki_status;
+    // one verdict per coset: status[k] = 0 <=> e(A_k + c_k proof_k, g2) e(-proof_k, [tau^l]_2) == 1; lhs_out_aff: n x u64[8] or null
+    pub fn keaki_hip_kzg_verify_cosets_each(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, com_aff: *const u64, com_stride: i32,
+                                            tau_l_g2_aff: *const u64, points: *const u64, point_mode: i32, values: *const u64, item_stride: usize,
+                                            t_stride: usize, log2l: u32, omega_l_inv: *const u64, inv_l: *const u64, proofs_aff: *const u64, n: usize,
+                                            status: *mut u8, n_bad: *mut u64, first_bad: *mut u64, lhs_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_cosets_each_dev(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, d_com_aff: *const c_void, com_stride: i32,
+                                                d_tau_l_g2_aff: *const c_void, d_points: *const c_void, point_mode: i32, d_values: *const c_void,
+                                                item_stride: usize, t_stride: usize, log2l: u32, omega_l_inv: *const u64, inv_l: *const u64,
+                                                d_proofs_aff: *const c_void, n: usize, d_status: *mut c_void, n_bad: *mut u64, first_bad: *mut u64,
+                                                d_lhs_out_aff: *mut c_void) -> keaki_status;
     // one verdict per opening: status[i] = 0 <=> e(C_i - y_i g1 + z_i proof_i, g2) e(-proof_i, [tau]_2) == 1; lhs_out_aff: n x u64[8] or null
     pub fn keaki_hip_kzg_verify_each(ctx: *mut keaki_hip_ctx, com_aff: *const u64, com_stride: i32, tau_g2_aff: *const u64, points: *const u64,
                                      point_mode: i32, values: *const u64, proofs_aff: *const u64, n: usize, status: *mut u8, n_bad: *mut u64,

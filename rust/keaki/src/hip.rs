@@ -497,6 +497,35 @@ pub fn verify_cosets(srs: &HipSrs, commitments: &[G1Projective], tau_l_g2: &G2Pr
     ok != 0
 }
 
+/// One verdict per coset (`keaki_hip_kzg_verify_cosets_each`): item k is valid iff `e(C_k - [I_k(tau)]_1, g2) == e(proof_k, [tau^l]_2 - shifts[k]^l g2)`,
+/// the predicate of a set proof on the coset `shifts[k] * <omega_l>`. Arguments as [`verify_cosets`], without gammas: the verdict is exact.
+/// Returns `true` for every valid item. A zero shift is refused here (the library does not look). Single-GPU device.
+pub fn verify_cosets_each(srs: &HipSrs, commitments: &[G1Projective], tau_l_g2: &G2Projective, shifts: &[Fr], l: usize, values: &[Fr],
+                          proofs: &[G1Projective]) -> Vec<bool> {
+    use ark_poly::{EvaluationDomain, Radix2EvaluationDomain};
+    let dev = Device::global();
+    let n = shifts.len();
+    assert!(dev.group.is_null() && l.is_power_of_two() && l <= 1024 && l <= srs.len());
+    assert!(values.len() == n * l && proofs.len() == n && (commitments.len() == 1 || commitments.len() == n));
+    assert!(shifts.iter().all(|h| *h != Fr::from(0u64)), "verify_cosets_each: a zero shift is no coset");
+    let dom = Radix2EvaluationDomain::<Fr>::new(l).unwrap();
+    let one = |x: &Fr| fr_ptr(core::slice::from_ref(x));
+    let flat = |v: &[G1Projective]| -> Vec<u64> { G1Projective::normalize_batch(v).iter().flat_map(|p| g1_words(p)).collect() };
+    let (c, p, t) = (flat(commitments), flat(proofs), g2_words(&tau_l_g2.into_affine()));
+    let mut status = vec![0u8; n];
+    let mut n_bad = 0u64;
+    dev.check(
+        unsafe {
+            sys::keaki_hip_kzg_verify_cosets_each(
+                dev.ctx, srs.srs(), c.as_ptr(), if commitments.len() == 1 { 0 } else { 1 }, t.as_ptr(), fr_ptr(shifts), 0, fr_ptr(values), l, 1, l.trailing_zeros(),
+                one(&dom.group_gen_inv), one(&dom.size_inv), p.as_ptr(), n, status.as_mut_ptr(), &mut n_bad, core::ptr::null_mut(), core::ptr::null_mut(),
+            )
+        },
+        "kzg_verify_cosets_each",
+    );
+    status.iter().map(|&s| s == 0).collect()
+}
+
 /// One verdict per opening (`keaki_hip_kzg_verify_each`): item i is valid iff `e(C_i - y_i g1 + z_i proof_i, g2) * e(-proof_i, [tau]_2) == 1`,
 /// the predicate of `verify` with `z_i proof_i` moved across the pairing. Arguments as [`verify_batch`], without gammas: the verdict is exact.
 /// Returns `true` for every valid item.
