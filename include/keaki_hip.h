@@ -1025,6 +1025,85 @@ typedef enum {
 } keaki_tower_op;
 keaki_status keaki_hip_selftest_tower_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out);
 
+/* Point probe: ONE shipped function of the group law in the 9 x 29-bit lazy limbs (xyzz29.hip.h, xyzz29_g2.hip.h, jac29.hip.h), of its GLV code
+ * or of the saturated formulas it falls back to (bn254_curve.hip.h) on operands the HOST chose; the raw limbs, words, flags and return values
+ * of that call come back (tests/test_gpu_point_ops.py judges them with Python integers, tests/point_ref.py). The field probe hands over the
+ * streams these formulas are made of, the tower probe what the pairing builds on them; this is the layer between. Record layout:
+ *   operands: n records of KEAKI_POP_SLOTS slots x KEAKI_POP_SLOT_WORDS uint32_t. A lazy coordinate (nine limbs, exactly as given) fills its
+ *             slot; a saturated coordinate or a scalar (eight words) uses words 0..7. Flags are the words of slot KEAKI_POP_FLAG_SLOT.
+ *   out:      n records of KEAKI_POP_OUT_SLOTS slots x KEAKI_POP_SLOT_WORDS uint32_t, zero where the call wrote nothing; flags, return value
+ *             and `special` are the words of slot KEAKI_POP_OUT_FLAG_SLOT.
+ * The slots of every op are listed at its enumerator (in: ... -> out: ...). Point forms:
+ *   X29    x, y, zz, zzz (4 lazy slots) + flag `inf`          X29G2  x.re, x.im, y.re, y.im, zz.re, zz.im, zzz.re, zzz.im (8 lazy slots) + flag `empty`
+ *   J29    x, y, z (3 lazy slots)                             sat    Xyzz / Jac / Aff of Fq (one slot per coordinate) or of Fq2 (c0, c1: two slots)
+ * Lazy values are residues x 2^261, saturated coordinates residues x 2^256 (canonical, < p); scalars of the ladders and of
+ * KEAKI_POP_GLV_UNIFORM_DIGITS are Fr in Montgomery form, KEAKI_POP_GLV_DECOMPOSE takes k itself (canonical, < r).
+ * Geometry: one record per lane, 64 lanes per workgroup, all 64 lanes run (the library pads the launch to whole waves with copies of record 0
+ * and only the first n records are stored). The wave-uniform forms (KEAKI_POP_GLV_UNIFORM_DIGITS, KEAKI_POP_LADDER_UNIFORM, KEAKI_POP_LADDER_MUL2)
+ * take the scalars (and negB) of the WAVE'S FIRST record for the whole wave, as the shipped kernels take one twiddle per wave, and keep their
+ * digits in that wave's LDS; every lane still has its own points. KEAKI_POP_LADDER_GTAB has its 1 KB of table per lane in a workspace of the
+ * context. 1 <= n <= KEAKI_POP_MAX_RECORDS; an unknown op, n out of range or a null pointer is KEAKI_ERR_BAD_ARG and launches nothing. Operand
+ * bounds are the callee's own; the probe does not check them. Every op is one call with the template arguments of a shipped call site
+ * (KEAKI_POP_LADDER_MUL2 builds its tables with j29_build_pair first, as its only caller does).
+ * Not probed: the inline mixed addition of k_msm_accumulate_g1_u29 (not a function; making it one would change a hot kernel); fb_accumulate*
+ * (tests/test_gpu_fb_digit_edges.py); the Straus kernels of fk_coset.hip and vec_update.hip (their building blocks are the ops here); the
+ * branch "u29_maybe_zero fires, u29_is_zero does not" (18 in 2^29 additions; the field probe covers the two predicates themselves). */
+#define KEAKI_POP_SLOTS 17
+#define KEAKI_POP_SLOT_WORDS 9
+#define KEAKI_POP_FLAG_SLOT 16
+#define KEAKI_POP_OUT_SLOTS 50
+#define KEAKI_POP_OUT_FLAG_SLOT 49
+#define KEAKI_POP_MAX_RECORDS 4096
+#define KEAKI_POP_FIRST_G2 KEAKI_POP_X29G2_ADD_MIXED
+typedef enum {
+  /* xyzz29.hip.h */
+  KEAKI_POP_X29_ADD = 0,             /* in: a 0..3, b 4..7, flags a.inf, b.inf -> out: X29 0..3, flag inf */
+  KEAKI_POP_X29_DBL = 1,             /* in: a 0..3, flag a.inf -> out: X29 0..3, flag inf */
+  KEAKI_POP_X29_STORE = 2,           /* in: a 0..3, flag a.inf -> out: Xyzz<Fq> 0..3 */
+  KEAKI_POP_X29_LOAD_STORE = 3,      /* x29_store(x29_load(.)): in: Xyzz<Fq> 0..3 -> out: Xyzz<Fq> 0..3 */
+  /* jac29.hip.h, point level */
+  KEAKI_POP_J29_DBL = 4,             /* in: J29 0..2 -> out: J29 0..2 */
+  KEAKI_POP_J29_MADD = 5,            /* in: a 0..2, x2 3, y2 4 -> out: J29 0..2, *ratio 3 (0 when not written), flag special */
+  KEAKI_POP_J29_ADDSUB = 6,          /* in: u 0..2, v 3..5 -> out: sum 0..2, diff 3..5, flag return value */
+  KEAKI_POP_J29_SAT_ROUNDTRIP = 7,   /* j29_to_sat(j29_from_sat(.)): in: Jac<Fq> 0..2 -> out: Jac<Fq> 0..2 */
+  KEAKI_POP_J29_BUILD_TABLE = 8,     /* j29_build_table<false> through J29ArrTable: in: Jac<Fq> 0..2 -> out: entry e (x, beta x, y) at 3e..3e+2, zfix 24 */
+  KEAKI_POP_J29_BUILD_TABLE_ODD = 9, /* j29_build_table<true>, the same slots */
+  KEAKI_POP_J29_BUILD_PAIR = 10,     /* in: A 0..2, B 3..5 (Jac<Fq>) -> out: TA entries 0..23, TB entries 24..47, zfix 48 */
+  /* GLV */
+  KEAKI_POP_GLV_DECOMPOSE = 11,      /* in: k 0 (8 words) -> out: |k1| 0 (5 words), |k2| 1 (5 words), flags neg1, neg2 */
+  KEAKI_POP_GLV_FIXED_DIGITS = 12,   /* in: magnitude 0 (5 words) -> out: dig 0 (5 words), sg 1 (2 words) */
+  KEAKI_POP_GLV_UNIFORM_DIGITS = 13, /* in: Fr 0 (wave's first record) -> out: the 2 x UNIFORM_DIG_STRIDE bytes as 66 words from word 0, flags neg1, neg2 */
+  /* ladders: in: Jac<Fq> 0..2, Fr 3 -> out: J29 0..2, flag return value */
+  KEAKI_POP_LADDER_FIXED = 14,       /* jac_scalar_mul_u29_j */
+  KEAKI_POP_LADDER_GTAB = 15,        /* jac_scalar_mul_gtab_u29_j */
+  KEAKI_POP_LADDER_UNIFORM = 16,     /* jac_scalar_mul_uniform_u29_j: Fr of the wave's first record */
+  KEAKI_POP_LADDER_MUL2 = 17,        /* j29_build_pair, j29_mul2_uniform: in: A 0..2, B 3..5, kA 6, kB 7, flag word 2 negB (kA, kB, negB of the wave's first record) */
+  /* saturated formulas of bn254_curve.hip.h over Fq: in: first point from 0, second point behind it -> out: the point from 0 */
+  KEAKI_POP_XYZZ_ADD_MIXED_FQ = 18,  /* in: Xyzz 0..3, Aff 4..5 */
+  KEAKI_POP_XYZZ_ADD_FQ = 19,        /* in: Xyzz 0..3, Xyzz 4..7 */
+  KEAKI_POP_XYZZ_DBL_FQ = 20,
+  KEAKI_POP_XYZZ_DBL_AFF_FQ = 21,    /* in: Aff 0..1 */
+  KEAKI_POP_JAC_ADD_FQ = 22,         /* in: Jac 0..2, Jac 3..5 */
+  KEAKI_POP_JAC_ADD_MIXED_FQ = 23,   /* in: Jac 0..2, Aff 3..4 */
+  KEAKI_POP_JAC_DBL_FQ = 24,
+  /* xyzz29_g2.hip.h: every op from here on lives in point_probe_g2.hip */
+  KEAKI_POP_X29G2_ADD_MIXED = 25,    /* in: acc 0..7, flag acc.empty, Aff<Fq2> 8..11 -> out: X29G2 0..7, flag empty */
+  KEAKI_POP_X29G2_ADD = 26,          /* in: a 0..7, b 8..15, flags a.empty, b.empty -> out: X29G2 0..7, flag empty */
+  KEAKI_POP_X29G2_DBL = 27,
+  KEAKI_POP_X29G2_DBL_OF_ACC = 28,
+  KEAKI_POP_X29G2_STORE = 29,        /* in: a 0..7, flag a.empty -> out: Xyzz<Fq2> 0..7 */
+  /* the saturated formulas over Fq2: a coordinate is two slots (c0, c1) */
+  KEAKI_POP_XYZZ_ADD_MIXED_FQ2 = 30, /* in: Xyzz 0..7, Aff 8..11 */
+  KEAKI_POP_XYZZ_ADD_FQ2 = 31,       /* in: Xyzz 0..7, Xyzz 8..15 */
+  KEAKI_POP_XYZZ_DBL_FQ2 = 32,
+  KEAKI_POP_XYZZ_DBL_AFF_FQ2 = 33,
+  KEAKI_POP_JAC_ADD_FQ2 = 34,        /* in: Jac 0..5, Jac 6..11 */
+  KEAKI_POP_JAC_ADD_MIXED_FQ2 = 35,  /* in: Jac 0..5, Aff 6..9 */
+  KEAKI_POP_JAC_DBL_FQ2 = 36,
+  KEAKI_POP_COUNT = 37
+} keaki_point_op;
+keaki_status keaki_hip_selftest_point_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

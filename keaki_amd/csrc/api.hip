@@ -3046,5 +3046,21 @@ keaki_status keaki_hip_selftest_tower_ops(keaki_hip_ctx* ctx, uint32_t op, const
   ST_TRY(tower_probe_run(ctx, op, ctx->io_a.p, n, ctx->io_b.p));
   return download(feed, out, ctx->io_b.p, n * KEAKI_TOP_OUT_WORDS * 4);
 }
+keaki_status keaki_hip_selftest_point_ops(keaki_hip_ctx* ctx, uint32_t op, const uint32_t* operands, size_t n, uint32_t* out) {
+  CTX_GUARD(ctx);
+  if (!operands || !out || op >= KEAKI_POP_COUNT || n == 0 || n > KEAKI_POP_MAX_RECORDS)
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "selftest_point_ops: bad argument");
+  const size_t rec = (size_t)KEAKI_POP_SLOTS * KEAKI_POP_SLOT_WORDS * 4, orec = (size_t)KEAKI_POP_OUT_SLOTS * KEAKI_POP_SLOT_WORDS * 4;
+  const size_t padded = point_probe_padded(n), tab = point_probe_table_bytes(op, n);
+  CopyFeed feed(ctx);
+  ST_TRY(reserve(ctx, ctx->io_a, padded * rec));
+  ST_TRY(reserve(ctx, ctx->io_b, padded * orec));          // every lane that runs has a record; the first n come back
+  if (tab) ST_TRY(reserve(ctx, ctx->fk_tab, tab));
+  ST_TRY(feed.put(0, ctx->io_a.p, operands, n * rec));
+  for (size_t i = n; i < padded; i++) ST_TRY(feed.put(0, (char*)ctx->io_a.p + i * rec, operands, rec));     // the tail lanes of a wave run record 0
+  HIP_TRY(ctx, hipMemsetAsync(ctx->io_b.p, 0, padded * orec, ctx->stream));
+  ST_TRY(point_probe_run(ctx, op, ctx->io_a.p, n, ctx->io_b.p, tab ? ctx->fk_tab.p : nullptr));
+  return download(feed, out, ctx->io_b.p, n * orec);
+}
 
 }  // extern "C"

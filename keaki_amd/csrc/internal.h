@@ -434,5 +434,11 @@ keaki_status field_probe_run(keaki_hip_ctx* ctx, uint32_t op, const void* d_oper
 bool tower_probe_is_wide(uint32_t op);
 size_t tower_probe_padded(uint32_t op, size_t n);
 keaki_status tower_probe_run(keaki_hip_ctx* ctx, uint32_t op, const void* d_operands, size_t n, void* d_out);
+// point probe (point_probe.hip, point_probe_g2.hip): op `op` of keaki_point_op on n records at d_operands; whole waves run, so d_operands AND d_out
+// hold point_probe_padded(n) records (d_out zeroed by the caller) and d_table point_probe_table_bytes(op, n) bytes (0: none needed). Checks op and
+// n itself (KEAKI_ERR_BAD_ARG, nothing launched).
+size_t point_probe_padded(size_t n);
+size_t point_probe_table_bytes(uint32_t op, size_t n);
+keaki_status point_probe_run(keaki_hip_ctx* ctx, uint32_t op, const void* d_operands, size_t n, void* d_out, void* d_table);
 
 }  // namespace keaki_internal

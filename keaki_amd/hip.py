@@ -28,7 +28,7 @@ EXPORTS = [
     "keaki_hip_encrypt_batch", "keaki_hip_encrypt_batch_dev", "keaki_hip_decrypt_batch", "keaki_hip_decrypt_batch_dev",
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
     "keaki_hip_encap_multi", "keaki_hip_encap_multi_dev", "keaki_hip_encrypt_multi", "keaki_hip_encrypt_multi_dev",
-    "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_selftest_tower_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
+    "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_selftest_tower_ops", "keaki_hip_selftest_point_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
     "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_srs_g1_precompute_update", "keaki_hip_vec_update", "keaki_hip_vec_update_dev",
     "keaki_hip_kzg_set_polys", "keaki_hip_kzg_set_polys_dev", "keaki_hip_kzg_open_multi", "keaki_hip_kzg_open_multi_dev",
@@ -70,6 +70,18 @@ def tower_op_codes() -> dict:
     for m in re.finditer(r"#define\s+KEAKI_TOP_([A-Z_]+)\s+(\w+)", hdr):
         v = m.group(2)
         codes[m.group(1)] = int(v) if v.isdigit() else codes[v[len("KEAKI_TOP_"):]]
+    return codes
+
+
+def point_op_codes() -> dict:
+    """{'X29_ADD': 0, ...}: the op codes of keaki_hip_selftest_point_ops with the record geometry ('SLOTS', 'SLOT_WORDS', 'FLAG_SLOT', 'OUT_SLOTS',
+    'OUT_FLAG_SLOT', 'MAX_RECORDS', 'FIRST_G2'), read from include/keaki_hip.h so that no second list exists"""
+    import re
+    hdr = open(os.path.join(os.path.dirname(_HERE), "include", "keaki_hip.h")).read()
+    codes = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bKEAKI_POP_([A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    for m in re.finditer(r"#define\s+KEAKI_POP_([A-Z0-9_]+)\s+(\w+)", hdr):
+        v = m.group(2)
+        codes[m.group(1)] = int(v) if v.isdigit() else codes[v[len("KEAKI_POP_"):]]
     return codes
 
 
@@ -153,6 +165,7 @@ def load_library():
         lib.keaki_hip_selftest_field.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.keaki_hip_selftest_field_ops.argtypes = [vp, C.c_uint32, vp, sz, vp]
         lib.keaki_hip_selftest_tower_ops.argtypes = [vp, C.c_uint32, vp, sz, vp]
+        lib.keaki_hip_selftest_point_ops.argtypes = [vp, C.c_uint32, vp, sz, vp]
         lib.keaki_hip_open_fk.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
         lib.keaki_hip_open_fk_poly.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
         lib.keaki_hip_fr_fft.argtypes = [vp, vp, C.c_uint32, vp, vp]
@@ -433,6 +446,15 @@ class KeakiHip:
         a = np.ascontiguousarray(operands, dtype=np.uint32).reshape(-1, 344)
         out = np.zeros((a.shape[0], 12, 8), np.uint32)
         self._ck(self.lib.keaki_hip_selftest_tower_ops(self.ctx, op, _ptr(a), a.shape[0], _ptr(out)))
+        return out
+
+    def point_ops(self, op: int, operands) -> np.ndarray:
+        """one shipped function of the lazy-limb group law on host-chosen operands (keaki_hip_selftest_point_ops): operands n x SLOTS x SLOT_WORDS uint32 ->
+        the raw result slots n x OUT_SLOTS x SLOT_WORDS uint32 (flags, return value and `special` in slot OUT_FLAG_SLOT; geometry: point_op_codes())"""
+        g = point_op_codes()
+        a = np.ascontiguousarray(operands, dtype=np.uint32).reshape(-1, g["SLOTS"], g["SLOT_WORDS"])
+        out = np.zeros((a.shape[0], g["OUT_SLOTS"], g["SLOT_WORDS"]), np.uint32)
+        self._ck(self.lib.keaki_hip_selftest_point_ops(self.ctx, op, _ptr(a), a.shape[0], _ptr(out)))
         return out
 
     # ---- SRS

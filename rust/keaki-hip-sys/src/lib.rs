@@ -324,4 +324,5 @@ extern "C" {
     pub fn keaki_hip_selftest_field(ctx: *mut keaki_hip_ctx, blocks: u32, iters: u32, seed: u32, mismatches_out: *mut u64) -> keaki_status;
     pub fn keaki_hip_selftest_field_ops(ctx: *mut keaki_hip_ctx, op: u32, operands: *const u32, n: usize, out: *mut u32) -> keaki_status;
     pub fn keaki_hip_selftest_tower_ops(ctx: *mut keaki_hip_ctx, op: u32, operands: *const u32, n: usize, out: *mut u32) -> keaki_status;
+    pub fn keaki_hip_selftest_point_ops(ctx: *mut keaki_hip_ctx, op: u32, operands: *const u32, n: usize, out: *mut u32) -> keaki_status;
 }
