@@ -1,5 +1,5 @@
-"""One small, successful call for every host-array entry that feeds its arrays through CopyFeed (keaki_amd/csrc/api.hip), in one process,
-for a trace:
+"""One small, successful call for every host-array entry that feeds its arrays through CopyFeed (keaki_amd/csrc/api.hip), and for the _dev
+forms of the KZG verification family, in one process, for a trace:
   rocprofv3 --kernel-trace --memory-copy-trace --output-format csv json -- python bench_tools/host_form_calls.py
 run against two builds, every call's ordered (kernel, grid, workgroup) list per stream and its sorted (direction, bytes) list of copies
 must be equal (profiles/host_forms_call_order.txt; --compare A B reads the two traces). Every call is followed by a separator the trace
@@ -95,6 +95,57 @@ def run():
     call("kzg_verify_batch n=70000, general form (copy stream)", lambda: h.kzg_verify_batch(coms, tau, zs, ys, proofs, gs))
     call("kzg_verify_batch n=70000, general form, pipe_chunks=0", lambda: h.kzg_verify_batch(coms, tau, zs, ys, proofs, gs), pipe_chunks=0)
     h.set_option("pipe_chunks", 1)
+
+    # the rest of the KZG verification family (profiles/kzg_verify_family_call_order.txt): host forms, then the _dev forms on torch tensors
+    call("kzg_verify", lambda: h.kzg_verify(coms[0], tau, z, ys[0], proofs[0]))
+    call("kzg_verify_multi k=4", lambda: h.kzg_verify_multi(srs, srs2, coms[0], zs[:4], ys[:4], proofs[0], want_pair=True))
+    n = 1000
+    call("kzg_verify_each n=1000, one commitment, points omega^i", lambda: h.kzg_verify_each(coms[:1], tau, z, ys[:n], proofs[:n], point_mode=1))
+    call("kzg_verify_each n=1000, general form", lambda: h.kzg_verify_each(coms[:n], tau, zs[:n], ys[:n], proofs[:n]))
+    call("kzg_verify_each n=1000, general form, want_lhs", lambda: h.kzg_verify_each(coms[:n], tau, zs[:n], ys[:n], proofs[:n], want_lhs=True))
+    n, ll = 64, 4; l = 1 << ll
+    wl = pow(5, (R_MOD - 1) >> ll, R_MOD)
+    winv, linv, vals = mont_fr(pow(wl, -1, R_MOD)), mont_fr(pow(l, -1, R_MOD)), random_fr_limbs(n * l, 8)
+    call("kzg_verify_cosets n=64 l=16, one commitment, shifts omega^k",
+         lambda: h.kzg_verify_cosets(srs, coms[:1], tau, z, vals, l, 1, ll, winv, linv, proofs[:n], gs[:n], point_mode=1))
+    call("kzg_verify_cosets n=64 l=16, general form", lambda: h.kzg_verify_cosets(srs, coms[:n], tau, zs[:n], vals, l, 1, ll, winv, linv, proofs[:n], gs[:n]))
+    for route in (1, 2):
+        call("kzg_coset_pairs n=64 l=16 coset_rows_route=%d" % route, lambda: h.kzg_coset_pairs(srs, coms[:n], zs[:n], vals, l, 1, ll, winv, linv, n),
+             coset_rows_route=route)
+    h.set_option("coset_rows_route", 0)
+    call("kzg_verify_cosets_each n=64 l=16, want_lhs", lambda: h.kzg_verify_cosets_each(srs, coms[:n], tau, zs[:n], vals, l, 1, ll, winv, linv, proofs[:n], want_lhs=True))
+
+    import torch
+
+    def dev(a, dtype=np.uint64):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype).view(np.int64 if dtype == np.uint64 else dtype).copy()).cuda()
+
+    def back(*ts):
+        h.synchronize()
+        return tuple(t.cpu().numpy() for t in ts)
+
+    m = 1000
+    def uploads():
+        ts = tuple(dev(a) for a in (coms[:m], tau, z, zs[:m], ys[:m], proofs[:m], gs[:m], vals, np.zeros((m, 8)), np.zeros((m, 4)))) + (dev(np.zeros(m), np.uint8),)
+        torch.cuda.synchronize()
+        return ts
+
+    d_com, d_tau, d_z, d_zs, d_ys, d_pr, d_gs, d_vals, d_lhs, d_c, d_status = call("(uploads for the _dev forms)", uploads)
+    call("kzg_verify_batch_dev n=1000, one commitment, points omega^i", lambda: h.kzg_verify_batch_dev(d_com, 0, d_tau, d_z, 1, d_ys, d_pr, d_gs, m))
+    call("kzg_verify_batch_dev n=1000, general form", lambda: h.kzg_verify_batch_dev(d_com, 1, d_tau, d_zs, 0, d_ys, d_pr, d_gs, m))
+    call("kzg_verify_each_dev n=1000, one commitment, points omega^i",
+         lambda: (h.kzg_verify_each_dev(d_com, 0, d_tau, d_z, 1, d_ys, d_pr, m, d_status),) + back(d_status))
+    call("kzg_verify_each_dev n=1000, general form, with lhs",
+         lambda: (h.kzg_verify_each_dev(d_com, 1, d_tau, d_zs, 0, d_ys, d_pr, m, d_status, d_lhs),) + back(d_status, d_lhs))
+    call("kzg_verify_cosets_dev n=64 l=16, one commitment, shifts omega^k",
+         lambda: h.kzg_verify_cosets_dev(srs, d_com, 0, d_tau, d_z, 1, d_vals, l, 1, ll, winv, linv, d_pr, d_gs, n))
+    call("kzg_verify_cosets_dev n=64 l=16, general form", lambda: h.kzg_verify_cosets_dev(srs, d_com, 1, d_tau, d_zs, 0, d_vals, l, 1, ll, winv, linv, d_pr, d_gs, n))
+    for route in (1, 2):
+        call("kzg_coset_pairs_dev n=64 l=16 coset_rows_route=%d" % route,
+             lambda: (h.kzg_coset_pairs_dev(srs, d_com, 1, d_zs, 0, d_vals, l, 1, ll, winv, linv, n, d_lhs, d_c),) + back(d_lhs[:n], d_c[:n]), coset_rows_route=route)
+    h.set_option("coset_rows_route", 0)
+    call("kzg_verify_cosets_each_dev n=64 l=16, with lhs",
+         lambda: (h.kzg_verify_cosets_each_dev(srs, d_com, 1, d_tau, d_zs, 0, d_vals, l, 1, ll, winv, linv, d_pr, n, d_status, d_lhs),) + back(d_status[:n], d_lhs[:n]))
     srs.free(); srs2.free(); h.close()
     print("done")
 

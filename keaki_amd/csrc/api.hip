@@ -186,6 +186,7 @@ struct CopyFeed {
   CopyFeed& operator=(const CopyFeed&) = delete;
   void also_drain(hipStream_t s) { if (std::find(drain, drain + n_drain, s) == drain + n_drain) drain[n_drain++] = s; }
   void settled() { n_drain = 0; }
+  keaki_status closed_by(keaki_status last) { if (last == KEAKI_OK) settled(); return last; }      // `last`: of the call's last step, which synchronises
   keaki_status begin(bool side_stream) {
     if (!side_stream) return KEAKI_OK;
     ST_TRY(ctx->pipe.ready(ctx));
@@ -211,8 +212,40 @@ keaki_status upload(CopyFeed& feed, DevBuf& b, const void* host, size_t bytes) {
   return feed.put(0, b.p, host, bytes);
 }
 keaki_status download(CopyFeed& feed, void* host, const void* dev, size_t bytes) {     // the last step of a successful call
-  ST_TRY(download(feed.ctx, host, dev, bytes));
-  feed.settled();
+  return feed.closed_by(download(feed.ctx, host, dev, bytes));
+}
+// The items of a KZG host form on their way to the device, told ONCE what the call has: ONE commitment (com_stride 0) goes to `com_slot`, omega alone
+// (point_mode 1) to `omega_slot`, or where the call keeps no such slot (null) to the front of the per-item buffer; n commitments go to io_e, n points to io_c, the n
+// proofs (null: none) to io_b. reserve() covers every buffer before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only. put(feed,
+// what) enqueues the inputs `what` selects, in the order commitment, points, proofs; put(feed, dst, src, bytes) one of the call's own arrays; d_*(): where each is read.
+struct ItemStager {
+  enum : unsigned { ONE_COM = 1, COMS = 2, OMEGA = 4, POINTS = 8, PROOFS = 16, COM = ONE_COM | COMS, PTS = OMEGA | POINTS, ALL = COM | PTS | PROOFS };
+  keaki_hip_ctx* ctx;
+  const void* com; int32_t com_stride; void* com_slot;
+  const void* points; int32_t point_mode; void* omega_slot;
+  const void* proofs; size_t n, piece = 0;
+  void* d_com() const { return !com_stride && com_slot ? com_slot : ctx->io_e.p; }
+  void* d_points() const { return point_mode && omega_slot ? omega_slot : ctx->io_c.p; }
+  void* d_proofs() const { return ctx->io_b.p; }
+  keaki_status reserve() {
+    if (proofs) ST_TRY(keaki_internal::reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
+    if (d_points() == ctx->io_c.p) ST_TRY(keaki_internal::reserve(ctx, ctx->io_c, (point_mode ? 1 : n) * 32));
+    return d_com() == ctx->io_e.p ? keaki_internal::reserve(ctx, ctx->io_e, (com_stride ? n : 1) * G1_AFF_BYTES) : KEAKI_OK;
+  }
+  keaki_status put(CopyFeed& feed, void* dst, const void* src, size_t bytes) { return feed.put(feed.side ? piece++ : 0, dst, src, bytes); }
+  keaki_status put(CopyFeed& feed, unsigned what) {
+    if (what & (com_stride ? COMS : ONE_COM)) ST_TRY(put(feed, d_com(), com, (com_stride ? n : 1) * G1_AFF_BYTES));
+    if (what & (point_mode ? OMEGA : POINTS)) ST_TRY(put(feed, d_points(), points, (point_mode ? 1 : n) * 32));
+    return proofs && (what & PROOFS) ? put(feed, d_proofs(), proofs, n * G1_AFF_BYTES) : KEAKI_OK;
+  }
+};
+// The two pairings of a verdict in ONE launch; `sums_out_aff` (or null) takes the 128 bytes of d_ps, enqueued before the download of the 768 GT bytes, which synchronises.
+keaki_status pair2_verdict(keaki_hip_ctx* ctx, const void* d_ps, const void* d_qs, void* d_gt, uint64_t* sums_out_aff, int32_t* ok_out) {
+  ST_TRY(pairing_run(ctx, d_ps, d_qs, 1, 2, d_gt));
+  uint8_t gt[768];
+  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, d_ps, 128, hipMemcpyDeviceToHost, ctx->stream));
+  ST_TRY(download(ctx, gt, d_gt, 768));
+  *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
   return KEAKI_OK;
 }
 
@@ -2280,14 +2313,11 @@ keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, c
   memcpy(in + 16, value, 32);
   memcpy(in + 20, point, 32);
   memcpy(in + 24, tau_g2_aff, 128);
-  HIP_TRY(ctx, hipMemcpyAsync(io + O_IN, in, 320, hipMemcpyHostToDevice, ctx->stream));
+  CopyFeed feed(ctx);                       // declared after `in`: a failing call drains the copy while the array is alive
+  ST_TRY(feed.put(0, io + O_IN, in, 320));
   HIP_TRY(ctx, hipMemcpyAsync(io + O_P + 64, io + O_IN + 64, 64, hipMemcpyDeviceToDevice, ctx->stream));      // the proof into the pairing's first slot
   ST_TRY(verify_points_run(ctx, k.fbs_g1_gen.p, k.fbs_g2_gen.p, FB_WB_SMALL, io + O_IN, io + O_IN + 192, io + O_IN + 128, io + O_IN + 160, io + O_P, io + O_Q + 128));
-  ST_TRY(pairing_run(ctx, io + O_P, io + O_Q, 1, 2, io + O_GT));
-  uint8_t gt[768];
-  ST_TRY(download(ctx, gt, io + O_GT, 768));                                       // synchronises: `in` stays alive until here
-  *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
-  return KEAKI_OK;
+  return feed.closed_by(pair2_verdict(ctx, io + O_P, io + O_Q, io + O_GT, nullptr, ok_out));
 }
 
 // The set predicate e(C - [I(tau)]_1, g2) == e(proof, [Z(tau)]_2): the two set polynomials (kzg_multi.hip), [Z]_2 and [I]_1 by the library's MSMs over
@@ -2334,10 +2364,30 @@ keaki_status keaki_hip_kzg_verify_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_
 //              [qs: g2 128 | tau 128] [omega 32] [gt 768] [partials]
 extern "C++" {
 namespace {
-struct VbLayout {
-  static constexpr size_t O_SC = 0, O_PTS = 64, O_MUL = 192, O_SUM = 320, O_L = 608, O_R = 704, O_PS = 800, O_QS = 928, O_OMEGA = 1184, O_GT = 1216,
-                          O_PART = 1984;
-};
+// The sum block that both combination layouts end in, placed at AT: the three terms of L, the two sums, the pairing's arguments and its result.
+//   [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64] [qs: g2 128 | tau 128] [omega 32] [gt 768]
+template <size_t AT> struct SumBlock { static constexpr size_t O_SUM = AT, O_L = AT + 288, O_R = AT + 384, O_PS = AT + 480, O_QS = AT + 608, O_OMEGA = AT + 864, O_GT = AT + 896, O_END = AT + 1664; };
+// how both combinations finish, `sum` = the block on the device: L = K + M + T, both sums affine, the two pairings and the verdict
+keaki_status combination_finish(keaki_hip_ctx* ctx, char* sum, int32_t* ok_out, uint64_t* sums_out_aff) {
+  using B = SumBlock<0>;
+  ST_TRY(g1_sum_run(ctx, sum, 3, sum + B::O_L));
+  ST_TRY(verify_batch_jac_to_aff_run(ctx, sum + B::O_L, sum + B::O_R, sum + B::O_PS));
+  return pair2_verdict(ctx, sum + B::O_PS, sum + B::O_QS, sum + B::O_GT, sums_out_aff, ok_out);
+}
+struct VbLayout : SumBlock<320> { static constexpr size_t O_SC = 0, O_PTS = 64, O_MUL = 192, O_PART = O_END; };
+// com_stride and point_mode, the two switches every entry of the family has (`what`: the entry's name)
+keaki_status kzg_modes_ok(keaki_hip_ctx* ctx, const char* what, int32_t com_stride, int32_t point_mode) {
+  if ((com_stride == 0 || com_stride == 1) && (point_mode == 0 || point_mode == 1)) return KEAKI_OK;
+  return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: com_stride = %d, point_mode = %d: both must be 0 or 1", what, (int)com_stride, (int)point_mode);
+}
+// The ONE argument check of verify_batch and verify_each. `out` / `out_name`: the output required at any n; `arrays_ok`: the call's arrays are there (asked for n > 0).
+keaki_status openings_args(keaki_hip_ctx* ctx, const char* what, int32_t com_stride, int32_t point_mode, const void* out, const char* out_name, bool arrays_ok, size_t n) {
+  ST_TRY(kzg_modes_ok(ctx, what, com_stride, point_mode));
+  if (!out) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, out_name);
+  if (n && !arrays_ok) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
+  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n must be < 2^31 per device", what);
+  return KEAKI_OK;
+}
 // `stage(phase)`: the host form uploads what the phase reads and makes ctx->stream wait for it (0: gammas and proofs, in front of the first MSM;
 // 1: commitments, points, values). The commitment (com_stride 0), [tau]_2 and omega (point_mode 1) are already in their vb_io slots.
 keaki_status verify_batch_core(keaki_hip_ctx* ctx, const void* d_coms, int32_t com_stride, const void* d_points, int32_t point_mode, const void* d_values,
@@ -2362,23 +2412,7 @@ keaki_status verify_batch_core(keaki_hip_ctx* ctx, const void* d_coms, int32_t c
     ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
     ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL + 64, 1, io + V::O_SUM + 192));
   }
-  ST_TRY(g1_sum_run(ctx, io + V::O_SUM, 3, io + V::O_L));
-  ST_TRY(verify_batch_jac_to_aff_run(ctx, io + V::O_L, io + V::O_R, io + V::O_PS));
-  ST_TRY(pairing_run(ctx, io + V::O_PS, io + V::O_QS, 1, 2, io + V::O_GT));
-  uint8_t gt[768];
-  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, io + V::O_PS, 128, hipMemcpyDeviceToHost, ctx->stream));
-  ST_TRY(download(ctx, gt, io + V::O_GT, 768));
-  *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
-  return KEAKI_OK;
-}
-keaki_status verify_batch_args(keaki_hip_ctx* ctx, const void* com, int32_t com_stride, const void* tau, const void* points, int32_t point_mode,
-                               const void* values, const void* proofs, const void* gammas, size_t n, const int32_t* ok_out) {
-  if ((com_stride != 0 && com_stride != 1) || (point_mode != 0 && point_mode != 1))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: com_stride = %d, point_mode = %d: both must be 0 or 1", (int)com_stride, (int)point_mode);
-  if (!ok_out) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: ok_out is null");
-  if (n && (!com || !tau || !points || !values || !proofs || !gammas)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: null pointer");
-  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_batch: n must be < 2^31 per device");
-  return KEAKI_OK;
+  return combination_finish(ctx, io + V::O_SUM, ok_out, sums_out_aff);
 }
 // the empty combination: both sums are the identity, which pairs to GT one on both sides
 void verify_batch_empty(int32_t* ok_out, uint64_t* sums_out_aff) {
@@ -2397,7 +2431,7 @@ keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_co
                                             int32_t* ok_out, uint64_t* sums_out_aff) {
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.kzg_verify_batch");
-  ST_TRY(verify_batch_args(ctx, d_com_aff, com_stride, d_tau_g2_aff, d_points, point_mode, d_values, d_proofs_aff, d_gammas, n, ok_out));
+  ST_TRY(openings_args(ctx, "kzg_verify_batch", com_stride, point_mode, ok_out, "ok_out", d_com_aff && d_tau_g2_aff && d_points && d_values && d_proofs_aff && d_gammas, n));
   if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
   ST_TRY(verify_batch_reserve(ctx, n));
   char* io = (char*)ctx->vb_io.p;
@@ -2412,38 +2446,32 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
                                         int32_t* ok_out, uint64_t* sums_out_aff) {
   CTX_GUARD(ctx);                 // held across stage -> kernels -> download: the io buffers belong to this call until it returns
   TRACE_SCOPE("keaki.kzg_verify_batch");
-  ST_TRY(verify_batch_args(ctx, com_aff, com_stride, tau_g2_aff, points, point_mode, values, proofs_aff, gammas, n, ok_out));
+  ST_TRY(openings_args(ctx, "kzg_verify_batch", com_stride, point_mode, ok_out, "ok_out", com_aff && tau_g2_aff && points && values && proofs_aff && gammas, n));
   if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
-  // every buffer is reserved before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only
   ST_TRY(verify_batch_reserve(ctx, n));
   ST_TRY(reserve(ctx, ctx->io_a, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
   ST_TRY(reserve(ctx, ctx->io_d, n * 32));
-  if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
-  if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
   char* io = (char*)ctx->vb_io.p;
+  ItemStager items{ctx, com_aff, com_stride, io + VbLayout::O_PTS, points, point_mode, io + VbLayout::O_OMEGA, proofs_aff, n};
+  ST_TRY(items.reserve());
   CopyFeed feed(ctx);
-  if (!com_stride) ST_TRY(feed.put(0, io + VbLayout::O_PTS, com_aff, 64));
+  ST_TRY(items.put(feed, ItemStager::ONE_COM));
   ST_TRY(feed.put(0, io + VbLayout::O_QS + 128, tau_g2_aff, 128));
-  if (point_mode) ST_TRY(feed.put(0, io + VbLayout::O_OMEGA, points, 32));
+  ST_TRY(items.put(feed, ItemStager::OMEGA));
   // Large batches (160 B per item) go up on the context's copy stream in the order the kernels ask for them: gammas and proofs, then -- under
   // the first MSM -- commitments, points and values. Small ones, and a context told to use no other stream (pipe_chunks = 0), copy in front.
   ST_TRY(feed.begin(ctx->tune.pipe_chunks && n >= PIPE_CHUNK));
-  size_t piece = 0;
-  auto put = [&](void* dst, const void* src, size_t bytes) { return feed.put(piece++, dst, src, bytes); };
   const std::function<keaki_status(int)> stage = [&](int phase) -> keaki_status {
     if (phase == 0) {
-      ST_TRY(put(ctx->io_a.p, gammas, n * 32));
-      return put(ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES);
+      ST_TRY(items.put(feed, ctx->io_a.p, gammas, n * 32));
+      return items.put(feed, ItemStager::PROOFS);
     }
-    if (!point_mode) ST_TRY(put(ctx->io_c.p, points, n * 32));
-    ST_TRY(put(ctx->io_d.p, values, n * 32));
-    if (com_stride) ST_TRY(put(ctx->io_e.p, com_aff, n * G1_AFF_BYTES));
-    return KEAKI_OK;
+    ST_TRY(items.put(feed, ItemStager::POINTS));
+    ST_TRY(items.put(feed, ctx->io_d.p, values, n * 32));
+    return items.put(feed, ItemStager::COMS);
   };
-  ST_TRY(verify_batch_core(ctx, ctx->io_e.p, com_stride, ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, ctx->io_a.p, n, stage, ok_out, sums_out_aff));
-  feed.settled();                 // verify_batch_core has downloaded the result
-  return KEAKI_OK;
+  return feed.closed_by(verify_batch_core(ctx, items.d_com(), com_stride, items.d_points(), point_mode, ctx->io_d.p, items.d_proofs(), ctx->io_a.p, n, stage, ok_out,
+                                          sums_out_aff));
 }
 
 // ---- KZG coset batch verification: n set proofs over cosets of size l, one linear combination, two pairings ----------------------------------
@@ -2455,9 +2483,9 @@ keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_
 // vc_io block: [pts: C 64] [mul: g C 64] [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64] [qs: g2 128 | tau^l 128] [omega 32] [gt 768]
 extern "C++" {
 namespace {
-struct VcLayout {
-  static constexpr size_t O_PTS = 0, O_MUL = 64, O_SUM = 128, O_L = 416, O_R = 512, O_PS = 608, O_QS = 736, O_OMEGA = 992, O_GT = 1024, TOTAL = 1792;
-};
+struct VcLayout : SumBlock<128> { static constexpr size_t O_PTS = 0, O_MUL = 64, TOTAL = O_END; };
+// the values of n items as ONE span of the caller's array: up to the last value the strides name
+inline size_t coset_span(size_t n, size_t l, size_t item_stride, size_t t_stride) { return (n - 1) * item_stride + (l - 1) * t_stride + 1; }
 struct VcArgs {
   const keaki_hip_srs_g1* srs;
   const void *com, *tau_l, *points, *values, *proofs, *gammas;
@@ -2483,14 +2511,7 @@ keaki_status verify_cosets_core(keaki_hip_ctx* ctx, const VcArgs& a, const VcWor
     ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, w.g, 1, io + V::O_MUL));                                   // g C
     ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
   }
-  ST_TRY(g1_sum_run(ctx, io + V::O_SUM, 3, io + V::O_L));
-  ST_TRY(verify_batch_jac_to_aff_run(ctx, io + V::O_L, io + V::O_R, io + V::O_PS));
-  ST_TRY(pairing_run(ctx, io + V::O_PS, io + V::O_QS, 1, 2, io + V::O_GT));
-  uint8_t gt[768];
-  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, io + V::O_PS, 128, hipMemcpyDeviceToHost, ctx->stream));
-  ST_TRY(download(ctx, gt, io + V::O_GT, 768));
-  *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
-  return KEAKI_OK;
+  return combination_finish(ctx, io + V::O_SUM, ok_out, sums_out_aff);
 }
 // Two values (k, t) != (k', t') of the call share an address iff a item_stride = b t_stride for some 0 <= a < n, 0 <= b < l, not both zero; the
 // smallest such pair is (t_stride / g, item_stride / g), g = gcd.
@@ -2504,8 +2525,7 @@ bool verify_cosets_strides_overlap(size_t n, size_t l, size_t item_stride, size_
 // The ONE argument check of the coset calls (`what`: kzg_verify_cosets, kzg_coset_pairs, kzg_verify_cosets_each). `out_ok` / `out_name`: the output that is
 // required at any n; `rest_ok`: the call's own arrays beyond the commitment, the shifts, the values and the two constants are there (asked for n > 0).
 keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const char* what, bool out_ok, const char* out_name, bool rest_ok) {
-  if ((a.com_stride != 0 && a.com_stride != 1) || (a.point_mode != 0 && a.point_mode != 1))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: com_stride = %d, point_mode = %d: both must be 0 or 1", what, (int)a.com_stride, (int)a.point_mode);
+  ST_TRY(kzg_modes_ok(ctx, what, a.com_stride, a.point_mode));
   if (!out_ok || !a.srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, out_ok ? "srs_g1" : out_name);
   if (a.log2l > 31 || ((size_t)1 << a.log2l) > KEAKI_SET_MAX)
     return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: l = 2^%u exceeds KEAKI_SET_MAX = %d", what, a.log2l, (int)KEAKI_SET_MAX);
@@ -2523,9 +2543,6 @@ keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const char*
                 a.item_stride, a.t_stride, a.n, l);
   return srs_holds(ctx, a.srs, what, l, "kzg cosets: I has %zu coefficients but the G1 SRS holds %zu points");
 }
-keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const int32_t* ok_out) {
-  return verify_cosets_args(ctx, a, "kzg_verify_cosets", ok_out != nullptr, "ok_out", a.tau_l && a.proofs && a.gammas);
-}
 }  // namespace
 }  // extern "C++"
 
@@ -2537,7 +2554,7 @@ keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip
   TRACE_SCOPE("keaki.kzg_verify_cosets");
   const VcArgs a = {srs_g1, d_com_aff, d_tau_l_g2_aff, d_points, d_values, d_proofs_aff, d_gammas, com_stride, point_mode, item_stride, t_stride, n, log2l,
                     omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, ok_out));
+  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets", ok_out != nullptr, "ok_out", a.tau_l && a.proofs && a.gammas));
   if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
   ST_TRY(reserve(ctx, ctx->vc_io, VcLayout::TOTAL));
   ST_TRY(reserve(ctx, ctx->vc_work, verify_cosets_work_bytes(n, log2l)));
@@ -2554,31 +2571,26 @@ keaki_status keaki_hip_kzg_verify_cosets(keaki_hip_ctx* ctx, const keaki_hip_srs
   CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
   TRACE_SCOPE("keaki.kzg_verify_cosets");
   VcArgs a = {srs_g1, com_aff, tau_l_g2_aff, points, values, proofs_aff, gammas, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, ok_out));
+  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets", ok_out != nullptr, "ok_out", a.tau_l && a.proofs && a.gammas));
   if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
   // the values go up as the one span the strides name, behind the kernels' own workspace; every buffer is reserved before the first copy
-  const size_t l = (size_t)1 << log2l, span = (n - 1) * item_stride + (l - 1) * t_stride + 1, work = (verify_cosets_work_bytes(n, log2l) + 255) & ~(size_t)255;
+  const size_t span = coset_span(n, (size_t)1 << log2l, item_stride, t_stride), work = (verify_cosets_work_bytes(n, log2l) + 255) & ~(size_t)255;
   ST_TRY(reserve(ctx, ctx->vc_io, VcLayout::TOTAL));
   ST_TRY(reserve(ctx, ctx->vc_work, work + span * 32));
   ST_TRY(reserve(ctx, ctx->io_a, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
-  if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
-  if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
   char* io = (char*)ctx->vc_io.p;
+  ItemStager items{ctx, com_aff, com_stride, io + VcLayout::O_PTS, points, point_mode, io + VcLayout::O_OMEGA, proofs_aff, n};
+  ST_TRY(items.reserve());
   char* d_values = (char*)ctx->vc_work.p + work;
   CopyFeed feed(ctx);
-  if (com_stride) ST_TRY(feed.put(0, ctx->io_e.p, com_aff, n * G1_AFF_BYTES));
-  else ST_TRY(feed.put(0, io + VcLayout::O_PTS, com_aff, 64));
+  ST_TRY(items.put(feed, ItemStager::COM));
   ST_TRY(feed.put(0, io + VcLayout::O_QS + 128, tau_l_g2_aff, 128));
-  if (point_mode) ST_TRY(feed.put(0, io + VcLayout::O_OMEGA, points, 32));
-  else ST_TRY(feed.put(0, ctx->io_c.p, points, n * 32));
+  ST_TRY(items.put(feed, ItemStager::PTS));
   ST_TRY(feed.put(0, ctx->io_a.p, gammas, n * 32));
-  ST_TRY(feed.put(0, ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES));
+  ST_TRY(items.put(feed, ItemStager::PROOFS));
   ST_TRY(feed.put(0, d_values, values, span * 32));
-  a.com = ctx->io_e.p; a.points = point_mode ? (const void*)(io + VcLayout::O_OMEGA) : ctx->io_c.p; a.values = d_values; a.proofs = ctx->io_b.p; a.gammas = ctx->io_a.p;
-  ST_TRY(verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff));
-  feed.settled();                 // verify_cosets_core has downloaded the result
-  return KEAKI_OK;
+  a.com = items.d_com(); a.points = items.d_points(); a.values = d_values; a.proofs = items.d_proofs(); a.gammas = ctx->io_a.p;
+  return feed.closed_by(verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff));
 }
 
 // ---- KZG verify_each: n openings, one verdict each ---------------------------------------------------------------------------------------
@@ -2593,18 +2605,21 @@ keaki_status keaki_hip_kzg_verify_cosets(keaki_hip_ctx* ctx, const keaki_hip_srs
 extern "C++" {
 namespace {
 struct VeLayout { static constexpr size_t O_BAD = 0, O_COM = 16, O_TAU = 80, O_OMEGA = 208, BYTES = 240; };
-keaki_status verify_each_args(keaki_hip_ctx* ctx, const void* com, int32_t com_stride, const void* tau, const void* points, int32_t point_mode,
-                              const void* values, const void* proofs, size_t n, const void* status, const uint64_t* n_bad) {
-  if ((com_stride != 0 && com_stride != 1) || (point_mode != 0 && point_mode != 1))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: com_stride = %d, point_mode = %d: both must be 0 or 1", (int)com_stride, (int)point_mode);
-  if (!n_bad) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: n_bad is null");
-  if (n && (!com || !tau || !points || !values || !proofs || !status)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: null pointer");
-  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify_each: n must be < 2^31 per device");
-  return KEAKI_OK;
-}
 void verify_each_empty(uint64_t* n_bad, uint64_t* first_bad) {
   *n_bad = 0;
   if (first_bad) *first_bad = ~0ull;
+}
+// What a host form with a verdict per item keeps on the device, [status: n B, rounded up to 64 | L: n x 64 B when the caller asked for them], and how it
+// goes back once the counters are in, so that the status bytes are final: one download (status and L lie in one buffer, but go to two arrays of the caller).
+struct EachOut {
+  size_t n, lhs_off, bytes; uint64_t* lhs_host;
+  EachOut(size_t n_, uint64_t* lhs) : n(n_), lhs_off((n_ + 63) & ~(size_t)63), bytes(lhs_off + (lhs ? n_ * G1_AFF_BYTES : 0)), lhs_host(lhs) {}
+  char* d_lhs(char* out) const { return lhs_host ? out + lhs_off : nullptr; }
+};
+keaki_status each_result(CopyFeed& feed, const EachOut& r, const char* out, uint8_t* status) {
+  prefault_out(feed.ctx, r.lhs_host, r.lhs_host ? r.n * G1_AFF_BYTES : 0);
+  if (r.lhs_host) HIP_TRY(feed.ctx, hipMemcpyAsync(r.lhs_host, out + r.lhs_off, r.n * G1_AFF_BYTES, hipMemcpyDeviceToHost, feed.ctx->stream));
+  return download(feed, status, out, r.n);
 }
 // Everything is device memory: d_com / d_tau / d_omega_or_points as the kernels read them, tau_host = the 128 bytes of [tau]_2 (the key of its line
 // table). d_lhs: n x 64 B for the L_i, or null (they stay in the chunk's workspace). Ends with the read-back of the counters: synchronises.
@@ -2663,7 +2678,7 @@ keaki_status keaki_hip_kzg_verify_each_dev(keaki_hip_ctx* ctx, const void* d_com
                                            uint64_t* first_bad, void* d_lhs_out_aff) {
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.kzg_verify_each");
-  ST_TRY(verify_each_args(ctx, d_com_aff, com_stride, d_tau_g2_aff, d_points, point_mode, d_values, d_proofs_aff, n, d_status, n_bad));
+  ST_TRY(openings_args(ctx, "kzg_verify_each", com_stride, point_mode, n_bad, "n_bad", d_com_aff && d_tau_g2_aff && d_points && d_values && d_proofs_aff && d_status, n));
   if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
   ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
   uint64_t tau_host[16];
@@ -2677,31 +2692,23 @@ keaki_status keaki_hip_kzg_verify_each(keaki_hip_ctx* ctx, const uint64_t* com_a
                                        uint64_t* first_bad, uint64_t* lhs_out_aff) {
   CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
   TRACE_SCOPE("keaki.kzg_verify_each");
-  ST_TRY(verify_each_args(ctx, com_aff, com_stride, tau_g2_aff, points, point_mode, values, proofs_aff, n, status, n_bad));
+  ST_TRY(openings_args(ctx, "kzg_verify_each", com_stride, point_mode, n_bad, "n_bad", com_aff && tau_g2_aff && points && values && proofs_aff && status, n));
   if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  // every buffer is reserved before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only
-  const size_t lhs_off = (n + 63) & ~(size_t)63, out_bytes = lhs_off + (lhs_out_aff ? n * G1_AFF_BYTES : 0);
+  const EachOut r(n, lhs_out_aff);
   ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
-  ST_TRY(reserve(ctx, ctx->ve_out, out_bytes));
-  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
+  ST_TRY(reserve(ctx, ctx->ve_out, r.bytes));
   ST_TRY(reserve(ctx, ctx->io_d, n * 32));
-  if (!point_mode) ST_TRY(reserve(ctx, ctx->io_c, n * 32));
-  if (com_stride) ST_TRY(reserve(ctx, ctx->io_e, n * G1_AFF_BYTES));
   char* io = (char*)ctx->ve_io.p;
+  ItemStager items{ctx, com_aff, com_stride, io + VeLayout::O_COM, points, point_mode, io + VeLayout::O_OMEGA, proofs_aff, n};
+  ST_TRY(items.reserve());
   CopyFeed feed(ctx);             // one upload in front, on the context's stream; a failing call drains it before it returns
   ST_TRY(feed.put(0, io + VeLayout::O_TAU, tau_g2_aff, 128));
-  if (com_stride) ST_TRY(feed.put(0, ctx->io_e.p, com_aff, n * G1_AFF_BYTES)); else ST_TRY(feed.put(0, io + VeLayout::O_COM, com_aff, 64));
-  if (point_mode) ST_TRY(feed.put(0, io + VeLayout::O_OMEGA, points, 32)); else ST_TRY(feed.put(0, ctx->io_c.p, points, n * 32));
+  ST_TRY(items.put(feed, ItemStager::COM | ItemStager::PTS));
   ST_TRY(feed.put(0, ctx->io_d.p, values, n * 32));
-  ST_TRY(feed.put(0, ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES));
+  ST_TRY(items.put(feed, ItemStager::PROOFS));
   char* out = (char*)ctx->ve_out.p;
-  ST_TRY(verify_each_core(ctx, com_stride ? ctx->io_e.p : (void*)(io + VeLayout::O_COM), com_stride, io + VeLayout::O_TAU, tau_g2_aff,
-                          point_mode ? (void*)(io + VeLayout::O_OMEGA) : ctx->io_c.p, point_mode, ctx->io_d.p, ctx->io_b.p, n, out,
-                          lhs_out_aff ? out + lhs_off : nullptr, n_bad, first_bad));
-  // the counters are back, so the status bytes are final: one download (status and L lie in one buffer, but go to two arrays of the caller)
-  prefault_out(ctx, lhs_out_aff, lhs_out_aff ? n * G1_AFF_BYTES : 0);
-  if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out + lhs_off, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  return download(feed, status, out, n);
+  ST_TRY(verify_each_core(ctx, items.d_com(), com_stride, io + VeLayout::O_TAU, tau_g2_aff, items.d_points(), point_mode, ctx->io_d.p, items.d_proofs(), n, out, r.d_lhs(out), n_bad, first_bad));
+  return each_result(feed, r, out, status);
 }
 
 // ---- KZG coset pairs and per-coset verdicts ------------------------------------------------------------------------------------------------
@@ -2796,16 +2803,15 @@ keaki_status keaki_hip_kzg_coset_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs
   VcArgs a = {srs_g1, com_aff, nullptr, points, values, nullptr, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
   ST_TRY(verify_cosets_args(ctx, a, "kzg_coset_pairs", true, "", lhs_out_aff && c_out));
   if (n == 0) return KEAKI_OK;
-  const size_t l = (size_t)1 << log2l, span = (n - 1) * item_stride + (l - 1) * t_stride + 1;
+  const size_t span = coset_span(n, (size_t)1 << log2l, item_stride, t_stride);
   ST_TRY(reserve(ctx, ctx->cp_pairs, n * 96));
   ST_TRY(reserve(ctx, ctx->cp_in, span * 32));
-  ST_TRY(reserve(ctx, ctx->io_c, point_mode ? 32 : n * 32));
-  ST_TRY(reserve(ctx, ctx->io_e, (com_stride ? n : 1) * G1_AFF_BYTES));
+  ItemStager items{ctx, com_aff, com_stride, nullptr, points, point_mode, nullptr, nullptr, n};      // one commitment and omega: in io_e and io_c
+  ST_TRY(items.reserve());
   CopyFeed feed(ctx);
-  ST_TRY(feed.put(0, ctx->io_e.p, com_aff, (com_stride ? n : 1) * G1_AFF_BYTES));
-  ST_TRY(feed.put(0, ctx->io_c.p, points, point_mode ? 32 : n * 32));
+  ST_TRY(items.put(feed, ItemStager::ALL));
   ST_TRY(feed.put(0, ctx->cp_in.p, values, span * 32));
-  a.com = ctx->io_e.p; a.points = ctx->io_c.p; a.values = ctx->cp_in.p;
+  a.com = items.d_com(); a.points = items.d_points(); a.values = ctx->cp_in.p;
   char* out = (char*)ctx->cp_pairs.p;
   ST_TRY(coset_pairs_core(ctx, srs_g1, a, out, out + n * G1_AFF_BYTES));
   HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
@@ -2840,28 +2846,22 @@ keaki_status keaki_hip_kzg_verify_cosets_each(keaki_hip_ctx* ctx, keaki_hip_srs_
   VcArgs a = {srs_g1, com_aff, tau_l_g2_aff, points, values, proofs_aff, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
   ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets_each", n_bad != nullptr, "n_bad", tau_l_g2_aff && proofs_aff && status));
   if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  // every buffer is reserved before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only
-  const size_t l = (size_t)1 << log2l, span = (n - 1) * item_stride + (l - 1) * t_stride + 1;
-  const size_t lhs_off = (n + 63) & ~(size_t)63, out_bytes = lhs_off + (lhs_out_aff ? n * G1_AFF_BYTES : 0);
+  const size_t span = coset_span(n, (size_t)1 << log2l, item_stride, t_stride);
+  const EachOut r(n, lhs_out_aff);
   CpPairs w;
-  ST_TRY(coset_each_reserve(ctx, n, out_bytes, &w));
+  ST_TRY(coset_each_reserve(ctx, n, r.bytes, &w));
   ST_TRY(reserve(ctx, ctx->cp_in, span * 32));
-  ST_TRY(reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
-  ST_TRY(reserve(ctx, ctx->io_c, point_mode ? 32 : n * 32));
-  ST_TRY(reserve(ctx, ctx->io_e, (com_stride ? n : 1) * G1_AFF_BYTES));
+  ItemStager items{ctx, com_aff, com_stride, nullptr, points, point_mode, nullptr, proofs_aff, n};   // one commitment and omega: in io_e and io_c
+  ST_TRY(items.reserve());
   char* io = (char*)ctx->ve_io.p;
   CopyFeed feed(ctx);
   ST_TRY(feed.put(0, io + VeLayout::O_TAU, tau_l_g2_aff, 128));
-  ST_TRY(feed.put(0, ctx->io_e.p, com_aff, (com_stride ? n : 1) * G1_AFF_BYTES));
-  ST_TRY(feed.put(0, ctx->io_c.p, points, point_mode ? 32 : n * 32));
-  ST_TRY(feed.put(0, ctx->io_b.p, proofs_aff, n * G1_AFF_BYTES));
+  ST_TRY(items.put(feed, ItemStager::ALL));
   ST_TRY(feed.put(0, ctx->cp_in.p, values, span * 32));
-  a.com = ctx->io_e.p; a.tau_l = io + VeLayout::O_TAU; a.points = ctx->io_c.p; a.values = ctx->cp_in.p; a.proofs = ctx->io_b.p;
+  a.com = items.d_com(); a.tau_l = io + VeLayout::O_TAU; a.points = items.d_points(); a.values = ctx->cp_in.p; a.proofs = items.d_proofs();
   char* out = w.zeros + n * 32;
-  ST_TRY(coset_each_core(ctx, srs_g1, a, tau_l_g2_aff, w, out, lhs_out_aff ? out + lhs_off : nullptr, n_bad, first_bad));
-  prefault_out(ctx, lhs_out_aff, lhs_out_aff ? n * G1_AFF_BYTES : 0);
-  if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out + lhs_off, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  return download(feed, status, out, n);
+  ST_TRY(coset_each_core(ctx, srs_g1, a, tau_l_g2_aff, w, out, r.d_lhs(out), n_bad, first_bad));
+  return each_result(feed, r, out, status);
 }
 
 // ---- SRS ingest: on-curve check (row f-3) ------------------------------------------------------------------------
@@ -2886,9 +2886,7 @@ keaki_status keaki_hip_g2_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, 
   if (!n_off_curve || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_check: null pointer");
   CopyFeed feed(ctx);
   ST_TRY(upload(feed, ctx->io_a, points_aff, n * 128));
-  ST_TRY(curve_check_common(ctx, true, ctx->io_a.p, n, n_off_curve, first_off_curve));
-  feed.settled();                 // curve_check_common has downloaded the counters
-  return KEAKI_OK;
+  return feed.closed_by(curve_check_common(ctx, true, ctx->io_a.p, n, n_off_curve, first_off_curve));      // which has downloaded the counters
 }
 
 // ---- compressed point wire format (point_codec.hip): compress, decompress with validation, G2 subgroup check --------------------------------
