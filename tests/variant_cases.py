@@ -1,5 +1,5 @@
 """Which kernel instantiation a call reaches, and the cases that reach them all -- TEST INFRASTRUCTURE (a plain module, imported by
-tests/test_variant_cases_model.py and tests/test_gpu_variants.py; no GPU import).
+tests/test_variant_cases_model.py and tests/test_gpu_variants.py; tests/heavy_cases.py builds on its plan and sort model; no GPU import).
 
 The library ships several instantiations of its MSM, FK23 and fixed-base kernels; host code picks one from the input size and the tuning
 switches of keaki_hip_ctx_set_option (also settable through KEAKI_* at context creation). This module restates those host-side choices
@@ -28,9 +28,13 @@ def header_consts():
     """the sort's limits as the headers define them (read, not copied)"""
     t = _src("msm.hip.h")
     out = {}
-    for name in ("T1_THREADS", "T1_PER", "T1_CAP", "PART_MAX_BINS", "C2_CAP", "PART_MAX_FINE_SHIFT", "HEAVY_MIN"):
+    for name in ("T1_THREADS", "T1_PER", "T1_CAP", "PART_MAX_BINS", "C2_CAP", "PART_MAX_FINE_SHIFT", "SEG_INLINE", "CNT_BINS", "HEAVY_MIN",
+                 "HEAVY_SLICE"):
         m = re.search(r"constexpr u32 (?:\w+ = \d+, )*%s = (\d+)" % name, t)
         out[name] = int(m.group(1))
+    # the chunks of a bin that one trip of k_msm_heavy's segment search covers (one per lane of the workgroup)
+    m = re.search(r"for \(u32 cb = 0; cb < bm\.nch && vbase < hi; cb \+= (\d+)\)", t)
+    out["HEAVY_CHUNK_STRIDE"] = int(m.group(1))
     m = re.search(r"constexpr int MSM_C_MAX = (\d+), MSM_C_SHARED_MAX = (\d+);", _src("internal.h"))
     out["MSM_C_MAX"], out["MSM_C_SHARED_MAX"] = int(m.group(1)), int(m.group(2))
     return out
@@ -131,7 +135,8 @@ def width_refused(c, shared):
 
 
 def part_make_shape(n, W, nb, lb_override=-1):
-    """-> dict(lb, geom, tile, te) or None (refused: 'window too large')"""
+    """-> dict(lb, geom, tile, te, lg, shift, hb) or None (refused: 'window too large'). shift / hb: the low / high fine bits around the
+    bin bits of a global bucket id (part_bin)"""
     lg = 0
     while (1 << lg) < nb:
         lg += 1
@@ -151,7 +156,19 @@ def part_make_shape(n, W, nb, lb_override=-1):
     te = tile * W
     mean = te >> lb
     geom = 0 if mean <= 24 else 1 if mean <= 48 else 2 if mean <= 100 else 3
-    return {"lb": lb, "geom": geom, "tile": tile, "te": te, "lg": lg}
+    hb = min(lg - lb, 3)
+    return {"lb": lb, "geom": geom, "tile": tile, "te": te, "lg": lg, "shift": lg - lb - hb, "hb": hb}
+
+
+def part_bin(shape, g):
+    """the bin of global bucket id g (msm.hip.h: part_bin): the lb bits above the `shift` low fine bits"""
+    return (g >> shape["shift"]) & ((1 << shape["lb"]) - 1)
+
+
+def bucket_base(p, w):
+    """first global bucket id of window w on the generic path (msm.hip.h: msm_bucket_base; over window tables every window starts at 0)"""
+    c, k = p["c"], p["k"]
+    return w * (1 << (c - 1)) if w <= k else k * (1 << (c - 1)) + (w - k) * (1 << (c - 2))
 
 
 def reduce_len(max_b, g2=False, reduce_l=0):
