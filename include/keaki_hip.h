@@ -68,6 +68,7 @@ enum {
   KEAKI_ERR_TOO_LARGE = -5     /* polynomial longer than the SRS: KZGError::PolynomialTooLarge */
 };
 enum { KEAKI_SET_MAX = 1024 };  /* most points of a KZG set opening (keaki_hip_kzg_set_polys and the calls built on it) */
+enum { KEAKI_VERIFY_SETS_K_MAX = 64 };  /* most points per item of keaki_hip_kzg_verify_sets */
 
 typedef struct keaki_hip_ctx keaki_hip_ctx;
 typedef struct keaki_hip_srs_g1 keaki_hip_srs_g1; /* device-resident [tau^i]_1, affine */
@@ -111,6 +112,8 @@ const char* keaki_hip_version(void);
  * form), "fk_coset_min_lanes" (that kernel splits the terms of a position over lanes while its launch has fewer lanes than this: 1 .. 2^31, 0 = the
  * built-in 131,072; other values of the two are refused with KEAKI_ERR_BAD_ARG, in the environment ignored), "verify_cosets_blocks" (workgroups of
  * keaki_hip_kzg_verify_cosets' transform kernel: 1 .. 1,024, 0 = automatic, three per compute unit; results do not depend on it; other values refused),
+ * "verify_sets_blocks" (workgroups of keaki_hip_kzg_verify_sets' polynomial kernel: 1 .. 1,024, 0 = automatic, three per compute unit; results do not
+ * depend on it; other values refused),
  * "coset_rows_min_lanes" (keaki_hip_kzg_coset_pairs: the row kernel splits an item's l bases over lanes while a launch has fewer lanes than this: 1 .. 2^31,
  * 0 = the built-in 131,072), "coset_rows_route" (how that call sums its rows: 1 = the handle's window table over the first l SRS points, 2 = the batched
  * MSM, 0 = by plan), "coset_rows_wb" (window bits of that table: 8, 10 or 13, 0 = by plan -- the switch of the width sweep; a table the allocator refuses
@@ -542,6 +545,85 @@ keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip
                                              size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
                                              const uint64_t* inv_l, const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out,
                                              uint64_t* sums_out_aff);
+
+/* ---- KZG set batch verification: n set proofs over ARBITRARY point sets of one size in one call -------------------------------------------------
+ * What keaki_hip_kzg_verify_multi checks one proof at a time, for n items at once, the sets being any k distinct points each (the proofs that
+ * kzg::open_set, kzg::aggregate_proofs and vec::vec_open_subset hand out; cosets of one size are keaki_hip_kzg_verify_cosets' case). Item i < n: a
+ * commitment C_i, the k points z_(i,0) .. z_(i,k-1), the k claimed values y_(i,j) = p_i(z_(i,j)), a proof pi_i, the caller's coefficient gamma_i.
+ *     Z_i(X) = prod_j (X - z_(i,j)) = sum_(t <= k) Z_(i,t) X^t  (monic: Z_(i,k) = 1)       I_i(X) = sum_(t < k) I_(i,t) X^t, the interpolant of (z_(i,j), y_(i,j))
+ * The single check e(C_i - [I_i(tau)]_1, g2) == e(pi_i, [Z_i(tau)]_2) has the right side prod_t e(Z_(i,t) pi_i, [tau^t]_2): the sets differ, so no one
+ * G2 point serves all items, but the COEFFICIENTS of Z cross the pairing as G1 scalars, and [tau^0]_2 = g2 folds into the left side.
+ * The call evaluates EXACTLY this combination:
+ *     J_t = sum_i gamma_i I_(i,t)  (t < k)       L = sum_i gamma_i C_i - sum_t J_t [tau^t]_1 - sum_i (gamma_i Z_(i,0)) pi_i
+ *     R_t = sum_i (gamma_i Z_(i,t)) pi_i  (1 <= t <= k;  R_k = sum_i gamma_i pi_i)
+ *     *ok_out = 1  <=>  e(-L, g2) prod_(t = 1 .. k) e(R_t, [tau^t]_2) == 1
+ * for the gammas it is given; that is a deterministic contract. If all n items are valid it always accepts. If one is invalid it rejects except
+ * with probability <= 1/r -- PROVIDED the gamma_i are independent, uniform in Fr and unknown to whoever produced the proofs. Badly chosen gammas
+ * void the bound: with all gamma_i equal, two errors can cancel, and gamma = 0 accepts anything. gammas are drawn by the caller, one Fr::rand per item
+ * in index order (the rule encap_batch follows for r), so the randomness stream stays the caller's and every result is reproducible. At k = 1 the
+ * equation is keaki_hip_kzg_verify_batch's (Z = X - z: -gamma Z_0 = gamma z, J_0 = sum gamma y, [tau^0]_1 = g1): sums_out_aff is byte for byte what that
+ * call returns.
+ *   srs_g1, srs_g2   srs_g1 is read at its points 0 .. k - 1 ([tau^t]_1, through its window tables where it has them), srs_g2 at its points 1 .. k ([tau^t]_2,
+ *                as keaki_hip_kzg_verify_multi reads it)
+ *   com_aff      com_stride = 0: ONE affine G1 point u64[8], the commitment of all items (subsets of one vector); 1: n points
+ *   points       point_mode = 0: Fr, item i's point j at word 4 (i item_stride + j). 1: u32 domain indices at the same ELEMENT offsets (index (i, j) is
+ *                the u32 at points + 4 (i item_stride + j) bytes) and omega ONE Fr: z = omega^idx, derived on the device (what vec_verify_subsets needs).
+ *                omega is NULL in point_mode 0.
+ *   values       value (i, j) is the Fr at word 4 (i item_stride + j); item_stride >= k, the gap between two rows is never read
+ *   proofs_aff, gammas   n affine G1 points, n Fr
+ *   sums_out_aff (k + 1) x u64[8] = L, then R_1 .. R_k, affine ((0,0) = identity): what the Miller loops ran on, before L is negated; or NULL
+ *   repeated point   two equal points within an item are no set. The library does NOT look: a repeated point zeroes a weight -- and the weights of the up to
+ *                16 (item, point) pairs that share its inversion -- and the results are meaningless. Distinct points are the caller's contract, exactly as
+ *                for keaki_hip_kzg_set_polys; the host layers (host/keaki.cpp, rust/keaki/src/hip.rs) refuse repeats.
+ * Identity commitments and proofs, zero values and gammas are ordinary inputs. n = 0: *ok_out = 1, the sums are the identity.
+ *   errors     a null required pointer, k = 0 or k > KEAKI_VERIFY_SETS_K_MAX, item_stride < k, com_stride or point_mode outside {0, 1}, n k >= 2^31 (or n >=
+ *              2^31), (n - 1) item_stride of 2^47 or more, point_mode 1 without omega -> KEAKI_ERR_BAD_ARG; k + 1 > len(srs_g2) or k > len(srs_g1) ->
+ *              KEAKI_ERR_TOO_LARGE; a refused workspace -> KEAKI_ERR_OOM. Nothing is written in any of these cases, nothing is launched, and the context
+ *              stays usable.
+ *   kernels    csrc/kzg_sets.hip: (point_mode 1) one launch derives the points; one launch the weights 1 / Z_i'(z_(i,j)) (k - 1 products per pair, ONE Fermat
+ *              inversion per 16 pairs); one launch Z_i and I_i of ALL items in LDS (tiles of 256 / kp items, kp = the power of two >= k; O(k^2) products per
+ *              item), the k + 1 scalar rows and the per-workgroup sums of gamma I; a fourth folds those into -J and sum gamma. Then: the batched MSM
+ *              of the k + 1 rows over the proofs (rows of more than 16,384 items: one MSM per row), the MSM of -J over [tau^t]_1, the MSM of gamma over the
+ *              commitments (or (sum gamma) C), one sum, k + 1 Miller loops, their product (csrc/gt_product.hip) and ONE final exponentiation:
+ *              keaki_hip_pairing_product, below. 384 GT bytes come back and are compared with GT one on the host. Nothing here is n pairings or in G2.
+ *   host form  one upload in front of the kernels (the spans of the points and values the stride names; no chunk pipeline), the kernels, 384 bytes
+ *              (+ 64 (k + 1)) back; returns only when nothing reads or writes caller memory, also on failure.
+ *   _dev       every array is a device pointer (16-byte aligned; 4-byte for the indices of point_mode 1); omega (read before the call returns), ok_out and
+ *              sums_out_aff stay HOST pointers, so this form synchronises as well. Workspace: 32 (2 k + 1) B per item (32 (3 k + 1) in point_mode 1) + 32
+ *              (k + 1) B per tile of at most 1,024 + 24 KB + the batched MSM's, grow-only, counted in keaki_hip_ctx_memory out4[1], released by
+ *              keaki_hip_ctx_trim.
+ *   out of scope  a per-item verdict (a verify_sets_each); k > 64; a G2-side route for few items with large sets; the multi-GPU form (the host layers refuse a
+ *              device group). Items of unequal k are grouped by k, one call per size, by the host layers.
+ *   numbers    (MI355X, medians of alternating rounds in one process: profiles/verify_sets_times.txt, bench_tools/bench_verify_sets.py) resident / from host
+ *              arrays, one commitment per item, k = 2 / 8 / 64: n = 2 6.6 / 6.7 / 8.3 ms, n = 64 6.4 / 6.6 / 7.9, n = 4,096 6.4 / 6.9 / 11.1 (host 6.6 / 7.0 / 11.4),
+ *              n = 2^16 10.3 / 22.5 / 153.7 (host 10.6 / 23.4 / 158.6), n = 2^20 15.6 / 41.2 ms at k = 2 / 8 (host 21.0 / 53.8). Against (a) the only route before, n
+ *              calls of keaki_hip_kzg_verify_multi (7.6 - 8.9 ms each; 64 calls timed, EXTRAPOLATED beyond): the call wins at every shape, from n = 1 on (n = 1,
+ *              measured: 5.0 / 5.1 / 7.2 ms against 8.4 / 8.9 / 7.6; n = 2: 6.4 / 6.6 / 8.7 against 16.6 / 17.0 / 15.3; n = 2^16, k = 8: 22.5 ms against 570 s): the k + 1
+ *              Miller loops run side by side and share one final exponentiation, so they do not make small n lose. Against (b) keaki_hip_kzg_verify_cosets_dev
+ *              on coset-shaped inputs of the same n and k, the floor: 0.74 - 0.99 of its time up to n = 4,096 at k <= 8 and n = 64 at k = 64, and it LOSES beyond:
+ *              n = 4,096, k = 64 1.38 x; n = 2^16 1.25 / 2.67 / 17.4 x; n = 2^20 1.31 / 3.35 x -- rows of more than 16,384 items leave the batched MSM and cost one
+ *              full MSM each (k + 1 of them), and the polynomial kernel's n k^2 products show at k = 64. The kernels at n = 2^16, k = 2 / 8 / 64: k_vs_weights 0.44 /
+ *              0.59 / 5.66 ms, k_vs_polys 0.03 / 0.30 / 18.1 ms, k_vs_finish 0.02 / 0.03 / 0.06 ms, k_gt_product 0.11 / 0.11 / 0.18 ms; the Miller loops 0.70 - 0.72 ms,
+ *              the final exponentiation 0.76 - 0.77 ms. There is no route switch. */
+keaki_status keaki_hip_kzg_verify_sets(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                       int32_t com_stride, const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values,
+                                       size_t item_stride, size_t k, const uint64_t* proofs_aff, const uint64_t* gammas, size_t n, int32_t* ok_out,
+                                       uint64_t* sums_out_aff);
+keaki_status keaki_hip_kzg_verify_sets_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const void* d_com_aff,
+                                           int32_t com_stride, const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values,
+                                           size_t item_stride, size_t k, const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out,
+                                           uint64_t* sums_out_aff);
+
+/* ---- pairing product: prod_i e(g1[i], g2[i]) with ONE final exponentiation ------------------------------------------------------------------------
+ * gt_out = the 384 bytes of serialize_uncompressed(prod_(i < n) e(g1[i], g2[i])): n Miller loops, a product tree over their outputs (csrc/gt_product.hip:
+ * the elements in the representation keaki_hip_miller_loop_batch documents, multiplied by the pairing kernels' own Fq12 product; a second launch when n
+ * exceeds one workgroup's share of 128), ONE final exponentiation. An identity in either slot contributes GT one; n = 0 gives GT one. n < 2^31.
+ *   errors     a null required pointer (gt_out at any n; the point arrays for n > 0), n >= 2^31 -> KEAKI_ERR_BAD_ARG; a refused workspace -> KEAKI_ERR_OOM;
+ *              nothing is written then.
+ *   _dev       device pointers (d_gt_out: 384 bytes, 16-byte aligned); asynchronous on the context's stream. Workspace: 384 B per pair + 96 KB, grow-only,
+ *              counted in keaki_hip_ctx_memory out4[1], released by keaki_hip_ctx_trim. */
+keaki_status keaki_hip_pairing_product(keaki_hip_ctx* ctx, const uint64_t* g1_aff, const uint64_t* g2_aff, size_t n, uint8_t* gt_out);
+keaki_status keaki_hip_pairing_product_dev(keaki_hip_ctx* ctx, const void* d_g1_aff, const void* d_g2_aff, size_t n, void* d_gt_out);
 
 /* ---- KZG coset pairs and per-coset verdicts: the per-item side of the coset check, all n cosets in one call -----------------
  * verify_cosets answers "are all n set proofs valid?" in two pairings. Two things need the PER-ITEM points of the same check

@@ -678,6 +678,11 @@ bool verify_cosets_blocks_refuses(keaki_hip_ctx* ctx, const char*, long long v) 
   if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: verify_cosets_blocks = %lld out of range (1 .. %u; 0 = automatic)", v, VC_MAX_BLOCKS);
   return true;
 }
+bool verify_sets_blocks_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= (long long)VS_MAX_BLOCKS) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: verify_sets_blocks = %lld out of range (1 .. %u; 0 = automatic)", v, VS_MAX_BLOCKS);
+  return true;
+}
 bool coset_rows_min_lanes_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
   if (v >= 0 && v <= ((long long)1 << 31)) return false;
   if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: coset_rows_min_lanes = %lld out of range (1 .. 2^31; 0 = %u)", v, CR_MIN_LANES);
@@ -703,7 +708,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(encap_gt), TUNE_OPTION(encap_multi_single_min), TUNE_OPTION(host_prefault), TUNE_OPTION(pipe_chunks), TUNE_OPTION(msm_pipe_chunks), TUNE_OPTION(msm_pipe_min),
     TUNE_OPTION(msm_pipe_growth), TUNE_OPTION(vec_update_k_pass, vec_update_k_pass_refuses),
     TUNE_OPTION(fk_coset_group, fk_coset_group_refuses), TUNE_OPTION(fk_coset_min_lanes, fk_coset_min_lanes_refuses),
-    TUNE_OPTION(verify_cosets_blocks, verify_cosets_blocks_refuses),
+    TUNE_OPTION(verify_cosets_blocks, verify_cosets_blocks_refuses), TUNE_OPTION(verify_sets_blocks, verify_sets_blocks_refuses),
     TUNE_OPTION(coset_rows_min_lanes, coset_rows_min_lanes_refuses), TUNE_OPTION(coset_rows_route, coset_rows_route_refuses),
     TUNE_OPTION(coset_rows_wb, coset_rows_wb_refuses),
 #ifdef KEAKI_DIAG
@@ -2591,6 +2596,181 @@ keaki_status keaki_hip_kzg_verify_cosets(keaki_hip_ctx* ctx, const keaki_hip_srs
   ST_TRY(feed.put(0, d_values, values, span * 32));
   a.com = items.d_com(); a.points = items.d_points(); a.values = d_values; a.proofs = items.d_proofs(); a.gammas = ctx->io_a.p;
   return feed.closed_by(verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff));
+}
+
+// ---- pairing product: n Miller loops, a GT product tree, ONE final exponentiation ------------------------------------------------------------
+// gp_work block: [product 384] [partial products of the first launch] [Miller-loop outputs: 384 per pair]
+extern "C++" {
+namespace {
+size_t pairing_product_work_bytes(size_t n) { return 384 + gt_product_part_bytes() + n * 384; }
+keaki_status pairing_product_args(keaki_hip_ctx* ctx, const void* out, bool arrays_ok, size_t n) {
+  if (!out || (n && !arrays_ok)) return fail(ctx, KEAKI_ERR_BAD_ARG, "pairing_product: null pointer");
+  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "pairing_product: n must be < 2^31");
+  return KEAKI_OK;
+}
+// gp_work is reserved for n pairs; everything is a device pointer. Asynchronous on ctx->stream.
+keaki_status pairing_product_core(keaki_hip_ctx* ctx, const void* d_g1, const void* d_g2, size_t n, void* d_gt_out) {
+  char* wk = (char*)ctx->gp_work.p;
+  char* miller = wk + 384 + gt_product_part_bytes();
+  if (n) ST_TRY(miller_only_run(ctx, d_g1, d_g2, n, miller));
+  ST_TRY(gt_product_run(ctx, miller, n, wk + 384, wk));
+  return final_exp_only_run(ctx, wk, 1, d_gt_out);
+}
+// serialize_uncompressed(GT one): the canonical words of c0.c0.c0 = 1 come first, every other component is zero
+bool gt_bytes_are_one(const uint8_t* gt) {
+  if (gt[0] != 1) return false;
+  for (size_t i = 1; i < 384; i++) if (gt[i]) return false;
+  return true;
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_pairing_product_dev(keaki_hip_ctx* ctx, const void* d_g1_aff, const void* d_g2_aff, size_t n, void* d_gt_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.pairing_product");
+  ST_TRY(pairing_product_args(ctx, d_gt_out, d_g1_aff && d_g2_aff, n));
+  ST_TRY(reserve(ctx, ctx->gp_work, pairing_product_work_bytes(n)));
+  return pairing_product_core(ctx, d_g1_aff, d_g2_aff, n, d_gt_out);
+}
+
+keaki_status keaki_hip_pairing_product(keaki_hip_ctx* ctx, const uint64_t* g1_aff, const uint64_t* g2_aff, size_t n, uint8_t* gt_out) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.pairing_product");
+  ST_TRY(pairing_product_args(ctx, gt_out, g1_aff && g2_aff, n));
+  ST_TRY(reserve(ctx, ctx->gp_work, pairing_product_work_bytes(n)));
+  ST_TRY(reserve(ctx, ctx->io_a, n * G1_AFF_BYTES + 16));
+  ST_TRY(reserve(ctx, ctx->io_b, n * G2_AFF_BYTES + 16));
+  ST_TRY(reserve(ctx, ctx->io_c, 384));
+  CopyFeed feed(ctx);
+  ST_TRY(feed.put(0, ctx->io_a.p, g1_aff, n * G1_AFF_BYTES));
+  ST_TRY(feed.put(0, ctx->io_b.p, g2_aff, n * G2_AFF_BYTES));
+  ST_TRY(pairing_product_core(ctx, ctx->io_a.p, ctx->io_b.p, n, ctx->io_c.p));
+  return download(feed, gt_out, ctx->io_c.p, 384);
+}
+
+// ---- KZG set batch verification: n set proofs over arbitrary sets of k points, one linear combination, k + 1 Miller loops ---------------------
+// J_t = sum gamma_i I_(i,t), L = sum gamma_i C_i - sum_t J_t [tau^t]_1 - sum (gamma_i Z_(i,0)) proof_i, R_t = sum (gamma_i Z_(i,t)) proof_i (1 <= t <= k),
+// accept <=> e(-L, g2) prod_t e(R_t, [tau^t]_2) == 1: sum gamma_i x (verify_multi's predicate with the coefficients of Z_i moved across the pairing as G1
+// scalars, the t = 0 term folded into the left side). Kernel sequence, all on ctx->stream: k_vs_points (point_mode 1) + k_vs_weights + k_vs_polys + k_vs_finish
+// (kzg_sets.hip: the k + 1 scalar rows, -J, g) | the batched MSM of the rows over the proofs as an ad-hoc base vector (row 0 -> M, rows 1 .. k -> R_t; rows
+// longer than N_BATCH_MAX run row by row inside msm_g1_batch_run) | MSM T (-J over the first k points of the SRS, with the handle's window tables) | K: MSM
+// (gammas over the commitments) or g C | g1_sum of K, T, M | k_vs_pairs (the k + 1 sums affine, and -L) | pairing_product_core on (-L, R_1 .. R_k) x (g2,
+// [tau]_2 .. [tau^k]_2) | 384 GT bytes + the sums back, the bytes compared with GT one here.
+// vs_io block (KP = KEAKI_VERIFY_SETS_K_MAX + 1): [pts: C 64] [mul: g C 64] [sum_in: K 96 | T 96] [rows: M 96 | R_1 .. R_k 96 each: KP x 96] [L 96]
+//              [aff: L, R_t: KP x 64] [ps: -L, R_t: KP x 64] [qs: g2, [tau^t]_2: KP x 128] [gt 384]
+extern "C++" {
+namespace {
+struct VsLayout {
+  static constexpr size_t KP = (size_t)KEAKI_VERIFY_SETS_K_MAX + 1;
+  static constexpr size_t O_PTS = 0, O_MUL = 64, O_SUM = 128, O_ROWS = O_SUM + 192, O_L = O_ROWS + KP * 96, O_AFF = O_L + 96, O_PS = O_AFF + KP * 64,
+                          O_QS = O_PS + KP * 64, O_GT = O_QS + KP * 128, TOTAL = O_GT + 384;
+};
+struct VsArgs {
+  const keaki_hip_srs_g1* srs1;
+  const keaki_hip_srs_g2* srs2;
+  const void *com, *points, *values, *proofs, *gammas;
+  const uint64_t* omega;
+  int32_t com_stride, point_mode;
+  size_t item_stride, k, n;
+};
+// the points or values of n items as ONE span of the caller's array: up to the last element the stride names
+inline size_t sets_span(size_t n, size_t k, size_t item_stride) { return (n - 1) * item_stride + k; }
+// The ONE argument check of the set-batch calls; `out`: the output that is required at any n.
+keaki_status verify_sets_args(keaki_hip_ctx* ctx, const VsArgs& a, const char* what, const void* out) {
+  ST_TRY(kzg_modes_ok(ctx, what, a.com_stride, a.point_mode));
+  if (!out || !a.srs1 || !a.srs2) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, !out ? "ok_out" : a.srs1 ? "srs_g2" : "srs_g1");
+  if (a.k == 0 || a.k > KEAKI_VERIFY_SETS_K_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: k = %zu must be in 1 .. %d", what, a.k, (int)KEAKI_VERIFY_SETS_K_MAX);
+  if (a.item_stride < a.k) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu is less than k = %zu", what, a.item_stride, a.k);
+  if (a.point_mode && !a.omega) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: point_mode 1 needs omega", what);
+  if (a.n && (!a.com || !a.points || !a.values || !a.proofs || !a.gammas)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
+  if (a.n >= ((size_t)1 << 31) || a.n * a.k >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n * k = %zu * %zu must be < 2^31", what, a.n, a.k);
+  // the extent (n - 1) item_stride + k stays below 2^48 elements (checked without forming a product that could wrap): 32 x the extent, the bytes the host
+  // form uploads and the kernels' address arithmetic, fits 64 bits with room to spare
+  if (a.n > 1 && a.item_stride >= ((size_t)1 << 47) / (a.n - 1))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu puts the last of the %zu items 2^47 or more elements behind the first", what, a.item_stride, a.n);
+  ST_TRY(srs_holds(ctx, a.srs2, what, a.k + 1, "kzg sets: Z has %zu coefficients but the G2 SRS holds %zu points"));
+  return srs_holds(ctx, a.srs1, what, a.k, "kzg sets: I has %zu coefficients but the G1 SRS holds %zu points");
+}
+// the empty combination: every sum is the identity, and the empty product is GT one
+void verify_sets_empty(int32_t* ok_out, uint64_t* sums_out_aff, size_t k) {
+  *ok_out = 1;
+  if (sums_out_aff) memset(sums_out_aff, 0, (k + 1) * G1_AFF_BYTES);
+}
+// every workspace of a call, before its first copy or launch
+keaki_status verify_sets_reserve(keaki_hip_ctx* ctx, const VsArgs& a) {
+  ST_TRY(reserve(ctx, ctx->vs_io, VsLayout::TOTAL));
+  ST_TRY(reserve(ctx, ctx->vs_work, verify_sets_work_bytes(a.n, a.k, a.point_mode)));
+  return reserve(ctx, ctx->gp_work, pairing_product_work_bytes(a.k + 1));
+}
+// The commitment (com_stride 0) is already in its vs_io slot; a.* are device pointers but a.omega.
+keaki_status verify_sets_core(keaki_hip_ctx* ctx, const VsArgs& a, int32_t* ok_out, uint64_t* sums_out_aff) {
+  using V = VsLayout;
+  char* io = (char*)ctx->vs_io.p;
+  const size_t n = a.n, k = a.k;
+  const VsWork w = verify_sets_layout(n, k, ctx->vs_work.p);
+  ST_TRY(verify_sets_scalars_run(ctx, a.gammas, a.points, a.point_mode, a.omega, a.values, a.item_stride, k, n, w));
+  ST_TRY(msm_g1_batch_run(ctx, a.proofs, n, nullptr, 0, w.s, n, k + 1, n, io + V::O_ROWS));
+  const auto t1 = srs_tables(a.srs1);
+  ST_TRY(msm_g1_run(ctx, a.srs1->d, a.srs1->n, w.neg_j, k, io + V::O_SUM + 96, t1.first, t1.second));
+  if (a.com_stride) {
+    ST_TRY(msm_g1_run(ctx, a.com, n, a.gammas, n, io + V::O_SUM));
+  } else {
+    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, w.g, 1, io + V::O_MUL));                                   // g C
+    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
+  }
+  ST_TRY(g1_sum_run(ctx, io + V::O_SUM, 3, io + V::O_L));                                                     // K + T + M: the row M lies behind them
+  ST_TRY(verify_sets_pairs_run(ctx, io + V::O_L, io + V::O_ROWS, k, io + V::O_AFF, io + V::O_PS));
+  ST_TRY(g2_generator_to(ctx, io + V::O_QS));
+  HIP_TRY(ctx, hipMemcpyAsync(io + V::O_QS + G2_AFF_BYTES, (const char*)a.srs2->d + G2_AFF_BYTES, k * G2_AFF_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
+  ST_TRY(pairing_product_core(ctx, io + V::O_PS, io + V::O_QS, k + 1, io + V::O_GT));
+  uint8_t gt[384];
+  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, io + V::O_AFF, (k + 1) * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  ST_TRY(download(ctx, gt, io + V::O_GT, 384));
+  *ok_out = gt_bytes_are_one(gt) ? 1 : 0;
+  return KEAKI_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_kzg_verify_sets_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const void* d_com_aff,
+                                           int32_t com_stride, const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values,
+                                           size_t item_stride, size_t k, const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out,
+                                           uint64_t* sums_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_sets");
+  const VsArgs a = {srs_g1, srs_g2, d_com_aff, d_points, d_values, d_proofs_aff, d_gammas, omega, com_stride, point_mode, item_stride, k, n};
+  ST_TRY(verify_sets_args(ctx, a, "kzg_verify_sets", ok_out));
+  if (n == 0) { verify_sets_empty(ok_out, sums_out_aff, k); return KEAKI_OK; }
+  ST_TRY(verify_sets_reserve(ctx, a));
+  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->vs_io.p + VsLayout::O_PTS, d_com_aff, G1_AFF_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
+  return verify_sets_core(ctx, a, ok_out, sums_out_aff);
+}
+
+keaki_status keaki_hip_kzg_verify_sets(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                       int32_t com_stride, const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values,
+                                       size_t item_stride, size_t k, const uint64_t* proofs_aff, const uint64_t* gammas, size_t n, int32_t* ok_out,
+                                       uint64_t* sums_out_aff) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_verify_sets");
+  VsArgs a = {srs_g1, srs_g2, com_aff, points, values, proofs_aff, gammas, omega, com_stride, point_mode, item_stride, k, n};
+  ST_TRY(verify_sets_args(ctx, a, "kzg_verify_sets", ok_out));
+  if (n == 0) { verify_sets_empty(ok_out, sums_out_aff, k); return KEAKI_OK; }
+  // points (or indices) and values go up as the one span the stride names; every buffer is reserved before the first copy
+  const size_t span = sets_span(n, k, item_stride), point_bytes = span * (point_mode ? 4 : 32);
+  ST_TRY(verify_sets_reserve(ctx, a));
+  ST_TRY(reserve(ctx, ctx->io_a, n * 32));
+  ST_TRY(reserve(ctx, ctx->io_c, std::max(point_bytes, n * 32)));
+  ST_TRY(reserve(ctx, ctx->io_d, span * 32));
+  ItemStager items{ctx, com_aff, com_stride, (char*)ctx->vs_io.p + VsLayout::O_PTS, nullptr, 0, nullptr, proofs_aff, n};
+  ST_TRY(items.reserve());
+  CopyFeed feed(ctx);
+  ST_TRY(items.put(feed, ItemStager::COM));
+  ST_TRY(items.put(feed, ctx->io_c.p, points, point_bytes));
+  ST_TRY(items.put(feed, ctx->io_a.p, gammas, n * 32));
+  ST_TRY(items.put(feed, ItemStager::PROOFS));
+  ST_TRY(items.put(feed, ctx->io_d.p, values, span * 32));
+  a.com = items.d_com(); a.points = ctx->io_c.p; a.values = ctx->io_d.p; a.proofs = items.d_proofs(); a.gammas = ctx->io_a.p;
+  return feed.closed_by(verify_sets_core(ctx, a, ok_out, sums_out_aff));
 }
 
 // ---- KZG verify_each: n openings, one verdict each ---------------------------------------------------------------------------------------

@@ -31,6 +31,8 @@ constexpr int MSM_C_MAX = 19, MSM_C_SHARED_MAX = 23;
 constexpr uint32_t UPD_K_PASS = 8;
 // kzg verify_cosets (kzg_cosets.hip): Fr elements of one LDS tile (VC_TILE_ELEMS / l items) | most workgroups of the transform kernel (= partial rows the finish kernel folds)
 constexpr uint32_t VC_TILE_ELEMS = 1024, VC_MAX_BLOCKS = 1024;
+// kzg verify_sets (kzg_sets.hip): most workgroups of the polynomial kernel (= partial rows the finish kernel folds)
+constexpr uint32_t VS_MAX_BLOCKS = 1024;
 inline bool msm_c_too_wide(long long v, int max) { return v > max && v <= 24; }
 // Tuning / diagnostic switches of a context: every member but alloc_limit is an option of keaki_hip_ctx_set_option by its own name, with an
 // entry in TUNE_OPTIONS (api.hip). The environment is read ONCE, in keaki_hip_ctx_create (tune_from_env); afterwards only
@@ -66,6 +68,7 @@ struct Tuning {
   int fk_coset_group = 0;        // KEAKI_FK_COSET_GROUP / "fk_coset_group": terms per Straus group of the FK23 coset openings' pointwise kernel, 1, 2 or 4; 0 = FKC_G (fk_coset_plan.h); 1 = one ladder per term (A/B switch)
   long long fk_coset_min_lanes = 0;   // KEAKI_FK_COSET_MIN_LANES / "fk_coset_min_lanes": the pointwise launch of the FK23 coset openings splits a position's terms over lanes while it has fewer lanes than this; 0 = FKC_SPLIT_MIN_LANES
   int verify_cosets_blocks = 0;  // KEAKI_VERIFY_COSETS_BLOCKS / "verify_cosets_blocks": workgroups of verify_cosets' transform kernel, 1 .. VC_MAX_BLOCKS; 0 = automatic (three per compute unit, what its LDS holds; a test sets 2 to make a workgroup run several tiles)
+  int verify_sets_blocks = 0;    // KEAKI_VERIFY_SETS_BLOCKS / "verify_sets_blocks": workgroups of verify_sets' polynomial kernel, 1 .. VS_MAX_BLOCKS; 0 = automatic (three per compute unit, what its registers allow; a test sets 1 or 2 to make a workgroup run several tiles)
   long long coset_rows_min_lanes = 0;   // KEAKI_COSET_ROWS_MIN_LANES / "coset_rows_min_lanes": the row kernel of kzg coset_pairs splits an item's l bases over lanes while a launch has fewer lanes than this; 0 = CR_MIN_LANES (coset_rows_plan.h)
   int coset_rows_route = 0;      // KEAKI_COSET_ROWS_ROUTE / "coset_rows_route": how kzg coset_pairs sums its rows: 1 = the handle's window table over the first l SRS points, 2 = the batched MSM; 0 = by plan (coset_rows_plan.h: cr_route)
   int coset_rows_wb = 0;         // KEAKI_COSET_ROWS_WB / "coset_rows_wb": window bits of that table, 8, 10 or 13; 0 = by plan (coset_rows_plan.h: cr_wb; the switch of the width sweep)
@@ -181,6 +184,8 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf ks_io, ks_q;               // KZG set openings: points, values, Z, weights, I and the small results of a call | the quotient and the work of its passes (kzg_multi.hip)
   keaki_internal::DevBuf vc_io, vc_work;            // kzg verify_cosets: the small in/out block (VcLayout, api.hip) | s, 1 / h, -J, g and the partial rows of a call (kzg_cosets.hip: verify_cosets_layout)
   keaki_internal::DevBuf cp_work, cp_pairs, cp_in;  // kzg coset_pairs: 1 / h (n Fr), then the rows, the XYZZ sums and (route 2) the Jacobian sums of a launch chunk | verify_cosets_each: A, c and the zero values of the call; host forms: + the outputs | host forms: the values
+  keaki_internal::DevBuf vs_io, vs_work;            // kzg verify_sets: the small in/out block (VsLayout, api.hip) | the scalar rows, the weights, -J, g, the partial rows and (point_mode 1) the derived points of a call (kzg_sets.hip: verify_sets_layout)
+  keaki_internal::DevBuf gp_work;                   // pairing_product: the Miller-loop outputs of a call (384 B per pair), the partial products and the product
   keaki_internal::DevBuf fc_work;                   // FK23 coset openings (fk_coset.hip): twiddles, hat_a, the partial sums and the two transforms of a call; host forms: + coefficients and proofs
   // every DevBuf above with its memory class, kem's included (KemState::for_each_buf): what keaki_hip_ctx_destroy and _trim free and
   // keaki_hip_ctx_memory counts. A new workspace is added HERE.
@@ -188,7 +193,7 @@ struct keaki_hip_ctx {
     f(&fb_bases, 2);
     for (keaki_internal::DevBuf* b : {&digits, &hist, &offsets, &cursor, &sorted, &buckets, &acc29, &partials, &wsums, &tmp_a, &tmp_b, &tmp_c, &io_a, &io_b, &io_c,
                                       &io_d, &io_e, &perm, &heavy, &pair_ws, &fk_tab, &mb_canon, &mb_wsums, &mb_q, &fkb_pts, &fkb_fr, &em_offsets, &vb_io, &vb_s,
-                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work, &cp_work, &cp_pairs, &cp_in})
+                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work, &cp_work, &cp_pairs, &cp_in, &vs_io, &vs_work, &gp_work})
       f(b, 1);
     kem.for_each_buf(f);
   }
@@ -335,6 +340,22 @@ size_t verify_cosets_work_bytes(size_t n, uint32_t log2l);
 VcWork verify_cosets_layout(size_t n, uint32_t log2l, void* d_work);
 keaki_status verify_cosets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const void* d_values, size_t item_stride,
                                        size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, const VcWork& w);
+// kzg verify_sets (kzg_sets.hip), n items of k points each, 1 <= n, 1 <= k <= KEAKI_VERIFY_SETS_K_MAX <= item_stride, n * k < 2^31. The workspace of a call
+// (verify_sets_work_bytes) holds the k + 1 scalar rows of the batched MSM over the proofs (row t at s + 32 (t n + i): -gamma_i Z_(i,0) | gamma_i Z_(i,t) | gamma_i) |
+// the weights 1 / Z_i'(z_(i,j)) (n k Fr) | -J_t (the scalars of the MSM over [tau^t]_1) | g = sum gamma_i | the partial rows | (point_mode 1) the derived points.
+// point_mode 0: z_(i,j) = the Fr at d_points + 32 (i item_stride + j); 1: omega^idx, idx the u32 at d_points + 4 (i item_stride + j), omega a HOST pointer read
+// before the call returns. Value (i, j) is the Fr at d_values + 32 (i item_stride + j). verify_sets_pairs_run: d_sums_aff = L (d_l_jac), R_1 .. R_k (d_rows_jac[1 ..
+// k]) affine, (0, 0) for the identity; d_ps_aff = the same with -L in front (the first slots of the k + 1 pairings).
+struct VsWork { void *s, *w, *neg_j, *g, *part, *pts; };
+size_t verify_sets_work_bytes(size_t n, size_t k, int point_mode);
+VsWork verify_sets_layout(size_t n, size_t k, void* d_work);
+keaki_status verify_sets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const uint64_t* omega, const void* d_values,
+                                     size_t item_stride, size_t k, size_t n, const VsWork& w);
+keaki_status verify_sets_pairs_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_rows_jac, size_t k, void* d_sums_aff, void* d_ps_aff);
+// GT product (gt_product.hip): d_out = prod of the n Fq12 at d_in (12 Fq each, 2^256 Montgomery form, slot 2k + parity: what miller_only_run writes and
+// final_exp_only_run reads), n < 2^31; n = 0: one. d_part: gt_product_part_bytes() of workspace (may not overlap d_in or d_out).
+size_t gt_product_part_bytes();
+keaki_status gt_product_run(keaki_hip_ctx* ctx, const void* d_in, size_t n, void* d_part, void* d_out);
 // kzg coset_pairs. Fr side (kzg_cosets.hip, the PAIRS / ROWS instantiations of the kernels above): d_c_out[k] = h_k^l (Montgomery), d_hinv[k] = 1 / h_k for the n
 // items of a call | d_rows[(i << log2l) + j] = -a_(first + i, j) for the m items of a launch chunk (m * l < 2^31), canonical integers or (mont) Montgomery form.
 // Group side (kzg_coset_pairs.hip): the window table of the first l SRS points (coset_rows_plan.h: cr_table_bytes) | d_xyzz[i] = C_(first + i) + sum_j

@@ -35,6 +35,7 @@ EXPORTS = [
     "keaki_hip_kzg_aggregate", "keaki_hip_kzg_aggregate_dev", "keaki_hip_kzg_verify_multi",
     "keaki_hip_srs_g1_precompute_fk_cosets", "keaki_hip_open_fk_cosets", "keaki_hip_open_fk_cosets_poly", "keaki_hip_open_fk_cosets_poly_dev",
     "keaki_hip_kzg_verify_cosets", "keaki_hip_kzg_verify_cosets_dev",
+    "keaki_hip_kzg_verify_sets", "keaki_hip_kzg_verify_sets_dev", "keaki_hip_pairing_product", "keaki_hip_pairing_product_dev",
     "keaki_hip_srs_g1_precompute_cosets", "keaki_hip_kzg_coset_pairs", "keaki_hip_kzg_coset_pairs_dev",
     "keaki_hip_kzg_verify_cosets_each", "keaki_hip_kzg_verify_cosets_each_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
@@ -227,6 +228,10 @@ def load_library():
         lib.keaki_hip_kzg_aggregate_dev.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_kzg_verify_cosets.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_kzg_verify_cosets_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, vp, sz, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_kzg_verify_sets.argtypes = lib.keaki_hip_kzg_verify_sets_dev.argtypes = [
+            vp, vp, vp, vp, i32, vp, i32, vp, vp, sz, sz, vp, vp, sz, C.POINTER(C.c_int32), vp]
+        lib.keaki_hip_pairing_product.argtypes = [vp, vp, vp, sz, vp]
+        lib.keaki_hip_pairing_product_dev.argtypes = [vp, vp, vp, sz, vp]
         lib.keaki_hip_srs_g1_precompute_cosets.argtypes = [vp, vp, C.c_uint32]
         lib.keaki_hip_kzg_coset_pairs.argtypes = lib.keaki_hip_kzg_coset_pairs_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, sz, vp, vp]
         lib.keaki_hip_kzg_verify_cosets_each.argtypes = lib.keaki_hip_kzg_verify_cosets_each_dev.argtypes = [
@@ -756,6 +761,52 @@ class KeakiHip:
                                                           dp(d_values), int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)), _ptr(_np(inv_l)),
                                                           dp(d_proofs), dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
         return bool(ok.value), sums[:8].copy(), sums[8:].copy()
+
+    VERIFY_SETS_K_MAX = 64
+
+    def kzg_verify_sets(self, srs_g1: "SrsG1", srs_g2: "SrsG2", com_aff, points, values, k: int, proofs_aff, gammas, item_stride: int = None, omega=None):
+        """n set proofs over arbitrary sets of k points in one call (keaki_hip_kzg_verify_sets) -> (ok, sums u64[k + 1, 8]: L, then R_1 .. R_k).
+        com_aff: one affine point or n of them; points: a flat Fr array in which point (i, j) is entry i * item_stride + j (item_stride defaults to
+        k), or -- with omega, ONE Fr -- a flat uint32 array of domain indices at the same offsets (point_mode 1: z = omega^idx); values: a flat Fr
+        array addressed the same way; srs_g2 holds [tau^t]_2; gammas: n Fr the CALLER drew"""
+        pr, g, c, v = _np(proofs_aff, 8), _np(gammas, 4), _np(com_aff, 8), _np(values, 4)
+        n, k = g.shape[0], int(k)
+        stride = k if item_stride is None else int(item_stride)
+        point_mode = 0 if omega is None else 1
+        z = np.ascontiguousarray(points, np.uint32).reshape(-1) if point_mode else _np(points, 4)
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if pr.shape[0] != n or (com_stride and c.shape[0] != n):
+            raise ValueError("kzg_verify_sets: array lengths disagree")
+        if n and stride >= k >= 1 and min(z.shape[0], v.shape[0]) < (n - 1) * stride + k:
+            raise ValueError("kzg_verify_sets: the stride reaches past the %d points / %d values given" % (z.shape[0], v.shape[0]))
+        ok = C.c_int32(0); sums = np.zeros((max(k, 0) + 1, 8), np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_sets(self.ctx, srs_g1.handle, srs_g2.handle, _ptr(c), com_stride, _ptr(z), point_mode,
+                                                    _ptr(_np(omega)) if point_mode else None, _ptr(v), stride, k, _ptr(pr), _ptr(g), n, C.byref(ok), _ptr(sums)))
+        return bool(ok.value), sums
+
+    def kzg_verify_sets_dev(self, srs_g1: "SrsG1", srs_g2: "SrsG2", d_com, com_stride: int, d_points, point_mode: int, omega, d_values, item_stride: int,
+                            k: int, d_proofs, d_gammas, n: int):
+        """the same with every array resident: device pointers (ints) or torch tensors; omega stays a host array (None in point_mode 0) -> (ok, sums)
+        on the host (the call synchronises). The caller answers for the extent of d_points and d_values under the stride"""
+        dp = lambda x: C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+        ok = C.c_int32(0); sums = np.zeros((max(int(k), 0) + 1, 8), np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_verify_sets_dev(self.ctx, srs_g1.handle, srs_g2.handle, dp(d_com), int(com_stride), dp(d_points), int(point_mode),
+                                                        _ptr(_np(omega)) if omega is not None else None, dp(d_values), int(item_stride), int(k), dp(d_proofs),
+                                                        dp(d_gammas), int(n), C.byref(ok), _ptr(sums)))
+        return bool(ok.value), sums
+
+    def pairing_product(self, g1, g2) -> np.ndarray:
+        """serialize_uncompressed(prod_i e(g1[i], g2[i])): n Miller loops, a GT product tree, ONE final exponentiation -> uint8[384]"""
+        p = _np(g1, 8); q = _np(g2, 16); n = p.shape[0]
+        if q.shape[0] != n:
+            raise ValueError("pairing_product: %d G1 points but %d G2 points" % (n, q.shape[0]))
+        out = np.zeros(384, np.uint8)
+        self._ck(self.lib.keaki_hip_pairing_product(self.ctx, _ptr(p) if n else None, _ptr(q) if n else None, n, _ptr(out)))
+        return out
+
+    def pairing_product_dev(self, d_g1, d_g2, n: int, d_gt):
+        dp = lambda x: C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+        self._ck(self.lib.keaki_hip_pairing_product_dev(self.ctx, dp(d_g1), dp(d_g2), int(n), dp(d_gt)))
 
     def srs_g1_precompute_cosets(self, srs: "SrsG1", log2l: int):
         """builds the handle's window table over its first l = 2^log2l points ahead of the first kzg_coset_pairs / kzg_verify_cosets_each call

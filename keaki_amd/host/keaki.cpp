@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <thread>
 #include <sys/mman.h>
 
@@ -619,6 +620,91 @@ bool verify_cosets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commi
   return verify_cosets_flat(rng, setup, commitments.empty() ? nullptr : commitments[0].w.data(), commitments.size(), shifts.data(), false, values.data(), l, 1, l, n ? proofs[0].w.data() : nullptr, n);
 }
 
+bool verify_sets_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const void* points, const Fr* omega, const Fr* values, size_t k,
+                      const uint64_t* proofs, const Fr* gammas, size_t n) {
+  if (k < 1 || k > (size_t)KEAKI_VERIFY_SETS_K_MAX) throw SetError("verify_sets: a set holds 1 .. " + std::to_string((int)KEAKI_VERIFY_SETS_K_MAX) + " points");
+  if (k > setup.g1_pow().size()) throw SetError("verify_sets: the set is larger than the SRS");
+  if (n_coms != 1 && n_coms != n) throw SetError("verify_sets: one commitment, or one per item");
+  if (setup.g2_pow().size() <= k) throw SetError("verify_sets: this KZGSetup holds no [tau^k]_2: build it with G2 powers beyond k (setup_with_g2, from_powers_g2)");
+  const Device& dev = *setup.device();
+  if (dev.group()) throw SetError("verify_sets: single device only");
+  if (n == 0) return true;
+  int32_t ok = 0;
+  dev.check(keaki_hip_kzg_verify_sets(dev.ctx(), setup.srs(), setup.srs_g2(), coms, n_coms == 1 ? 0 : 1, points, omega ? 1 : 0, omega ? omega->l : nullptr, values[0].l,
+                                      k, k, proofs, gammas[0].l, n, &ok, nullptr));
+  return ok != 0;
+}
+namespace {
+// Items of unequal size in one call per size: `sizes[i]` = k of item i; `fill(i, dst)` appends item i's k point words (32 B each, or 4 B indices) to the
+// group's flat buffer. The gammas were drawn by the caller, one per item in index order; the verdict is the AND over the groups (every group runs).
+template <class Elem, class Fill>
+bool verify_sets_grouped(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<size_t>& sizes, Fill fill, const Fr* omega,
+                         const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs, const std::vector<Fr>& gammas) {
+  std::map<size_t, std::vector<size_t>> groups;
+  for (size_t i = 0; i < sizes.size(); i++) groups[sizes[i]].push_back(i);
+  bool all = true;
+  for (const auto& [k, items] : groups) {
+    const size_t m = items.size();
+    std::vector<Elem> pts;
+    std::vector<Fr> vals, gam(m);
+    std::vector<G1> pr(m), coms(commitments.size() == 1 ? 1 : m);
+    pts.reserve(m * k);
+    vals.reserve(m * k);
+    for (size_t t = 0; t < m; t++) {
+      const size_t i = items[t];
+      fill(i, pts);
+      vals.insert(vals.end(), values[i].begin(), values[i].end());
+      gam[t] = gammas[i];
+      pr[t] = proofs[i];
+      if (commitments.size() != 1) coms[t] = commitments[i];
+    }
+    if (commitments.size() == 1) coms[0] = commitments[0];
+    all &= verify_sets_flat(setup, coms[0].w.data(), coms.size(), pts.data(), omega, vals.data(), k, pr[0].w.data(), gam.data(), m);
+  }
+  return all;
+}
+}  // namespace
+bool verify_sets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points,
+                 const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  const size_t n = points.size();
+  if (values.size() != n || proofs.size() != n || (commitments.size() != 1 && commitments.size() != n))
+    throw SetError("verify_sets: points, values and proofs must have one entry per item, commitments one or n");
+  std::vector<Fr> gammas(n);
+  for (size_t i = 0; i < n; i++) gammas[i] = fr_rand(rng);       // one draw per item in index order
+  std::vector<size_t> sizes(n);
+  for (size_t i = 0; i < n; i++) {
+    if (points[i].empty() || points[i].size() > (size_t)KEAKI_VERIFY_SETS_K_MAX)
+      throw SetError("verify_sets: a set holds 1 .. " + std::to_string((int)KEAKI_VERIFY_SETS_K_MAX) + " points");
+    check_set("verify_sets", points[i], values[i].size());
+    sizes[i] = points[i].size();
+  }
+  if (setup.device()->group()) throw SetError("verify_sets: single device only");
+  return verify_sets_grouped<Fr>(setup, commitments, sizes, [&](size_t i, std::vector<Fr>& dst) { dst.insert(dst.end(), points[i].begin(), points[i].end()); }, nullptr,
+                                 values, proofs, gammas);
+}
+bool verify_sets_indexed(Rng& rng, const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                         const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  const size_t n = idx_rows.size();
+  if (values.size() != n || proofs.size() != n) throw SetError("vec_verify_subsets: idx_rows, values and proofs must have one entry per item");
+  std::vector<Fr> gammas(n);
+  for (size_t i = 0; i < n; i++) gammas[i] = fr_rand(rng);       // one draw per item in index order
+  std::vector<size_t> sizes(n);
+  for (size_t i = 0; i < n; i++) {
+    const std::vector<size_t>& row = idx_rows[i];
+    if (row.empty() || row.size() > (size_t)KEAKI_VERIFY_SETS_K_MAX)
+      throw SetError("vec_verify_subsets: a subset holds 1 .. " + std::to_string((int)KEAKI_VERIFY_SETS_K_MAX) + " positions");
+    if (values[i].size() != row.size()) throw SetError("vec_verify_subsets: one value per position");
+    std::vector<size_t> s(row);
+    std::sort(s.begin(), s.end());
+    if (s.back() >= domain || s.back() > 0xFFFFFFFFull) throw SetError("vec_verify_subsets: index outside the domain");
+    if (std::adjacent_find(s.begin(), s.end()) != s.end()) throw SetError("vec_verify_subsets: repeated index in a subset");
+    sizes[i] = row.size();
+  }
+  if (setup.device()->group()) throw SetError("vec_verify_subsets: single device only");
+  return verify_sets_grouped<uint32_t>(setup, {com}, sizes, [&](size_t i, std::vector<uint32_t>& dst) { for (size_t e : idx_rows[i]) dst.push_back((uint32_t)e); }, &omega,
+                                       values, proofs, gammas);
+}
+
 }  // namespace kzg
 
 // ------------------------------------------------------------------------------------------------ kem / enc
@@ -1076,6 +1162,11 @@ G1 vec_open_subset(const kzg::KZGSetup& setup, size_t domain_size, const std::ve
 }
 bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const std::vector<Fr>& values, const G1& proof) {
   return kzg::verify_set(setup, com, subset_points(domain_size, idx, "vec_verify_subset"), values, proof);
+}
+bool vec_verify_subsets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
+                        const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  const Radix2Domain dom = Radix2Domain::create(domain_size);
+  return kzg::verify_sets_indexed(rng, setup, com, dom.group_gen, dom.size, idx_rows, values, proofs);
 }
 std::vector<G1> vec_open_cosets(const kzg::KZGSetup& setup, const std::vector<Fr>& evals, size_t l) {
   if (evals.empty()) throw kzg::SetError("vec_open_cosets: no evaluations");

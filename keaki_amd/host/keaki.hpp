@@ -257,6 +257,25 @@ void coset_pairs_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms
 // drawn --, and equal to verify_set on the l points of the item. Arguments and refusals as verify_cosets_flat.
 std::vector<uint8_t> verify_cosets_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const Fr* shifts, bool roots_of_unity, const Fr* values,
                                              size_t item_stride, size_t t_stride, size_t l, const uint64_t* proofs, size_t n);
+// n set proofs over ARBITRARY point sets -- what open_set, aggregate_proofs and vec_open_subset hand out -- in one device call per set size
+// (keaki_hip_kzg_verify_sets: a batched MSM over the proofs, two or three more MSMs, k + 1 Miller loops and ONE final exponentiation whatever n is,
+// against n x verify_set). Item i: commitments[i] (or the one commitment of all items), its points[i] (1 .. KEAKI_VERIFY_SETS_K_MAX of them, distinct),
+// values[i] (one per point), proofs[i]. Draws one Fr::rand per item in index order BEFORE anything else is looked at per group; items of unequal size
+// are grouped by size into one call each (the device call takes one k), and the verdict is the AND of the groups'. All items valid: always true; one
+// invalid: false except with probability <= 1 / r. Refuses (SetError): a repeated point within an item -- the device library does not look --, an empty
+// or too large set, array sizes that disagree, a setup whose G2 powers do not reach the largest set (g2_pow().size() > k), a set larger than the SRS,
+// and a device group (single device only). A rejected batch says nothing about WHICH item: verify_set per item does.
+bool verify_sets(Rng& rng, const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points,
+                 const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
+// ONE group of the above on contiguous buffers: n items of k points, point (i, j) = points[i * k + j] -- or, with `omega`, the u32 domain index at that
+// place (z = omega^index, derived on the device) --, value (i, j) = values[i * k + j], the gammas GIVEN (the grouping layers draw them). Refuses what
+// can be told without looking at the points: k, n_coms, the G2 powers, the SRS, a device group.
+bool verify_sets_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const void* points, const Fr* omega, const Fr* values, size_t k,
+                      const uint64_t* proofs, const Fr* gammas, size_t n);
+// verify_sets for ONE commitment with the points given as indices into the powers of `omega` (an element of order `domain`): what vec::vec_verify_subsets
+// is made of. Draws, grouping and refusals as verify_sets; also refuses an index >= domain and a repeated index within an item.
+bool verify_sets_indexed(Rng& rng, const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                         const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
 
 }  // namespace kzg
 
@@ -341,6 +360,12 @@ size_t vec_verify_each_flat(const kzg::KZGSetup& setup, const G1& com, const Fr*
 // The holder of vec_commit's d proofs aggregates the k of them at idx (distinct, < domain_size) into one set proof, without the vector.
 G1 vec_open_subset(const kzg::KZGSetup& setup, size_t domain_size, const std::vector<size_t>& idx, const std::vector<G1>& proofs);
 bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<size_t>& idx, const std::vector<Fr>& values, const G1& proof);
+// n subset proofs of ONE committed vector in one device call per subset size (kzg::verify_sets_flat with the indices as they are: the points omega^idx
+// are derived on the device). Item i: the positions idx_rows[i] (distinct, < the domain), values[i] (one per position), proofs[i]. One draw per item in
+// index order; subsets of unequal size are grouped by size. Refuses (kzg::SetError) a repeated index within an item, an index outside the domain,
+// sizes that disagree, and what kzg::verify_sets refuses about the setup and the device.
+bool vec_verify_subsets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
+                        const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
 // For the holder of the vector who wants EVERY block proof: evals are the evaluations over Radix2Domain::create(evals.size()) (what vec_commit
 // commits to: the vector, its padding scalar, zeros); the inverse transform, then kzg::open_fk_cosets: r = size / l proofs, proof i for the
 // positions vec_coset_indices(size, l, i) = {i + t r : t < l} -- the index list vec_verify_subset and vec_encrypt_subset_batch take.

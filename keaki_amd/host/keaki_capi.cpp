@@ -317,6 +317,38 @@ int keaki_host_verify_cosets(void* rng, void* s, const uint64_t* coms, size_t n_
     return 0;
   });
 }
+// set batch verification (include/keaki_hip.h: keaki_hip_kzg_verify_sets). Item i has sizes[i] points; points / values (idx / values): the items' rows one
+// behind the other (sum of sizes entries); n_coms: 1 or n; the gammas are drawn from rng, one per item
+int keaki_host_verify_sets(void* rng, void* s, const uint64_t* coms, size_t n_coms, const uint64_t* sizes, const uint64_t* points, const uint64_t* values,
+                           const uint64_t* proofs, size_t n, int* out_ok) {
+  return guard([&] {
+    std::vector<G1> c(n_coms), pr(n);
+    std::vector<std::vector<Fr>> z(n), y(n);
+    for (size_t i = 0; i < n_coms; i++) c[i] = g1_of(coms + 8 * i);
+    for (size_t i = 0, at = 0; i < n; at += sizes[i], i++) {
+      pr[i] = g1_of(proofs + 8 * i);
+      z[i] = frs_of(points + 4 * at, sizes[i]);
+      y[i] = frs_of(values + 4 * at, sizes[i]);
+    }
+    *out_ok = kzg::verify_sets(*(Rng*)rng, ((Setup*)s)->s, c, z, y, pr) ? 1 : 0;
+    return 0;
+  });
+}
+int keaki_host_vec_verify_subsets(void* rng, void* s, const uint64_t* com, size_t domain_size, const uint64_t* sizes, const uint64_t* idx, const uint64_t* values,
+                                  const uint64_t* proofs, size_t n, int* out_ok) {
+  return guard([&] {
+    std::vector<G1> pr(n);
+    std::vector<std::vector<size_t>> rows(n);
+    std::vector<std::vector<Fr>> y(n);
+    for (size_t i = 0, at = 0; i < n; at += sizes[i], i++) {
+      pr[i] = g1_of(proofs + 8 * i);
+      rows[i] = idx_of(idx + at, sizes[i]);
+      y[i] = frs_of(values + 4 * at, sizes[i]);
+    }
+    *out_ok = vec::vec_verify_subsets(*(Rng*)rng, ((Setup*)s)->s, g1_of(com), domain_size, rows, y, pr) ? 1 : 0;
+    return 0;
+  });
+}
 // all cosets of a vector: evals n <= domain Fr (zero-padded to the next power of two d), proofs d / l affine points
 int keaki_host_vec_verify_cosets(void* rng, void* s, const uint64_t* com, const uint64_t* evals, size_t n, size_t l, const uint64_t* proofs, size_t n_proofs,
                                  int* out_ok) {

@@ -512,6 +512,47 @@ def verify_cosets(rng: "Rng", setup: KZGSetup, commitments, shifts, l: int, valu
     return bool(ok.value)
 
 
+def _ragged(rows, width):
+    """rows of unequal length one behind the other -> (sizes u64[n], the flat array)"""
+    rows = [np.ascontiguousarray(r, np.uint64).reshape(-1, width) if width else np.ascontiguousarray(r, np.uint64).reshape(-1) for r in rows]
+    sizes = np.array([r.shape[0] for r in rows], np.uint64)
+    flat = np.concatenate(rows) if rows else np.zeros((0, width) if width else 0, np.uint64)
+    return sizes, np.ascontiguousarray(flat)
+
+
+def verify_sets(rng: "Rng", setup: KZGSetup, commitments, points, values, proofs) -> bool:
+    """kzg::verify_sets: n set proofs over ARBITRARY point sets in one device call per set size. points, values: n rows (row i: the k_i <= 64 distinct points
+    of item i, and one value per point); the rows may differ in length (the host layer groups them by length). One gamma per item is drawn from `rng` in
+    index order. commitments: one G1 (shared) or n. A repeated point within an item, sizes that disagree, a setup whose G2 powers do not reach the
+    largest set, a device group: SetError"""
+    coms = np.ascontiguousarray(_u64(commitments, 8)); pr = np.ascontiguousarray(_u64(proofs, 8)); n = pr.shape[0]
+    zs, z = _ragged(points, 4)
+    ys, y = _ragged(values, 4)
+    if zs.shape[0] != n or ys.shape[0] != n or coms.shape[0] not in (1, n):
+        raise SetError("verify_sets: points, values and proofs must have one entry per item, commitments one or n")
+    if not np.array_equal(zs, ys):
+        raise SetError("verify_sets: one value per point")
+    ok = C.c_int(0)
+    _ck(_lib().keaki_host_verify_sets(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(zs), _p(z), _p(y), _p(pr), C.c_size_t(n), C.byref(ok)))
+    return bool(ok.value)
+
+
+def vec_verify_subsets(rng: "Rng", setup: KZGSetup, com, domain_size: int, idx_rows, values, proofs) -> bool:
+    """vec::vec_verify_subsets: n subset proofs (vec_open_subset) of ONE committed vector in one device call per subset size. idx_rows, values: n rows
+    (positions < the domain, distinct within a row; one value per position). One gamma per item is drawn from `rng` in index order. A repeated index,
+    an index outside the domain, sizes that disagree, a setup without enough G2 powers, a device group: SetError"""
+    pr = np.ascontiguousarray(_u64(proofs, 8)); n = pr.shape[0]
+    ks, ix = _ragged(idx_rows, 0)
+    ys, y = _ragged(values, 4)
+    if ks.shape[0] != n or ys.shape[0] != n:
+        raise SetError("vec_verify_subsets: idx_rows, values and proofs must have one entry per item")
+    if not np.array_equal(ks, ys):
+        raise SetError("vec_verify_subsets: one value per position")
+    ok = C.c_int(0)
+    _ck(_lib().keaki_host_vec_verify_subsets(rng.h, setup.h, _p(_u64(com)), C.c_size_t(domain_size), _p(ks), _p(ix), _p(y), _p(pr), C.c_size_t(n), C.byref(ok)))
+    return bool(ok.value)
+
+
 def vec_verify_cosets(rng: "Rng", setup: KZGSetup, com, evals, l: int, proofs) -> bool:
     """vec::vec_verify_cosets: are the size / l proofs of vec_open_cosets(evals, l) the block proofs of `com`? One device call over the evaluations
     in domain order; one gamma per coset is drawn from `rng`"""

@@ -187,6 +187,18 @@ extern "C" {
                                            d_tau_l_g2_aff: *const c_void, d_points: *const c_void, point_mode: i32, d_values: *const c_void,
                                            item_stride: usize, t_stride: usize, log2l: u32, omega_l_inv: *const u64, inv_l: *const u64,
                                            d_proofs_aff: *const c_void, d_gammas: *const c_void, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
+    // n set proofs over ARBITRARY sets of k <= 64 points: e(-L, g2) prod_t e(R_t, [tau^t]_2) == 1; point / value (i, j) at element i item_stride + j (points: Fr,
+    // or with point_mode 1 u32 domain indices and ONE Fr omega); sums_out_aff: (k + 1) x u64[8] = L, R_1 .. R_k or null
+    pub fn keaki_hip_kzg_verify_sets(ctx: *mut keaki_hip_ctx, srs_g1: *const keaki_hip_srs_g1, srs_g2: *const keaki_hip_srs_g2, com_aff: *const u64,
+                                     com_stride: i32, points: *const c_void, point_mode: i32, omega: *const u64, values: *const u64, item_stride: usize,
+                                     k: usize, proofs_aff: *const u64, gammas: *const u64, n: usize, ok_out: *mut i32, sums_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_sets_dev(ctx: *mut keaki_hip_ctx, srs_g1: *const keaki_hip_srs_g1, srs_g2: *const keaki_hip_srs_g2, d_com_aff: *const c_void,
+                                         com_stride: i32, d_points: *const c_void, point_mode: i32, omega: *const u64, d_values: *const c_void,
+                                         item_stride: usize, k: usize, d_proofs_aff: *const c_void, d_gammas: *const c_void, n: usize, ok_out: *mut i32,
+                                         sums_out_aff: *mut u64) -> keaki_status;
+    // gt_out = serialize(prod_i e(g1[i], g2[i])): n Miller loops, a GT product tree, ONE final exponentiation
+    pub fn keaki_hip_pairing_product(ctx: *mut keaki_hip_ctx, g1_aff: *const u64, g2_aff: *const u64, n: usize, gt_out: *mut u8) -> keaki_status;
+    pub fn keaki_hip_pairing_product_dev(ctx: *mut keaki_hip_ctx, d_g1_aff: *const c_void, d_g2_aff: *const c_void, n: usize, d_gt_out: *mut c_void) -> keaki_status;
     // the per-item points of the coset check, n cosets per call: lhs_out_aff[k] = C_k - [I_k(tau)]_1 (n x u64[8]), c_out[k] = h_k^l (n x u64[4], Montgomery);
     // the handle's window table over its first l points is built on first use or by _precompute_cosets
     pub fn keaki_hip_srs_g1_precompute_cosets(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g1, log2l: u32) -> keaki_status;

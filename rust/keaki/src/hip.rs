@@ -526,6 +526,36 @@ pub fn verify_cosets_each(srs: &HipSrs, commitments: &[G1Projective], tau_l_g2: 
     status.iter().map(|&s| s == 0).collect()
 }
 
+/// n set proofs over ARBITRARY point sets of one size in one call (`keaki_hip_kzg_verify_sets`): item i has the `k` distinct points `points[i * k ..]`
+/// (1 ..= 64 of them) with the values `values[i * k ..]`; `e(-L, g2) * prod_t e(R_t, [tau^t]_2) == 1` with L = sum gamma_i C_i - sum_t J_t [tau^t]_1 -
+/// sum (gamma_i Z_(i,0)) proof_i and R_t = sum (gamma_i Z_(i,t)) proof_i, Z_i the vanishing polynomial and I_i (in J) the interpolant of item i.
+/// `g2_powers`: `[tau^t]_2` for t = 0 ..= k at least (`KZGSetup::g2_aff`). `commitments`: one for all items or one per item. `gammas`: drawn by the CALLER,
+/// one `Fr::rand` per item in index order; the soundness bound 1/r needs them independent, uniform and unknown to whoever made the proofs. A repeated
+/// point within an item is refused here (the library does not look). Items of another size go into another call. Single-GPU device.
+pub fn verify_sets(srs: &HipSrs, g2_powers: &[G2Affine], commitments: &[G1Projective], points: &[Fr], k: usize, values: &[Fr], proofs: &[G1Projective],
+                   gammas: &[Fr]) -> bool {
+    let dev = Device::global();
+    let n = gammas.len();
+    assert!(dev.group.is_null() && k >= 1 && k <= 64 && k <= srs.len() && g2_powers.len() > k);
+    assert!(points.len() == n * k && values.len() == n * k && proofs.len() == n && (commitments.len() == 1 || commitments.len() == n));
+    points.chunks(k).for_each(assert_distinct);
+    let flat = |v: &[G1Projective]| -> Vec<u64> { G1Projective::normalize_batch(v).iter().flat_map(|p| g1_words(p)).collect() };
+    let (c, p) = (flat(commitments), flat(proofs));
+    let g2: Vec<u64> = g2_powers[..=k].iter().flat_map(|q| g2_words(q)).collect();
+    let mut srs_g2 = core::ptr::null_mut();
+    dev.check(unsafe { sys::keaki_hip_srs_g2_upload(dev.ctx, g2.as_ptr(), k + 1, &mut srs_g2) }, "srs_g2_upload");
+    let mut ok = 0i32;
+    let st = unsafe {
+        sys::keaki_hip_kzg_verify_sets(
+            dev.ctx, srs.srs(), srs_g2, c.as_ptr(), if commitments.len() == 1 { 0 } else { 1 }, fr_ptr(points) as *const core::ffi::c_void, 0, core::ptr::null(),
+            fr_ptr(values), k, k, p.as_ptr(), fr_ptr(gammas), n, &mut ok, core::ptr::null_mut(),
+        )
+    };
+    unsafe { sys::keaki_hip_srs_g2_free(dev.ctx, srs_g2) };
+    dev.check(st, "kzg_verify_sets");
+    ok != 0
+}
+
 /// One verdict per opening (`keaki_hip_kzg_verify_each`): item i is valid iff `e(C_i - y_i g1 + z_i proof_i, g2) * e(-proof_i, [tau]_2) == 1`,
 /// the predicate of `verify` with `z_i proof_i` moved across the pairing. Arguments as [`verify_batch`], without gammas: the verdict is exact.
 /// Returns `true` for every valid item.
