@@ -117,7 +117,11 @@ const char* keaki_hip_version(void);
  * "coset_rows_min_lanes" (keaki_hip_kzg_coset_pairs: the row kernel splits an item's l bases over lanes while a launch has fewer lanes than this: 1 .. 2^31,
  * 0 = the built-in 131,072), "coset_rows_route" (how that call sums its rows: 1 = the handle's window table over the first l SRS points, 2 = the batched
  * MSM, 0 = by plan), "coset_rows_wb" (window bits of that table: 8, 10 or 13, 0 = by plan -- the switch of the width sweep; a table the allocator refuses
- * means route 2); results do not depend on any of the three; other values are refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
+ * means route 2); results do not depend on any of the three; other values are refused with KEAKI_ERR_BAD_ARG, in the environment ignored),
+ * "set_rows_wb" (keaki_hip_kzg_set_pairs: window bits of the G2 handle's table, 8, 10 or 13, 0 = by plan), "set_rows_min_lanes" (its G2 row kernel splits an
+ * item's k bases over lanes while a launch has fewer lanes than this: 1 .. 2^31, 0 = the built-in 65,536), "set_each_route" (keaki_hip_kzg_verify_sets_each:
+ * 1 = the fused pairing kernel, 2 = two Miller loops per item through the existing kernels, 0 = by plan, which is 2); results do not depend on any of the three; other values
+ * are refused with KEAKI_ERR_BAD_ARG, in the environment ignored).
  * What the library does with HOST memory of the caller, and its off switches (round 5):
  *   "host_prefault" (default 1): while the kernels of a host-array call run, the library first-touches the caller's OUTPUT arrays (writes a zero
  *       into one byte per 4 KB page, the whole range being overwritten by the download that follows; outputs >= 1 MB only) and asks for transparent
@@ -592,8 +596,9 @@ keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip
  *              sums_out_aff stay HOST pointers, so this form synchronises as well. Workspace: 32 (2 k + 1) B per item (32 (3 k + 1) in point_mode 1) + 32
  *              (k + 1) B per tile of at most 1,024 + 24 KB + the batched MSM's, grow-only, counted in keaki_hip_ctx_memory out4[1], released by
  *              keaki_hip_ctx_trim.
- *   out of scope  a per-item verdict (a verify_sets_each); k > 64; a G2-side route for few items with large sets; the multi-GPU form (the host layers refuse a
- *              device group). Items of unequal k are grouped by k, one call per size, by the host layers.
+ *   out of scope  k > 64; a G2-side route for few items with large sets; the multi-GPU form (the host layers refuse a
+ *              device group). Items of unequal k are grouped by k, one call per size, by the host layers. The per-item verdict is
+ *              keaki_hip_kzg_verify_sets_each, below.
  *   numbers    (MI355X, medians of alternating rounds in one process: profiles/verify_sets_times.txt, bench_tools/bench_verify_sets.py) resident / from host
  *              arrays, one commitment per item, k = 2 / 8 / 64: n = 2 6.6 / 6.7 / 8.3 ms, n = 64 6.4 / 6.6 / 7.9, n = 4,096 6.4 / 6.9 / 11.1 (host 6.6 / 7.0 / 11.4),
  *              n = 2^16 10.3 / 22.5 / 153.7 (host 10.6 / 23.4 / 158.6), n = 2^20 15.6 / 41.2 ms at k = 2 / 8 (host 21.0 / 53.8). Against (a) the only route before, n
@@ -697,6 +702,88 @@ keaki_status keaki_hip_kzg_verify_cosets_each_dev(keaki_hip_ctx* ctx, keaki_hip_
                                                   size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
                                                   const uint64_t* inv_l, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
                                                   uint64_t* first_bad, void* d_lhs_out_aff);
+
+/* ---- KZG set pairs and per-set verdicts: the per-item side of the set check over ARBITRARY point sets, all n items in one call ------------------
+ * verify_sets answers "are all n set proofs valid?"; these calls give the PER-ITEM points of the same check
+ *     e(A_i, g2) == e(pi_i, Z2_i)        A_i = C_i - [I_i(tau)]_1  (G1)        Z2_i = [Z_i(tau)]_2  (G2)
+ * (Z_i, I_i the vanishing polynomial and the interpolant of item i, as for keaki_hip_kzg_verify_sets): a verdict per item, and encryption to the claimed
+ * values of every item (ct_i = r_i Z2_i, key_i = KDF(e(r_i A_i, g2)): keaki_hip_encap_multi / _encrypt_multi with n groups of one item, coms := A, points =
+ * values = 0, then keaki_hip_g2_mul_batch over the Z2_i).
+ *
+ * keaki_hip_kzg_set_pairs: lhs_out_aff[i] = A_i (affine G1, u64[8]), z2_out_aff[i] = Z2_i (affine G2, u64[16]); (0,0) = identity in both.
+ *   com_aff, com_stride, points, point_mode, omega, values, item_stride, k, n, the limits (k <= KEAKI_VERIFY_SETS_K_MAX, n k < 2^31) and the repeated-point rule
+ *   are keaki_hip_kzg_verify_sets'. srs_g1 is read at its points 0 .. k - 1, srs_g2 at 0 .. k; both handles are non-const: each keeps a window table that is built
+ *   on first use (srs_g1: the table of keaki_hip_kzg_coset_pairs at l = kp, the power of two >= k; srs_g2: below).
+ *   equalities lhs_out_aff[i] followed by z2_out_aff[i] is byte for byte the pair_out_aff of keaki_hip_kzg_verify_multi on item i (affine points are unique
+ *              encodings). At k = 1: A_i = C_i - y_i g1, Z2_i = [tau]_2 - z_i g2.
+ *   identities an identity commitment and zero values are ordinary inputs; A_i can be the identity, and Z2_i too (tau inside the point set: reachable with a
+ *              structured SRS).
+ *   errors     those of keaki_hip_kzg_verify_sets: a null required pointer, k = 0 or k > KEAKI_VERIFY_SETS_K_MAX, item_stride < k, a flag outside {0, 1},
+ *              point_mode 1 without omega, n k >= 2^31, extents of 2^47 -> KEAKI_ERR_BAD_ARG; k + 1 > len(srs_g2) or k > len(srs_g1) -> KEAKI_ERR_TOO_LARGE; a
+ *              refused workspace, or a G2 table refused at all three widths -> KEAKI_ERR_OOM. Nothing is written in any of these cases, nothing is launched,
+ *              and the context stays usable. n = 0: KEAKI_OK, nothing is written.
+ *   kernels    per launch chunk (csrc/set_rows_plan.h). Fr side, csrc/kzg_sets.hip: k_vs_points (point_mode 1), k_vs_weights, then the rows instantiation of
+ *              k_vs_polys (no gammas, no partial sums, no k_vs_finish): -I_(i,t) padded with zeros to kp at (i << log2 kp) + t, and Z_(i,t), t < k (Z is monic:
+ *              the coefficient of X^k is not stored). G1 side: the group side of keaki_hip_kzg_coset_pairs at log2l = log2 kp -- k_cp_rows over the G1 handle's
+ *              window table (zero digits are skipped: the padding costs loads only), k_cp_affine; the batched MSM + k_cp_join when that table is refused or
+ *              kp > len(srs_g1) >= k; "coset_rows_route" / "coset_rows_wb" / "coset_rows_min_lanes" keep their meaning. G2 side, csrc/kzg_set_pairs.hip:
+ *              k_sp_rows_g2 -- a lane owns (item, slice of the k bases), walks the signed wb-bit digits of its Z coefficients (carry included) and adds the
+ *              entries of the G2 handle's window table T2[j][w][d] = d 2^(wb w) [tau^j]_2 (affine, 128 B, base-major: a table of kb bases serves every k <=
+ *              kb) into a lazy-limb XYZZ accumulator with the complete addition (equal operands double, opposite ones give the identity and the walk goes
+ *              on, identity entries are skipped); the S slices of an item meet by cross-lane exchange in a wave, slice 0 adds [tau^k]_2. No doublings: a row
+ *              is k x ceil(254 / wb) G2 additions. k_sp_affine_g2: four items per lane under ONE Fq2 inversion.
+ *   table      built on first use or by keaki_hip_srs_g2_precompute_sets(ctx, srs, k_max) (k_max bases at the plan's width), cached in the G2 handle until a
+ *              larger k or another width arrives, counted in keaki_hip_ctx_memory out4[0], freed with the handle. With "set_rows_wb" = 0 a resident table that
+ *              covers k is used at the width it HAS: a handle first used at k = 64 (10 bits) or under a forced width keeps that width for smaller k, so
+ *              the plan's width holds for the first k of a handle (or the k_max of _precompute_sets), not for every later call. Width: "set_rows_wb" (8, 10 or 13), 0 = by plan
+ *              (csrc/set_rows_plan.h: the widest of 13 / 10 / 8 bits whose table stays under 512 MiB: 10.5 MB / 1.7 MB / 0.53 MB per base, so 13 bits up to
+ *              k = 51 and 10 bits beyond; the wider table won at every measured shape -- see that header). A refused table falls to the next narrower width,
+ *              then KEAKI_ERR_OOM. "set_rows_min_lanes": the slice threshold (1 .. 2^31, 0 = the built-in 65,536, measured). Results do not depend on either; other values are refused with KEAKI_ERR_BAD_ARG, in the
+ *              environment ignored.
+ *   host form  one upload in front (the spans of points and values the stride names, through the family's stager), the kernels, one download; returns only
+ *              when nothing reads or writes caller memory, also on failure.
+ *   _dev       device pointers (16-byte aligned; 4-byte for the indices of point_mode 1); omega stays a HOST pointer, read before the call returns.
+ *              Asynchronous on the context's stream. Workspace: per item of a launch chunk 32 (kp + 2 k) B (+ 32 k in point_mode 1) + 384 B (+ 96 B on the MSM
+ *              route), grow-only, counted in out4[1], released by keaki_hip_ctx_trim.
+ *
+ * keaki_hip_kzg_verify_sets_each: status[i] = 0 <=> keaki_hip_kzg_verify_multi accepts item i; *n_bad = 0 <=> keaki_hip_kzg_verify_sets accepts (valid items, any
+ * gammas). At k = 1 the bytes are keaki_hip_kzg_verify_each's. With R_i = (pi_i is the identity or Z2_i is the identity): if A_i or R_i is an identity, the
+ * item is valid iff both are; no arithmetic decides such an item. A bad item never fails the call. lhs_out_aff / z2_out_aff (or NULL): the pairs the verdicts
+ * were computed from. n = 0: *n_bad = 0, *first_bad = UINT64_MAX, nothing else is written. Errors: those above; status, n_bad required.
+ *   kernels    set_pairs into the workspace, then per launch chunk (as keaki_hip_kzg_verify_each: at most 2^16 items, halved on a refused reservation down
+ *              to 32) the verdicts, then k_ve_count. "set_each_route" = 1: csrc/kzg_set_each_pair.hip, k_pairing2v, one lane pair per item: a Miller
+ *              step squares f ONCE, multiplies by the tabulated line of g2 at A_i and by the on-the-fly line of the running point T (from Z2_i) at -pi_i -- 64
+ *              squarings for the two pairings together -- then ONE final exponentiation and the comparison with one; one status byte. = 2: existing kernels
+ *              -- the Miller loops of (A_i, g2) and (-pi_i, Z2_i) in one launch, a pairwise product (csrc/gt_product.hip: k_gt_pair_product), the final
+ *              exponentiation, a comparison of the 384 bytes with GT one (k_sp_status). The two routes agree to the byte. 0 = by plan, which is route 2 at
+ *              every n: MEASURED, the fused kernel lost at every size but one (n = 32,768) and by 23 % at n = 2^20; it stays as the A/B form.
+ *   _dev       n_bad, first_bad and omega stay HOST pointers: this form synchronises, like keaki_hip_kzg_verify_each_dev.
+ *   out of scope  a C-ABI encapsulation to sets (compose as above); k > 64; device groups and the multi-GPU form.
+ *   numbers    (MI355X, medians of alternating rounds in one process: profiles/set_each_times.txt, bench_tools/bench_set_each.py) one commitment per item, k = 2 /
+ *              8 / 64. set_pairs resident: n = 2 1.00 / 1.31 / 3.11 ms, n = 64 1.23 / 1.34 / 3.00, n = 4,096 1.13 / 1.39 / 5.35, n = 2^16 1.61 / 4.53 / 54.8 (from host
+ *              arrays 2.44 / 5.95 / 60.7). verify_sets_each resident, by plan: n = 2 2.5 / 2.9 / 4.4 ms, n = 64 2.7 / 2.9 / 4.5, n = 4,096 4.8 / 4.9 / 8.8, n = 2^16 16.4 /
+ *              18.3 / 68.2. Against n calls of keaki_hip_kzg_verify_multi (7.7 - 8.7 ms each; 64 timed, EXTRAPOLATED beyond): it wins at every shape, 3.6 - 6.7 x at
+ *              n = 2, 109 - 207 x at n = 64, 7,400 - 34,000 x at n = 2^16. Against keaki_hip_kzg_verify_sets_dev on the same items (ONE verdict, the floor) it
+ *              is FASTER up to n = 4,096 (0.39 - 0.79 of its time: that call's k + 1 Miller loops and MSMs have a floor of 6.4 ms) and at n = 2^16, k = 8 / 64
+ *              (0.82 / 0.45), and LOSES at n = 2^16, k = 2 (1.6 x). Against keaki_hip_kzg_verify_cosets_each_dev on coset-shaped inputs it is faster up to
+ *              n = 64 and at n = 4,096, k <= 8 (0.39 - 0.76) and LOSES at n = 4,096, k = 64 (1.20 x) and at n = 2^16 (1.27 / 1.33 / 3.0 x): Z2_i costs k x 20 - 26
+ *              G2 additions per item where the cosets share ONE G2 point. Encryption to sets (host mirror: enc::encrypt_sets, vec::vec_encrypt_subsets) is
+ *              tested, NOT measured. */
+keaki_status keaki_hip_srs_g2_precompute_sets(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t k_max);
+keaki_status keaki_hip_kzg_set_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff, int32_t com_stride,
+                                     const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values, size_t item_stride, size_t k,
+                                     size_t n, uint64_t* lhs_out_aff, uint64_t* z2_out_aff);
+keaki_status keaki_hip_kzg_set_pairs_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const void* d_com_aff, int32_t com_stride,
+                                         const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values, size_t item_stride, size_t k,
+                                         size_t n, void* d_lhs_out_aff, void* d_z2_out_aff);
+keaki_status keaki_hip_kzg_verify_sets_each(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                            int32_t com_stride, const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values,
+                                            size_t item_stride, size_t k, const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad,
+                                            uint64_t* first_bad, uint64_t* lhs_out_aff, uint64_t* z2_out_aff);
+keaki_status keaki_hip_kzg_verify_sets_each_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const void* d_com_aff,
+                                                int32_t com_stride, const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values,
+                                                size_t item_stride, size_t k, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
+                                                uint64_t* first_bad, void* d_lhs_out_aff, void* d_z2_out_aff);
 
 /* ---- KZG verify_each: one verdict per opening, n openings in one call ---------------------------------------------------
  * verify_batch answers "are all n openings valid?"; this call says WHICH are not. Per item, by bilinearity (z_i proof_i moved across the

@@ -6,6 +6,7 @@
 #include "encap_multi_plan.h"
 #include "fk_coset_plan.h"
 #include "coset_rows_plan.h"
+#include "set_rows_plan.h"
 
 #include <algorithm>
 #include <cctype>
@@ -42,13 +43,15 @@ struct SrsCache {
 // fk: FK23, hat_s = DFT_2d(reversed SRS), 2d Jacobian points, key log2d | upd: vec_update, the update tables of d (vec_update.hip: a | u | omega_d^-i |
 // 1 / (omega_d^t - 1)), key log2d | fkc: FK23 coset openings, the l transforms hat_s_j = DFT_2r(row j of the SRS, reversed), 2d Jacobian points
 // (fk_coset.hip), key (log2d, log2l) | cr: kzg coset_pairs, the window table over the first l points (kzg_coset_pairs.hip, coset_rows_plan.h), key (log2l, wb).
-// The four are independent of each other; a new cache is added HERE (srs_free walks them).
+// The four are independent of each other; a new cache is added HERE (srs_free walks them). The G2 handle has one: sr, kzg set_pairs, the window table over
+// the first kb points (kzg_set_pairs.hip, set_rows_plan.h), key (kb, wb); base-major, so it serves every k <= kb.
 struct keaki_hip_srs_g1 : SrsHandle {
   SrsCache fk, upd, fkc, cr;
   template <class F> void for_each_cache(F&& f) { for (SrsCache* c : {&fk, &upd, &fkc, &cr}) f(*c); }
 };
 struct keaki_hip_srs_g2 : SrsHandle {
-  template <class F> void for_each_cache(F&&) {}
+  SrsCache sr;
+  template <class F> void for_each_cache(F&& f) { f(sr); }
 };
 
 #include <dlfcn.h>
@@ -272,12 +275,12 @@ keaki_status srs_holds(keaki_hip_ctx* ctx, const SrsHandle* srs, const char* wha
   if (k > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, too_short, k, srs->n);
   return KEAKI_OK;
 }
-// The ONE owner of every cache of a G1 handle: afterwards c.p is the table of key (k0, k1), `bytes` long, that `build(c.p)` enqueues on the
+// The ONE owner of every cache of a handle: afterwards c.p is the table of key (k0, k1), `bytes` long, that `build(c.p)` enqueues on the
 // context's stream; the caller holds srs->mu. A table of another key is dropped first (after the stream's work that may read it), the new
 // one is allocated through dev_alloc and named only once its build is enqueued in full; on every exit -- a refused allocation
 // included -- c.bytes and the `tables` count of the handle's accounting context (srs->acct, as for the window tables) say what c.p holds.
-template <class Build>
-keaki_status srs_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, SrsCache& c, int k0, int k1, size_t bytes, Build build) {
+template <class H, class Build>
+keaki_status srs_cache_ensure(keaki_hip_ctx* ctx, H* srs, SrsCache& c, int k0, int k1, size_t bytes, Build build) {
   if (c.holds(k0, k1)) return KEAKI_OK;
   auto book = [&](size_t now) {
     const size_t before = c.bytes;
@@ -698,6 +701,21 @@ bool coset_rows_wb_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
   if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: coset_rows_wb = %lld must be 8, 10 or 13 (0 = by plan)", v);
   return true;
 }
+bool set_rows_wb_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v == 0 || v == 8 || v == 10 || v == 13) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: set_rows_wb = %lld must be 8, 10 or 13 (0 = by plan)", v);
+  return true;
+}
+bool set_rows_min_lanes_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= ((long long)1 << 31)) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: set_rows_min_lanes = %lld out of range (1 .. 2^31; 0 = %u)", v, SR_MIN_LANES);
+  return true;
+}
+bool set_each_route_refuses(keaki_hip_ctx* ctx, const char*, long long v) {
+  if (v >= 0 && v <= 2) return false;
+  if (ctx) fail(ctx, KEAKI_ERR_BAD_ARG, "ctx_set_option: set_each_route = %lld must be 0 (by plan), 1 (the fused pairing kernel) or 2 (two Miller loops per item)", v);
+  return true;
+}
 #define TUNE_OPTION(member, ...) TuneOption{#member, assign_member<&Tuning::member>, __VA_ARGS__}
 const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(msm_c, msm_c_refuses<MSM_C_MAX>), TUNE_OPTION(msm_c_shared, msm_c_refuses<MSM_C_SHARED_MAX>), TUNE_OPTION(msm_short_tables),
@@ -711,6 +729,7 @@ const TuneOption TUNE_OPTIONS[] = {
     TUNE_OPTION(verify_cosets_blocks, verify_cosets_blocks_refuses), TUNE_OPTION(verify_sets_blocks, verify_sets_blocks_refuses),
     TUNE_OPTION(coset_rows_min_lanes, coset_rows_min_lanes_refuses), TUNE_OPTION(coset_rows_route, coset_rows_route_refuses),
     TUNE_OPTION(coset_rows_wb, coset_rows_wb_refuses),
+    TUNE_OPTION(set_rows_wb, set_rows_wb_refuses), TUNE_OPTION(set_rows_min_lanes, set_rows_min_lanes_refuses), TUNE_OPTION(set_each_route, set_each_route_refuses),
 #ifdef KEAKI_DIAG
     TUNE_OPTION(diag_row_mask, nullptr, nullptr, false),       // set_option only: no environment variable
 #endif
@@ -2672,17 +2691,18 @@ struct VsArgs {
   const uint64_t* omega;
   int32_t com_stride, point_mode;
   size_t item_stride, k, n;
+  bool no_proofs = false, no_gammas = false;      // arrays the call does not take (set_pairs: neither; verify_sets_each: no gammas)
 };
 // the points or values of n items as ONE span of the caller's array: up to the last element the stride names
 inline size_t sets_span(size_t n, size_t k, size_t item_stride) { return (n - 1) * item_stride + k; }
 // The ONE argument check of the set-batch calls; `out`: the output that is required at any n.
-keaki_status verify_sets_args(keaki_hip_ctx* ctx, const VsArgs& a, const char* what, const void* out) {
+keaki_status verify_sets_args(keaki_hip_ctx* ctx, const VsArgs& a, const char* what, const void* out, const char* out_name = "ok_out") {
   ST_TRY(kzg_modes_ok(ctx, what, a.com_stride, a.point_mode));
-  if (!out || !a.srs1 || !a.srs2) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, !out ? "ok_out" : a.srs1 ? "srs_g2" : "srs_g1");
+  if (!out || !a.srs1 || !a.srs2) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, !out ? out_name : a.srs1 ? "srs_g2" : "srs_g1");
   if (a.k == 0 || a.k > KEAKI_VERIFY_SETS_K_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: k = %zu must be in 1 .. %d", what, a.k, (int)KEAKI_VERIFY_SETS_K_MAX);
   if (a.item_stride < a.k) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu is less than k = %zu", what, a.item_stride, a.k);
   if (a.point_mode && !a.omega) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: point_mode 1 needs omega", what);
-  if (a.n && (!a.com || !a.points || !a.values || !a.proofs || !a.gammas)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
+  if (a.n && (!a.com || !a.points || !a.values || (!a.no_proofs && !a.proofs) || (!a.no_gammas && !a.gammas))) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
   if (a.n >= ((size_t)1 << 31) || a.n * a.k >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n * k = %zu * %zu must be < 2^31", what, a.n, a.k);
   // the extent (n - 1) item_stride + k stays below 2^48 elements (checked without forming a product that could wrap): 32 x the extent, the bytes the host
   // form uploads and the kernels' address arithmetic, fits 64 bits with room to spare
@@ -3042,6 +3062,241 @@ keaki_status keaki_hip_kzg_verify_cosets_each(keaki_hip_ctx* ctx, keaki_hip_srs_
   char* out = w.zeros + n * 32;
   ST_TRY(coset_each_core(ctx, srs_g1, a, tau_l_g2_aff, w, out, r.d_lhs(out), n_bad, first_bad));
   return each_result(feed, r, out, status);
+}
+
+// ---- KZG set pairs and per-set verdicts --------------------------------------------------------------------------------------------------------
+// set_pairs: A_i = C_i - [I_i(tau)]_1 and Z2_i = [Z_i(tau)]_2 for n items of k arbitrary points (kzg_set_pairs.hip has the derivation and the G2 kernels). Kernel
+// sequence per launch chunk (set_rows_plan.h), all on ctx->stream: k_vs_points (point_mode 1) + k_vs_weights + k_vs_polys<1 / 2> (kzg_sets.hip: the rows -I padded
+// to kp and Z) | G1: coset_pairs' group side at log2l = log2 kp -- k_cp_rows over the G1 handle's window table, or msm_g1_batch_run + k_cp_join -- and k_cp_affine |
+// G2: k_sp_rows_g2 over the G2 handle's window table, k_sp_affine_g2. verify_sets_each is set_pairs into sp_pairs [A: n x 64 | Z2: n x 128 | status | the chunk
+// block of the pairing side] (or into the caller's arrays), then per launch chunk route 1 k_sp_points (-proof) + k_pairing2v, or route 2 k_sp_points + the Miller
+// loops of the 2m pairs + k_gt_pair_product + the final exponentiation + k_sp_status; then k_ve_count.
+extern "C++" {
+namespace {
+// The argument check of the set-pairs calls: the family's gate, told which arrays these calls do not take. `out`: an output required at any n.
+keaki_status set_pairs_args(keaki_hip_ctx* ctx, VsArgs a, const char* what, bool with_proofs, const void* out, const char* out_name) {
+  a.no_gammas = true;
+  a.no_proofs = !with_proofs;
+  return verify_sets_args(ctx, a, what, out, out_name);
+}
+// afterwards srs->sr.p is the table over at least k bases and *wb_out its width; the caller holds srs->mu. A resident table that covers k is used at its
+// width unless set_rows_wb names another; a refused table falls to the next narrower width.
+keaki_status set_table_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t k, uint32_t* wb_out) {
+  SrsCache& c = srs->sr;
+  const uint32_t opt = (uint32_t)ctx->tune.set_rows_wb;
+  if (c.p && c.key[0] >= (int)k && (opt == 0 || c.key[1] == (int)opt)) { *wb_out = (uint32_t)c.key[1]; return KEAKI_OK; }
+  for (uint32_t wb = opt ? opt : sr_wb(k); wb; wb = sr_wb_narrower(wb)) {
+    const keaki_status st = srs_cache_ensure(ctx, srs, c, (int)k, (int)wb, sr_table_bytes(k, wb), [&](void* t) { return g2_fb_tables_run(ctx, srs->d, (uint32_t)k, t, wb); });
+    if (st == KEAKI_OK) { *wb_out = wb; return KEAKI_OK; }
+    if (st != KEAKI_ERR_OOM) return st;
+    ctx->err.clear();
+  }
+  return fail(ctx, KEAKI_ERR_OOM, "kzg_set_pairs: the window table over the first %zu G2 points was refused at every width", k);
+}
+// a.* are device pointers but a.omega; the caller holds the context. Every allocation that can be refused (the tables, the workspace) comes before the first
+// launch that writes an output.
+keaki_status set_pairs_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs1, keaki_hip_srs_g2* srs2, const VsArgs& a, void* d_lhs, void* d_z2) {
+  const size_t n = a.n, k = a.k;
+  const uint32_t log2kp = sr_log2kp(k);
+  const size_t kp = (size_t)1 << log2kp;
+  std::lock_guard<std::recursive_mutex> hl1(srs1->mu);     // the tables belong to the handles: one call per handle at a time
+  std::lock_guard<std::recursive_mutex> hl2(srs2->mu);
+  int route = kp > srs1->n ? 2 : cr_route(ctx->tune.coset_rows_route, log2kp);      // kp > len(srs_g1) >= k: no table over kp points
+  const uint32_t wb1 = ctx->tune.coset_rows_wb ? (uint32_t)ctx->tune.coset_rows_wb : cr_wb(log2kp);
+  if (route == 1) {
+    const keaki_status st = coset_table_ensure(ctx, srs1, log2kp, wb1);
+    if (st == KEAKI_ERR_OOM) { ctx->err.clear(); route = 2; }      // optional memory, as for coset_pairs
+    else if (st != KEAKI_OK) return st;
+  }
+  uint32_t wb2 = 0;
+  ST_TRY(set_table_ensure(ctx, srs2, k, &wb2));
+  const size_t per_item = sr_item_bytes(k, log2kp, a.point_mode, route == 2);
+  size_t ch = sr_chunk_items(n, log2kp);
+  for (;;) {
+    const keaki_status st = reserve(ctx, ctx->sp_work, ch * per_item);
+    if (st == KEAKI_OK) break;
+    if (st != KEAKI_ERR_OOM || ch <= 1) return st;
+    ctx->err.clear();
+    ch = sr_chunk_halve(ch);
+  }
+  char* w = (char*)ctx->sp_work.p;
+  char* pts = w + ch * k * 32;
+  char* rows_i = pts + (a.point_mode ? ch * k * 32 : 0);
+  char* rows_z = rows_i + ch * kp * 32;
+  char* xyzz1 = rows_z + ch * k * 32;
+  char* xyzz2 = xyzz1 + ch * 128;
+  char* jac = xyzz2 + ch * 256;
+  const auto tb = srs_tables(srs1);
+  const char* tau_k = (const char*)srs2->d + k * G2_AFF_BYTES;
+  for (size_t lo = 0; lo < n; lo += ch) {
+    const size_t m = std::min(ch, n - lo);
+    ST_TRY(set_pairs_rows_run(ctx, a.points, a.point_mode, a.omega, a.values, a.item_stride, k, lo, m, route == 2, w, pts, rows_i, rows_z));
+    if (route == 1) {
+      ST_TRY(coset_rows_table_run(ctx, srs1->cr.p, wb1, rows_i, log2kp, cr_slices(m, log2kp, (uint64_t)ctx->tune.coset_rows_min_lanes), a.com, a.com_stride, lo, m, xyzz1));
+    } else {
+      ST_TRY(msm_g1_batch_run(ctx, srs1->d, srs1->n, tb.first, tb.second, rows_i, k, m, kp, jac));
+      ST_TRY(coset_rows_join_run(ctx, jac, a.com, a.com_stride, lo, m, xyzz1));
+    }
+    ST_TRY(coset_rows_affine_run(ctx, xyzz1, m, (char*)d_lhs + lo * G1_AFF_BYTES));
+    ST_TRY(set_rows_g2_run(ctx, srs2->sr.p, wb2, rows_z, k, sr_slices(m, log2kp, (uint64_t)ctx->tune.set_rows_min_lanes), tau_k, m, xyzz2));
+    ST_TRY(set_rows_affine_g2_run(ctx, xyzz2, m, (char*)d_z2 + lo * G2_AFF_BYTES));
+  }
+  return KEAKI_OK;
+}
+// sp_pairs of verify_sets_each: [A: n x 64 | Z2: n x 128 | status: n B rounded up to 64 (host form) | the chunk block]; `ch` = the items of a pairing launch chunk
+struct SeWork { char *a, *z2, *status, *chunk; size_t ch; bool route2; };
+keaki_status set_each_reserve(keaki_hip_ctx* ctx, size_t n, bool host_form, SeWork* out) {
+  const bool route2 = se_route(ctx->tune.set_each_route, n) == 2;
+  const size_t fixed = n * (G1_AFF_BYTES + G2_AFF_BYTES) + (host_form ? (n + 63) & ~(size_t)63 : 0);
+  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
+  size_t ch = se_chunk_items(n, pairing_launch_items());
+  for (;;) {
+    keaki_status st = reserve(ctx, ctx->sp_pairs, fixed + ch * se_item_bytes(route2));
+    if (st == KEAKI_OK) st = reserve(ctx, ctx->pair_ws, ch * pairing_slot_bytes());
+    if (st == KEAKI_OK) break;
+    if (st != KEAKI_ERR_OOM || ch <= SE_CHUNK_MIN) return st;
+    ctx->err.clear();
+    ch = se_chunk_halve(ch);
+  }
+  out->a = (char*)ctx->sp_pairs.p; out->z2 = out->a + n * G1_AFF_BYTES; out->status = out->z2 + n * G2_AFF_BYTES;
+  out->chunk = (char*)ctx->sp_pairs.p + fixed; out->ch = ch; out->route2 = route2;
+  return KEAKI_OK;
+}
+// a.* are device pointers but a.omega. d_lhs / d_z2: where the pairs go (the caller's arrays or sp_pairs). Ends with the read-back of the counters: synchronises.
+keaki_status set_each_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs1, keaki_hip_srs_g2* srs2, const VsArgs& a, const SeWork& w, void* d_lhs, void* d_z2,
+                           void* d_status, uint64_t* n_bad, uint64_t* first_bad) {
+  const size_t n = a.n, ch = w.ch;
+  if (!w.route2) ST_TRY(generator_tables(ctx, false));               // g2's line sequence
+  ST_TRY(set_pairs_core(ctx, srs1, srs2, a, d_lhs, d_z2));
+  char* io = (char*)ctx->ve_io.p;
+  const uint64_t init[2] = {0, ~0ull};
+  HIP_TRY(ctx, hipMemcpyAsync(io + VeLayout::O_BAD, init, 16, hipMemcpyHostToDevice, ctx->stream));
+  for (size_t lo = 0; lo < n; lo += ch) {
+    const size_t m = std::min(ch, n - lo);
+    const char* as = (const char*)d_lhs + lo * G1_AFF_BYTES;
+    const char* zs = (const char*)d_z2 + lo * G2_AFF_BYTES;
+    const char* proofs = (const char*)a.proofs + lo * G1_AFF_BYTES;
+    char* status = (char*)d_status + lo;
+    if (!w.route2) {
+      ST_TRY(set_each_points_run(ctx, as, proofs, zs, m, w.chunk, nullptr));
+      ST_TRY(pairing2v_run(ctx, as, w.chunk, zs, m, ctx->kem.g2gen_lines.p, ctx->pair_ws.p, ch, status));
+    } else {
+      char* ps = w.chunk;
+      char* qs = ps + ch * 2 * G1_AFF_BYTES;
+      char* mil = qs + ch * 2 * G2_AFF_BYTES;
+      char* prod = mil + ch * 768;
+      char* gt = prod + ch * 384;
+      ST_TRY(set_each_points_run(ctx, as, proofs, zs, m, ps, qs));
+      ST_TRY(miller_only_run(ctx, ps, qs, 2 * m, mil));
+      ST_TRY(gt_pair_product_run(ctx, mil, mil + m * 384, m, prod));
+      ST_TRY(final_exp_only_run(ctx, prod, m, gt));
+      ST_TRY(set_each_status_run(ctx, gt, as, proofs, zs, m, status));
+    }
+  }
+  ST_TRY(verify_each_count_run(ctx, d_status, n, io + VeLayout::O_BAD));
+  uint64_t res[2];
+  ST_TRY(download(ctx, res, io + VeLayout::O_BAD, 16));
+  *n_bad = res[0];
+  if (first_bad) *first_bad = res[1];
+  return KEAKI_OK;
+}
+// the host forms' inputs: the spans of points (or indices) and values in sp_in, the commitments and the proofs through the family's stager
+struct SetHostIn {
+  size_t point_bytes, value_bytes, value_off;
+  SetHostIn(const VsArgs& a) : point_bytes(sets_span(a.n, a.k, a.item_stride) * (a.point_mode ? 4 : 32)), value_bytes(sets_span(a.n, a.k, a.item_stride) * 32),
+                               value_off((point_bytes + 255) & ~(size_t)255) {}
+  keaki_status reserve(keaki_hip_ctx* ctx) const { return keaki_internal::reserve(ctx, ctx->sp_in, value_off + value_bytes); }
+  // uploads everything and turns a's pointers into device pointers
+  keaki_status put(keaki_hip_ctx* ctx, CopyFeed& feed, ItemStager& items, VsArgs& a) const {
+    char* in = (char*)ctx->sp_in.p;
+    ST_TRY(items.put(feed, ItemStager::COM));
+    ST_TRY(items.put(feed, in, a.points, point_bytes));
+    ST_TRY(items.put(feed, in + value_off, a.values, value_bytes));
+    ST_TRY(items.put(feed, ItemStager::PROOFS));
+    a.com = items.d_com(); a.points = in; a.values = in + value_off; a.proofs = items.d_proofs();
+    return KEAKI_OK;
+  }
+};
+}  // namespace
+}  // extern "C++"
+
+keaki_status keaki_hip_srs_g2_precompute_sets(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t k_max) {
+  CTX_GUARD(ctx);
+  if (!srs || k_max == 0 || k_max > KEAKI_VERIFY_SETS_K_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g2_precompute_sets: bad argument");
+  ST_TRY(srs_holds(ctx, srs, "srs_g2_precompute_sets", k_max + 1, "kzg sets: Z has %zu coefficients but the G2 SRS holds %zu points"));
+  std::lock_guard<std::recursive_mutex> hl(srs->mu);
+  uint32_t wb = 0;
+  return set_table_ensure(ctx, srs, k_max, &wb);
+}
+
+keaki_status keaki_hip_kzg_set_pairs_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const void* d_com_aff, int32_t com_stride,
+                                         const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values, size_t item_stride, size_t k,
+                                         size_t n, void* d_lhs_out_aff, void* d_z2_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_set_pairs");
+  const VsArgs a = {srs_g1, srs_g2, d_com_aff, d_points, d_values, nullptr, nullptr, omega, com_stride, point_mode, item_stride, k, n};
+  ST_TRY(set_pairs_args(ctx, a, "kzg_set_pairs", false, n == 0 || (d_lhs_out_aff && d_z2_out_aff) ? (const void*)ctx : nullptr, "lhs_out_aff or z2_out_aff"));
+  if (n == 0) return KEAKI_OK;
+  return set_pairs_core(ctx, srs_g1, srs_g2, a, d_lhs_out_aff, d_z2_out_aff);
+}
+
+keaki_status keaki_hip_kzg_set_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff, int32_t com_stride,
+                                     const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values, size_t item_stride, size_t k,
+                                     size_t n, uint64_t* lhs_out_aff, uint64_t* z2_out_aff) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_set_pairs");
+  VsArgs a = {srs_g1, srs_g2, com_aff, points, values, nullptr, nullptr, omega, com_stride, point_mode, item_stride, k, n};
+  ST_TRY(set_pairs_args(ctx, a, "kzg_set_pairs", false, n == 0 || (lhs_out_aff && z2_out_aff) ? (const void*)ctx : nullptr, "lhs_out_aff or z2_out_aff"));
+  if (n == 0) return KEAKI_OK;
+  const SetHostIn in(a);
+  ST_TRY(in.reserve(ctx));
+  ST_TRY(reserve(ctx, ctx->sp_pairs, n * (G1_AFF_BYTES + G2_AFF_BYTES)));
+  ItemStager items{ctx, com_aff, com_stride, nullptr, nullptr, 0, nullptr, nullptr, n};      // one commitment: in io_e
+  ST_TRY(items.reserve());
+  CopyFeed feed(ctx);
+  ST_TRY(in.put(ctx, feed, items, a));
+  char* out = (char*)ctx->sp_pairs.p;
+  ST_TRY(set_pairs_core(ctx, srs_g1, srs_g2, a, out, out + n * G1_AFF_BYTES));
+  prefault_out(ctx, z2_out_aff, n * G2_AFF_BYTES);
+  HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, z2_out_aff, out + n * G1_AFF_BYTES, n * G2_AFF_BYTES);
+}
+
+keaki_status keaki_hip_kzg_verify_sets_each_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const void* d_com_aff,
+                                                int32_t com_stride, const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values,
+                                                size_t item_stride, size_t k, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
+                                                uint64_t* first_bad, void* d_lhs_out_aff, void* d_z2_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_sets_each");
+  const VsArgs a = {srs_g1, srs_g2, d_com_aff, d_points, d_values, d_proofs_aff, nullptr, omega, com_stride, point_mode, item_stride, k, n};
+  ST_TRY(set_pairs_args(ctx, a, "kzg_verify_sets_each", true, n_bad && (n == 0 || d_status) ? (const void*)n_bad : nullptr, "n_bad or status"));
+  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
+  SeWork w;
+  ST_TRY(set_each_reserve(ctx, n, false, &w));
+  return set_each_core(ctx, srs_g1, srs_g2, a, w, d_lhs_out_aff ? d_lhs_out_aff : w.a, d_z2_out_aff ? d_z2_out_aff : w.z2, d_status, n_bad, first_bad);
+}
+
+keaki_status keaki_hip_kzg_verify_sets_each(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                            int32_t com_stride, const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values,
+                                            size_t item_stride, size_t k, const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad,
+                                            uint64_t* first_bad, uint64_t* lhs_out_aff, uint64_t* z2_out_aff) {
+  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
+  TRACE_SCOPE("keaki.kzg_verify_sets_each");
+  VsArgs a = {srs_g1, srs_g2, com_aff, points, values, proofs_aff, nullptr, omega, com_stride, point_mode, item_stride, k, n};
+  ST_TRY(set_pairs_args(ctx, a, "kzg_verify_sets_each", true, n_bad && (n == 0 || status) ? (const void*)n_bad : nullptr, "n_bad or status"));
+  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
+  const SetHostIn in(a);
+  SeWork w;
+  ST_TRY(set_each_reserve(ctx, n, true, &w));
+  ST_TRY(in.reserve(ctx));
+  ItemStager items{ctx, com_aff, com_stride, nullptr, nullptr, 0, nullptr, proofs_aff, n};      // one commitment: in io_e
+  ST_TRY(items.reserve());
+  CopyFeed feed(ctx);
+  ST_TRY(in.put(ctx, feed, items, a));
+  ST_TRY(set_each_core(ctx, srs_g1, srs_g2, a, w, w.a, w.z2, w.status, n_bad, first_bad));
+  if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, w.a, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  if (z2_out_aff) HIP_TRY(ctx, hipMemcpyAsync(z2_out_aff, w.z2, n * G2_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  return download(feed, status, w.status, n);
 }
 
 // ---- SRS ingest: on-curve check (row f-3) ------------------------------------------------------------------------

@@ -11,7 +11,7 @@
 //                 split nor the order changes a bit of the result.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, this file): k_gt_product 256 VGPRs + 12 AGPRs (one wave per SIMD: the kernel
 // runs at most 256 workgroups of one wave, so occupancy buys nothing), 36,864 B LDS (12 KB parking area, two 12 KB buffers of the tree), no scratch
-// memory, no atomics.
+// memory, no atomics. k_gt_pair_product (the pairwise mode of kzg verify_sets_each: out[i] = a[i] b[i], no tree) 232 VGPRs, 12,288 B LDS, no scratch memory.
 #define KEAKI_FQ2_OUTLINE 1
 #include <algorithm>
 #include "internal.h"
@@ -65,6 +65,39 @@ static __global__ void __launch_bounds__(64) k_gt_product(const Fq* __restrict__
 #pragma unroll
     for (int k = 0; k < 6; k++) o[2 * k + par] = to256(c[k].v);
   }
+}
+
+// The pairwise mode (kzg verify_sets_each, route 2): out[i] = a[i] b[i], one lane pair per item and no tree; the same representation, the same product.
+static __global__ void __launch_bounds__(64) k_gt_pair_product(const Fq* __restrict__ a, const Fq* __restrict__ b, u32 n, Fq* __restrict__ out) {
+  __shared__ uint4 park[12 * 64];
+  const u32 tid = threadIdx.x, par = lane_odd();
+  const u32 e = blockIdx.x * GP_PAIRS + (tid >> 1);
+  const bool live = e < n;
+  const size_t at = (size_t)12 * (live ? e : n - 1u);       // tail pairs redo the last item and write nothing: all 64 lanes stay active
+  Fq12 acc;
+  Fq2d* c = reinterpret_cast<Fq2d*>(&acc);
+#pragma unroll
+  for (int k = 0; k < 6; k++) c[k].v = to261(a[at + 2 * k + par]);
+  const Fq* src = b + at;
+  fq12_mul_ld<true>(&acc, &acc, [&](int h) {
+    Fq6 x;
+    Fq2d* xc = reinterpret_cast<Fq2d*>(&x);
+#pragma unroll
+    for (int k = 0; k < 3; k++) xc[k].v = to261(src[6 * h + 2 * k + par]);
+    return x;
+  }, park);
+  if (live) {
+    Fq* o = out + at;
+#pragma unroll
+    for (int k = 0; k < 6; k++) o[2 * k + par] = to256(c[k].v);
+  }
+}
+
+keaki_status gt_pair_product_run(keaki_hip_ctx* ctx, const void* d_a, const void* d_b, size_t m, void* d_out) {
+  if (m == 0) return KEAKI_OK;
+  if (m >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "gt_pair_product: m = %zu must be < 2^31", m);
+  hipLaunchKernelGGL(k_gt_pair_product, dim3(cdiv(m, GP_PAIRS)), dim3(64), 0, ctx->stream, (const Fq*)d_a, (const Fq*)d_b, (u32)m, (Fq*)d_out);
+  return launch_check(ctx, "gt_pair_product");
 }
 
 size_t gt_product_part_bytes() { return (size_t)GP_MAX_BLOCKS * 12 * sizeof(Fq); }

@@ -72,6 +72,9 @@ struct Tuning {
   long long coset_rows_min_lanes = 0;   // KEAKI_COSET_ROWS_MIN_LANES / "coset_rows_min_lanes": the row kernel of kzg coset_pairs splits an item's l bases over lanes while a launch has fewer lanes than this; 0 = CR_MIN_LANES (coset_rows_plan.h)
   int coset_rows_route = 0;      // KEAKI_COSET_ROWS_ROUTE / "coset_rows_route": how kzg coset_pairs sums its rows: 1 = the handle's window table over the first l SRS points, 2 = the batched MSM; 0 = by plan (coset_rows_plan.h: cr_route)
   int coset_rows_wb = 0;         // KEAKI_COSET_ROWS_WB / "coset_rows_wb": window bits of that table, 8, 10 or 13; 0 = by plan (coset_rows_plan.h: cr_wb; the switch of the width sweep)
+  int set_rows_wb = 0;           // KEAKI_SET_ROWS_WB / "set_rows_wb": window bits of the G2 handle's table of kzg set_pairs, 8, 10 or 13; 0 = by plan (set_rows_plan.h: sr_wb; the switch of the width sweep)
+  long long set_rows_min_lanes = 0;     // KEAKI_SET_ROWS_MIN_LANES / "set_rows_min_lanes": the G2 row kernel of kzg set_pairs splits an item's k bases over lanes while a launch has fewer lanes than this; 0 = SR_MIN_LANES (set_rows_plan.h)
+  int set_each_route = 0;        // KEAKI_SET_EACH_ROUTE / "set_each_route": how kzg verify_sets_each decides its items: 1 = the fused kernel k_pairing2v, 2 = two Miller loops per item, a pairwise GT product, the final exponentiation and a comparison with one; 0 = by plan (set_rows_plan.h: se_route, which is route 2 at every n, as measured)
   int vec_update_k_pass = 0;     // KEAKI_VEC_UPDATE_K_PASS / "vec_update_k_pass": entries of the change list per pass of vec_update's proof kernel, 1 .. UPD_K_PASS; 0 = UPD_K_PASS
 #ifdef KEAKI_DIAG
   unsigned diag_row_mask = 0;    // "diag_row_mask" (ONLY in the diagnostic build, `make -C keaki_amd/csrc diag`; never in libkeaki_hip.so): the table-row index of every (row, sign) entry of the bucket-ordered stream is ANDed with this mask before the bucket kernel runs, so its gathers hit a table of (mask + 1) x 64 B -- the arithmetic, the instruction stream and the kernel binary stay the shipped ones, the RESULT IS WRONG by construction (bench_tools/r6_bucket_clock_diag.py)
@@ -185,6 +188,7 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf vc_io, vc_work;            // kzg verify_cosets: the small in/out block (VcLayout, api.hip) | s, 1 / h, -J, g and the partial rows of a call (kzg_cosets.hip: verify_cosets_layout)
   keaki_internal::DevBuf cp_work, cp_pairs, cp_in;  // kzg coset_pairs: 1 / h (n Fr), then the rows, the XYZZ sums and (route 2) the Jacobian sums of a launch chunk | verify_cosets_each: A, c and the zero values of the call; host forms: + the outputs | host forms: the values
   keaki_internal::DevBuf vs_io, vs_work;            // kzg verify_sets: the small in/out block (VsLayout, api.hip) | the scalar rows, the weights, -J, g, the partial rows and (point_mode 1) the derived points of a call (kzg_sets.hip: verify_sets_layout)
+  keaki_internal::DevBuf sp_work, sp_pairs, sp_in;  // kzg set_pairs: weights, derived points, the two scalar rows, the XYZZ sums and (G1 route 2) the Jacobian sums of a launch chunk | verify_sets_each: A, Z2 and the pairing side's blocks of a launch chunk; host forms: + the outputs | host forms: points and values
   keaki_internal::DevBuf gp_work;                   // pairing_product: the Miller-loop outputs of a call (384 B per pair), the partial products and the product
   keaki_internal::DevBuf fc_work;                   // FK23 coset openings (fk_coset.hip): twiddles, hat_a, the partial sums and the two transforms of a call; host forms: + coefficients and proofs
   // every DevBuf above with its memory class, kem's included (KemState::for_each_buf): what keaki_hip_ctx_destroy and _trim free and
@@ -193,7 +197,7 @@ struct keaki_hip_ctx {
     f(&fb_bases, 2);
     for (keaki_internal::DevBuf* b : {&digits, &hist, &offsets, &cursor, &sorted, &buckets, &acc29, &partials, &wsums, &tmp_a, &tmp_b, &tmp_c, &io_a, &io_b, &io_c,
                                       &io_d, &io_e, &perm, &heavy, &pair_ws, &fk_tab, &mb_canon, &mb_wsums, &mb_q, &fkb_pts, &fkb_fr, &em_offsets, &vb_io, &vb_s,
-                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work, &cp_work, &cp_pairs, &cp_in, &vs_io, &vs_work, &gp_work})
+                                      &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work, &cp_work, &cp_pairs, &cp_in, &vs_io, &vs_work, &sp_work, &sp_pairs, &sp_in, &gp_work})
       f(b, 1);
     kem.for_each_buf(f);
   }
@@ -352,6 +356,27 @@ VsWork verify_sets_layout(size_t n, size_t k, void* d_work);
 keaki_status verify_sets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, const void* d_points, int point_mode, const uint64_t* omega, const void* d_values,
                                      size_t item_stride, size_t k, size_t n, const VsWork& w);
 keaki_status verify_sets_pairs_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_rows_jac, size_t k, void* d_sums_aff, void* d_ps_aff);
+// kzg set_pairs / verify_sets_each. Fr side (kzg_sets.hip, the rows instantiations of k_vs_polys): for the m items [first, first + m) of the caller's arrays
+// (m * kp < 2^31, kp = the power of two >= k) d_rows_i[(i << log2 kp) + t] = -I_(first + i, t) (t < k, zeros up to kp; canonical integers, or with `mont` the
+// Montgomery form the batched MSM takes) and d_rows_z[i k + t] = Z_(first + i, t) (t < k, canonical; Z is monic, the coefficient of X^k is not stored).
+// d_w: m k Fr (the weights), d_pts: m k Fr (point_mode 1 only); d_rows_i doubles as the weights' scratch. G2 side (kzg_set_pairs.hip): the window table over the
+// first n_bases G2 points (set_rows_plan.h: sr_table_bytes) | d_xyzz[i] = [tau^k]_2 + sum_t rows_z[i][t] [tau^t]_2 by the table walk in S slices per item |
+// m XYZZ points -> affine, (0,0) for the identity. Verdict side: kzg_set_each_pair.hip (the fused kernel) and the pieces of route 2 (set_each_*; gt_product.hip).
+keaki_status set_pairs_rows_run(keaki_hip_ctx* ctx, const void* d_points, int point_mode, const uint64_t* omega, const void* d_values, size_t item_stride, size_t k,
+                                size_t first, size_t m, bool mont, void* d_w, void* d_pts, void* d_rows_i, void* d_rows_z);
+keaki_status g2_fb_tables_run(keaki_hip_ctx* ctx, const void* d_bases, uint32_t n_bases, void* d_table, uint32_t wb);   // table[(b windows + j) entries + d] = d 2^(wb j) bases[b]
+keaki_status set_rows_g2_run(keaki_hip_ctx* ctx, const void* d_table, uint32_t wb, const void* d_rows_z, size_t k, uint32_t S, const void* d_tau_k_g2, size_t m,
+                             void* d_xyzz);
+keaki_status set_rows_affine_g2_run(keaki_hip_ctx* ctx, const void* d_xyzz, size_t m, void* d_out_aff);
+// d_status[i] = 0 iff e(a_i, g2) == e(proof_i, z2_i); R = (proof_i or z2_i is the identity): with a_i or R an identity the item is valid iff both are. ONE launch
+// of n <= ws_items <= pairing_launch_items() items over the final exponentiation's slots at d_ws; d_lines_g2: g2's line table.
+keaki_status pairing2v_run(keaki_hip_ctx* ctx, const void* d_a, const void* d_proofs, const void* d_z2, size_t n, const void* d_lines_g2, void* d_ws,
+                           size_t ws_items, void* d_status);
+// route 2: d_ps = [a_i : m | -proof_i : m], d_qs = [g2 : m | z2_i : m] (the 2m pairs of miller_only_run) | d_out[i] = d_a[i] d_b[i] (12 Fq each, the 2^256 form of
+// miller_only_run) | the status bytes from the 384 serialised bytes per item and the identity rule
+keaki_status set_each_points_run(keaki_hip_ctx* ctx, const void* d_a, const void* d_proofs, const void* d_z2, size_t m, void* d_ps, void* d_qs);
+keaki_status gt_pair_product_run(keaki_hip_ctx* ctx, const void* d_a, const void* d_b, size_t m, void* d_out);
+keaki_status set_each_status_run(keaki_hip_ctx* ctx, const void* d_gt_bytes, const void* d_a, const void* d_proofs, const void* d_z2, size_t m, void* d_status);
 // GT product (gt_product.hip): d_out = prod of the n Fq12 at d_in (12 Fq each, 2^256 Montgomery form, slot 2k + parity: what miller_only_run writes and
 // final_exp_only_run reads), n < 2^31; n = 0: one. d_part: gt_product_part_bytes() of workspace (may not overlap d_in or d_out).
 size_t gt_product_part_bytes();

@@ -25,7 +25,8 @@
 // lanes of a slot hit consecutive coefficients. 24 KB a workgroup.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, this file; no kernel uses scratch memory or atomics):
 //   k_vs_points   48 VGPRs, no LDS           k_vs_weights  80 VGPRs, no LDS
-//   k_vs_polys    140 VGPRs, 24,576 B LDS    k_vs_finish   70 VGPRs, 33,280 B LDS    k_vs_pairs  33 VGPRs, no LDS
+//   k_vs_polys<0>  140 VGPRs, 24,576 B LDS    k_vs_finish   70 VGPRs, 33,280 B LDS    k_vs_pairs  33 VGPRs, no LDS
+//   k_vs_polys<1>, <2> (the rows of kzg set_pairs: no gammas, no partial sums)  112 VGPRs, 24,576 B LDS
 #include <algorithm>
 #include "internal.h"
 #include "bn254_curve.hip.h"
@@ -98,6 +99,10 @@ static __global__ void __launch_bounds__(VS_THREADS) k_vs_weights(const Fr* __re
 
 // rows: S[t n + i] as in the file header; part[blockIdx.x (k + 1) + t] = sum over the items i of this workgroup's tiles of gamma_i I_(i,t) (t < k),
 // and of gamma_i (t = k). z_(i,j) at z + i zstride + j, y_(i,j) at y + i ystride + j, w dense (i k + j).
+// ROWS != 0 (kzg set_pairs: no gammas, no partial sums, no k_vs_finish): S[(i << log2kp) + t] = -I_(i,t) for t < k and zero up to kp (the layout k_cp_rows
+// reads; canonical integers, ROWS = 2: the Montgomery form the batched MSM takes) and part[i k + t] = Z_(i,t), t < k, canonical (the monic top coefficient is
+// not stored).
+template <int ROWS>
 static __global__ void __launch_bounds__(VS_THREADS) k_vs_polys(const Fr* __restrict__ z, u64 zstride, const Fr* __restrict__ y, u64 ystride, const Fr* __restrict__ w,
                                                                 const Fr* __restrict__ gammas, u32 n, u32 k, u32 log2kp, Fr* __restrict__ S, Fr* __restrict__ part) {
   __shared__ VsArr pz, zc, ic;
@@ -140,6 +145,21 @@ static __global__ void __launch_bounds__(VS_THREADS) k_vs_polys(const Fr* __rest
       }
       __syncthreads();
     }
+    if constexpr (ROWS != 0) {
+      if (item < n) {
+        Fr ni = fp_zero<FrParams>(), out;
+        if (c < k) ni = fp_neg<FrParams>(vs_ld(ic, tid));
+        if (ROWS == 2) out = ni;
+        else fp_from_mont<FrParams>(out.l, ni);
+        S[((size_t)item << log2kp) + c] = out;
+        if (c < k) {
+          fp_from_mont<FrParams>(out.l, cur);
+          part[(size_t)item * k + c] = out;
+        }
+      }
+      __syncthreads();
+      continue;
+    }
     if (live) {
       const Fr gamma = gammas[item];
       Fr row = fp_mul<FrParams>(gamma, cur);
@@ -154,6 +174,7 @@ static __global__ void __launch_bounds__(VS_THREADS) k_vs_polys(const Fr* __rest
     __syncthreads();                                // the next tile overwrites the three arrays
   }
 
+  if constexpr (ROWS != 0) return;
   // fold the T slots: entry slot * kp + c, a tree over the slots; then the same tree down to one entry for g
   vs_st(ic, tid, acc);
   vs_st(zc, tid, accg);
@@ -258,10 +279,41 @@ keaki_status verify_sets_scalars_run(keaki_hip_ctx* ctx, const void* d_gammas, c
   const int opt = ctx->tune.verify_sets_blocks;
   const u32 cap = opt > 0 ? (u32)opt : ctx->n_cu * 3u;
   const u32 blocks = std::min<u32>(vs_rows_max(n, k), cap);
-  hipLaunchKernelGGL(k_vs_polys, dim3(blocks), dim3(VS_THREADS), 0, ctx->stream, z, zstride, (const Fr*)d_values, (u64)item_stride, (const Fr*)w.w,
+  hipLaunchKernelGGL(k_vs_polys<0>, dim3(blocks), dim3(VS_THREADS), 0, ctx->stream, z, zstride, (const Fr*)d_values, (u64)item_stride, (const Fr*)w.w,
                      (const Fr*)d_gammas, (u32)n, (u32)k, vs_log2kp(k), (Fr*)w.s, (Fr*)w.part);
   hipLaunchKernelGGL(k_vs_finish, dim3(1), dim3(VS_FIN_THREADS), 0, ctx->stream, (const Fr*)w.part, blocks, (u32)k, (Fr*)w.neg_j, (Fr*)w.g);
   return launch_check(ctx, "verify_sets_scalars");
+}
+
+// kzg set_pairs: the rows of the m items [first, first + m) of the caller's arrays (internal.h). The same three kernels on the chunk's part of the arrays; the
+// products of k_vs_weights wait in d_rows_i (m kp >= m k Fr), which the rows kernel writes only afterwards.
+keaki_status set_pairs_rows_run(keaki_hip_ctx* ctx, const void* d_points, int point_mode, const uint64_t* omega, const void* d_values, size_t item_stride, size_t k,
+                                size_t first, size_t m, bool mont, void* d_w, void* d_pts, void* d_rows_i, void* d_rows_z) {
+  const u32 log2kp = vs_log2kp(k);
+  if (m == 0 || k == 0 || k > KEAKI_VERIFY_SETS_K_MAX || item_stride < k || (m << log2kp) >= ((size_t)1 << 31))
+    return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_set_pairs: a chunk of %zu items of %zu points out of range on the device side", m, k);
+  const u32 total = (u32)(m * k);
+  const Fr* z = (const Fr*)d_points + first * item_stride;
+  u64 zstride = item_stride;
+  if (point_mode) {
+    Fr om;
+    memcpy(&om, omega, 32);
+    hipLaunchKernelGGL(k_vs_points, dim3(std::min<u32>(cdiv(total, VS_THREADS), ctx->n_cu * 8u)), dim3(VS_THREADS), 0, ctx->stream,
+                       (const u32*)d_points + first * item_stride, (u64)item_stride, om, (u32)m, (u32)k, (Fr*)d_pts);
+    z = (const Fr*)d_pts;
+    zstride = k;
+  }
+  hipLaunchKernelGGL(k_vs_weights, dim3(std::min<u32>(cdiv(cdiv(total, VS_INV), VS_THREADS), ctx->n_cu * 8u)), dim3(VS_THREADS), 0, ctx->stream, z, zstride, (u32)m,
+                     (u32)k, (Fr*)d_w, (Fr*)d_rows_i);
+  const u32 blocks = std::min<u32>(vs_tiles(m, k), ctx->n_cu * 3u);
+  const Fr* y = (const Fr*)d_values + first * item_stride;
+  if (mont)
+    hipLaunchKernelGGL(k_vs_polys<2>, dim3(blocks), dim3(VS_THREADS), 0, ctx->stream, z, zstride, y, (u64)item_stride, (const Fr*)d_w, (const Fr*)nullptr, (u32)m,
+                       (u32)k, log2kp, (Fr*)d_rows_i, (Fr*)d_rows_z);
+  else
+    hipLaunchKernelGGL(k_vs_polys<1>, dim3(blocks), dim3(VS_THREADS), 0, ctx->stream, z, zstride, y, (u64)item_stride, (const Fr*)d_w, (const Fr*)nullptr, (u32)m,
+                       (u32)k, log2kp, (Fr*)d_rows_i, (Fr*)d_rows_z);
+  return launch_check(ctx, "set_pairs_rows");
 }
 
 keaki_status verify_sets_pairs_run(keaki_hip_ctx* ctx, const void* d_l_jac, const void* d_rows_jac, size_t k, void* d_sums_aff, void* d_ps_aff) {

@@ -38,6 +38,8 @@ EXPORTS = [
     "keaki_hip_kzg_verify_sets", "keaki_hip_kzg_verify_sets_dev", "keaki_hip_pairing_product", "keaki_hip_pairing_product_dev",
     "keaki_hip_srs_g1_precompute_cosets", "keaki_hip_kzg_coset_pairs", "keaki_hip_kzg_coset_pairs_dev",
     "keaki_hip_kzg_verify_cosets_each", "keaki_hip_kzg_verify_cosets_each_dev",
+    "keaki_hip_srs_g2_precompute_sets", "keaki_hip_kzg_set_pairs", "keaki_hip_kzg_set_pairs_dev",
+    "keaki_hip_kzg_verify_sets_each", "keaki_hip_kzg_verify_sets_each_dev",
     "keaki_hip_group_create", "keaki_hip_group_destroy", "keaki_hip_group_size", "keaki_hip_group_ctx", "keaki_hip_group_last_error",
     "keaki_hip_group_peer_note", "keaki_hip_group_srs_g1_upload", "keaki_hip_group_srs_g1_len", "keaki_hip_group_srs_g1_has_tables", "keaki_hip_group_srs_g1_free", "keaki_hip_group_msm_g1",
     "keaki_hip_group_kzg_open", "keaki_hip_group_encap_batch", "keaki_hip_group_decap_batch",
@@ -236,6 +238,10 @@ def load_library():
         lib.keaki_hip_kzg_coset_pairs.argtypes = lib.keaki_hip_kzg_coset_pairs_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, sz, vp, vp]
         lib.keaki_hip_kzg_verify_cosets_each.argtypes = lib.keaki_hip_kzg_verify_cosets_each_dev.argtypes = [
             vp, vp, vp, i32, vp, vp, i32, vp, sz, sz, C.c_uint32, vp, vp, vp, sz, vp, vp, vp, vp]
+        lib.keaki_hip_srs_g2_precompute_sets.argtypes = [vp, vp, sz]
+        lib.keaki_hip_kzg_set_pairs.argtypes = lib.keaki_hip_kzg_set_pairs_dev.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, sz, sz, sz, vp, vp]
+        lib.keaki_hip_kzg_verify_sets_each.argtypes = lib.keaki_hip_kzg_verify_sets_each_dev.argtypes = [
+            vp, vp, vp, vp, i32, vp, i32, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
         lib.keaki_hip_kzg_verify_multi.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_int32), vp]
         lib.keaki_hip_srs_g1_precompute_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
         lib.keaki_hip_open_fk_cosets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -866,6 +872,69 @@ class KeakiHip:
         self._ck(self.lib.keaki_hip_kzg_verify_cosets_each_dev(self.ctx, srs_g1.handle, dp(d_com), int(com_stride), dp(d_tau_l_g2), dp(d_points), int(point_mode),
                                                                dp(d_values), int(item_stride), int(t_stride), int(log2l), _ptr(_np(omega_l_inv)),
                                                                _ptr(_np(inv_l)), dp(d_proofs), int(n), dp(d_status), C.byref(bad), C.byref(first), dp(d_lhs)))
+        return bad.value, (None if bad.value == 0 else first.value)
+
+    def srs_g2_precompute_sets(self, srs: "SrsG2", k_max: int):
+        """builds the G2 handle's window table over its first k_max points ahead of the first kzg_set_pairs / kzg_verify_sets_each call
+        (keaki_hip_srs_g2_precompute_sets); results never depend on it"""
+        self._ck(self.lib.keaki_hip_srs_g2_precompute_sets(self.ctx, srs.handle, int(k_max)))
+
+    def _set_items(self, what, com_aff, points, values, k, n, item_stride, omega):
+        c, v = _np(com_aff, 8), _np(values, 4)
+        n, k = int(n), int(k)
+        stride = k if item_stride is None else int(item_stride)
+        point_mode = 0 if omega is None else 1
+        z = np.ascontiguousarray(points, np.uint32).reshape(-1) if point_mode else _np(points, 4)
+        com_stride = 0 if c.shape[0] == 1 else 1
+        if com_stride and c.shape[0] != n:
+            raise ValueError("%s: array lengths disagree" % what)
+        if n and stride >= k >= 1 and min(z.shape[0], v.shape[0]) < (n - 1) * stride + k:
+            raise ValueError("%s: the stride reaches past the %d points / %d values given" % (what, z.shape[0], v.shape[0]))
+        return c, com_stride, z, point_mode, (_ptr(_np(omega)) if point_mode else None), v, stride, k, n
+
+    def kzg_set_pairs(self, srs_g1: "SrsG1", srs_g2: "SrsG2", com_aff, points, values, k: int, n: int, item_stride: int = None, omega=None):
+        """the per-item points of the set check over arbitrary point sets (keaki_hip_kzg_set_pairs) -> (A u64[n, 8], Z2 u64[n, 16]): A_i = C_i - [I_i(tau)]_1
+        and Z2_i = [Z_i(tau)]_2. Arguments as kzg_verify_sets, without proofs and gammas; n is explicit because with one commitment no array carries it"""
+        c, com_stride, z, point_mode, om, v, stride, k, n = self._set_items("kzg_set_pairs", com_aff, points, values, k, n, item_stride, omega)
+        lhs = np.zeros((n, 8), np.uint64); z2 = np.zeros((n, 16), np.uint64)
+        self._ck(self.lib.keaki_hip_kzg_set_pairs(self.ctx, srs_g1.handle, srs_g2.handle, _ptr(c), com_stride, _ptr(z), point_mode, om, _ptr(v), stride, k, n,
+                                                  _ptr(lhs), _ptr(z2)))
+        return lhs, z2
+
+    def kzg_set_pairs_dev(self, srs_g1: "SrsG1", srs_g2: "SrsG2", d_com, com_stride: int, d_points, point_mode: int, omega, d_values, item_stride: int, k: int,
+                          n: int, d_lhs_out, d_z2_out):
+        """the same with every array resident: device pointers (ints) or torch tensors; omega stays a host array (None in point_mode 0). Asynchronous on
+        the context's stream. The caller answers for the extent of d_points and d_values under the stride"""
+        dp = lambda x: C.c_void_p(None if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else x))
+        self._ck(self.lib.keaki_hip_kzg_set_pairs_dev(self.ctx, srs_g1.handle, srs_g2.handle, dp(d_com), int(com_stride), dp(d_points), int(point_mode),
+                                                      _ptr(_np(omega)) if omega is not None else None, dp(d_values), int(item_stride), int(k), int(n),
+                                                      dp(d_lhs_out), dp(d_z2_out)))
+
+    def kzg_verify_sets_each(self, srs_g1: "SrsG1", srs_g2: "SrsG2", com_aff, points, values, k: int, proofs_aff, item_stride: int = None, omega=None,
+                             want_pairs: bool = False):
+        """one verdict per set proof over arbitrary point sets (keaki_hip_kzg_verify_sets_each) -> (status uint8[n]: 0 valid / 1 invalid, n_bad, first_bad
+        or None), and with want_pairs two more elements: A (u64[n, 8]) and Z2 (u64[n, 16]). Arguments as kzg_verify_sets, without gammas"""
+        pr = _np(proofs_aff, 8)
+        c, com_stride, z, point_mode, om, v, stride, k, n = self._set_items("kzg_verify_sets_each", com_aff, points, values, k, pr.shape[0], item_stride, omega)
+        status = np.zeros(n, np.uint8)
+        lhs = np.zeros((n, 8), np.uint64) if want_pairs else None
+        z2 = np.zeros((n, 16), np.uint64) if want_pairs else None
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_kzg_verify_sets_each(self.ctx, srs_g1.handle, srs_g2.handle, _ptr(c), com_stride, _ptr(z), point_mode, om, _ptr(v), stride, k,
+                                                         _ptr(pr), n, _ptr(status), C.byref(bad), C.byref(first), _ptr(lhs) if want_pairs else None,
+                                                         _ptr(z2) if want_pairs else None))
+        res = (status, bad.value, (None if bad.value == 0 else first.value))
+        return res + (lhs, z2) if want_pairs else res
+
+    def kzg_verify_sets_each_dev(self, srs_g1: "SrsG1", srs_g2: "SrsG2", d_com, com_stride: int, d_points, point_mode: int, omega, d_values, item_stride: int,
+                                 k: int, d_proofs, n: int, d_status, d_lhs=None, d_z2=None):
+        """the same with every array resident; the status bytes (and the pairs) stay on the device -> (n_bad, first_bad or None) on the host (the call
+        synchronises)"""
+        dp = lambda x: C.c_void_p(None if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else x))
+        bad, first = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.keaki_hip_kzg_verify_sets_each_dev(self.ctx, srs_g1.handle, srs_g2.handle, dp(d_com), int(com_stride), dp(d_points), int(point_mode),
+                                                             _ptr(_np(omega)) if omega is not None else None, dp(d_values), int(item_stride), int(k),
+                                                             dp(d_proofs), int(n), dp(d_status), C.byref(bad), C.byref(first), dp(d_lhs), dp(d_z2)))
         return bad.value, (None if bad.value == 0 else first.value)
 
     def kzg_verify_each(self, com_aff, tau_g2_aff, points, values, proofs_aff, point_mode: int = 0, want_lhs: bool = False):

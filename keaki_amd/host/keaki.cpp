@@ -705,6 +705,145 @@ bool verify_sets_indexed(Rng& rng, const KZGSetup& setup, const G1& com, const F
                                        values, proofs, gammas);
 }
 
+namespace {
+void sets_flat_check(const char* what, const KZGSetup& setup, size_t n_coms, size_t k, size_t n) {
+  const std::string w(what);
+  if (k < 1 || k > (size_t)KEAKI_VERIFY_SETS_K_MAX) throw SetError(w + ": a set holds 1 .. " + std::to_string((int)KEAKI_VERIFY_SETS_K_MAX) + " points");
+  if (k > setup.g1_pow().size()) throw SetError(w + ": the set is larger than the SRS");
+  if (n_coms != 1 && n_coms != n) throw SetError(w + ": one commitment, or one per item");
+  if (setup.g2_pow().size() <= k) throw SetError(w + ": this KZGSetup holds no [tau^k]_2: build it with G2 powers beyond k (setup_with_g2, from_powers_g2)");
+  if (setup.device()->group()) throw SetError(w + ": single device only");
+}
+// what the grouping layers refuse, before any device call (and before any draw of their callers): -> the size of every item
+std::vector<size_t> sets_rows_check(const char* what, const KZGSetup& setup, size_t n_coms, const std::vector<std::vector<Fr>>& points,
+                                    const std::vector<std::vector<Fr>>& values, size_t n_proofs) {
+  const std::string w(what);
+  const size_t n = points.size();
+  if (values.size() != n || n_proofs != n || (n_coms != 1 && n_coms != n)) throw SetError(w + ": points, values and proofs must have one entry per item, commitments one or n");
+  std::vector<size_t> sizes(n);
+  for (size_t i = 0; i < n; i++) {
+    if (points[i].empty() || points[i].size() > (size_t)KEAKI_VERIFY_SETS_K_MAX)
+      throw SetError(w + ": a set holds 1 .. " + std::to_string((int)KEAKI_VERIFY_SETS_K_MAX) + " points");
+    check_set(what, points[i], values[i].size());
+    sizes[i] = points[i].size();
+    sets_flat_check(what, setup, n_coms, sizes[i], n);
+  }
+  if (setup.device()->group()) throw SetError(w + ": single device only");
+  return sizes;
+}
+std::vector<size_t> sets_idx_check(const char* what, const KZGSetup& setup, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                                   const std::vector<std::vector<Fr>>& values, size_t n_proofs) {
+  const std::string w(what);
+  const size_t n = idx_rows.size();
+  if (values.size() != n || n_proofs != n) throw SetError(w + ": idx_rows, values and proofs must have one entry per item");
+  std::vector<size_t> sizes(n);
+  for (size_t i = 0; i < n; i++) {
+    const std::vector<size_t>& row = idx_rows[i];
+    if (row.empty() || row.size() > (size_t)KEAKI_VERIFY_SETS_K_MAX) throw SetError(w + ": a subset holds 1 .. " + std::to_string((int)KEAKI_VERIFY_SETS_K_MAX) + " positions");
+    if (values[i].size() != row.size()) throw SetError(w + ": one value per position");
+    std::vector<size_t> s(row);
+    std::sort(s.begin(), s.end());
+    if (s.back() >= domain || s.back() > 0xFFFFFFFFull) throw SetError(w + ": index outside the domain");
+    if (std::adjacent_find(s.begin(), s.end()) != s.end()) throw SetError(w + ": repeated index in a subset");
+    sizes[i] = row.size();
+    sets_flat_check(what, setup, 1, sizes[i], n);
+  }
+  if (setup.device()->group()) throw SetError(w + ": single device only");
+  return sizes;
+}
+// One call of `run(k, items, coms, n_coms, pts, vals)` per set size: items = the indices of the group's items in the caller's order, the buffers flat as the
+// _flat entries take them. `fill(i, dst)` appends item i's point words (Fr, or u32 indices).
+template <class Elem, class Fill, class Run>
+void sets_each_group(const std::vector<G1>& commitments, const std::vector<size_t>& sizes, Fill fill, const std::vector<std::vector<Fr>>& values, Run run) {
+  std::map<size_t, std::vector<size_t>> groups;
+  for (size_t i = 0; i < sizes.size(); i++) groups[sizes[i]].push_back(i);
+  for (const auto& [k, items] : groups) {
+    const size_t m = items.size();
+    std::vector<Elem> pts;
+    std::vector<Fr> vals;
+    std::vector<G1> coms(commitments.size() == 1 ? 1 : m);
+    pts.reserve(m * k);
+    vals.reserve(m * k);
+    for (size_t t = 0; t < m; t++) {
+      fill(items[t], pts);
+      vals.insert(vals.end(), values[items[t]].begin(), values[items[t]].end());
+      if (commitments.size() != 1) coms[t] = commitments[items[t]];
+    }
+    if (commitments.size() == 1) coms[0] = commitments[0];
+    run(k, items, coms[0].w.data(), coms.size(), (const void*)pts.data(), vals.data());
+  }
+}
+template <class Elem, class Fill>
+void set_pairs_grouped(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<size_t>& sizes, Fill fill, const Fr* omega,
+                       const std::vector<std::vector<Fr>>& values, uint64_t* lhs_out, uint64_t* z2_out) {
+  sets_each_group<Elem>(commitments, sizes, fill, values, [&](size_t k, const std::vector<size_t>& items, const uint64_t* coms, size_t n_coms, const void* pts, const Fr* vals) {
+    const size_t m = items.size();
+    std::vector<uint64_t> a(m * 8), z(m * 16);
+    set_pairs_flat(setup, coms, n_coms, pts, omega, vals, k, m, a.data(), z.data());
+    for (size_t t = 0; t < m; t++) {
+      memcpy(lhs_out + 8 * items[t], a.data() + 8 * t, 64);
+      memcpy(z2_out + 16 * items[t], z.data() + 16 * t, 128);
+    }
+  });
+}
+template <class Elem, class Fill>
+std::vector<uint8_t> verify_sets_each_grouped(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<size_t>& sizes, Fill fill, const Fr* omega,
+                                              const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  std::vector<uint8_t> status(sizes.size());
+  sets_each_group<Elem>(commitments, sizes, fill, values, [&](size_t k, const std::vector<size_t>& items, const uint64_t* coms, size_t n_coms, const void* pts, const Fr* vals) {
+    const size_t m = items.size();
+    std::vector<G1> pr(m);
+    for (size_t t = 0; t < m; t++) pr[t] = proofs[items[t]];
+    const std::vector<uint8_t> st = verify_sets_each_flat(setup, coms, n_coms, pts, omega, vals, k, pr[0].w.data(), m);
+    for (size_t t = 0; t < m; t++) status[items[t]] = st[t];
+  });
+  return status;
+}
+}  // namespace
+void set_pairs_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const void* points, const Fr* omega, const Fr* values, size_t k, size_t n,
+                    uint64_t* lhs_out, uint64_t* z2_out) {
+  sets_flat_check("set_pairs", setup, n_coms, k, n);
+  if (n == 0) return;
+  const Device& dev = *setup.device();
+  dev.check(keaki_hip_kzg_set_pairs(dev.ctx(), setup.srs(), setup.srs_g2(), coms, n_coms == 1 ? 0 : 1, points, omega ? 1 : 0, omega ? omega->l : nullptr, values[0].l, k, k,
+                                    n, lhs_out, z2_out));
+}
+std::vector<uint8_t> verify_sets_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const void* points, const Fr* omega, const Fr* values, size_t k,
+                                           const uint64_t* proofs, size_t n) {
+  sets_flat_check("verify_sets_each", setup, n_coms, k, n);
+  std::vector<uint8_t> status(n);
+  if (n == 0) return status;
+  const Device& dev = *setup.device();
+  uint64_t n_bad = 0;
+  dev.check(keaki_hip_kzg_verify_sets_each(dev.ctx(), setup.srs(), setup.srs_g2(), coms, n_coms == 1 ? 0 : 1, points, omega ? 1 : 0, omega ? omega->l : nullptr,
+                                           values[0].l, k, k, proofs, n, status.data(), &n_bad, nullptr, nullptr, nullptr));
+  return status;
+}
+void set_pairs(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points, const std::vector<std::vector<Fr>>& values,
+               uint64_t* lhs_out, uint64_t* z2_out) {
+  const std::vector<size_t> sizes = sets_rows_check("set_pairs", setup, commitments.size(), points, values, points.size());
+  set_pairs_grouped<Fr>(setup, commitments, sizes, [&](size_t i, std::vector<Fr>& dst) { dst.insert(dst.end(), points[i].begin(), points[i].end()); }, nullptr, values,
+                        lhs_out, z2_out);
+}
+void set_pairs_indexed(const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                       const std::vector<std::vector<Fr>>& values, uint64_t* lhs_out, uint64_t* z2_out) {
+  const std::vector<size_t> sizes = sets_idx_check("set_pairs", setup, domain, idx_rows, values, idx_rows.size());
+  set_pairs_grouped<uint32_t>(setup, {com}, sizes, [&](size_t i, std::vector<uint32_t>& dst) { for (size_t e : idx_rows[i]) dst.push_back((uint32_t)e); }, &omega, values,
+                              lhs_out, z2_out);
+}
+std::vector<uint8_t> verify_sets_each(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points,
+                                      const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  const std::vector<size_t> sizes = sets_rows_check("verify_sets_each", setup, commitments.size(), points, values, proofs.size());
+  return verify_sets_each_grouped<Fr>(setup, commitments, sizes, [&](size_t i, std::vector<Fr>& dst) { dst.insert(dst.end(), points[i].begin(), points[i].end()); }, nullptr,
+                                      values, proofs);
+}
+std::vector<uint8_t> verify_sets_each_indexed(const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                                              const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  const std::vector<size_t> sizes = sets_idx_check("vec_verify_subsets_each", setup, domain, idx_rows, values, proofs.size());
+  return verify_sets_each_grouped<uint32_t>(setup, {com}, sizes, [&](size_t i, std::vector<uint32_t>& dst) { for (size_t e : idx_rows[i]) dst.push_back((uint32_t)e); },
+                                            &omega, values, proofs);
+}
+
 }  // namespace kzg
 
 // ------------------------------------------------------------------------------------------------ kem / enc
@@ -742,6 +881,40 @@ std::pair<G2, std::vector<uint8_t>> encapsulate_set(Rng& rng, const kzg::KZGSetu
   return encap_pair(setup, az, r, msg_len);
 }
 
+void seal_pairs(Rng& rng, const kzg::KZGSetup& setup, const uint64_t* lhs, const uint64_t* z2, size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out,
+                uint8_t* bodies_out) {
+  if (!n) return;
+  const Device& dev = *setup.device();
+  std::vector<Fr> rs(n), zeros(n);
+  for (size_t i = 0; i < n; i++) rs[i] = fr_rand(rng);      // one r per item in index order, as everywhere else
+  std::vector<uint64_t> offsets(n + 1);
+  for (size_t i = 0; i <= n; i++) offsets[i] = i;
+  // n groups of one item with coms := A, points = values = 0: key_i = KDF(e(r_i A_i, g2)); the G2 output of this call (r_i [tau]_2) is replaced below
+  const uint64_t* tau = setup.tau_g2().w.data();
+  if (msgs && msg_len) {
+    dev.check(keaki_hip_encrypt_multi(dev.ctx(), lhs, offsets.data(), n, tau, zeros[0].l, zeros[0].l, rs[0].l, msgs, n, ct_g2_out, bodies_out, msg_len));
+  } else {
+    std::vector<uint8_t> gt_unused(n * 384);
+    dev.check(keaki_hip_encap_multi(dev.ctx(), lhs, offsets.data(), n, tau, zeros[0].l, zeros[0].l, rs[0].l, n, ct_g2_out, gt_unused.data(), msg_len ? bodies_out : nullptr,
+                                    msg_len));
+  }
+  dev.check(keaki_hip_g2_mul_batch(dev.ctx(), z2, 1, rs[0].l, n, ct_g2_out));      // ct_i = r_i Z2_i
+}
+std::vector<std::pair<G2, std::vector<uint8_t>>> encapsulate_sets(Rng& rng, const kzg::KZGSetup& setup, const std::vector<G1>& commitments,
+                                                                  const std::vector<std::vector<Fr>>& points, const std::vector<std::vector<Fr>>& values, size_t msg_len) {
+  const size_t n = points.size();
+  std::vector<uint64_t> a(n * 8), z(n * 16), ct(n * 16);
+  std::vector<uint8_t> keys(n * msg_len);
+  kzg::set_pairs(setup, commitments, points, values, a.data(), z.data());      // throws before the draws: a refused call leaves `rng` alone
+  seal_pairs(rng, setup, a.data(), z.data(), n, nullptr, msg_len, ct.data(), keys.data());
+  std::vector<std::pair<G2, std::vector<uint8_t>>> out(n);
+  for (size_t i = 0; i < n; i++) {
+    memcpy(out[i].first.w.data(), ct.data() + 16 * i, 128);
+    out[i].second.assign(keys.begin() + i * msg_len, keys.begin() + (i + 1) * msg_len);
+  }
+  return out;
+}
+
 void prepare(const kzg::KZGSetup& setup, size_t batch_hint) {
   const Device& dev = *setup.device();
   if (dev.group() && batch_hint >= GROUP_MIN_ITEMS) {
@@ -770,6 +943,21 @@ Ciphertext encrypt_set(Rng& rng, const kzg::KZGSetup& setup, const G1& com, cons
   std::vector<uint8_t> ct(msg.size());
   for (size_t i = 0; i < msg.size(); i++) ct[i] = kc.second[i] ^ msg[i];
   return {kc.first, ct};
+}
+std::vector<Ciphertext> encrypt_sets(Rng& rng, const kzg::KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points,
+                                     const std::vector<std::vector<Fr>>& values, const std::vector<std::vector<uint8_t>>& messages) {
+  const size_t n = points.size(), len = messages.empty() ? 0 : messages[0].size();
+  if (messages.size() != n) throw kzg::SetError("encrypt_sets: one message per item");
+  for (const auto& m : messages)
+    if (m.size() != len) throw kzg::SetError("encrypt_sets: all messages of one length");
+  auto kc = kem::encapsulate_sets(rng, setup, commitments, points, values, len);
+  std::vector<Ciphertext> out(n);
+  for (size_t i = 0; i < n; i++) {
+    out[i].first = kc[i].first;
+    out[i].second.resize(len);
+    for (size_t j = 0; j < len; j++) out[i].second[j] = kc[i].second[j] ^ messages[i][j];
+  }
+  return out;
 }
 std::vector<uint8_t> decrypt(const kzg::KZGSetup& setup, const G1& proof, const Ciphertext& ct) {
   std::vector<uint8_t> key = kem::decapsulate(setup, proof, ct.first, ct.second.size());
@@ -1167,6 +1355,23 @@ bool vec_verify_subsets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, siz
                         const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
   const Radix2Domain dom = Radix2Domain::create(domain_size);
   return kzg::verify_sets_indexed(rng, setup, com, dom.group_gen, dom.size, idx_rows, values, proofs);
+}
+std::vector<uint8_t> vec_verify_subsets_each(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
+                                             const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs) {
+  const Radix2Domain dom = Radix2Domain::create(domain_size);
+  return kzg::verify_sets_each_indexed(setup, com, dom.group_gen, dom.size, idx_rows, values, proofs);
+}
+void vec_encrypt_subsets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
+                         const std::vector<std::vector<Fr>>& values, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  const Radix2Domain dom = Radix2Domain::create(domain_size);
+  const size_t n = idx_rows.size();
+  std::vector<uint64_t> a(n * 8), z(n * 16);
+  kzg::set_pairs_indexed(setup, com, dom.group_gen, dom.size, idx_rows, values, a.data(), z.data());      // every refusal comes before the first draw from rng
+  if (msg_len) {
+    kem::seal_pairs(rng, setup, a.data(), z.data(), n, msgs, msg_len, ct_g2_out, ct_msg_out);
+  } else {
+    kem::seal_pairs(rng, setup, a.data(), z.data(), n, nullptr, 0, ct_g2_out, nullptr);
+  }
 }
 std::vector<G1> vec_open_cosets(const kzg::KZGSetup& setup, const std::vector<Fr>& evals, size_t l) {
   if (evals.empty()) throw kzg::SetError("vec_open_cosets: no evaluations");

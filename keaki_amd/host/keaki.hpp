@@ -277,9 +277,36 @@ bool verify_sets_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms
 bool verify_sets_indexed(Rng& rng, const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
                          const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
 
+// The per-item side of verify_sets (keaki_hip_kzg_set_pairs, keaki_hip_kzg_verify_sets_each). Nothing is drawn: the results are exact.
+// set_pairs_flat: ONE group on contiguous buffers, addressed as verify_sets_flat: lhs_out[8 i ..] = A_i = C_i - [I_i(tau)]_1, z2_out[16 i ..] = Z2_i =
+// [Z_i(tau)]_2 (affine words, zeros = the identity). verify_sets_each_flat: one byte per item, 0 = the set proof holds (= verify_set on the item).
+// Both refuse what verify_sets_flat refuses.
+void set_pairs_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const void* points, const Fr* omega, const Fr* values, size_t k, size_t n,
+                    uint64_t* lhs_out, uint64_t* z2_out);
+std::vector<uint8_t> verify_sets_each_flat(const KZGSetup& setup, const uint64_t* coms, size_t n_coms, const void* points, const Fr* omega, const Fr* values, size_t k,
+                                           const uint64_t* proofs, size_t n);
+// Items of unequal size, grouped by size into one device call each as verify_sets does, the results back in item order. Refusals as verify_sets (a repeated
+// point within an item, an empty or too large set, sizes that disagree, G2 powers that do not reach the largest set, a device group), all before any call.
+// set_pairs: lhs_out n x 8 words, z2_out n x 16 words. The _indexed forms take ONE commitment and domain indices (z = omega^index, derived on the device)
+// and also refuse an index >= domain and a repeated index.
+void set_pairs(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points, const std::vector<std::vector<Fr>>& values,
+               uint64_t* lhs_out, uint64_t* z2_out);
+void set_pairs_indexed(const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                       const std::vector<std::vector<Fr>>& values, uint64_t* lhs_out, uint64_t* z2_out);
+std::vector<uint8_t> verify_sets_each(const KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points,
+                                      const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
+std::vector<uint8_t> verify_sets_each_indexed(const KZGSetup& setup, const G1& com, const Fr& omega, size_t domain, const std::vector<std::vector<size_t>>& idx_rows,
+                                              const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
+
 }  // namespace kzg
 
 namespace kem {
+// What encapsulate_sets, enc::encrypt_sets and vec::vec_encrypt_subsets end in, on the n pairs of kzg::set_pairs: one r per item in index order, ONE
+// keaki_hip_encrypt_multi / _encap_multi call with n groups of one item (coms := A, points = values = 0: key_i = KDF(e(r_i A_i, g2))), then ct_i = r_i Z2_i by ONE
+// keaki_hip_g2_mul_batch. msgs (n x msg_len) given: bodies_out = msgs ^ keys; null: bodies_out = the keys. Every item equals encapsulate_set / encrypt_set
+// alone with the same r, byte for byte.
+void seal_pairs(Rng& rng, const kzg::KZGSetup& setup, const uint64_t* lhs, const uint64_t* z2, size_t n, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out,
+                uint8_t* bodies_out);
 // src/kem.rs:13-50 / :55-72
 std::pair<G2, std::vector<uint8_t>> encapsulate(Rng& rng, const kzg::KZGSetup& setup, const G1& commitment, const Fr& point,
                                                 const Fr& value, size_t msg_len);
@@ -292,6 +319,10 @@ void prepare(const kzg::KZGSetup& setup, size_t batch_hint);
 // Decapsulation is the UNCHANGED decapsulate(setup, pi_S, ct, msg_len) above: e(pi_S, r [Z]_2) is the same GT element; there is no second function.
 std::pair<G2, std::vector<uint8_t>> encapsulate_set(Rng& rng, const kzg::KZGSetup& setup, const G1& commitment, const std::vector<Fr>& points,
                                                     const std::vector<Fr>& values, size_t msg_len);
+// encapsulate_set for n items, each with its own point set (and its own commitment, or the one of all), in one kzg::set_pairs and one seal_pairs. Every refusal
+// (kzg::set_pairs's) comes before the first draw; then one r per item in index order.
+std::vector<std::pair<G2, std::vector<uint8_t>>> encapsulate_sets(Rng& rng, const kzg::KZGSetup& setup, const std::vector<G1>& commitments,
+                                                                  const std::vector<std::vector<Fr>>& points, const std::vector<std::vector<Fr>>& values, size_t msg_len);
 }  // namespace kem
 
 namespace enc {
@@ -301,6 +332,10 @@ std::vector<uint8_t> decrypt(const kzg::KZGSetup& setup, const G1& proof, const 
 // encapsulate_set plus the XOR; decryption is the unchanged decrypt(setup, pi_S, ct)
 Ciphertext encrypt_set(Rng& rng, const kzg::KZGSetup& setup, const G1& com, const std::vector<Fr>& points, const std::vector<Fr>& values,
                        const std::vector<uint8_t>& msg);
+// encrypt_set for n items with their own point sets (kem::encapsulate_sets plus the XOR); messages: one per item, all of one length. The unchanged decrypt
+// with the set proof of item i opens ciphertext i.
+std::vector<Ciphertext> encrypt_sets(Rng& rng, const kzg::KZGSetup& setup, const std::vector<G1>& commitments, const std::vector<std::vector<Fr>>& points,
+                                     const std::vector<std::vector<Fr>>& values, const std::vector<std::vector<uint8_t>>& messages);
 // Ciphertexts on the wire: n x (64 B compressed G2 point + body), the point as ark-serialize `serialize_compressed` writes it
 // (include/keaki_hip.h: compressed point wire format), all bodies of one length. The points are compressed / decompressed on the device in one
 // call. `ciphertexts_from_bytes` VALIDATES like `deserialize_compressed`: canonical encoding, on the twist, in the order-r subgroup (the points
@@ -366,6 +401,14 @@ bool vec_verify_subset(const kzg::KZGSetup& setup, const G1& com, size_t domain_
 // sizes that disagree, and what kzg::verify_sets refuses about the setup and the device.
 bool vec_verify_subsets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
                         const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
+// WHICH subset proofs are wrong: one byte per item (0 = valid) from kzg::verify_sets_each_indexed; nothing is drawn. Refusals as vec_verify_subsets.
+std::vector<uint8_t> vec_verify_subsets_each(const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
+                                             const std::vector<std::vector<Fr>>& values, const std::vector<G1>& proofs);
+// Message i to the claimed values[i] at the positions idx_rows[i] of ONE committed vector, every item with its OWN index set (vec_encrypt_subset_batch shares
+// one): kzg::set_pairs_indexed, then kem::seal_pairs. msgs n x msg_len. Every refusal comes before the first draw; item i equals enc::encrypt_set on the points
+// omega^idx with the same r, and the unchanged decrypt with vec_open_subset's proof opens it.
+void vec_encrypt_subsets(Rng& rng, const kzg::KZGSetup& setup, const G1& com, size_t domain_size, const std::vector<std::vector<size_t>>& idx_rows,
+                         const std::vector<std::vector<Fr>>& values, const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out);
 // For the holder of the vector who wants EVERY block proof: evals are the evaluations over Radix2Domain::create(evals.size()) (what vec_commit
 // commits to: the vector, its padding scalar, zeros); the inverse transform, then kzg::open_fk_cosets: r = size / l proofs, proof i for the
 // positions vec_coset_indices(size, l, i) = {i + t r : t < l} -- the index list vec_verify_subset and vec_encrypt_subset_batch take.

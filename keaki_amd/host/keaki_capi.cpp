@@ -334,6 +334,87 @@ int keaki_host_verify_sets(void* rng, void* s, const uint64_t* coms, size_t n_co
     return 0;
   });
 }
+// the per-item side (include/keaki_hip.h: keaki_hip_kzg_set_pairs, keaki_hip_kzg_verify_sets_each); arrays as keaki_host_verify_sets. status_out: n bytes, 0 = valid;
+// a_out n x 8 words, z2_out n x 16 words; msgs n x msg_len; ct_g2_out n x 16 words, bodies n x msg_len
+namespace {
+struct SetRows { std::vector<G1> c; std::vector<std::vector<Fr>> z, y; std::vector<std::vector<size_t>> rows; };
+SetRows set_rows(const uint64_t* coms, size_t n_coms, const uint64_t* sizes, const uint64_t* points, const uint64_t* idx, const uint64_t* values, size_t n) {
+  SetRows r;
+  r.c.resize(n_coms); r.z.resize(n); r.y.resize(n); r.rows.resize(n);
+  for (size_t i = 0; i < n_coms; i++) r.c[i] = g1_of(coms + 8 * i);
+  for (size_t i = 0, at = 0; i < n; at += sizes[i], i++) {
+    if (points) r.z[i] = frs_of(points + 4 * at, sizes[i]);
+    if (idx) r.rows[i] = idx_of(idx + at, sizes[i]);
+    r.y[i] = frs_of(values + 4 * at, sizes[i]);
+  }
+  return r;
+}
+std::vector<G1> g1s_of(const uint64_t* p, size_t n) {
+  std::vector<G1> v(n);
+  for (size_t i = 0; i < n; i++) v[i] = g1_of(p + 8 * i);
+  return v;
+}
+}  // namespace
+int keaki_host_set_pairs(void* s, const uint64_t* coms, size_t n_coms, const uint64_t* sizes, const uint64_t* points, const uint64_t* values, size_t n, uint64_t* a_out,
+                         uint64_t* z2_out) {
+  return guard([&] {
+    const SetRows r = set_rows(coms, n_coms, sizes, points, nullptr, values, n);
+    kzg::set_pairs(((Setup*)s)->s, r.c, r.z, r.y, a_out, z2_out);
+    return 0;
+  });
+}
+int keaki_host_verify_sets_each(void* s, const uint64_t* coms, size_t n_coms, const uint64_t* sizes, const uint64_t* points, const uint64_t* values, const uint64_t* proofs,
+                                size_t n, uint8_t* status_out) {
+  return guard([&] {
+    const SetRows r = set_rows(coms, n_coms, sizes, points, nullptr, values, n);
+    const std::vector<uint8_t> st = kzg::verify_sets_each(((Setup*)s)->s, r.c, r.z, r.y, g1s_of(proofs, n));
+    if (n) memcpy(status_out, st.data(), n);
+    return 0;
+  });
+}
+int keaki_host_vec_verify_subsets_each(void* s, const uint64_t* com, size_t domain_size, const uint64_t* sizes, const uint64_t* idx, const uint64_t* values,
+                                       const uint64_t* proofs, size_t n, uint8_t* status_out) {
+  return guard([&] {
+    const SetRows r = set_rows(com, 1, sizes, nullptr, idx, values, n);
+    const std::vector<uint8_t> st = vec::vec_verify_subsets_each(((Setup*)s)->s, r.c[0], domain_size, r.rows, r.y, g1s_of(proofs, n));
+    if (n) memcpy(status_out, st.data(), n);
+    return 0;
+  });
+}
+int keaki_host_encapsulate_sets(void* rng, void* s, const uint64_t* coms, size_t n_coms, const uint64_t* sizes, const uint64_t* points, const uint64_t* values, size_t n,
+                                size_t msg_len, uint64_t* ct_g2_out, uint8_t* keys_out) {
+  return guard([&] {
+    const SetRows r = set_rows(coms, n_coms, sizes, points, nullptr, values, n);
+    const auto kc = kem::encapsulate_sets(*(Rng*)rng, ((Setup*)s)->s, r.c, r.z, r.y, msg_len);
+    for (size_t i = 0; i < n; i++) {
+      memcpy(ct_g2_out + 16 * i, kc[i].first.w.data(), 128);
+      if (msg_len) memcpy(keys_out + i * msg_len, kc[i].second.data(), msg_len);
+    }
+    return 0;
+  });
+}
+int keaki_host_encrypt_sets(void* rng, void* s, const uint64_t* coms, size_t n_coms, const uint64_t* sizes, const uint64_t* points, const uint64_t* values, size_t n,
+                            const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  return guard([&] {
+    const SetRows r = set_rows(coms, n_coms, sizes, points, nullptr, values, n);
+    std::vector<std::vector<uint8_t>> m(n);
+    for (size_t i = 0; i < n; i++) m[i].assign(msgs + i * msg_len, msgs + (i + 1) * msg_len);
+    const auto cts = enc::encrypt_sets(*(Rng*)rng, ((Setup*)s)->s, r.c, r.z, r.y, m);
+    for (size_t i = 0; i < n; i++) {
+      memcpy(ct_g2_out + 16 * i, cts[i].first.w.data(), 128);
+      if (msg_len) memcpy(ct_msg_out + i * msg_len, cts[i].second.data(), msg_len);
+    }
+    return 0;
+  });
+}
+int keaki_host_vec_encrypt_subsets(void* rng, void* s, const uint64_t* com, size_t domain_size, const uint64_t* sizes, const uint64_t* idx, const uint64_t* values, size_t n,
+                                   const uint8_t* msgs, size_t msg_len, uint64_t* ct_g2_out, uint8_t* ct_msg_out) {
+  return guard([&] {
+    const SetRows r = set_rows(com, 1, sizes, nullptr, idx, values, n);
+    vec::vec_encrypt_subsets(*(Rng*)rng, ((Setup*)s)->s, r.c[0], domain_size, r.rows, r.y, msgs, msg_len, ct_g2_out, ct_msg_out);
+    return 0;
+  });
+}
 int keaki_host_vec_verify_subsets(void* rng, void* s, const uint64_t* com, size_t domain_size, const uint64_t* sizes, const uint64_t* idx, const uint64_t* values,
                                   const uint64_t* proofs, size_t n, int* out_ok) {
   return guard([&] {

@@ -553,6 +553,89 @@ def vec_verify_subsets(rng: "Rng", setup: KZGSetup, com, domain_size: int, idx_r
     return bool(ok.value)
 
 
+def _set_rows(what, commitments, points, values, n, width):
+    """the ragged rows of a per-item set call -> (coms, sizes, flat points or indices, flat values)"""
+    coms = np.ascontiguousarray(_u64(commitments, 8))
+    zs, z = _ragged(points, width)
+    ys, y = _ragged(values, 4)
+    if zs.shape[0] != n or ys.shape[0] != n or coms.shape[0] not in (1, n):
+        raise SetError("%s: points, values and proofs must have one entry per item, commitments one or n" % what)
+    if not np.array_equal(zs, ys):
+        raise SetError("%s: one value per point" % what)
+    pad = lambda arr, shape: arr if arr.shape[0] else np.zeros(shape, np.uint64)
+    return coms, pad(zs, 1), pad(z, (1, 4) if width else 1), pad(y, (1, 4))
+
+
+def set_pairs(setup: KZGSetup, commitments, points, values):
+    """kzg::set_pairs: the two points of every item's set check, A_i = C_i - [I_i(tau)]_1 (n, 8) and Z2_i = [Z_i(tau)]_2 (n, 16); rows as verify_sets"""
+    n = len(points)
+    coms, zs, z, y = _set_rows("set_pairs", commitments, points, values, n, 4)
+    a = np.zeros((max(n, 1), 8), np.uint64); z2 = np.zeros((max(n, 1), 16), np.uint64)
+    _ck(_lib().keaki_host_set_pairs(setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(zs), _p(z), _p(y), C.c_size_t(n), _p(a), _p(z2)))
+    return a[:n], z2[:n]
+
+
+def verify_sets_each(setup: KZGSetup, commitments, points, values, proofs) -> np.ndarray:
+    """kzg::verify_sets_each: WHICH of n set proofs over arbitrary point sets are wrong -> uint8[n], 0 = valid, 1 = invalid; one device call per set size,
+    nothing is drawn. Arguments and refusals as verify_sets"""
+    pr = np.ascontiguousarray(_u64(proofs, 8)); n = pr.shape[0]
+    coms, zs, z, y = _set_rows("verify_sets_each", commitments, points, values, n, 4)
+    status = np.zeros(max(n, 1), np.uint8)
+    _ck(_lib().keaki_host_verify_sets_each(setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(zs), _p(z), _p(y), _p(pr if n else np.zeros((1, 8), np.uint64)),
+                                           C.c_size_t(n), _p(status)))
+    return status[:n]
+
+
+def vec_verify_subsets_each(setup: KZGSetup, com, domain_size: int, idx_rows, values, proofs) -> np.ndarray:
+    """vec::vec_verify_subsets_each: WHICH subset proofs of ONE committed vector are wrong -> uint8[n]; arguments and refusals as vec_verify_subsets"""
+    pr = np.ascontiguousarray(_u64(proofs, 8)); n = pr.shape[0]
+    coms, ks, ix, y = _set_rows("vec_verify_subsets_each", _u64(com), idx_rows, values, n, 0)
+    status = np.zeros(max(n, 1), np.uint8)
+    _ck(_lib().keaki_host_vec_verify_subsets_each(setup.h, _p(coms), C.c_size_t(domain_size), _p(ks), _p(ix), _p(y), _p(pr if n else np.zeros((1, 8), np.uint64)),
+                                                  C.c_size_t(n), _p(status)))
+    return status[:n]
+
+
+def _msgs(messages, n):
+    msgs = np.ascontiguousarray(messages, np.uint8).reshape(n, -1) if n else np.zeros((0, 0), np.uint8)
+    ml = msgs.shape[1]
+    body = np.zeros((max(n, 1), max(ml, 1)), np.uint8)
+    return (msgs if ml and n else body), ml, body
+
+
+def encapsulate_sets(rng: "Rng", setup: KZGSetup, commitments, points, values, msg_len: int):
+    """kem::encapsulate_sets: encapsulate_set for n items with their own point sets in one batch -> (ct_g2 (n, 16), keys (n, msg_len)). One r per item in
+    index order, after every refusal; item i equals encapsulate_set alone with the same r"""
+    n = len(points)
+    coms, zs, z, y = _set_rows("encapsulate_sets", commitments, points, values, n, 4)
+    ct = np.zeros((max(n, 1), 16), np.uint64); keys = np.zeros((max(n, 1), max(msg_len, 1)), np.uint8)
+    _ck(_lib().keaki_host_encapsulate_sets(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(zs), _p(z), _p(y), C.c_size_t(n), C.c_size_t(msg_len), _p(ct), _p(keys)))
+    return ct[:n], keys[:n, :msg_len]
+
+
+def encrypt_sets(rng: "Rng", setup: KZGSetup, commitments, points, values, messages: np.ndarray):
+    """enc::encrypt_sets: message i to the claimed values of item i's own point set; messages (n, msg_len) uint8 -> (ct_g2 (n, 16), bodies (n, msg_len)).
+    Item i equals encrypt_set alone with the same r; decrypt(setup, set_proof_i, ct_i) opens it. Refusals (SetError) leave rng untouched"""
+    n = len(points)
+    coms, zs, z, y = _set_rows("encrypt_sets", commitments, points, values, n, 4)
+    msgs, ml, body = _msgs(messages, n)
+    ct = np.zeros((max(n, 1), 16), np.uint64)
+    _ck(_lib().keaki_host_encrypt_sets(rng.h, setup.h, _p(coms), C.c_size_t(coms.shape[0]), _p(zs), _p(z), _p(y), C.c_size_t(n), _p(msgs), C.c_size_t(ml), _p(ct), _p(body)))
+    return ct[:n], body[:n, :ml]
+
+
+def vec_encrypt_subsets(rng: "Rng", setup: KZGSetup, com, domain_size: int, idx_rows, values, messages: np.ndarray):
+    """vec::vec_encrypt_subsets: message i to the claimed values[i] at the positions idx_rows[i] of ONE committed vector, every item with its own index set
+    -> (ct_g2 (n, 16), bodies (n, msg_len)). vec_open_subset's proof and the unchanged decrypt open item i. Refusals (SetError) leave rng untouched"""
+    n = len(idx_rows)
+    coms, ks, ix, y = _set_rows("vec_encrypt_subsets", _u64(com), idx_rows, values, n, 0)
+    msgs, ml, body = _msgs(messages, n)
+    ct = np.zeros((max(n, 1), 16), np.uint64)
+    _ck(_lib().keaki_host_vec_encrypt_subsets(rng.h, setup.h, _p(coms), C.c_size_t(domain_size), _p(ks), _p(ix), _p(y), C.c_size_t(n), _p(msgs), C.c_size_t(ml), _p(ct),
+                                              _p(body)))
+    return ct[:n], body[:n, :ml]
+
+
 def vec_verify_cosets(rng: "Rng", setup: KZGSetup, com, evals, l: int, proofs) -> bool:
     """vec::vec_verify_cosets: are the size / l proofs of vec_open_cosets(evals, l) the block proofs of `com`? One device call over the evaluations
     in domain order; one gamma per coset is drawn from `rng`"""

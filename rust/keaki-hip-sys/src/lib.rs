@@ -218,6 +218,24 @@ extern "C" {
                                                 item_stride: usize, t_stride: usize, log2l: u32, omega_l_inv: *const u64, inv_l: *const u64,
                                                 d_proofs_aff: *const c_void, n: usize, d_status: *mut c_void, n_bad: *mut u64, first_bad: *mut u64,
                                                 d_lhs_out_aff: *mut c_void) -> keaki_status;
+    // the per-item points of the set check over ARBITRARY point sets, n items of k <= 64 points per call: lhs_out_aff[i] = C_i - [I_i(tau)]_1 (n x u64[8]),
+    // z2_out_aff[i] = [Z_i(tau)]_2 (n x u64[16]); arguments as keaki_hip_kzg_verify_sets. Both handles keep a window table, built on first use (the G2 one also
+    // by _precompute_sets). verify_sets_each: status[i] = 0 <=> e(lhs_i, g2) == e(proof_i, z2_i); the two outputs may be null
+    pub fn keaki_hip_srs_g2_precompute_sets(ctx: *mut keaki_hip_ctx, srs: *mut keaki_hip_srs_g2, k_max: usize) -> keaki_status;
+    pub fn keaki_hip_kzg_set_pairs(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, srs_g2: *mut keaki_hip_srs_g2, com_aff: *const u64, com_stride: i32,
+                                   points: *const c_void, point_mode: i32, omega: *const u64, values: *const u64, item_stride: usize, k: usize, n: usize,
+                                   lhs_out_aff: *mut u64, z2_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_set_pairs_dev(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, srs_g2: *mut keaki_hip_srs_g2, d_com_aff: *const c_void,
+                                       com_stride: i32, d_points: *const c_void, point_mode: i32, omega: *const u64, d_values: *const c_void, item_stride: usize,
+                                       k: usize, n: usize, d_lhs_out_aff: *mut c_void, d_z2_out_aff: *mut c_void) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_sets_each(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, srs_g2: *mut keaki_hip_srs_g2, com_aff: *const u64,
+                                          com_stride: i32, points: *const c_void, point_mode: i32, omega: *const u64, values: *const u64, item_stride: usize,
+                                          k: usize, proofs_aff: *const u64, n: usize, status: *mut u8, n_bad: *mut u64, first_bad: *mut u64,
+                                          lhs_out_aff: *mut u64, z2_out_aff: *mut u64) -> keaki_status;
+    pub fn keaki_hip_kzg_verify_sets_each_dev(ctx: *mut keaki_hip_ctx, srs_g1: *mut keaki_hip_srs_g1, srs_g2: *mut keaki_hip_srs_g2, d_com_aff: *const c_void,
+                                              com_stride: i32, d_points: *const c_void, point_mode: i32, omega: *const u64, d_values: *const c_void,
+                                              item_stride: usize, k: usize, d_proofs_aff: *const c_void, n: usize, d_status: *mut c_void, n_bad: *mut u64,
+                                              first_bad: *mut u64, d_lhs_out_aff: *mut c_void, d_z2_out_aff: *mut c_void) -> keaki_status;
     // one verdict per opening: status[i] = 0 <=> e(C_i - y_i g1 + z_i proof_i, g2) e(-proof_i, [tau]_2) == 1; lhs_out_aff: n x u64[8] or null
     pub fn keaki_hip_kzg_verify_each(ctx: *mut keaki_hip_ctx, com_aff: *const u64, com_stride: i32, tau_g2_aff: *const u64, points: *const u64,
                                      point_mode: i32, values: *const u64, proofs_aff: *const u64, n: usize, status: *mut u8, n_bad: *mut u64,

@@ -556,6 +556,36 @@ pub fn verify_sets(srs: &HipSrs, g2_powers: &[G2Affine], commitments: &[G1Projec
     ok != 0
 }
 
+/// One verdict per set proof over ARBITRARY point sets of one size (`keaki_hip_kzg_verify_sets_each`): item i is valid iff
+/// `e(C_i - [I_i(tau)]_1, g2) == e(proof_i, [Z_i(tau)]_2)`, the predicate of `verify_multi` on item i. Arguments as [`verify_sets`], without gammas: the
+/// verdict is exact. A repeated point within an item is refused here (the library does not look). Returns `true` for every valid item. Single-GPU device.
+/// Like [`verify_sets`] this uploads `g2_powers` as a fresh G2 handle per call and frees it, so the handle's window table (3 - 8 ms to build) is rebuilt
+/// by every call: a caller with many batches over one setup should keep a G2 handle and call `keaki_hip_kzg_verify_sets_each` (or
+/// `keaki_hip_srs_g2_precompute_sets` + `keaki_hip_kzg_set_pairs`, which have no glue here) through `keaki_hip_sys` directly.
+pub fn verify_sets_each(srs: &HipSrs, g2_powers: &[G2Affine], commitments: &[G1Projective], points: &[Fr], k: usize, values: &[Fr], proofs: &[G1Projective]) -> Vec<bool> {
+    let dev = Device::global();
+    let n = proofs.len();
+    assert!(dev.group.is_null() && k >= 1 && k <= 64 && k <= srs.len() && g2_powers.len() > k);
+    assert!(points.len() == n * k && values.len() == n * k && (commitments.len() == 1 || commitments.len() == n));
+    points.chunks(k).for_each(assert_distinct);
+    let flat = |v: &[G1Projective]| -> Vec<u64> { G1Projective::normalize_batch(v).iter().flat_map(|p| g1_words(p)).collect() };
+    let (c, p) = (flat(commitments), flat(proofs));
+    let g2: Vec<u64> = g2_powers[..=k].iter().flat_map(|q| g2_words(q)).collect();
+    let mut srs_g2 = core::ptr::null_mut();
+    dev.check(unsafe { sys::keaki_hip_srs_g2_upload(dev.ctx, g2.as_ptr(), k + 1, &mut srs_g2) }, "srs_g2_upload");
+    let mut status = vec![0u8; n];
+    let mut n_bad = 0u64;
+    let st = unsafe {
+        sys::keaki_hip_kzg_verify_sets_each(
+            dev.ctx, srs.srs(), srs_g2, c.as_ptr(), if commitments.len() == 1 { 0 } else { 1 }, fr_ptr(points) as *const core::ffi::c_void, 0, core::ptr::null(),
+            fr_ptr(values), k, k, p.as_ptr(), n, status.as_mut_ptr(), &mut n_bad, core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut(),
+        )
+    };
+    unsafe { sys::keaki_hip_srs_g2_free(dev.ctx, srs_g2) };
+    dev.check(st, "kzg_verify_sets_each");
+    status.iter().map(|&s| s == 0).collect()
+}
+
 /// One verdict per opening (`keaki_hip_kzg_verify_each`): item i is valid iff `e(C_i - y_i g1 + z_i proof_i, g2) * e(-proof_i, [tau]_2) == 1`,
 /// the predicate of `verify` with `z_i proof_i` moved across the pairing. Arguments as [`verify_batch`], without gammas: the verdict is exact.
 /// Returns `true` for every valid item.
