@@ -1,4 +1,4 @@
-"""One small, successful call for every host-array entry that feeds its arrays through CopyFeed (keaki_amd/csrc/api.hip), and for the _dev
+"""One small, successful call for every host-array entry that feeds its arrays through CopyFeed (keaki_amd/csrc/api_host.h), and for the _dev
 forms of the KZG verification family, in one process, for a trace:
   rocprofv3 --kernel-trace --memory-copy-trace --output-format csv json -- python bench_tools/host_form_calls.py
 run against two builds, every call's ordered (kernel, grid, workgroup) list per stream and its sorted (direction, bytes) list of copies

@@ -1,65 +1,24 @@
 // libkeaki_hip.so -- C ABI (include/keaki_hip.h) over the gfx950 kernels. Host side only does
 // launch plumbing: workspace management, stream ordering, error codes. No arithmetic happens on
 // the CPU here and there is no CPU fallback: without a gfx950 device every entry point fails.
-#include "internal.h"
+#include "api_host.h"
 #include "host_plan.h"
 #include "encap_multi_plan.h"
 #include "fk_coset_plan.h"
 #include "coset_rows_plan.h"
 #include "set_rows_plan.h"
 
-#include <algorithm>
+#include <dlfcn.h>
+#include <sys/mman.h>
 #include <cctype>
-#include <set>
+#include <chrono>
+#include <memory>
+#include <thread>
 #include <type_traits>
-#include <utility>
 #include <vector>
 
 using namespace keaki_internal;
 
-// An SRS handle is device memory, not context state: every context ON THE SAME DEVICE may pass it to msm / open / open_fk (read-only use
-// of the points, the window tables and the cached FK23 transform), so N host threads with a context each share ONE set of tables.
-// `mu` guards the lazily built members (table, fk); `acct` is the context whose keaki_hip_ctx_memory counts them.
-struct SrsHandle {
-  const void* d = nullptr;
-  size_t n = 0;
-  bool owned = false;
-  int device = -1;
-  std::recursive_mutex mu;
-  keaki_hip_ctx* acct = nullptr;
-  // precomputed window tables (keaki_hip_srs_g*_precompute): table[w * n + i] = 2^(offset_w) * P_i
-  void* table = nullptr;
-  size_t table_bytes = 0;
-  int c_table = 0;
-};
-// A device table derived from the points of a G1 handle for the LAST requested shape, reused by later calls on the handle. Owned by
-// srs_cache_ensure: the key names a table only when its build was enqueued in full (an unused part stays -1), bytes is what p holds (and `acct` counts).
-struct SrsCache {
-  void* p = nullptr;
-  int key[2] = {-1, -1};
-  size_t bytes = 0;
-  bool holds(int k0, int k1 = -1) const { return key[0] == k0 && key[1] == k1; }
-};
-// fk: FK23, hat_s = DFT_2d(reversed SRS), 2d Jacobian points, key log2d | upd: vec_update, the update tables of d (vec_update.hip: a | u | omega_d^-i |
-// 1 / (omega_d^t - 1)), key log2d | fkc: FK23 coset openings, the l transforms hat_s_j = DFT_2r(row j of the SRS, reversed), 2d Jacobian points
-// (fk_coset.hip), key (log2d, log2l) | cr: kzg coset_pairs, the window table over the first l points (kzg_coset_pairs.hip, coset_rows_plan.h), key (log2l, wb).
-// The four are independent of each other; a new cache is added HERE (srs_free walks them). The G2 handle has one: sr, kzg set_pairs, the window table over
-// the first kb points (kzg_set_pairs.hip, set_rows_plan.h), key (kb, wb); base-major, so it serves every k <= kb.
-struct keaki_hip_srs_g1 : SrsHandle {
-  SrsCache fk, upd, fkc, cr;
-  template <class F> void for_each_cache(F&& f) { for (SrsCache* c : {&fk, &upd, &fkc, &cr}) f(*c); }
-};
-struct keaki_hip_srs_g2 : SrsHandle {
-  SrsCache sr;
-  template <class F> void for_each_cache(F&& f) { f(sr); }
-};
-
-#include <dlfcn.h>
-#include <sys/mman.h>
-#include <memory>
-#include <thread>
-#include <atomic>
-#include <chrono>
 namespace {
 // roctx ranges around the kernel families (tracing), visible to `rocprofv3 --marker-trace`. The marker library is
 // looked up at run time so that the ABI has no link-time dependency on the profiler; without it the scopes are no-ops.
@@ -77,34 +36,15 @@ struct Roctx {
   }
 };
 const Roctx& roctx() { static Roctx r; return r; }
-struct RoctxScope {
-  bool on;
-  explicit RoctxScope(const char* name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
-  ~RoctxScope() { if (on) roctx().pop(); }
-};
-#define TRACE_SCOPE(name) RoctxScope roctx_scope_(name)
 thread_local std::string g_create_error;
-// The contexts that are alive: an SRS handle is shared by every context of its device, and whoever frees it (or rebuilds its FK23 transform)
-// must be able to undo the byte accounting on the context that built the tables -- if that context still exists.
-std::mutex g_live_mu;
-std::set<keaki_hip_ctx*> g_live_ctx;
-// runs `f(acct)` when acct is a live context. Under g_live_mu ONLY: the caller may already hold its own context's lock, and taking another
-// context's lock from here would order the two locks both ways (thread A: ctx1 -> live -> ctx2, thread B: ctx2 -> live). What f touches --
-// the byte count `mem_tables` -- is an atomic for that reason.
-template <class Fn>
-void with_live_ctx(keaki_hip_ctx* acct, Fn f) {
-  std::lock_guard<std::mutex> lk(g_live_mu);
-  if (acct && g_live_ctx.count(acct)) f(acct);
-}
-// saturating subtraction on the byte count (a handle freed twice over, or booked before a trim, must not wrap it)
-void mem_sub(std::atomic<size_t>& m, size_t v) {
-  size_t cur = m.load();
-  while (!m.compare_exchange_weak(cur, cur - std::min(cur, v))) {}
-}
-constexpr size_t G1_AFF_BYTES = 64, G2_AFF_BYTES = 128, G1_JAC_BYTES = 96, G2_JAC_BYTES = 192;
 }  // namespace
 
 namespace keaki_internal {
+
+RoctxScope::RoctxScope(const char* name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
+RoctxScope::~RoctxScope() { if (on) roctx().pop(); }
+std::mutex g_live_mu;
+std::set<keaki_hip_ctx*> g_live_ctx;
 
 keaki_status fail(keaki_hip_ctx* ctx, keaki_status code, const char* fmt, ...) {
   char buf[512];
@@ -147,69 +87,11 @@ keaki_status launch_check(keaki_hip_ctx* ctx, const char* what) {
   return KEAKI_OK;
 }
 
-}  // namespace keaki_internal
-
-namespace {
-
-void resolve_timing(keaki_hip_ctx* ctx) {
-  if (!ctx->timing_pending) return;
-  if (hipEventSynchronize(ctx->ev[3]) == hipSuccess) {
-    (void)hipEventElapsedTime(&ctx->last_bucket_ms, ctx->ev[1], ctx->ev[2]);
-    (void)hipEventElapsedTime(&ctx->last_total_ms, ctx->ev[0], ctx->ev[3]);
-  }
-  ctx->timing_pending = false;
-}
-void resolve_fk_timing(keaki_hip_ctx* ctx) {
-  if (!ctx->fk_timing_pending) return;
-  if (hipEventSynchronize(ctx->fk_ev[3]) == hipSuccess) {
-    (void)hipEventElapsedTime(&ctx->last_fk_ms[0], ctx->fk_ev[0], ctx->fk_ev[1]);
-    (void)hipEventElapsedTime(&ctx->last_fk_ms[1], ctx->fk_ev[1], ctx->fk_ev[2]);
-    (void)hipEventElapsedTime(&ctx->last_fk_ms[2], ctx->fk_ev[0], ctx->fk_ev[3]);
-  }
-  ctx->fk_timing_pending = false;
-}
-
 keaki_status download(keaki_hip_ctx* ctx, void* host, const void* dev, size_t bytes) {
   if (bytes) HIP_TRY(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return KEAKI_OK;
 }
-// How the caller's HOST arrays reach the device, for every host-array entry: the copies go on the context's stream, or after begin(true) on
-// the copy stream, where `put` makes the stream that reads a piece wait for it. The feed also keeps the rule of the header: a call that
-// FAILS returns, too, only when no copy reads the caller's arrays any more and nothing of it is left on a side stream -- unless the call
-// said `settled()` (where its own download has synchronised), the destructor drains every stream that carried a copy or was handed in.
-struct CopyFeed {
-  keaki_hip_ctx* ctx;
-  bool side = false;
-  hipStream_t drain[3] = {nullptr, nullptr, nullptr};
-  int n_drain = 0;
-  explicit CopyFeed(keaki_hip_ctx* c) : ctx(c) {}
-  ~CopyFeed() { for (int i = 0; i < n_drain; i++) (void)hipStreamSynchronize(drain[i]); }
-  CopyFeed(const CopyFeed&) = delete;
-  CopyFeed& operator=(const CopyFeed&) = delete;
-  void also_drain(hipStream_t s) { if (std::find(drain, drain + n_drain, s) == drain + n_drain) drain[n_drain++] = s; }
-  void settled() { n_drain = 0; }
-  keaki_status closed_by(keaki_status last) { if (last == KEAKI_OK) settled(); return last; }      // `last`: of the call's last step, which synchronises
-  keaki_status begin(bool side_stream) {
-    if (!side_stream) return KEAKI_OK;
-    ST_TRY(ctx->pipe.ready(ctx));
-    // the copy stream starts behind whatever the context's stream holds (an earlier call's kernels may still read the destination)
-    HIP_TRY(ctx, hipEventRecord(ctx->pipe.done[0], ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->pipe.copy_stream, ctx->pipe.done[0], 0));
-    side = true;
-    return KEAKI_OK;
-  }
-  // piece j of the call, host to device; `waiter` (default: the context's stream) is the stream whose kernels read it
-  keaki_status put(size_t j, void* dst, const void* src, size_t bytes, hipStream_t waiter = nullptr) {
-    const hipStream_t cs = side ? ctx->pipe.copy_stream : ctx->stream;
-    also_drain(cs);
-    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
-    if (!side) return KEAKI_OK;
-    HIP_TRY(ctx, hipEventRecord(ctx->pipe.in[j & 1], cs));
-    HIP_TRY(ctx, hipStreamWaitEvent(waiter ? waiter : ctx->stream, ctx->pipe.in[j & 1], 0));
-    return KEAKI_OK;
-  }
-};
 keaki_status upload(CopyFeed& feed, DevBuf& b, const void* host, size_t bytes) {
   ST_TRY(reserve(feed.ctx, b, bytes ? bytes : 16));
   return feed.put(0, b.p, host, bytes);
@@ -217,32 +99,6 @@ keaki_status upload(CopyFeed& feed, DevBuf& b, const void* host, size_t bytes) {
 keaki_status download(CopyFeed& feed, void* host, const void* dev, size_t bytes) {     // the last step of a successful call
   return feed.closed_by(download(feed.ctx, host, dev, bytes));
 }
-// The items of a KZG host form on their way to the device, told ONCE what the call has: ONE commitment (com_stride 0) goes to `com_slot`, omega alone
-// (point_mode 1) to `omega_slot`, or where the call keeps no such slot (null) to the front of the per-item buffer; n commitments go to io_e, n points to io_c, the n
-// proofs (null: none) to io_b. reserve() covers every buffer before the first copy is enqueued: a reserve that grows a buffer waits for ctx->stream only. put(feed,
-// what) enqueues the inputs `what` selects, in the order commitment, points, proofs; put(feed, dst, src, bytes) one of the call's own arrays; d_*(): where each is read.
-struct ItemStager {
-  enum : unsigned { ONE_COM = 1, COMS = 2, OMEGA = 4, POINTS = 8, PROOFS = 16, COM = ONE_COM | COMS, PTS = OMEGA | POINTS, ALL = COM | PTS | PROOFS };
-  keaki_hip_ctx* ctx;
-  const void* com; int32_t com_stride; void* com_slot;
-  const void* points; int32_t point_mode; void* omega_slot;
-  const void* proofs; size_t n, piece = 0;
-  void* d_com() const { return !com_stride && com_slot ? com_slot : ctx->io_e.p; }
-  void* d_points() const { return point_mode && omega_slot ? omega_slot : ctx->io_c.p; }
-  void* d_proofs() const { return ctx->io_b.p; }
-  keaki_status reserve() {
-    if (proofs) ST_TRY(keaki_internal::reserve(ctx, ctx->io_b, n * G1_AFF_BYTES));
-    if (d_points() == ctx->io_c.p) ST_TRY(keaki_internal::reserve(ctx, ctx->io_c, (point_mode ? 1 : n) * 32));
-    return d_com() == ctx->io_e.p ? keaki_internal::reserve(ctx, ctx->io_e, (com_stride ? n : 1) * G1_AFF_BYTES) : KEAKI_OK;
-  }
-  keaki_status put(CopyFeed& feed, void* dst, const void* src, size_t bytes) { return feed.put(feed.side ? piece++ : 0, dst, src, bytes); }
-  keaki_status put(CopyFeed& feed, unsigned what) {
-    if (what & (com_stride ? COMS : ONE_COM)) ST_TRY(put(feed, d_com(), com, (com_stride ? n : 1) * G1_AFF_BYTES));
-    if (what & (point_mode ? OMEGA : POINTS)) ST_TRY(put(feed, d_points(), points, (point_mode ? 1 : n) * 32));
-    return proofs && (what & PROOFS) ? put(feed, d_proofs(), proofs, n * G1_AFF_BYTES) : KEAKI_OK;
-  }
-};
-// The two pairings of a verdict in ONE launch; `sums_out_aff` (or null) takes the 128 bytes of d_ps, enqueued before the download of the 768 GT bytes, which synchronises.
 keaki_status pair2_verdict(keaki_hip_ctx* ctx, const void* d_ps, const void* d_qs, void* d_gt, uint64_t* sums_out_aff, int32_t* ok_out) {
   ST_TRY(pairing_run(ctx, d_ps, d_qs, 1, 2, d_gt));
   uint8_t gt[768];
@@ -251,72 +107,10 @@ keaki_status pair2_verdict(keaki_hip_ctx* ctx, const void* d_ps, const void* d_q
   *ok_out = memcmp(gt, gt + 384, 384) == 0 ? 1 : 0;
   return KEAKI_OK;
 }
-
-// (table, window target) of a handle, read under its lock: another context may be building the tables right now
-template <class H>
-std::pair<const void*, int> srs_tables(const H* srs) {
-  std::lock_guard<std::recursive_mutex> hl(const_cast<H*>(srs)->mu);
-  return {srs->table, srs->c_table};
-}
-template <class H>
-H* new_srs(keaki_hip_ctx* ctx, const void* d, size_t n, bool owned) {
-  H* h = new H();
-  h->d = d; h->n = n; h->owned = owned; h->device = ctx->device; h->acct = ctx;
-  return h;
-}
-// a handle may be used by any context of the device it lives on
-#define SRS_CHECK(ctx, srs, what)                                                                                                     \
-  if ((srs)->device != (ctx)->device)                                                                                                 \
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: the SRS handle lives on device %d, this context on device %d", what, (srs)->device, (ctx)->device)
-// ... and must hold the k points the call reads: `too_short` is the message of the MSM family or of the FK23 family
-constexpr const char *SRS_SHORT_MSM = "msm: %zu scalars but the SRS holds %zu points", *SRS_SHORT_FK = "open_fk: %zu coefficients but the SRS holds %zu points";
 keaki_status srs_holds(keaki_hip_ctx* ctx, const SrsHandle* srs, const char* what, size_t k, const char* too_short) {
   SRS_CHECK(ctx, srs, what);
   if (k > srs->n) return fail(ctx, KEAKI_ERR_TOO_LARGE, too_short, k, srs->n);
   return KEAKI_OK;
-}
-// The ONE owner of every cache of a handle: afterwards c.p is the table of key (k0, k1), `bytes` long, that `build(c.p)` enqueues on the
-// context's stream; the caller holds srs->mu. A table of another key is dropped first (after the stream's work that may read it), the new
-// one is allocated through dev_alloc and named only once its build is enqueued in full; on every exit -- a refused allocation
-// included -- c.bytes and the `tables` count of the handle's accounting context (srs->acct, as for the window tables) say what c.p holds.
-template <class H, class Build>
-keaki_status srs_cache_ensure(keaki_hip_ctx* ctx, H* srs, SrsCache& c, int k0, int k1, size_t bytes, Build build) {
-  if (c.holds(k0, k1)) return KEAKI_OK;
-  auto book = [&](size_t now) {
-    const size_t before = c.bytes;
-    with_live_ctx(srs->acct, [&](keaki_hip_ctx* a) { mem_sub(a->mem_tables, before); a->mem_tables += now; });
-    c.bytes = now;
-  };
-  c.key[0] = c.key[1] = -1;
-  if (c.p) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(c.p); c.p = nullptr; book(0); }
-  ST_TRY(dev_alloc(ctx, &c.p, bytes));
-  book(bytes);
-  ST_TRY(build(c.p));
-  c.key[0] = k0; c.key[1] = k1;
-  return KEAKI_OK;
-}
-// the FK23 transform of d = 2^log2d into srs->fk. d_tw: omega_2d^k, k < d, ready in stream order
-keaki_status fk_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_tw) {
-  return srs_cache_ensure(ctx, srs, srs->fk, (int)log2d, -1, ((size_t)2 << log2d) * G1_JAC_BYTES,
-                          [&](void* hat_s) { return fk_hat_s_run(ctx, srs->d, log2d, d_tw, hat_s); });
-}
-// How every FK23 entry starts: its pointers are there (`args_ok`) and log2d is in range, the handle lives on this device and holds the
-// d = 2^log2d points (`too_short`: the family's message when it does not), and `hl` takes the handle's lock: the caches belong to the
-// handle, one call per handle at a time.
-keaki_status fk_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, const char* what, std::unique_lock<std::recursive_mutex>& hl,
-                      const char* too_short = SRS_SHORT_FK) {
-  if (!srs || !args_ok || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", what);
-  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, too_short));
-  hl = std::unique_lock<std::recursive_mutex>(srs->mu);
-  return KEAKI_OK;
-}
-// the d openings of the polynomial at d_p (d Fr, device) -> d_proofs_aff: scalar half, the handle's transform, point half, in that order
-keaki_status open_fk_from_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_p, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
-                               const uint64_t* inv_2d, void* d_fr_work, void* d_g_work, void* d_proofs_aff) {
-  FkPolyScalars s;
-  ST_TRY(open_fk_poly_scalars_run(ctx, log2d, d_p, omega_2d, omega_2d_inv, inv_2d, d_fr_work, &s));
-  ST_TRY(fk_cache_ensure(ctx, srs, log2d, s.tw));
-  return open_fk_run(ctx, srs->fk.p, log2d, s.hat_a, s.tw, s.twi, d_g_work, d_proofs_aff);
 }
 
 // The caller's OUTPUT buffer is usually fresh memory (calloc / vec![0; n] / numpy.zeros): its pages do not exist until first touched, and a
@@ -348,6 +142,111 @@ void prefault_out(const keaki_hip_ctx* ctx, void* p, size_t bytes) {
   c[bytes - 1] = 0;
 }
 
+keaki_status generator_tables(keaki_hip_ctx* ctx, bool use_tables) {
+  KemState& k = ctx->kem;
+  ST_TRY(reserve(ctx, ctx->tmp_c, G2_AFF_BYTES));
+  ST_TRY(g2_generator_to(ctx, ctx->tmp_c.p));
+  if (use_tables && !k.fb_ready) {
+    const size_t FBL = fb_table_entries(FB_WB_LONG);
+    ST_TRY(reserve(ctx, k.fb_g1_gen, FBL * G1_AFF_BYTES + G1_AFF_BYTES));
+    ST_TRY(reserve(ctx, k.fb_g2_gen, FBL * G2_AFF_BYTES));
+    ST_TRY(reserve(ctx, k.fb_com, fb_table_entries(FB_WB_BATCH) * G1_AFF_BYTES));
+    ST_TRY(reserve(ctx, k.fb_tau.buf, FBL * G2_AFF_BYTES));
+    void* g1pt = (char*)k.fb_g1_gen.p + FBL * G1_AFF_BYTES;   // scratch slot behind the table
+    ST_TRY(g1_generator_to(ctx, g1pt));
+    ST_TRY(g1_fb_table_run(ctx, g1pt, k.fb_g1_gen.p, FB_WB_LONG));
+    ST_TRY(g2_fb_table_run(ctx, ctx->tmp_c.p, k.fb_g2_gen.p, FB_WB_LONG));
+    k.fb_ready = true;
+  }
+  if (!k.g2gen_lines_ready) {
+    ST_TRY(reserve(ctx, k.g2gen_lines, g2_prepared_bytes()));
+    ST_TRY(g2_prepare_run(ctx, ctx->tmp_c.p, k.g2gen_lines.p));
+    k.g2gen_lines_ready = true;
+  }
+  return KEAKI_OK;
+}
+keaki_status small_g2_tables(keaki_hip_ctx* ctx, const void* d_g2_generator) {
+  KemState& k = ctx->kem;
+  if (k.fbs_ready) return KEAKI_OK;
+  const size_t FBX = fb_table_entries(FB_WB_SMALL);
+  ST_TRY(reserve(ctx, k.fbs_g2_gen, FBX * G2_AFF_BYTES));
+  ST_TRY(reserve(ctx, k.fbs_tau.buf, FBX * G2_AFF_BYTES));
+  ST_TRY(g2_fb_table_run(ctx, d_g2_generator, k.fbs_g2_gen.p, FB_WB_SMALL));
+  k.fbs_ready = true;                 // fbs_tau is not valid yet: it is only ever built behind this point
+  return KEAKI_OK;
+}
+keaki_status small_g1_table(keaki_hip_ctx* ctx) {
+  KemState& k = ctx->kem;
+  if (k.fbs_g1_ready) return KEAKI_OK;
+  const size_t FBX = fb_table_entries(FB_WB_SMALL);
+  ST_TRY(reserve(ctx, k.fbs_g1_gen, FBX * G1_AFF_BYTES + G1_AFF_BYTES));
+  void* g1pt = (char*)k.fbs_g1_gen.p + FBX * G1_AFF_BYTES;    // scratch slot behind the table
+  ST_TRY(g1_generator_to(ctx, g1pt));
+  ST_TRY(g1_fb_table_run(ctx, g1pt, k.fbs_g1_gen.p, FB_WB_SMALL));
+  k.fbs_g1_ready = true;
+  return KEAKI_OK;
+}
+keaki_status read_constants(keaki_hip_ctx* ctx, const void* d_tau, const void* d_com, uint64_t* tau_host, uint64_t* com_host) {
+  HIP_TRY(ctx, hipMemcpyAsync(tau_host, d_tau, 128, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_com) HIP_TRY(ctx, hipMemcpyAsync(com_host, d_com, 64, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return KEAKI_OK;
+}
+
+}  // namespace keaki_internal
+
+namespace {
+
+void resolve_timing(keaki_hip_ctx* ctx) {
+  if (!ctx->timing_pending) return;
+  if (hipEventSynchronize(ctx->ev[3]) == hipSuccess) {
+    (void)hipEventElapsedTime(&ctx->last_bucket_ms, ctx->ev[1], ctx->ev[2]);
+    (void)hipEventElapsedTime(&ctx->last_total_ms, ctx->ev[0], ctx->ev[3]);
+  }
+  ctx->timing_pending = false;
+}
+void resolve_fk_timing(keaki_hip_ctx* ctx) {
+  if (!ctx->fk_timing_pending) return;
+  if (hipEventSynchronize(ctx->fk_ev[3]) == hipSuccess) {
+    (void)hipEventElapsedTime(&ctx->last_fk_ms[0], ctx->fk_ev[0], ctx->fk_ev[1]);
+    (void)hipEventElapsedTime(&ctx->last_fk_ms[1], ctx->fk_ev[1], ctx->fk_ev[2]);
+    (void)hipEventElapsedTime(&ctx->last_fk_ms[2], ctx->fk_ev[0], ctx->fk_ev[3]);
+  }
+  ctx->fk_timing_pending = false;
+}
+
+template <class H>
+H* new_srs(keaki_hip_ctx* ctx, const void* d, size_t n, bool owned) {
+  H* h = new H();
+  h->d = d; h->n = n; h->owned = owned; h->device = ctx->device; h->acct = ctx;
+  return h;
+}
+// `too_short` of srs_holds: the message of the MSM family and of the FK23 family
+constexpr const char *SRS_SHORT_MSM = "msm: %zu scalars but the SRS holds %zu points", *SRS_SHORT_FK = "open_fk: %zu coefficients but the SRS holds %zu points";
+// the FK23 transform of d = 2^log2d into srs->fk. d_tw: omega_2d^k, k < d, ready in stream order
+keaki_status fk_cache_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_tw) {
+  return srs_cache_ensure(ctx, srs, srs->fk, (int)log2d, -1, ((size_t)2 << log2d) * G1_JAC_BYTES,
+                          [&](void* hat_s) { return fk_hat_s_run(ctx, srs->d, log2d, d_tw, hat_s); });
+}
+// How every FK23 entry starts: its pointers are there (`args_ok`) and log2d is in range, the handle lives on this device and holds the
+// d = 2^log2d points (`too_short`: the family's message when it does not), and `hl` takes the handle's lock: the caches belong to the
+// handle, one call per handle at a time.
+keaki_status fk_enter(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, bool args_ok, const char* what, std::unique_lock<std::recursive_mutex>& hl,
+                      const char* too_short = SRS_SHORT_FK) {
+  if (!srs || !args_ok || log2d > 27) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: bad argument", what);
+  ST_TRY(srs_holds(ctx, srs, what, (size_t)1 << log2d, too_short));
+  hl = std::unique_lock<std::recursive_mutex>(srs->mu);
+  return KEAKI_OK;
+}
+// the d openings of the polynomial at d_p (d Fr, device) -> d_proofs_aff: scalar half, the handle's transform, point half, in that order
+keaki_status open_fk_from_poly(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_p, const uint64_t* omega_2d, const uint64_t* omega_2d_inv,
+                               const uint64_t* inv_2d, void* d_fr_work, void* d_g_work, void* d_proofs_aff) {
+  FkPolyScalars s;
+  ST_TRY(open_fk_poly_scalars_run(ctx, log2d, d_p, omega_2d, omega_2d_inv, inv_2d, d_fr_work, &s));
+  ST_TRY(fk_cache_ensure(ctx, srs, log2d, s.tw));
+  return open_fk_run(ctx, srs->fk.p, log2d, s.hat_a, s.tw, s.twi, d_g_work, d_proofs_aff);
+}
+
 // ---- host-pointer batches in CHUNKS ------------------------------------------------------------------------------------------
 // A batch call that takes host arrays is upload -> kernels -> download; done in that order the device idles during both copies and the host
 // thread during the kernels (vec_encrypt of 2^20 items: 8.1 ms per 2^18-item piece for 7.0 ms of kernels, profiles/r04_vec_encrypt_timeline.txt).
@@ -357,7 +256,6 @@ void prefault_out(const keaki_hip_ctx* ctx, void* p, size_t bytes) {
 // calls -- upload k, launch k, download k - 1 -- is what keeps the device busy. `up(lo, m, half, stream)` enqueues the uploads of items
 // [lo, lo + m) into buffer half `half`, `run(lo, m, half)` the kernels (on ctx->stream), `down(lo, m, half, stream)` first-touches the
 // caller's output pages and enqueues the downloads.
-constexpr size_t PIPE_CHUNK = 65536;
 // chunk size of a batch of n items: `unit` items (PIPE_CHUNK: two rounds of the GT exponentiation kernel; the pairing path passes its own launch
 // size -- 16 launches of 2^16 pairings take 3.6 ms longer than 8 of 2^17), the whole batch below two units
 inline size_t pipe_chunk_items(const keaki_hip_ctx* ctx, size_t n, size_t unit = PIPE_CHUNK) { return ctx->tune.pipe_chunks && n >= 2 * unit ? unit : n; }
@@ -500,12 +398,6 @@ static keaki_status msm_from_host(CopyFeed& feed, const uint64_t* scalars, size_
   return run(nullptr);
 }
 
-#define CTX_GUARD(ctx)                                \
-  if (!(ctx)) return KEAKI_ERR_BAD_ARG;               \
-  std::lock_guard<std::recursive_mutex> lock_((ctx)->mu);       \
-  keaki_internal::DeviceScope dev_((ctx)->device);              \
-  if (!dev_.ok) return fail(ctx, KEAKI_ERR_HIP, "hipSetDevice(%d) failed", (ctx)->device)
-
 // What tells the G1 and G2 forms of the SRS, MSM and mul_batch entries apart: the point sizes, the launchers and the names in messages and traces.
 struct GroupEntries {
   size_t aff, jac;
@@ -616,7 +508,6 @@ keaki_status mul_batch_host(const GroupEntries& g, keaki_hip_ctx* ctx, const uin
 
 }  // namespace
 
-extern "C" {
 
 #ifndef KEAKI_SRC_HASH
 #define KEAKI_SRC_HASH "unknown"
@@ -629,7 +520,6 @@ const char* keaki_hip_version(void) { return "keaki-hip 0.3 (gfx950) DIAGNOSTIC 
 const char* keaki_hip_version(void) { return "keaki-hip 0.3 (gfx950) src=" KEAKI_SRC_HASH; }
 #endif
 
-extern "C++" {
 namespace {
 // The tuning options (Tuning, internal.h), each declared ONCE: keaki_hip_ctx_set_option and the environment (tune_from_env) both go through
 // this table. An option is named after its member, its variable is KEAKI_<NAME>, and its value converts as the member's type does ((int)v,
@@ -754,7 +644,6 @@ std::vector<BufClass> all_bufs(keaki_hip_ctx* ctx) {      // the list is keaki_h
   return v;
 }
 }  // namespace
-}  // extern "C++"
 
 keaki_status keaki_hip_ctx_create(int32_t device, void* stream, keaki_hip_ctx** out) {
   if (!out) return fail(nullptr, KEAKI_ERR_BAD_ARG, "ctx_create: out is null");
@@ -1017,9 +906,8 @@ struct EncapArgs {
   bool xor_into = false;                                   // the KDF XORs the key into d_key_out in place (the DEM)
   const EncapHost* host = nullptr;
 };
-// window widths of the fixed-base tables: 16 bits for bases that outlive a batch (generators: per context, [tau]_2: per setup), 13 bits for the
-// commitment's table (rebuilt per batch in the per-item-pairing path), 8 bits for the small tables of batches below FB_TABLES_MIN = 256 items
-constexpr uint32_t FB_WB_LONG = 16, FB_WB_BATCH = 13, FB_WB_SMALL = 8, FB_TABLES_MIN = 256;
+// the fixed-base tables (window widths: api_host.h, FB_WB_*): batches below FB_TABLES_MIN items use the small 8-bit tables
+constexpr uint32_t FB_TABLES_MIN = 256;
 // window widths of the GT tables. The constant B = e(g1, g2) is tabulated once per context: 20-bit windows (13 products per item, 2.6 GB; option
 // gt_wb_b picks another width). A = e(C, g2) per commitment: 13 bits on first sight (20 products per item, 31.5 MB: one launch of the twelve-lane pairing
 // kernel over the tabulated multiples of g2 + the fills, 1.7 ms); when it comes back, 16 bits (201 MB) from the powers still lying in gt_base (0.5 ms).
@@ -1038,60 +926,6 @@ static void note_commitment(KemState& k, const uint64_t* com_host, bool first_of
   const bool same = k.seen_com_runs && memcmp(com_host, k.seen_com, 64) == 0;
   if (same && first_of_batch && k.seen_com_runs < 1000000) k.seen_com_runs++;
   if (!same) { memcpy(k.seen_com, com_host, 64); k.seen_com_runs = 1; }
-}
-// g2 in tmp_c for the pairing's second slot (src/kem.rs:30), and once per context the generators' 16-bit tables and g2's line sequence (G2Prepared)
-static keaki_status generator_tables(keaki_hip_ctx* ctx, bool use_tables) {
-  KemState& k = ctx->kem;
-  ST_TRY(reserve(ctx, ctx->tmp_c, G2_AFF_BYTES));
-  ST_TRY(g2_generator_to(ctx, ctx->tmp_c.p));
-  if (use_tables && !k.fb_ready) {
-    const size_t FBL = fb_table_entries(FB_WB_LONG);
-    ST_TRY(reserve(ctx, k.fb_g1_gen, FBL * G1_AFF_BYTES + G1_AFF_BYTES));
-    ST_TRY(reserve(ctx, k.fb_g2_gen, FBL * G2_AFF_BYTES));
-    ST_TRY(reserve(ctx, k.fb_com, fb_table_entries(FB_WB_BATCH) * G1_AFF_BYTES));
-    ST_TRY(reserve(ctx, k.fb_tau.buf, FBL * G2_AFF_BYTES));
-    void* g1pt = (char*)k.fb_g1_gen.p + FBL * G1_AFF_BYTES;   // scratch slot behind the table
-    ST_TRY(g1_generator_to(ctx, g1pt));
-    ST_TRY(g1_fb_table_run(ctx, g1pt, k.fb_g1_gen.p, FB_WB_LONG));
-    ST_TRY(g2_fb_table_run(ctx, ctx->tmp_c.p, k.fb_g2_gen.p, FB_WB_LONG));
-    k.fb_ready = true;
-  }
-  if (!k.g2gen_lines_ready) {
-    ST_TRY(reserve(ctx, k.g2gen_lines, g2_prepared_bytes()));
-    ST_TRY(g2_prepare_run(ctx, ctx->tmp_c.p, k.g2gen_lines.p));
-    k.g2gen_lines_ready = true;
-  }
-  return KEAKI_OK;
-}
-// the small tables of g2 (from the generator at d_g2_generator) and room for [tau]_2's: encapsulate below FB_TABLES_MIN items and kzg verify
-static keaki_status small_g2_tables(keaki_hip_ctx* ctx, const void* d_g2_generator) {
-  KemState& k = ctx->kem;
-  if (k.fbs_ready) return KEAKI_OK;
-  const size_t FBX = fb_table_entries(FB_WB_SMALL);
-  ST_TRY(reserve(ctx, k.fbs_g2_gen, FBX * G2_AFF_BYTES));
-  ST_TRY(reserve(ctx, k.fbs_tau.buf, FBX * G2_AFF_BYTES));
-  ST_TRY(g2_fb_table_run(ctx, d_g2_generator, k.fbs_g2_gen.p, FB_WB_SMALL));
-  k.fbs_ready = true;                 // fbs_tau is not valid yet: it is only ever built behind this point
-  return KEAKI_OK;
-}
-// the small table of g1: kzg verify, and the fused route of encap_multi while the context has no long tables
-static keaki_status small_g1_table(keaki_hip_ctx* ctx) {
-  KemState& k = ctx->kem;
-  if (k.fbs_g1_ready) return KEAKI_OK;
-  const size_t FBX = fb_table_entries(FB_WB_SMALL);
-  ST_TRY(reserve(ctx, k.fbs_g1_gen, FBX * G1_AFF_BYTES + G1_AFF_BYTES));
-  void* g1pt = (char*)k.fbs_g1_gen.p + FBX * G1_AFF_BYTES;    // scratch slot behind the table
-  ST_TRY(g1_generator_to(ctx, g1pt));
-  ST_TRY(g1_fb_table_run(ctx, g1pt, k.fbs_g1_gen.p, FB_WB_SMALL));
-  k.fbs_g1_ready = true;
-  return KEAKI_OK;
-}
-// the two constants of the batch read back to the host: one synchronisation, for callers whose host copies did not come along. d_com null: [tau]_2 only
-static keaki_status read_constants(keaki_hip_ctx* ctx, const void* d_tau, const void* d_com, uint64_t* tau_host, uint64_t* com_host) {
-  HIP_TRY(ctx, hipMemcpyAsync(tau_host, d_tau, 128, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_com) HIP_TRY(ctx, hipMemcpyAsync(com_host, d_com, 64, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return KEAKI_OK;
 }
 // the table of a new commitment is built on the aux stream; `gt_a_pending_aux` says that the context's stream has not been made to wait for that build yet. It survives
 // an early error return, so a later call that finds the table published or rewrites gt_base orders itself behind the build first -- whatever happened in between.
@@ -1966,7 +1800,6 @@ keaki_status keaki_hip_kzg_quotient(keaki_hip_ctx* ctx, const uint64_t* coeffs, 
 // ---- KZG set openings: one proof for k points (kzg_multi.hip) -------------------------------------------------------------------------------
 // ks_io: [points | values | Z | weights | I], a slot of KEAKI_SET_MAX + 1 Fr each, then [proof 96 | I1 96 | Z2 192 | com 64 | C - I1 64 | Z2 affine 128]
 // ks_q:  [quotient: n Fr | work of multi_quotient_run]
-extern "C++" {
 namespace {
 struct KsLayout {
   static constexpr size_t SLOT = ((size_t)KEAKI_SET_MAX + 1) * 32;
@@ -1995,7 +1828,6 @@ keaki_status open_multi_core(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, co
   return msm_g1_run(ctx, srs->d, srs->n, q, n > k ? n - 1 : 0, d_proof_out_jac, tb.first, tb.second);     // n <= k: p = I, the quotient is zero
 }
 }  // namespace
-}  // extern "C++"
 
 keaki_status keaki_hip_kzg_set_polys_dev(keaki_hip_ctx* ctx, const void* d_points, const void* d_values, size_t k, void* d_z_coeffs_out, void* d_weights_out,
                                          void* d_i_coeffs_out) {
@@ -2074,8 +1906,41 @@ keaki_status keaki_hip_kzg_aggregate(keaki_hip_ctx* ctx, const uint64_t* points,
   return KEAKI_OK;
 }
 
+// The set predicate e(C - [I(tau)]_1, g2) == e(proof, [Z(tau)]_2): the two set polynomials (kzg_multi.hip), [Z]_2 and [I]_1 by the library's MSMs over
+// the powers, then keaki_hip_kzg_verify ITSELF with com := C - [I]_1, value := 0, point := 0, tau_g2 := [Z]_2 (the two points cross the host once:
+// 192 bytes, which pair_out hands to the tests).
+keaki_status keaki_hip_kzg_verify_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
+                                        const uint64_t* points, const uint64_t* values, size_t k, const uint64_t* proof_aff, int32_t* ok_out,
+                                        uint64_t* pair_out_aff) {
+  CTX_GUARD(ctx);
+  TRACE_SCOPE("keaki.kzg_verify_multi");
+  using S = KsLayout;
+  ST_TRY(set_args(ctx, "kzg_verify_multi", k, srs_g1 && srs_g2 && com_aff && points && values && proof_aff && ok_out));
+  ST_TRY(srs_holds(ctx, srs_g2, "kzg_verify_multi", k + 1, "kzg_verify_multi: Z has %zu coefficients but the G2 SRS holds %zu points"));
+  ST_TRY(srs_holds(ctx, srs_g1, "kzg_verify_multi", k, "kzg_verify_multi: I has %zu coefficients but the G1 SRS holds %zu points"));
+  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
+  char* io = (char*)ctx->ks_io.p;
+  uint64_t pair[24];
+  {
+    CopyFeed feed(ctx);
+    ST_TRY(feed.put(0, io + S::O_PTS, points, k * 32));
+    ST_TRY(feed.put(0, io + S::O_VAL, values, k * 32));
+    ST_TRY(feed.put(0, io + S::O_COM, com_aff, 64));
+    ST_TRY(set_polys_run(ctx, io + S::O_PTS, io + S::O_VAL, k, io + S::O_ZC, io + S::O_W, io + S::O_IC));
+    const auto t2 = srs_tables(srs_g2);
+    ST_TRY(msm_g2_run(ctx, srs_g2->d, srs_g2->n, io + S::O_ZC, k + 1, io + S::O_Z2, t2.first, t2.second));
+    const auto t1 = srs_tables(srs_g1);
+    ST_TRY(msm_g1_run(ctx, srs_g1->d, srs_g1->n, io + S::O_IC, k, io + S::O_I1, t1.first, t1.second));
+    ST_TRY(set_pair_points_run(ctx, io + S::O_COM, io + S::O_I1, io + S::O_Z2, io + S::O_PAIR, io + S::O_PAIR + 64));
+    ST_TRY(download(feed, pair, io + S::O_PAIR, 192));
+  }
+  const uint64_t zero[4] = {0, 0, 0, 0};
+  ST_TRY(keaki_hip_kzg_verify(ctx, pair, pair + 8, zero, zero, proof_aff, ok_out));
+  if (pair_out_aff) memcpy(pair_out_aff, pair, 192);
+  return KEAKI_OK;
+}
+
 // ---- batched commit / open: m rows over one SRS in one call (msm_batch.hip) ---------------------------------------------------------------
-extern "C++" {
 namespace {
 // the argument rules the four batch entries share; *empty: m = 0, nothing to do
 keaki_status batch_args(keaki_hip_ctx* ctx, const char* what, const void* srs, size_t n, size_t m, size_t stride, bool* empty) {
@@ -2118,7 +1983,6 @@ keaki_status open_batch_core(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, co
   return KEAKI_OK;
 }
 }  // namespace
-}  // extern "C++"
 
 keaki_status keaki_hip_msm_g1_batch_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, const void* d_scalars, size_t n, size_t m, size_t stride,
                                         void* d_out_jac) {
@@ -2179,7 +2043,6 @@ keaki_status keaki_hip_kzg_open_batch(keaki_hip_ctx* ctx, const keaki_hip_srs_g1
 }
 
 // ---- batched FK23 openings / vec_commit: m rows over one domain in one call (fk_batch.hip) --------------------------------------------------
-extern "C++" {
 namespace {
 // the domain constants of a call (host pointers, read before the call returns); omega_d_inv / inv_d: vec_commit only
 struct FkbConsts { const uint64_t *omega_d_inv, *inv_d, *omega_2d, *omega_2d_inv, *inv_2d; };
@@ -2245,7 +2108,6 @@ keaki_status fkb_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d,
   return KEAKI_OK;
 }
 }  // namespace
-}  // extern "C++"
 
 keaki_status keaki_hip_open_fk_poly_batch_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2d, const void* d_coeffs, size_t m, size_t stride,
                                               const uint64_t* omega_2d, const uint64_t* omega_2d_inv, const uint64_t* inv_2d, void* d_proofs_out_aff) {
@@ -2307,1009 +2169,16 @@ keaki_status keaki_hip_vec_commit_batch(keaki_hip_ctx* ctx, keaki_hip_srs_g1* sr
   return KEAKI_OK;
 }
 
-// ---- KZG verify -----------------------------------------------------------------------------------------------------
-keaki_status keaki_hip_kzg_verify(keaki_hip_ctx* ctx, const uint64_t* com_aff, const uint64_t* tau_g2_aff, const uint64_t* point,
-                                  const uint64_t* value, const uint64_t* proof_aff, int32_t* ok_out) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify");
-  if (!com_aff || !tau_g2_aff || !point || !value || !proof_aff || !ok_out) return fail(ctx, KEAKI_ERR_BAD_ARG, "kzg_verify: null pointer");
-  // The predicate exactly as src/kzg.rs:135-143 writes it: e(com - value g1, g2) == e(proof, [tau]_2 - point g2). Both inner points are fixed-base
-  // sums over the 8-bit tables of the generators (k_verify_points, 0.25 ms); the two pairings are ONE launch of the twelve-lane kernel with the
-  // lines computed on the fly (1.44 ms). (Rounds 2-4 moved point * proof across the pairing so that both second slots were tabulated: a variable-
-  // base ladder of 0.99 ms in front of 1.38 ms of pairings.)
-  // io block: [qs: g2 128 | Q 128] [in: com 64 | proof 64 | value 32 | point 32 | tau_g2 128] [ps: A 64 | proof 64] [gt 768]
-  constexpr size_t O_Q = 0, O_IN = 256, O_P = O_IN + 320, O_GT = O_P + 128, IO_BYTES = O_GT + 768;
-  KemState& k = ctx->kem;
-  if (!k.verify_ready) {
-    ST_TRY(reserve(ctx, k.verify_io, IO_BYTES));
-    ST_TRY(g2_generator_to(ctx, (char*)k.verify_io.p + O_Q));
-    k.verify_ready = true;                  // only after every step succeeded (a failed init is retried by the next call)
-  }
-  char* io = (char*)k.verify_io.p;
-  if (!k.verify_tables_ready) {
-    ST_TRY(small_g1_table(ctx));
-    ST_TRY(small_g2_tables(ctx, io + O_Q));   // shared with the small-batch path of encapsulate (which also keeps [tau]_2's table there)
-    k.verify_tables_ready = true;
-  }
-  uint64_t in[40];
-  memcpy(in, com_aff, 64);
-  memcpy(in + 8, proof_aff, 64);
-  memcpy(in + 16, value, 32);
-  memcpy(in + 20, point, 32);
-  memcpy(in + 24, tau_g2_aff, 128);
-  CopyFeed feed(ctx);                       // declared after `in`: a failing call drains the copy while the array is alive
-  ST_TRY(feed.put(0, io + O_IN, in, 320));
-  HIP_TRY(ctx, hipMemcpyAsync(io + O_P + 64, io + O_IN + 64, 64, hipMemcpyDeviceToDevice, ctx->stream));      // the proof into the pairing's first slot
-  ST_TRY(verify_points_run(ctx, k.fbs_g1_gen.p, k.fbs_g2_gen.p, FB_WB_SMALL, io + O_IN, io + O_IN + 192, io + O_IN + 128, io + O_IN + 160, io + O_P, io + O_Q + 128));
-  return feed.closed_by(pair2_verdict(ctx, io + O_P, io + O_Q, io + O_GT, nullptr, ok_out));
-}
-
-// The set predicate e(C - [I(tau)]_1, g2) == e(proof, [Z(tau)]_2): the two set polynomials (kzg_multi.hip), [Z]_2 and [I]_1 by the library's MSMs over
-// the powers, then keaki_hip_kzg_verify ITSELF with com := C - [I]_1, value := 0, point := 0, tau_g2 := [Z]_2 (the two points cross the host once:
-// 192 bytes, which pair_out hands to the tests).
-keaki_status keaki_hip_kzg_verify_multi(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
-                                        const uint64_t* points, const uint64_t* values, size_t k, const uint64_t* proof_aff, int32_t* ok_out,
-                                        uint64_t* pair_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_multi");
-  using S = KsLayout;
-  ST_TRY(set_args(ctx, "kzg_verify_multi", k, srs_g1 && srs_g2 && com_aff && points && values && proof_aff && ok_out));
-  ST_TRY(srs_holds(ctx, srs_g2, "kzg_verify_multi", k + 1, "kzg_verify_multi: Z has %zu coefficients but the G2 SRS holds %zu points"));
-  ST_TRY(srs_holds(ctx, srs_g1, "kzg_verify_multi", k, "kzg_verify_multi: I has %zu coefficients but the G1 SRS holds %zu points"));
-  ST_TRY(reserve(ctx, ctx->ks_io, S::TOTAL));
-  char* io = (char*)ctx->ks_io.p;
-  uint64_t pair[24];
-  {
-    CopyFeed feed(ctx);
-    ST_TRY(feed.put(0, io + S::O_PTS, points, k * 32));
-    ST_TRY(feed.put(0, io + S::O_VAL, values, k * 32));
-    ST_TRY(feed.put(0, io + S::O_COM, com_aff, 64));
-    ST_TRY(set_polys_run(ctx, io + S::O_PTS, io + S::O_VAL, k, io + S::O_ZC, io + S::O_W, io + S::O_IC));
-    const auto t2 = srs_tables(srs_g2);
-    ST_TRY(msm_g2_run(ctx, srs_g2->d, srs_g2->n, io + S::O_ZC, k + 1, io + S::O_Z2, t2.first, t2.second));
-    const auto t1 = srs_tables(srs_g1);
-    ST_TRY(msm_g1_run(ctx, srs_g1->d, srs_g1->n, io + S::O_IC, k, io + S::O_I1, t1.first, t1.second));
-    ST_TRY(set_pair_points_run(ctx, io + S::O_COM, io + S::O_I1, io + S::O_Z2, io + S::O_PAIR, io + S::O_PAIR + 64));
-    ST_TRY(download(feed, pair, io + S::O_PAIR, 192));
-  }
-  const uint64_t zero[4] = {0, 0, 0, 0};
-  ST_TRY(keaki_hip_kzg_verify(ctx, pair, pair + 8, zero, zero, proof_aff, ok_out));
-  if (pair_out_aff) memcpy(pair_out_aff, pair, 192);
-  return KEAKI_OK;
-}
-
-// ---- KZG batch verification: n openings, one random linear combination, two pairings ------------------------------------------------------
-// L = sum gamma_i C_i - (sum gamma_i y_i) g1 + sum (gamma_i z_i) proof_i, R = sum gamma_i proof_i, accept <=> e(L, g2) == e(R, [tau]_2):
-// sum gamma_i x (the predicate of src/kzg.rs:135-148 with z_i proof_i moved across the pairing). Kernel sequence, all on ctx->stream:
-//   MSM R (gammas over the proofs as an ad-hoc base vector, no tables) | k_vb_prepare + k_vb_finish (s_i = gamma_i z_i, g, -t) | MSM M (s over the
-//   proofs) | K: MSM (gammas over the commitments) or g C | (-t) g1 (the same scalar-mult launch as g C) | g1_sum of K, M, (-t) g1 | the two
-//   pairings in ONE launch | 768 GT bytes + the two sums back.
-// vb_io block: [gt: g 32 | -t 32] [pts: C 64 | g1 64] [mul: g C 64 | (-t) g1 64] [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64]
-//              [qs: g2 128 | tau 128] [omega 32] [gt 768] [partials]
-extern "C++" {
-namespace {
-// The sum block that both combination layouts end in, placed at AT: the three terms of L, the two sums, the pairing's arguments and its result.
-//   [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64] [qs: g2 128 | tau 128] [omega 32] [gt 768]
-template <size_t AT> struct SumBlock { static constexpr size_t O_SUM = AT, O_L = AT + 288, O_R = AT + 384, O_PS = AT + 480, O_QS = AT + 608, O_OMEGA = AT + 864, O_GT = AT + 896, O_END = AT + 1664; };
-// how both combinations finish, `sum` = the block on the device: L = K + M + T, both sums affine, the two pairings and the verdict
-keaki_status combination_finish(keaki_hip_ctx* ctx, char* sum, int32_t* ok_out, uint64_t* sums_out_aff) {
-  using B = SumBlock<0>;
-  ST_TRY(g1_sum_run(ctx, sum, 3, sum + B::O_L));
-  ST_TRY(verify_batch_jac_to_aff_run(ctx, sum + B::O_L, sum + B::O_R, sum + B::O_PS));
-  return pair2_verdict(ctx, sum + B::O_PS, sum + B::O_QS, sum + B::O_GT, sums_out_aff, ok_out);
-}
-struct VbLayout : SumBlock<320> { static constexpr size_t O_SC = 0, O_PTS = 64, O_MUL = 192, O_PART = O_END; };
-// com_stride and point_mode, the two switches every entry of the family has (`what`: the entry's name)
-keaki_status kzg_modes_ok(keaki_hip_ctx* ctx, const char* what, int32_t com_stride, int32_t point_mode) {
-  if ((com_stride == 0 || com_stride == 1) && (point_mode == 0 || point_mode == 1)) return KEAKI_OK;
-  return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: com_stride = %d, point_mode = %d: both must be 0 or 1", what, (int)com_stride, (int)point_mode);
-}
-// The ONE argument check of verify_batch and verify_each. `out` / `out_name`: the output required at any n; `arrays_ok`: the call's arrays are there (asked for n > 0).
-keaki_status openings_args(keaki_hip_ctx* ctx, const char* what, int32_t com_stride, int32_t point_mode, const void* out, const char* out_name, bool arrays_ok, size_t n) {
-  ST_TRY(kzg_modes_ok(ctx, what, com_stride, point_mode));
-  if (!out) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, out_name);
-  if (n && !arrays_ok) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
-  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n must be < 2^31 per device", what);
-  return KEAKI_OK;
-}
-// `stage(phase)`: the host form uploads what the phase reads and makes ctx->stream wait for it (0: gammas and proofs, in front of the first MSM;
-// 1: commitments, points, values). The commitment (com_stride 0), [tau]_2 and omega (point_mode 1) are already in their vb_io slots.
-keaki_status verify_batch_core(keaki_hip_ctx* ctx, const void* d_coms, int32_t com_stride, const void* d_points, int32_t point_mode, const void* d_values,
-                               const void* d_proofs, const void* d_gammas, size_t n, const std::function<keaki_status(int)>& stage, int32_t* ok_out,
-                               uint64_t* sums_out_aff) {
-  using V = VbLayout;
-  char* io = (char*)ctx->vb_io.p;
-  ST_TRY(g1_generator_to(ctx, io + V::O_PTS + 64));
-  ST_TRY(g2_generator_to(ctx, io + V::O_QS));
-  if (stage) ST_TRY(stage(0));
-  ST_TRY(msm_g1_run(ctx, d_proofs, n, d_gammas, n, io + V::O_R));
-  if (stage) ST_TRY(stage(1));
-  ST_TRY(verify_batch_scalars_run(ctx, d_gammas, point_mode ? (const void*)(io + V::O_OMEGA) : d_points, point_mode, d_values, n, ctx->vb_s.p, io + V::O_PART,
-                                  io + V::O_SC));
-  ST_TRY(msm_g1_run(ctx, d_proofs, n, ctx->vb_s.p, n, io + V::O_SUM + 96));
-  if (com_stride) {
-    ST_TRY(msm_g1_run(ctx, d_coms, n, d_gammas, n, io + V::O_SUM));
-    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS + 64, 1, io + V::O_SC + 32, 1, io + V::O_MUL + 64));           // (-t) g1
-    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL + 64, 1, io + V::O_SUM + 192));
-  } else {
-    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, io + V::O_SC, 2, io + V::O_MUL));                          // g C and (-t) g1, one launch
-    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
-    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL + 64, 1, io + V::O_SUM + 192));
-  }
-  return combination_finish(ctx, io + V::O_SUM, ok_out, sums_out_aff);
-}
-// the empty combination: both sums are the identity, which pairs to GT one on both sides
-void verify_batch_empty(int32_t* ok_out, uint64_t* sums_out_aff) {
-  *ok_out = 1;
-  if (sums_out_aff) memset(sums_out_aff, 0, 128);
-}
-keaki_status verify_batch_reserve(keaki_hip_ctx* ctx, size_t n) {
-  ST_TRY(reserve(ctx, ctx->vb_io, VbLayout::O_PART + verify_batch_partials_bytes()));
-  return reserve(ctx, ctx->vb_s, n * 32);
-}
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_kzg_verify_batch_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff, const void* d_points,
-                                            int32_t point_mode, const void* d_values, const void* d_proofs_aff, const void* d_gammas, size_t n,
-                                            int32_t* ok_out, uint64_t* sums_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_batch");
-  ST_TRY(openings_args(ctx, "kzg_verify_batch", com_stride, point_mode, ok_out, "ok_out", d_com_aff && d_tau_g2_aff && d_points && d_values && d_proofs_aff && d_gammas, n));
-  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
-  ST_TRY(verify_batch_reserve(ctx, n));
-  char* io = (char*)ctx->vb_io.p;
-  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_PTS, d_com_aff, 64, hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_QS + 128, d_tau_g2_aff, 128, hipMemcpyDeviceToDevice, ctx->stream));
-  if (point_mode) HIP_TRY(ctx, hipMemcpyAsync(io + VbLayout::O_OMEGA, d_points, 32, hipMemcpyDeviceToDevice, ctx->stream));
-  return verify_batch_core(ctx, d_com_aff, com_stride, d_points, point_mode, d_values, d_proofs_aff, d_gammas, n, nullptr, ok_out, sums_out_aff);
-}
-
-keaki_status keaki_hip_kzg_verify_batch(keaki_hip_ctx* ctx, const uint64_t* com_aff, int32_t com_stride, const uint64_t* tau_g2_aff, const uint64_t* points,
-                                        int32_t point_mode, const uint64_t* values, const uint64_t* proofs_aff, const uint64_t* gammas, size_t n,
-                                        int32_t* ok_out, uint64_t* sums_out_aff) {
-  CTX_GUARD(ctx);                 // held across stage -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_verify_batch");
-  ST_TRY(openings_args(ctx, "kzg_verify_batch", com_stride, point_mode, ok_out, "ok_out", com_aff && tau_g2_aff && points && values && proofs_aff && gammas, n));
-  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
-  ST_TRY(verify_batch_reserve(ctx, n));
-  ST_TRY(reserve(ctx, ctx->io_a, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_d, n * 32));
-  char* io = (char*)ctx->vb_io.p;
-  ItemStager items{ctx, com_aff, com_stride, io + VbLayout::O_PTS, points, point_mode, io + VbLayout::O_OMEGA, proofs_aff, n};
-  ST_TRY(items.reserve());
-  CopyFeed feed(ctx);
-  ST_TRY(items.put(feed, ItemStager::ONE_COM));
-  ST_TRY(feed.put(0, io + VbLayout::O_QS + 128, tau_g2_aff, 128));
-  ST_TRY(items.put(feed, ItemStager::OMEGA));
-  // Large batches (160 B per item) go up on the context's copy stream in the order the kernels ask for them: gammas and proofs, then -- under
-  // the first MSM -- commitments, points and values. Small ones, and a context told to use no other stream (pipe_chunks = 0), copy in front.
-  ST_TRY(feed.begin(ctx->tune.pipe_chunks && n >= PIPE_CHUNK));
-  const std::function<keaki_status(int)> stage = [&](int phase) -> keaki_status {
-    if (phase == 0) {
-      ST_TRY(items.put(feed, ctx->io_a.p, gammas, n * 32));
-      return items.put(feed, ItemStager::PROOFS);
-    }
-    ST_TRY(items.put(feed, ItemStager::POINTS));
-    ST_TRY(items.put(feed, ctx->io_d.p, values, n * 32));
-    return items.put(feed, ItemStager::COMS);
-  };
-  return feed.closed_by(verify_batch_core(ctx, items.d_com(), com_stride, items.d_points(), point_mode, ctx->io_d.p, items.d_proofs(), ctx->io_a.p, n, stage, ok_out,
-                                          sums_out_aff));
-}
-
-// ---- KZG coset batch verification: n set proofs over cosets of size l, one linear combination, two pairings ----------------------------------
-// L = sum gamma_k C_k - sum_j J_j [tau^j]_1 + sum (gamma_k c_k) proof_k, R = sum gamma_k proof_k, accept <=> e(L, g2) == e(R, [tau^l]_2): sum gamma_k x
-// (verify_multi's predicate on the coset h_k <omega_l>, whose Z is X^l - c_k, with c_k proof_k moved across the pairing). Kernel sequence, all on
-// ctx->stream, modelled on verify_batch_core: MSM R (gammas over the proofs) | k_vc_prepare + k_vc_transform + k_vc_finish (kzg_cosets.hip: s_k = gamma_k c_k,
-// -J, g) | MSM M (s over the proofs) | MSM T (-J over the first l points of the SRS, with the handle's window tables) | K: MSM (gammas over the
-// commitments) or g C | g1_sum of K, M, T | the two pairings in ONE launch | 768 GT bytes + the two sums back.
-// vc_io block: [pts: C 64] [mul: g C 64] [sum_in: K 96 | M 96 | T 96] [L 96] [R 96] [ps: L 64 | R 64] [qs: g2 128 | tau^l 128] [omega 32] [gt 768]
-extern "C++" {
-namespace {
-struct VcLayout : SumBlock<128> { static constexpr size_t O_PTS = 0, O_MUL = 64, TOTAL = O_END; };
-// the values of n items as ONE span of the caller's array: up to the last value the strides name
-inline size_t coset_span(size_t n, size_t l, size_t item_stride, size_t t_stride) { return (n - 1) * item_stride + (l - 1) * t_stride + 1; }
-struct VcArgs {
-  const keaki_hip_srs_g1* srs;
-  const void *com, *tau_l, *points, *values, *proofs, *gammas;
-  int32_t com_stride, point_mode;
-  size_t item_stride, t_stride, n;
-  uint32_t log2l;
-  const uint64_t *omega_l_inv, *inv_l;
-};
-// The commitment (com_stride 0) and [tau^l]_2 are already in their vc_io slots; a.* are device pointers.
-keaki_status verify_cosets_core(keaki_hip_ctx* ctx, const VcArgs& a, const VcWork& w, int32_t* ok_out, uint64_t* sums_out_aff) {
-  using V = VcLayout;
-  char* io = (char*)ctx->vc_io.p;
-  const size_t n = a.n, l = (size_t)1 << a.log2l;
-  ST_TRY(g2_generator_to(ctx, io + V::O_QS));
-  ST_TRY(msm_g1_run(ctx, a.proofs, n, a.gammas, n, io + V::O_R));
-  ST_TRY(verify_cosets_scalars_run(ctx, a.gammas, a.points, a.point_mode, a.values, a.item_stride, a.t_stride, a.log2l, a.omega_l_inv, a.inv_l, n, w));
-  ST_TRY(msm_g1_run(ctx, a.proofs, n, w.s, n, io + V::O_SUM + 96));
-  const auto t1 = srs_tables(a.srs);
-  ST_TRY(msm_g1_run(ctx, a.srs->d, a.srs->n, w.neg_j, l, io + V::O_SUM + 192, t1.first, t1.second));
-  if (a.com_stride) {
-    ST_TRY(msm_g1_run(ctx, a.com, n, a.gammas, n, io + V::O_SUM));
-  } else {
-    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, w.g, 1, io + V::O_MUL));                                   // g C
-    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
-  }
-  return combination_finish(ctx, io + V::O_SUM, ok_out, sums_out_aff);
-}
-// Two values (k, t) != (k', t') of the call share an address iff a item_stride = b t_stride for some 0 <= a < n, 0 <= b < l, not both zero; the
-// smallest such pair is (t_stride / g, item_stride / g), g = gcd.
-bool verify_cosets_strides_overlap(size_t n, size_t l, size_t item_stride, size_t t_stride) {
-  if ((n > 1 && item_stride == 0) || (l > 1 && t_stride == 0)) return true;
-  if (n <= 1 || l <= 1) return false;
-  size_t g = item_stride, b = t_stride;
-  while (b) { const size_t r = g % b; g = b; b = r; }
-  return t_stride / g < n && item_stride / g < l;
-}
-// The ONE argument check of the coset calls (`what`: kzg_verify_cosets, kzg_coset_pairs, kzg_verify_cosets_each). `out_ok` / `out_name`: the output that is
-// required at any n; `rest_ok`: the call's own arrays beyond the commitment, the shifts, the values and the two constants are there (asked for n > 0).
-keaki_status verify_cosets_args(keaki_hip_ctx* ctx, const VcArgs& a, const char* what, bool out_ok, const char* out_name, bool rest_ok) {
-  ST_TRY(kzg_modes_ok(ctx, what, a.com_stride, a.point_mode));
-  if (!out_ok || !a.srs) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, out_ok ? "srs_g1" : out_name);
-  if (a.log2l > 31 || ((size_t)1 << a.log2l) > KEAKI_SET_MAX)
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: l = 2^%u exceeds KEAKI_SET_MAX = %d", what, a.log2l, (int)KEAKI_SET_MAX);
-  const size_t l = (size_t)1 << a.log2l;
-  if (a.n && (!a.com || !a.points || !a.values || !a.omega_l_inv || !a.inv_l || !rest_ok)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
-  if (a.n >= ((size_t)1 << 31) || a.n * l >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n * l = %zu * %zu must be < 2^31", what, a.n, l);
-  if (a.n && verify_cosets_strides_overlap(a.n, l, a.item_stride, a.t_stride))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: under item_stride = %zu, t_stride = %zu two of the %zu x %zu values share an address", what, a.item_stride,
-                a.t_stride, a.n, l);
-  // the extent (n - 1) item_stride + (l - 1) t_stride stays below 2^48 values (each term below 2^47, checked without forming a product that could wrap): 32 x the
-  // extent, the bytes the host form uploads and the kernels' address arithmetic, fits 64 bits with room to spare
-  constexpr size_t HALF = (size_t)1 << 47;
-  if (a.n && ((a.n > 1 && a.item_stride >= HALF / (a.n - 1)) || (l > 1 && a.t_stride >= HALF / (l - 1))))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu, t_stride = %zu put the last of the %zu x %zu values 2^48 or more values behind the first", what,
-                a.item_stride, a.t_stride, a.n, l);
-  return srs_holds(ctx, a.srs, what, l, "kzg cosets: I has %zu coefficients but the G1 SRS holds %zu points");
-}
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_kzg_verify_cosets_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride,
-                                             const void* d_tau_l_g2_aff, const void* d_points, int32_t point_mode, const void* d_values,
-                                             size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
-                                             const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_cosets");
-  const VcArgs a = {srs_g1, d_com_aff, d_tau_l_g2_aff, d_points, d_values, d_proofs_aff, d_gammas, com_stride, point_mode, item_stride, t_stride, n, log2l,
-                    omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets", ok_out != nullptr, "ok_out", a.tau_l && a.proofs && a.gammas));
-  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
-  ST_TRY(reserve(ctx, ctx->vc_io, VcLayout::TOTAL));
-  ST_TRY(reserve(ctx, ctx->vc_work, verify_cosets_work_bytes(n, log2l)));
-  char* io = (char*)ctx->vc_io.p;
-  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync(io + VcLayout::O_PTS, d_com_aff, 64, hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(io + VcLayout::O_QS + 128, d_tau_l_g2_aff, 128, hipMemcpyDeviceToDevice, ctx->stream));
-  return verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff);
-}
-
-keaki_status keaki_hip_kzg_verify_cosets(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride,
-                                         const uint64_t* tau_l_g2_aff, const uint64_t* points, int32_t point_mode, const uint64_t* values,
-                                         size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
-                                         const uint64_t* proofs_aff, const uint64_t* gammas, size_t n, int32_t* ok_out, uint64_t* sums_out_aff) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_verify_cosets");
-  VcArgs a = {srs_g1, com_aff, tau_l_g2_aff, points, values, proofs_aff, gammas, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets", ok_out != nullptr, "ok_out", a.tau_l && a.proofs && a.gammas));
-  if (n == 0) { verify_batch_empty(ok_out, sums_out_aff); return KEAKI_OK; }
-  // the values go up as the one span the strides name, behind the kernels' own workspace; every buffer is reserved before the first copy
-  const size_t span = coset_span(n, (size_t)1 << log2l, item_stride, t_stride), work = (verify_cosets_work_bytes(n, log2l) + 255) & ~(size_t)255;
-  ST_TRY(reserve(ctx, ctx->vc_io, VcLayout::TOTAL));
-  ST_TRY(reserve(ctx, ctx->vc_work, work + span * 32));
-  ST_TRY(reserve(ctx, ctx->io_a, n * 32));
-  char* io = (char*)ctx->vc_io.p;
-  ItemStager items{ctx, com_aff, com_stride, io + VcLayout::O_PTS, points, point_mode, io + VcLayout::O_OMEGA, proofs_aff, n};
-  ST_TRY(items.reserve());
-  char* d_values = (char*)ctx->vc_work.p + work;
-  CopyFeed feed(ctx);
-  ST_TRY(items.put(feed, ItemStager::COM));
-  ST_TRY(feed.put(0, io + VcLayout::O_QS + 128, tau_l_g2_aff, 128));
-  ST_TRY(items.put(feed, ItemStager::PTS));
-  ST_TRY(feed.put(0, ctx->io_a.p, gammas, n * 32));
-  ST_TRY(items.put(feed, ItemStager::PROOFS));
-  ST_TRY(feed.put(0, d_values, values, span * 32));
-  a.com = items.d_com(); a.points = items.d_points(); a.values = d_values; a.proofs = items.d_proofs(); a.gammas = ctx->io_a.p;
-  return feed.closed_by(verify_cosets_core(ctx, a, verify_cosets_layout(n, log2l, ctx->vc_work.p), ok_out, sums_out_aff));
-}
-
-// ---- pairing product: n Miller loops, a GT product tree, ONE final exponentiation ------------------------------------------------------------
-// gp_work block: [product 384] [partial products of the first launch] [Miller-loop outputs: 384 per pair]
-extern "C++" {
-namespace {
-size_t pairing_product_work_bytes(size_t n) { return 384 + gt_product_part_bytes() + n * 384; }
-keaki_status pairing_product_args(keaki_hip_ctx* ctx, const void* out, bool arrays_ok, size_t n) {
-  if (!out || (n && !arrays_ok)) return fail(ctx, KEAKI_ERR_BAD_ARG, "pairing_product: null pointer");
-  if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "pairing_product: n must be < 2^31");
-  return KEAKI_OK;
-}
-// gp_work is reserved for n pairs; everything is a device pointer. Asynchronous on ctx->stream.
-keaki_status pairing_product_core(keaki_hip_ctx* ctx, const void* d_g1, const void* d_g2, size_t n, void* d_gt_out) {
-  char* wk = (char*)ctx->gp_work.p;
-  char* miller = wk + 384 + gt_product_part_bytes();
-  if (n) ST_TRY(miller_only_run(ctx, d_g1, d_g2, n, miller));
-  ST_TRY(gt_product_run(ctx, miller, n, wk + 384, wk));
-  return final_exp_only_run(ctx, wk, 1, d_gt_out);
-}
-// serialize_uncompressed(GT one): the canonical words of c0.c0.c0 = 1 come first, every other component is zero
-bool gt_bytes_are_one(const uint8_t* gt) {
-  if (gt[0] != 1) return false;
-  for (size_t i = 1; i < 384; i++) if (gt[i]) return false;
-  return true;
-}
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_pairing_product_dev(keaki_hip_ctx* ctx, const void* d_g1_aff, const void* d_g2_aff, size_t n, void* d_gt_out) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.pairing_product");
-  ST_TRY(pairing_product_args(ctx, d_gt_out, d_g1_aff && d_g2_aff, n));
-  ST_TRY(reserve(ctx, ctx->gp_work, pairing_product_work_bytes(n)));
-  return pairing_product_core(ctx, d_g1_aff, d_g2_aff, n, d_gt_out);
-}
-
-keaki_status keaki_hip_pairing_product(keaki_hip_ctx* ctx, const uint64_t* g1_aff, const uint64_t* g2_aff, size_t n, uint8_t* gt_out) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.pairing_product");
-  ST_TRY(pairing_product_args(ctx, gt_out, g1_aff && g2_aff, n));
-  ST_TRY(reserve(ctx, ctx->gp_work, pairing_product_work_bytes(n)));
-  ST_TRY(reserve(ctx, ctx->io_a, n * G1_AFF_BYTES + 16));
-  ST_TRY(reserve(ctx, ctx->io_b, n * G2_AFF_BYTES + 16));
-  ST_TRY(reserve(ctx, ctx->io_c, 384));
-  CopyFeed feed(ctx);
-  ST_TRY(feed.put(0, ctx->io_a.p, g1_aff, n * G1_AFF_BYTES));
-  ST_TRY(feed.put(0, ctx->io_b.p, g2_aff, n * G2_AFF_BYTES));
-  ST_TRY(pairing_product_core(ctx, ctx->io_a.p, ctx->io_b.p, n, ctx->io_c.p));
-  return download(feed, gt_out, ctx->io_c.p, 384);
-}
-
-// ---- KZG set batch verification: n set proofs over arbitrary sets of k points, one linear combination, k + 1 Miller loops ---------------------
-// J_t = sum gamma_i I_(i,t), L = sum gamma_i C_i - sum_t J_t [tau^t]_1 - sum (gamma_i Z_(i,0)) proof_i, R_t = sum (gamma_i Z_(i,t)) proof_i (1 <= t <= k),
-// accept <=> e(-L, g2) prod_t e(R_t, [tau^t]_2) == 1: sum gamma_i x (verify_multi's predicate with the coefficients of Z_i moved across the pairing as G1
-// scalars, the t = 0 term folded into the left side). Kernel sequence, all on ctx->stream: k_vs_points (point_mode 1) + k_vs_weights + k_vs_polys + k_vs_finish
-// (kzg_sets.hip: the k + 1 scalar rows, -J, g) | the batched MSM of the rows over the proofs as an ad-hoc base vector (row 0 -> M, rows 1 .. k -> R_t; rows
-// longer than N_BATCH_MAX run row by row inside msm_g1_batch_run) | MSM T (-J over the first k points of the SRS, with the handle's window tables) | K: MSM
-// (gammas over the commitments) or g C | g1_sum of K, T, M | k_vs_pairs (the k + 1 sums affine, and -L) | pairing_product_core on (-L, R_1 .. R_k) x (g2,
-// [tau]_2 .. [tau^k]_2) | 384 GT bytes + the sums back, the bytes compared with GT one here.
-// vs_io block (KP = KEAKI_VERIFY_SETS_K_MAX + 1): [pts: C 64] [mul: g C 64] [sum_in: K 96 | T 96] [rows: M 96 | R_1 .. R_k 96 each: KP x 96] [L 96]
-//              [aff: L, R_t: KP x 64] [ps: -L, R_t: KP x 64] [qs: g2, [tau^t]_2: KP x 128] [gt 384]
-extern "C++" {
-namespace {
-struct VsLayout {
-  static constexpr size_t KP = (size_t)KEAKI_VERIFY_SETS_K_MAX + 1;
-  static constexpr size_t O_PTS = 0, O_MUL = 64, O_SUM = 128, O_ROWS = O_SUM + 192, O_L = O_ROWS + KP * 96, O_AFF = O_L + 96, O_PS = O_AFF + KP * 64,
-                          O_QS = O_PS + KP * 64, O_GT = O_QS + KP * 128, TOTAL = O_GT + 384;
-};
-struct VsArgs {
-  const keaki_hip_srs_g1* srs1;
-  const keaki_hip_srs_g2* srs2;
-  const void *com, *points, *values, *proofs, *gammas;
-  const uint64_t* omega;
-  int32_t com_stride, point_mode;
-  size_t item_stride, k, n;
-  bool no_proofs = false, no_gammas = false;      // arrays the call does not take (set_pairs: neither; verify_sets_each: no gammas)
-};
-// the points or values of n items as ONE span of the caller's array: up to the last element the stride names
-inline size_t sets_span(size_t n, size_t k, size_t item_stride) { return (n - 1) * item_stride + k; }
-// The ONE argument check of the set-batch calls; `out`: the output that is required at any n.
-keaki_status verify_sets_args(keaki_hip_ctx* ctx, const VsArgs& a, const char* what, const void* out, const char* out_name = "ok_out") {
-  ST_TRY(kzg_modes_ok(ctx, what, a.com_stride, a.point_mode));
-  if (!out || !a.srs1 || !a.srs2) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: %s is null", what, !out ? out_name : a.srs1 ? "srs_g2" : "srs_g1");
-  if (a.k == 0 || a.k > KEAKI_VERIFY_SETS_K_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: k = %zu must be in 1 .. %d", what, a.k, (int)KEAKI_VERIFY_SETS_K_MAX);
-  if (a.item_stride < a.k) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu is less than k = %zu", what, a.item_stride, a.k);
-  if (a.point_mode && !a.omega) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: point_mode 1 needs omega", what);
-  if (a.n && (!a.com || !a.points || !a.values || (!a.no_proofs && !a.proofs) || (!a.no_gammas && !a.gammas))) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: null pointer", what);
-  if (a.n >= ((size_t)1 << 31) || a.n * a.k >= ((size_t)1 << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n * k = %zu * %zu must be < 2^31", what, a.n, a.k);
-  // the extent (n - 1) item_stride + k stays below 2^48 elements (checked without forming a product that could wrap): 32 x the extent, the bytes the host
-  // form uploads and the kernels' address arithmetic, fits 64 bits with room to spare
-  if (a.n > 1 && a.item_stride >= ((size_t)1 << 47) / (a.n - 1))
-    return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: item_stride = %zu puts the last of the %zu items 2^47 or more elements behind the first", what, a.item_stride, a.n);
-  ST_TRY(srs_holds(ctx, a.srs2, what, a.k + 1, "kzg sets: Z has %zu coefficients but the G2 SRS holds %zu points"));
-  return srs_holds(ctx, a.srs1, what, a.k, "kzg sets: I has %zu coefficients but the G1 SRS holds %zu points");
-}
-// the empty combination: every sum is the identity, and the empty product is GT one
-void verify_sets_empty(int32_t* ok_out, uint64_t* sums_out_aff, size_t k) {
-  *ok_out = 1;
-  if (sums_out_aff) memset(sums_out_aff, 0, (k + 1) * G1_AFF_BYTES);
-}
-// every workspace of a call, before its first copy or launch
-keaki_status verify_sets_reserve(keaki_hip_ctx* ctx, const VsArgs& a) {
-  ST_TRY(reserve(ctx, ctx->vs_io, VsLayout::TOTAL));
-  ST_TRY(reserve(ctx, ctx->vs_work, verify_sets_work_bytes(a.n, a.k, a.point_mode)));
-  return reserve(ctx, ctx->gp_work, pairing_product_work_bytes(a.k + 1));
-}
-// The commitment (com_stride 0) is already in its vs_io slot; a.* are device pointers but a.omega.
-keaki_status verify_sets_core(keaki_hip_ctx* ctx, const VsArgs& a, int32_t* ok_out, uint64_t* sums_out_aff) {
-  using V = VsLayout;
-  char* io = (char*)ctx->vs_io.p;
-  const size_t n = a.n, k = a.k;
-  const VsWork w = verify_sets_layout(n, k, ctx->vs_work.p);
-  ST_TRY(verify_sets_scalars_run(ctx, a.gammas, a.points, a.point_mode, a.omega, a.values, a.item_stride, k, n, w));
-  ST_TRY(msm_g1_batch_run(ctx, a.proofs, n, nullptr, 0, w.s, n, k + 1, n, io + V::O_ROWS));
-  const auto t1 = srs_tables(a.srs1);
-  ST_TRY(msm_g1_run(ctx, a.srs1->d, a.srs1->n, w.neg_j, k, io + V::O_SUM + 96, t1.first, t1.second));
-  if (a.com_stride) {
-    ST_TRY(msm_g1_run(ctx, a.com, n, a.gammas, n, io + V::O_SUM));
-  } else {
-    ST_TRY(g1_mul_batch_run(ctx, io + V::O_PTS, 1, w.g, 1, io + V::O_MUL));                                   // g C
-    ST_TRY(verify_batch_aff_to_jac_run(ctx, io + V::O_MUL, 1, io + V::O_SUM));
-  }
-  ST_TRY(g1_sum_run(ctx, io + V::O_SUM, 3, io + V::O_L));                                                     // K + T + M: the row M lies behind them
-  ST_TRY(verify_sets_pairs_run(ctx, io + V::O_L, io + V::O_ROWS, k, io + V::O_AFF, io + V::O_PS));
-  ST_TRY(g2_generator_to(ctx, io + V::O_QS));
-  HIP_TRY(ctx, hipMemcpyAsync(io + V::O_QS + G2_AFF_BYTES, (const char*)a.srs2->d + G2_AFF_BYTES, k * G2_AFF_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
-  ST_TRY(pairing_product_core(ctx, io + V::O_PS, io + V::O_QS, k + 1, io + V::O_GT));
-  uint8_t gt[384];
-  if (sums_out_aff) HIP_TRY(ctx, hipMemcpyAsync(sums_out_aff, io + V::O_AFF, (k + 1) * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  ST_TRY(download(ctx, gt, io + V::O_GT, 384));
-  *ok_out = gt_bytes_are_one(gt) ? 1 : 0;
-  return KEAKI_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_kzg_verify_sets_dev(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const void* d_com_aff,
-                                           int32_t com_stride, const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values,
-                                           size_t item_stride, size_t k, const void* d_proofs_aff, const void* d_gammas, size_t n, int32_t* ok_out,
-                                           uint64_t* sums_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_sets");
-  const VsArgs a = {srs_g1, srs_g2, d_com_aff, d_points, d_values, d_proofs_aff, d_gammas, omega, com_stride, point_mode, item_stride, k, n};
-  ST_TRY(verify_sets_args(ctx, a, "kzg_verify_sets", ok_out));
-  if (n == 0) { verify_sets_empty(ok_out, sums_out_aff, k); return KEAKI_OK; }
-  ST_TRY(verify_sets_reserve(ctx, a));
-  if (!com_stride) HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->vs_io.p + VsLayout::O_PTS, d_com_aff, G1_AFF_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
-  return verify_sets_core(ctx, a, ok_out, sums_out_aff);
-}
-
-keaki_status keaki_hip_kzg_verify_sets(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs_g1, const keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
-                                       int32_t com_stride, const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values,
-                                       size_t item_stride, size_t k, const uint64_t* proofs_aff, const uint64_t* gammas, size_t n, int32_t* ok_out,
-                                       uint64_t* sums_out_aff) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_verify_sets");
-  VsArgs a = {srs_g1, srs_g2, com_aff, points, values, proofs_aff, gammas, omega, com_stride, point_mode, item_stride, k, n};
-  ST_TRY(verify_sets_args(ctx, a, "kzg_verify_sets", ok_out));
-  if (n == 0) { verify_sets_empty(ok_out, sums_out_aff, k); return KEAKI_OK; }
-  // points (or indices) and values go up as the one span the stride names; every buffer is reserved before the first copy
-  const size_t span = sets_span(n, k, item_stride), point_bytes = span * (point_mode ? 4 : 32);
-  ST_TRY(verify_sets_reserve(ctx, a));
-  ST_TRY(reserve(ctx, ctx->io_a, n * 32));
-  ST_TRY(reserve(ctx, ctx->io_c, std::max(point_bytes, n * 32)));
-  ST_TRY(reserve(ctx, ctx->io_d, span * 32));
-  ItemStager items{ctx, com_aff, com_stride, (char*)ctx->vs_io.p + VsLayout::O_PTS, nullptr, 0, nullptr, proofs_aff, n};
-  ST_TRY(items.reserve());
-  CopyFeed feed(ctx);
-  ST_TRY(items.put(feed, ItemStager::COM));
-  ST_TRY(items.put(feed, ctx->io_c.p, points, point_bytes));
-  ST_TRY(items.put(feed, ctx->io_a.p, gammas, n * 32));
-  ST_TRY(items.put(feed, ItemStager::PROOFS));
-  ST_TRY(items.put(feed, ctx->io_d.p, values, span * 32));
-  a.com = items.d_com(); a.points = ctx->io_c.p; a.values = ctx->io_d.p; a.proofs = items.d_proofs(); a.gammas = ctx->io_a.p;
-  return feed.closed_by(verify_sets_core(ctx, a, ok_out, sums_out_aff));
-}
-
-// ---- KZG verify_each: n openings, one verdict each ---------------------------------------------------------------------------------------
-// L_i = C_i - y_i g1 + z_i proof_i, valid_i <=> e(L_i, g2) e(-proof_i, [tau]_2) == 1: the predicate of src/kzg.rs:135-148 with z_i proof_i moved
-// across the pairing, so that BOTH second arguments are fixed for the call and both line sequences are tables (g2's is the context's g2gen_lines,
-// [tau]_2's is built on first use and kept until another [tau]_2 arrives). Kernel sequence per launch chunk of at most pairing_launch_items()
-// items, all on ctx->stream: k_ve_g1 (L and -proof, kzg_each.hip) | k_pairing2 (kzg_each_pair.hip: one Miller loop over both tables, one final
-// exponentiation, one status byte); then k_ve_count over the n bytes. [tau]_2 = identity is decided here: no pairing, valid_i <=> L_i = identity.
-// The host form is one upload in front, the kernels, one download of n bytes (+ 64 n with lhs_out_aff), with no chunk pipeline: the inputs are
-// at most 192 B per item against >= 140 ns of pairing work (7.1 M pairings/s), a few per cent, which is not worth the stager's machinery.
-// ve_io block: [bad2 16] [com 64] [tau 128] [omega 32]
-extern "C++" {
-namespace {
-struct VeLayout { static constexpr size_t O_BAD = 0, O_COM = 16, O_TAU = 80, O_OMEGA = 208, BYTES = 240; };
-void verify_each_empty(uint64_t* n_bad, uint64_t* first_bad) {
-  *n_bad = 0;
-  if (first_bad) *first_bad = ~0ull;
-}
-// What a host form with a verdict per item keeps on the device, [status: n B, rounded up to 64 | L: n x 64 B when the caller asked for them], and how it
-// goes back once the counters are in, so that the status bytes are final: one download (status and L lie in one buffer, but go to two arrays of the caller).
-struct EachOut {
-  size_t n, lhs_off, bytes; uint64_t* lhs_host;
-  EachOut(size_t n_, uint64_t* lhs) : n(n_), lhs_off((n_ + 63) & ~(size_t)63), bytes(lhs_off + (lhs ? n_ * G1_AFF_BYTES : 0)), lhs_host(lhs) {}
-  char* d_lhs(char* out) const { return lhs_host ? out + lhs_off : nullptr; }
-};
-keaki_status each_result(CopyFeed& feed, const EachOut& r, const char* out, uint8_t* status) {
-  prefault_out(feed.ctx, r.lhs_host, r.lhs_host ? r.n * G1_AFF_BYTES : 0);
-  if (r.lhs_host) HIP_TRY(feed.ctx, hipMemcpyAsync(r.lhs_host, out + r.lhs_off, r.n * G1_AFF_BYTES, hipMemcpyDeviceToHost, feed.ctx->stream));
-  return download(feed, status, out, r.n);
-}
-// Everything is device memory: d_com / d_tau / d_omega_or_points as the kernels read them, tau_host = the 128 bytes of [tau]_2 (the key of its line
-// table). d_lhs: n x 64 B for the L_i, or null (they stay in the chunk's workspace). Ends with the read-back of the counters: synchronises.
-keaki_status verify_each_core(keaki_hip_ctx* ctx, const void* d_coms, int32_t com_stride, const void* d_tau, const uint64_t* tau_host, const void* d_points,
-                              int32_t point_mode, const void* d_values, const void* d_proofs, size_t n, void* d_status, void* d_lhs, uint64_t* n_bad,
-                              uint64_t* first_bad) {
-  KemState& k = ctx->kem;
-  bool tau_inf = true;
-  for (int j = 0; j < 16; j++) tau_inf = tau_inf && tau_host[j] == 0;
-  // the launch chunk: the final exponentiation's slots and the two points per item; a refused reservation halves it, down to one wave of items
-  size_t ch = std::min(n, pairing_launch_items());
-  for (;;) {
-    keaki_status st = reserve(ctx, ctx->ve_pts, ch * 2 * G1_AFF_BYTES);
-    if (st == KEAKI_OK && !tau_inf) st = reserve(ctx, ctx->pair_ws, ch * pairing_slot_bytes());
-    if (st == KEAKI_OK) break;
-    if (st != KEAKI_ERR_OOM || ch <= 32) return st;
-    ctx->err.clear();
-    ch = std::max<size_t>(32, ((ch + 1) / 2 + 31) & ~(size_t)31);
-  }
-  ST_TRY(generator_tables(ctx, false));               // g2's line sequence
-  if (!k.fb_ready) ST_TRY(small_g1_table(ctx));
-  if (!tau_inf && !k.tau_lines.holds(tau_host)) {
-    k.tau_lines.invalidate();
-    ST_TRY(reserve(ctx, k.tau_lines.buf, g2_prepared_bytes()));
-    ST_TRY(g2_prepare_run(ctx, d_tau, k.tau_lines.buf.p));
-    k.tau_lines.publish(tau_host, 0);
-  }
-  char* io = (char*)ctx->ve_io.p;
-  const uint64_t init[2] = {0, ~0ull};
-  HIP_TRY(ctx, hipMemcpyAsync(io + VeLayout::O_BAD, init, 16, hipMemcpyHostToDevice, ctx->stream));
-  const void* tab_g1 = (k.fb_ready ? k.fb_g1_gen : k.fbs_g1_gen).p;
-  const uint32_t wb = k.fb_ready ? FB_WB_LONG : FB_WB_SMALL;
-  char* pts = (char*)ctx->ve_pts.p;
-  for (size_t lo = 0; lo < n; lo += ch) {
-    const size_t m = std::min(ch, n - lo);
-    void* lhs = d_lhs ? (char*)d_lhs + lo * G1_AFF_BYTES : pts;
-    void* neg = pts + ch * G1_AFF_BYTES;
-    ST_TRY(verify_each_g1_run(ctx, d_coms, com_stride, tab_g1, wb, d_points, point_mode, d_values, d_proofs, lo, m, lhs, neg));
-    if (tau_inf)
-      ST_TRY(verify_each_tau_inf_run(ctx, lhs, m, (char*)d_status + lo));
-    else
-      ST_TRY(pairing2_fixed_run(ctx, lhs, neg, m, k.g2gen_lines.p, k.tau_lines.buf.p, ctx->pair_ws.p, ch, (char*)d_status + lo));
-  }
-  ST_TRY(verify_each_count_run(ctx, d_status, n, io + VeLayout::O_BAD));
-  uint64_t res[2];
-  ST_TRY(download(ctx, res, io + VeLayout::O_BAD, 16));
-  *n_bad = res[0];
-  if (first_bad) *first_bad = res[1];
-  return KEAKI_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_kzg_verify_each_dev(keaki_hip_ctx* ctx, const void* d_com_aff, int32_t com_stride, const void* d_tau_g2_aff, const void* d_points,
-                                           int32_t point_mode, const void* d_values, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
-                                           uint64_t* first_bad, void* d_lhs_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_each");
-  ST_TRY(openings_args(ctx, "kzg_verify_each", com_stride, point_mode, n_bad, "n_bad", d_com_aff && d_tau_g2_aff && d_points && d_values && d_proofs_aff && d_status, n));
-  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
-  uint64_t tau_host[16];
-  ST_TRY(read_constants(ctx, d_tau_g2_aff, nullptr, tau_host, nullptr));          // the key of the line table
-  return verify_each_core(ctx, d_com_aff, com_stride, d_tau_g2_aff, tau_host, d_points, point_mode, d_values, d_proofs_aff, n, d_status, d_lhs_out_aff, n_bad,
-                          first_bad);
-}
-
-keaki_status keaki_hip_kzg_verify_each(keaki_hip_ctx* ctx, const uint64_t* com_aff, int32_t com_stride, const uint64_t* tau_g2_aff, const uint64_t* points,
-                                       int32_t point_mode, const uint64_t* values, const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad,
-                                       uint64_t* first_bad, uint64_t* lhs_out_aff) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_verify_each");
-  ST_TRY(openings_args(ctx, "kzg_verify_each", com_stride, point_mode, n_bad, "n_bad", com_aff && tau_g2_aff && points && values && proofs_aff && status, n));
-  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  const EachOut r(n, lhs_out_aff);
-  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
-  ST_TRY(reserve(ctx, ctx->ve_out, r.bytes));
-  ST_TRY(reserve(ctx, ctx->io_d, n * 32));
-  char* io = (char*)ctx->ve_io.p;
-  ItemStager items{ctx, com_aff, com_stride, io + VeLayout::O_COM, points, point_mode, io + VeLayout::O_OMEGA, proofs_aff, n};
-  ST_TRY(items.reserve());
-  CopyFeed feed(ctx);             // one upload in front, on the context's stream; a failing call drains it before it returns
-  ST_TRY(feed.put(0, io + VeLayout::O_TAU, tau_g2_aff, 128));
-  ST_TRY(items.put(feed, ItemStager::COM | ItemStager::PTS));
-  ST_TRY(feed.put(0, ctx->io_d.p, values, n * 32));
-  ST_TRY(items.put(feed, ItemStager::PROOFS));
-  char* out = (char*)ctx->ve_out.p;
-  ST_TRY(verify_each_core(ctx, items.d_com(), com_stride, io + VeLayout::O_TAU, tau_g2_aff, items.d_points(), point_mode, ctx->io_d.p, items.d_proofs(), n, out, r.d_lhs(out), n_bad, first_bad));
-  return each_result(feed, r, out, status);
-}
-
-// ---- KZG coset pairs and per-coset verdicts ------------------------------------------------------------------------------------------------
-// coset_pairs: A_k = C_k - [I_k(tau)]_1 and c_k = h_k^l for n cosets (kzg_coset_pairs.hip has the derivation and the kernels). Kernel sequence, all on
-// ctx->stream: k_vc_prepare<., true> over the n items (c, 1 / h) | per launch chunk (coset_rows_plan.h): k_vc_transform<., true> (the rows), then route 1
-// k_cp_rows over the handle's window table, or route 2 msm_g1_batch_run over the rows + k_cp_join; k_cp_affine. verify_cosets_each is coset_pairs into
-// cp_pairs [A: n x 64 | c: n x 32 | zeros: n x 32] and verify_each_core on (coms := A, points := c, values := 0, [tau]_2 := [tau^l]_2).
-extern "C++" {
-namespace {
-keaki_status coset_table_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2l, uint32_t wb) {
-  return srs_cache_ensure(ctx, srs, srs->cr, (int)log2l, (int)wb, cr_table_bytes(log2l, wb), [&](void* t) { return coset_table_run(ctx, srs->d, log2l, wb, t); });
-}
-// a.* are device pointers; the caller holds the context. Every allocation that can be refused (the table, the workspace) comes before the first launch.
-keaki_status coset_pairs_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const VcArgs& a, void* d_lhs, void* d_c) {
-  const size_t n = a.n, l = (size_t)1 << a.log2l;
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);       // the table belongs to the handle: one call per handle at a time
-  int route = cr_route(ctx->tune.coset_rows_route, a.log2l);
-  const uint32_t wb = ctx->tune.coset_rows_wb ? (uint32_t)ctx->tune.coset_rows_wb : cr_wb(a.log2l);
-  if (route == 1) {
-    const keaki_status st = coset_table_ensure(ctx, srs, a.log2l, wb);
-    if (st == KEAKI_ERR_OOM) { ctx->err.clear(); route = 2; }      // optional memory, like the window tables of an MSM
-    else if (st != KEAKI_OK) return st;
-  }
-  const size_t hinv_bytes = (n * 32 + 255) & ~(size_t)255, per_item = l * 32 + sizeof(uint64_t) * 16 + (route == 2 ? G1_JAC_BYTES : 0);
-  size_t ch = cr_chunk_items(n, a.log2l);
-  for (;;) {
-    const keaki_status st = reserve(ctx, ctx->cp_work, hinv_bytes + ch * per_item);
-    if (st == KEAKI_OK) break;
-    if (st != KEAKI_ERR_OOM || ch <= 1) return st;
-    ctx->err.clear();
-    ch = cr_chunk_halve(ch);
-  }
-  char* hinv = (char*)ctx->cp_work.p;
-  char* rows = hinv + hinv_bytes;
-  char* xyzz = rows + ch * l * 32;
-  char* jac = xyzz + ch * 128;
-  const auto tb = srs_tables(srs);
-  ST_TRY(coset_pairs_shifts_run(ctx, a.points, a.point_mode, a.log2l, n, d_c, hinv));
-  for (size_t lo = 0; lo < n; lo += ch) {
-    const size_t m = std::min(ch, n - lo);
-    ST_TRY(coset_pairs_rows_run(ctx, a.values, a.item_stride, a.t_stride, hinv, a.log2l, a.omega_l_inv, a.inv_l, lo, m, route == 2, rows));
-    if (route == 1) {
-      ST_TRY(coset_rows_table_run(ctx, srs->cr.p, wb, rows, a.log2l, cr_slices(m, a.log2l, (uint64_t)ctx->tune.coset_rows_min_lanes), a.com, a.com_stride, lo, m, xyzz));
-    } else {
-      ST_TRY(msm_g1_batch_run(ctx, srs->d, srs->n, tb.first, tb.second, rows, l, m, l, jac));
-      ST_TRY(coset_rows_join_run(ctx, jac, a.com, a.com_stride, lo, m, xyzz));
-    }
-    ST_TRY(coset_rows_affine_run(ctx, xyzz, m, (char*)d_lhs + lo * G1_AFF_BYTES));
-  }
-  return KEAKI_OK;
-}
-struct CpPairs { char *a, *c, *zeros; };
-keaki_status coset_each_reserve(keaki_hip_ctx* ctx, size_t n, size_t extra, CpPairs* out) {
-  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
-  ST_TRY(reserve(ctx, ctx->cp_pairs, n * 128 + extra));
-  out->a = (char*)ctx->cp_pairs.p; out->c = out->a + n * G1_AFF_BYTES; out->zeros = out->c + n * 32;
-  return KEAKI_OK;
-}
-keaki_status coset_each_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, const VcArgs& a, const uint64_t* tau_host, const CpPairs& w, void* d_status, void* d_lhs,
-                             uint64_t* n_bad, uint64_t* first_bad) {
-  ST_TRY(coset_pairs_core(ctx, srs, a, w.a, w.c));
-  HIP_TRY(ctx, hipMemsetAsync(w.zeros, 0, a.n * 32, ctx->stream));
-  return verify_each_core(ctx, w.a, 1, a.tau_l, tau_host, w.c, 0, w.zeros, a.proofs, a.n, d_status, d_lhs, n_bad, first_bad);
-}
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_srs_g1_precompute_cosets(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs, uint32_t log2l) {
-  CTX_GUARD(ctx);
-  if (!srs || log2l > 31 || ((size_t)1 << log2l) > KEAKI_SET_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g1_precompute_cosets: bad argument");
-  ST_TRY(srs_holds(ctx, srs, "srs_g1_precompute_cosets", (size_t)1 << log2l, "kzg cosets: I has %zu coefficients but the G1 SRS holds %zu points"));
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);
-  return coset_table_ensure(ctx, srs, log2l, cr_wb(log2l));
-}
-
-keaki_status keaki_hip_kzg_coset_pairs_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride, const void* d_points,
-                                           int32_t point_mode, const void* d_values, size_t item_stride, size_t t_stride, uint32_t log2l,
-                                           const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, void* d_lhs_out_aff, void* d_c_out) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_coset_pairs");
-  const VcArgs a = {srs_g1, d_com_aff, nullptr, d_points, d_values, nullptr, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, "kzg_coset_pairs", true, "", d_lhs_out_aff && d_c_out));
-  if (n == 0) return KEAKI_OK;
-  return coset_pairs_core(ctx, srs_g1, a, d_lhs_out_aff, d_c_out);
-}
-
-keaki_status keaki_hip_kzg_coset_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride, const uint64_t* points,
-                                       int32_t point_mode, const uint64_t* values, size_t item_stride, size_t t_stride, uint32_t log2l,
-                                       const uint64_t* omega_l_inv, const uint64_t* inv_l, size_t n, uint64_t* lhs_out_aff, uint64_t* c_out) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_coset_pairs");
-  VcArgs a = {srs_g1, com_aff, nullptr, points, values, nullptr, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, "kzg_coset_pairs", true, "", lhs_out_aff && c_out));
-  if (n == 0) return KEAKI_OK;
-  const size_t span = coset_span(n, (size_t)1 << log2l, item_stride, t_stride);
-  ST_TRY(reserve(ctx, ctx->cp_pairs, n * 96));
-  ST_TRY(reserve(ctx, ctx->cp_in, span * 32));
-  ItemStager items{ctx, com_aff, com_stride, nullptr, points, point_mode, nullptr, nullptr, n};      // one commitment and omega: in io_e and io_c
-  ST_TRY(items.reserve());
-  CopyFeed feed(ctx);
-  ST_TRY(items.put(feed, ItemStager::ALL));
-  ST_TRY(feed.put(0, ctx->cp_in.p, values, span * 32));
-  a.com = items.d_com(); a.points = items.d_points(); a.values = ctx->cp_in.p;
-  char* out = (char*)ctx->cp_pairs.p;
-  ST_TRY(coset_pairs_core(ctx, srs_g1, a, out, out + n * G1_AFF_BYTES));
-  HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  return download(feed, c_out, out + n * G1_AFF_BYTES, n * 32);
-}
-
-keaki_status keaki_hip_kzg_verify_cosets_each_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const void* d_com_aff, int32_t com_stride,
-                                                  const void* d_tau_l_g2_aff, const void* d_points, int32_t point_mode, const void* d_values,
-                                                  size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv,
-                                                  const uint64_t* inv_l, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
-                                                  uint64_t* first_bad, void* d_lhs_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_cosets_each");
-  const VcArgs a = {srs_g1, d_com_aff, d_tau_l_g2_aff, d_points, d_values, d_proofs_aff, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l,
-                    omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets_each", n_bad != nullptr, "n_bad", d_tau_l_g2_aff && d_proofs_aff && d_status));
-  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  CpPairs w;
-  ST_TRY(coset_each_reserve(ctx, n, 0, &w));
-  uint64_t tau_host[16];
-  ST_TRY(read_constants(ctx, d_tau_l_g2_aff, nullptr, tau_host, nullptr));          // the key of the line table
-  return coset_each_core(ctx, srs_g1, a, tau_host, w, d_status, d_lhs_out_aff, n_bad, first_bad);
-}
-
-keaki_status keaki_hip_kzg_verify_cosets_each(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, const uint64_t* com_aff, int32_t com_stride,
-                                              const uint64_t* tau_l_g2_aff, const uint64_t* points, int32_t point_mode, const uint64_t* values,
-                                              size_t item_stride, size_t t_stride, uint32_t log2l, const uint64_t* omega_l_inv, const uint64_t* inv_l,
-                                              const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad, uint64_t* first_bad,
-                                              uint64_t* lhs_out_aff) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_verify_cosets_each");
-  VcArgs a = {srs_g1, com_aff, tau_l_g2_aff, points, values, proofs_aff, nullptr, com_stride, point_mode, item_stride, t_stride, n, log2l, omega_l_inv, inv_l};
-  ST_TRY(verify_cosets_args(ctx, a, "kzg_verify_cosets_each", n_bad != nullptr, "n_bad", tau_l_g2_aff && proofs_aff && status));
-  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  const size_t span = coset_span(n, (size_t)1 << log2l, item_stride, t_stride);
-  const EachOut r(n, lhs_out_aff);
-  CpPairs w;
-  ST_TRY(coset_each_reserve(ctx, n, r.bytes, &w));
-  ST_TRY(reserve(ctx, ctx->cp_in, span * 32));
-  ItemStager items{ctx, com_aff, com_stride, nullptr, points, point_mode, nullptr, proofs_aff, n};   // one commitment and omega: in io_e and io_c
-  ST_TRY(items.reserve());
-  char* io = (char*)ctx->ve_io.p;
-  CopyFeed feed(ctx);
-  ST_TRY(feed.put(0, io + VeLayout::O_TAU, tau_l_g2_aff, 128));
-  ST_TRY(items.put(feed, ItemStager::ALL));
-  ST_TRY(feed.put(0, ctx->cp_in.p, values, span * 32));
-  a.com = items.d_com(); a.tau_l = io + VeLayout::O_TAU; a.points = items.d_points(); a.values = ctx->cp_in.p; a.proofs = items.d_proofs();
-  char* out = w.zeros + n * 32;
-  ST_TRY(coset_each_core(ctx, srs_g1, a, tau_l_g2_aff, w, out, r.d_lhs(out), n_bad, first_bad));
-  return each_result(feed, r, out, status);
-}
-
-// ---- KZG set pairs and per-set verdicts --------------------------------------------------------------------------------------------------------
-// set_pairs: A_i = C_i - [I_i(tau)]_1 and Z2_i = [Z_i(tau)]_2 for n items of k arbitrary points (kzg_set_pairs.hip has the derivation and the G2 kernels). Kernel
-// sequence per launch chunk (set_rows_plan.h), all on ctx->stream: k_vs_points (point_mode 1) + k_vs_weights + k_vs_polys<1 / 2> (kzg_sets.hip: the rows -I padded
-// to kp and Z) | G1: coset_pairs' group side at log2l = log2 kp -- k_cp_rows over the G1 handle's window table, or msm_g1_batch_run + k_cp_join -- and k_cp_affine |
-// G2: k_sp_rows_g2 over the G2 handle's window table, k_sp_affine_g2. verify_sets_each is set_pairs into sp_pairs [A: n x 64 | Z2: n x 128 | status | the chunk
-// block of the pairing side] (or into the caller's arrays), then per launch chunk route 1 k_sp_points (-proof) + k_pairing2v, or route 2 k_sp_points + the Miller
-// loops of the 2m pairs + k_gt_pair_product + the final exponentiation + k_sp_status; then k_ve_count.
-extern "C++" {
-namespace {
-// The argument check of the set-pairs calls: the family's gate, told which arrays these calls do not take. `out`: an output required at any n.
-keaki_status set_pairs_args(keaki_hip_ctx* ctx, VsArgs a, const char* what, bool with_proofs, const void* out, const char* out_name) {
-  a.no_gammas = true;
-  a.no_proofs = !with_proofs;
-  return verify_sets_args(ctx, a, what, out, out_name);
-}
-// afterwards srs->sr.p is the table over at least k bases and *wb_out its width; the caller holds srs->mu. A resident table that covers k is used at its
-// width unless set_rows_wb names another; a refused table falls to the next narrower width.
-keaki_status set_table_ensure(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t k, uint32_t* wb_out) {
-  SrsCache& c = srs->sr;
-  const uint32_t opt = (uint32_t)ctx->tune.set_rows_wb;
-  if (c.p && c.key[0] >= (int)k && (opt == 0 || c.key[1] == (int)opt)) { *wb_out = (uint32_t)c.key[1]; return KEAKI_OK; }
-  for (uint32_t wb = opt ? opt : sr_wb(k); wb; wb = sr_wb_narrower(wb)) {
-    const keaki_status st = srs_cache_ensure(ctx, srs, c, (int)k, (int)wb, sr_table_bytes(k, wb), [&](void* t) { return g2_fb_tables_run(ctx, srs->d, (uint32_t)k, t, wb); });
-    if (st == KEAKI_OK) { *wb_out = wb; return KEAKI_OK; }
-    if (st != KEAKI_ERR_OOM) return st;
-    ctx->err.clear();
-  }
-  return fail(ctx, KEAKI_ERR_OOM, "kzg_set_pairs: the window table over the first %zu G2 points was refused at every width", k);
-}
-// a.* are device pointers but a.omega; the caller holds the context. Every allocation that can be refused (the tables, the workspace) comes before the first
-// launch that writes an output.
-keaki_status set_pairs_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs1, keaki_hip_srs_g2* srs2, const VsArgs& a, void* d_lhs, void* d_z2) {
-  const size_t n = a.n, k = a.k;
-  const uint32_t log2kp = sr_log2kp(k);
-  const size_t kp = (size_t)1 << log2kp;
-  std::lock_guard<std::recursive_mutex> hl1(srs1->mu);     // the tables belong to the handles: one call per handle at a time
-  std::lock_guard<std::recursive_mutex> hl2(srs2->mu);
-  int route = kp > srs1->n ? 2 : cr_route(ctx->tune.coset_rows_route, log2kp);      // kp > len(srs_g1) >= k: no table over kp points
-  const uint32_t wb1 = ctx->tune.coset_rows_wb ? (uint32_t)ctx->tune.coset_rows_wb : cr_wb(log2kp);
-  if (route == 1) {
-    const keaki_status st = coset_table_ensure(ctx, srs1, log2kp, wb1);
-    if (st == KEAKI_ERR_OOM) { ctx->err.clear(); route = 2; }      // optional memory, as for coset_pairs
-    else if (st != KEAKI_OK) return st;
-  }
-  uint32_t wb2 = 0;
-  ST_TRY(set_table_ensure(ctx, srs2, k, &wb2));
-  const size_t per_item = sr_item_bytes(k, log2kp, a.point_mode, route == 2);
-  size_t ch = sr_chunk_items(n, log2kp);
-  for (;;) {
-    const keaki_status st = reserve(ctx, ctx->sp_work, ch * per_item);
-    if (st == KEAKI_OK) break;
-    if (st != KEAKI_ERR_OOM || ch <= 1) return st;
-    ctx->err.clear();
-    ch = sr_chunk_halve(ch);
-  }
-  char* w = (char*)ctx->sp_work.p;
-  char* pts = w + ch * k * 32;
-  char* rows_i = pts + (a.point_mode ? ch * k * 32 : 0);
-  char* rows_z = rows_i + ch * kp * 32;
-  char* xyzz1 = rows_z + ch * k * 32;
-  char* xyzz2 = xyzz1 + ch * 128;
-  char* jac = xyzz2 + ch * 256;
-  const auto tb = srs_tables(srs1);
-  const char* tau_k = (const char*)srs2->d + k * G2_AFF_BYTES;
-  for (size_t lo = 0; lo < n; lo += ch) {
-    const size_t m = std::min(ch, n - lo);
-    ST_TRY(set_pairs_rows_run(ctx, a.points, a.point_mode, a.omega, a.values, a.item_stride, k, lo, m, route == 2, w, pts, rows_i, rows_z));
-    if (route == 1) {
-      ST_TRY(coset_rows_table_run(ctx, srs1->cr.p, wb1, rows_i, log2kp, cr_slices(m, log2kp, (uint64_t)ctx->tune.coset_rows_min_lanes), a.com, a.com_stride, lo, m, xyzz1));
-    } else {
-      ST_TRY(msm_g1_batch_run(ctx, srs1->d, srs1->n, tb.first, tb.second, rows_i, k, m, kp, jac));
-      ST_TRY(coset_rows_join_run(ctx, jac, a.com, a.com_stride, lo, m, xyzz1));
-    }
-    ST_TRY(coset_rows_affine_run(ctx, xyzz1, m, (char*)d_lhs + lo * G1_AFF_BYTES));
-    ST_TRY(set_rows_g2_run(ctx, srs2->sr.p, wb2, rows_z, k, sr_slices(m, log2kp, (uint64_t)ctx->tune.set_rows_min_lanes), tau_k, m, xyzz2));
-    ST_TRY(set_rows_affine_g2_run(ctx, xyzz2, m, (char*)d_z2 + lo * G2_AFF_BYTES));
-  }
-  return KEAKI_OK;
-}
-// sp_pairs of verify_sets_each: [A: n x 64 | Z2: n x 128 | status: n B rounded up to 64 (host form) | the chunk block]; `ch` = the items of a pairing launch chunk
-struct SeWork { char *a, *z2, *status, *chunk; size_t ch; bool route2; };
-keaki_status set_each_reserve(keaki_hip_ctx* ctx, size_t n, bool host_form, SeWork* out) {
-  const bool route2 = se_route(ctx->tune.set_each_route, n) == 2;
-  const size_t fixed = n * (G1_AFF_BYTES + G2_AFF_BYTES) + (host_form ? (n + 63) & ~(size_t)63 : 0);
-  ST_TRY(reserve(ctx, ctx->ve_io, VeLayout::BYTES));
-  size_t ch = se_chunk_items(n, pairing_launch_items());
-  for (;;) {
-    keaki_status st = reserve(ctx, ctx->sp_pairs, fixed + ch * se_item_bytes(route2));
-    if (st == KEAKI_OK) st = reserve(ctx, ctx->pair_ws, ch * pairing_slot_bytes());
-    if (st == KEAKI_OK) break;
-    if (st != KEAKI_ERR_OOM || ch <= SE_CHUNK_MIN) return st;
-    ctx->err.clear();
-    ch = se_chunk_halve(ch);
-  }
-  out->a = (char*)ctx->sp_pairs.p; out->z2 = out->a + n * G1_AFF_BYTES; out->status = out->z2 + n * G2_AFF_BYTES;
-  out->chunk = (char*)ctx->sp_pairs.p + fixed; out->ch = ch; out->route2 = route2;
-  return KEAKI_OK;
-}
-// a.* are device pointers but a.omega. d_lhs / d_z2: where the pairs go (the caller's arrays or sp_pairs). Ends with the read-back of the counters: synchronises.
-keaki_status set_each_core(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs1, keaki_hip_srs_g2* srs2, const VsArgs& a, const SeWork& w, void* d_lhs, void* d_z2,
-                           void* d_status, uint64_t* n_bad, uint64_t* first_bad) {
-  const size_t n = a.n, ch = w.ch;
-  if (!w.route2) ST_TRY(generator_tables(ctx, false));               // g2's line sequence
-  ST_TRY(set_pairs_core(ctx, srs1, srs2, a, d_lhs, d_z2));
-  char* io = (char*)ctx->ve_io.p;
-  const uint64_t init[2] = {0, ~0ull};
-  HIP_TRY(ctx, hipMemcpyAsync(io + VeLayout::O_BAD, init, 16, hipMemcpyHostToDevice, ctx->stream));
-  for (size_t lo = 0; lo < n; lo += ch) {
-    const size_t m = std::min(ch, n - lo);
-    const char* as = (const char*)d_lhs + lo * G1_AFF_BYTES;
-    const char* zs = (const char*)d_z2 + lo * G2_AFF_BYTES;
-    const char* proofs = (const char*)a.proofs + lo * G1_AFF_BYTES;
-    char* status = (char*)d_status + lo;
-    if (!w.route2) {
-      ST_TRY(set_each_points_run(ctx, as, proofs, zs, m, w.chunk, nullptr));
-      ST_TRY(pairing2v_run(ctx, as, w.chunk, zs, m, ctx->kem.g2gen_lines.p, ctx->pair_ws.p, ch, status));
-    } else {
-      char* ps = w.chunk;
-      char* qs = ps + ch * 2 * G1_AFF_BYTES;
-      char* mil = qs + ch * 2 * G2_AFF_BYTES;
-      char* prod = mil + ch * 768;
-      char* gt = prod + ch * 384;
-      ST_TRY(set_each_points_run(ctx, as, proofs, zs, m, ps, qs));
-      ST_TRY(miller_only_run(ctx, ps, qs, 2 * m, mil));
-      ST_TRY(gt_pair_product_run(ctx, mil, mil + m * 384, m, prod));
-      ST_TRY(final_exp_only_run(ctx, prod, m, gt));
-      ST_TRY(set_each_status_run(ctx, gt, as, proofs, zs, m, status));
-    }
-  }
-  ST_TRY(verify_each_count_run(ctx, d_status, n, io + VeLayout::O_BAD));
-  uint64_t res[2];
-  ST_TRY(download(ctx, res, io + VeLayout::O_BAD, 16));
-  *n_bad = res[0];
-  if (first_bad) *first_bad = res[1];
-  return KEAKI_OK;
-}
-// the host forms' inputs: the spans of points (or indices) and values in sp_in, the commitments and the proofs through the family's stager
-struct SetHostIn {
-  size_t point_bytes, value_bytes, value_off;
-  SetHostIn(const VsArgs& a) : point_bytes(sets_span(a.n, a.k, a.item_stride) * (a.point_mode ? 4 : 32)), value_bytes(sets_span(a.n, a.k, a.item_stride) * 32),
-                               value_off((point_bytes + 255) & ~(size_t)255) {}
-  keaki_status reserve(keaki_hip_ctx* ctx) const { return keaki_internal::reserve(ctx, ctx->sp_in, value_off + value_bytes); }
-  // uploads everything and turns a's pointers into device pointers
-  keaki_status put(keaki_hip_ctx* ctx, CopyFeed& feed, ItemStager& items, VsArgs& a) const {
-    char* in = (char*)ctx->sp_in.p;
-    ST_TRY(items.put(feed, ItemStager::COM));
-    ST_TRY(items.put(feed, in, a.points, point_bytes));
-    ST_TRY(items.put(feed, in + value_off, a.values, value_bytes));
-    ST_TRY(items.put(feed, ItemStager::PROOFS));
-    a.com = items.d_com(); a.points = in; a.values = in + value_off; a.proofs = items.d_proofs();
-    return KEAKI_OK;
-  }
-};
-}  // namespace
-}  // extern "C++"
-
-keaki_status keaki_hip_srs_g2_precompute_sets(keaki_hip_ctx* ctx, keaki_hip_srs_g2* srs, size_t k_max) {
-  CTX_GUARD(ctx);
-  if (!srs || k_max == 0 || k_max > KEAKI_VERIFY_SETS_K_MAX) return fail(ctx, KEAKI_ERR_BAD_ARG, "srs_g2_precompute_sets: bad argument");
-  ST_TRY(srs_holds(ctx, srs, "srs_g2_precompute_sets", k_max + 1, "kzg sets: Z has %zu coefficients but the G2 SRS holds %zu points"));
-  std::lock_guard<std::recursive_mutex> hl(srs->mu);
-  uint32_t wb = 0;
-  return set_table_ensure(ctx, srs, k_max, &wb);
-}
-
-keaki_status keaki_hip_kzg_set_pairs_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const void* d_com_aff, int32_t com_stride,
-                                         const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values, size_t item_stride, size_t k,
-                                         size_t n, void* d_lhs_out_aff, void* d_z2_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_set_pairs");
-  const VsArgs a = {srs_g1, srs_g2, d_com_aff, d_points, d_values, nullptr, nullptr, omega, com_stride, point_mode, item_stride, k, n};
-  ST_TRY(set_pairs_args(ctx, a, "kzg_set_pairs", false, n == 0 || (d_lhs_out_aff && d_z2_out_aff) ? (const void*)ctx : nullptr, "lhs_out_aff or z2_out_aff"));
-  if (n == 0) return KEAKI_OK;
-  return set_pairs_core(ctx, srs_g1, srs_g2, a, d_lhs_out_aff, d_z2_out_aff);
-}
-
-keaki_status keaki_hip_kzg_set_pairs(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff, int32_t com_stride,
-                                     const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values, size_t item_stride, size_t k,
-                                     size_t n, uint64_t* lhs_out_aff, uint64_t* z2_out_aff) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_set_pairs");
-  VsArgs a = {srs_g1, srs_g2, com_aff, points, values, nullptr, nullptr, omega, com_stride, point_mode, item_stride, k, n};
-  ST_TRY(set_pairs_args(ctx, a, "kzg_set_pairs", false, n == 0 || (lhs_out_aff && z2_out_aff) ? (const void*)ctx : nullptr, "lhs_out_aff or z2_out_aff"));
-  if (n == 0) return KEAKI_OK;
-  const SetHostIn in(a);
-  ST_TRY(in.reserve(ctx));
-  ST_TRY(reserve(ctx, ctx->sp_pairs, n * (G1_AFF_BYTES + G2_AFF_BYTES)));
-  ItemStager items{ctx, com_aff, com_stride, nullptr, nullptr, 0, nullptr, nullptr, n};      // one commitment: in io_e
-  ST_TRY(items.reserve());
-  CopyFeed feed(ctx);
-  ST_TRY(in.put(ctx, feed, items, a));
-  char* out = (char*)ctx->sp_pairs.p;
-  ST_TRY(set_pairs_core(ctx, srs_g1, srs_g2, a, out, out + n * G1_AFF_BYTES));
-  prefault_out(ctx, z2_out_aff, n * G2_AFF_BYTES);
-  HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, out, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  return download(feed, z2_out_aff, out + n * G1_AFF_BYTES, n * G2_AFF_BYTES);
-}
-
-keaki_status keaki_hip_kzg_verify_sets_each_dev(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const void* d_com_aff,
-                                                int32_t com_stride, const void* d_points, int32_t point_mode, const uint64_t* omega, const void* d_values,
-                                                size_t item_stride, size_t k, const void* d_proofs_aff, size_t n, void* d_status, uint64_t* n_bad,
-                                                uint64_t* first_bad, void* d_lhs_out_aff, void* d_z2_out_aff) {
-  CTX_GUARD(ctx);
-  TRACE_SCOPE("keaki.kzg_verify_sets_each");
-  const VsArgs a = {srs_g1, srs_g2, d_com_aff, d_points, d_values, d_proofs_aff, nullptr, omega, com_stride, point_mode, item_stride, k, n};
-  ST_TRY(set_pairs_args(ctx, a, "kzg_verify_sets_each", true, n_bad && (n == 0 || d_status) ? (const void*)n_bad : nullptr, "n_bad or status"));
-  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  SeWork w;
-  ST_TRY(set_each_reserve(ctx, n, false, &w));
-  return set_each_core(ctx, srs_g1, srs_g2, a, w, d_lhs_out_aff ? d_lhs_out_aff : w.a, d_z2_out_aff ? d_z2_out_aff : w.z2, d_status, n_bad, first_bad);
-}
-
-keaki_status keaki_hip_kzg_verify_sets_each(keaki_hip_ctx* ctx, keaki_hip_srs_g1* srs_g1, keaki_hip_srs_g2* srs_g2, const uint64_t* com_aff,
-                                            int32_t com_stride, const void* points, int32_t point_mode, const uint64_t* omega, const uint64_t* values,
-                                            size_t item_stride, size_t k, const uint64_t* proofs_aff, size_t n, uint8_t* status, uint64_t* n_bad,
-                                            uint64_t* first_bad, uint64_t* lhs_out_aff, uint64_t* z2_out_aff) {
-  CTX_GUARD(ctx);                 // held across upload -> kernels -> download: the io buffers belong to this call until it returns
-  TRACE_SCOPE("keaki.kzg_verify_sets_each");
-  VsArgs a = {srs_g1, srs_g2, com_aff, points, values, proofs_aff, nullptr, omega, com_stride, point_mode, item_stride, k, n};
-  ST_TRY(set_pairs_args(ctx, a, "kzg_verify_sets_each", true, n_bad && (n == 0 || status) ? (const void*)n_bad : nullptr, "n_bad or status"));
-  if (n == 0) { verify_each_empty(n_bad, first_bad); return KEAKI_OK; }
-  const SetHostIn in(a);
-  SeWork w;
-  ST_TRY(set_each_reserve(ctx, n, true, &w));
-  ST_TRY(in.reserve(ctx));
-  ItemStager items{ctx, com_aff, com_stride, nullptr, nullptr, 0, nullptr, proofs_aff, n};      // one commitment: in io_e
-  ST_TRY(items.reserve());
-  CopyFeed feed(ctx);
-  ST_TRY(in.put(ctx, feed, items, a));
-  ST_TRY(set_each_core(ctx, srs_g1, srs_g2, a, w, w.a, w.z2, w.status, n_bad, first_bad));
-  if (lhs_out_aff) HIP_TRY(ctx, hipMemcpyAsync(lhs_out_aff, w.a, n * G1_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  if (z2_out_aff) HIP_TRY(ctx, hipMemcpyAsync(z2_out_aff, w.z2, n * G2_AFF_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  return download(feed, status, w.status, n);
-}
-
 // ---- SRS ingest: on-curve check (row f-3) ------------------------------------------------------------------------
-static keaki_status curve_check_common(keaki_hip_ctx* ctx, bool g2, const void* d_pts, size_t n, uint64_t* n_off_curve, uint64_t* first_off_curve) {
+// The tally of the calls that count in io_e (the curve check, the codec): the 16-byte slot is reserved, then begun (api_host.h: BadTally).
+static keaki_status io_e_tally_begin(keaki_hip_ctx* ctx) {
   ST_TRY(reserve(ctx, ctx->io_e, 16));
-  const uint64_t init[2] = {0, ~0ull};
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_e.p, init, 16, hipMemcpyHostToDevice, ctx->stream));
+  return BadTally{ctx, ctx->io_e.p}.begin();
+}
+static keaki_status curve_check_common(keaki_hip_ctx* ctx, bool g2, const void* d_pts, size_t n, uint64_t* n_off_curve, uint64_t* first_off_curve) {
+  ST_TRY(io_e_tally_begin(ctx));
   if (n) ST_TRY(g2 ? g2_curve_check_run(ctx, d_pts, n, ctx->io_e.p) : g1_curve_check_run(ctx, d_pts, n, ctx->io_e.p));
-  uint64_t res[2];
-  ST_TRY(download(ctx, res, ctx->io_e.p, 16));
-  *n_off_curve = res[0];
-  if (first_off_curve) *first_off_curve = res[1];
-  return KEAKI_OK;
+  return BadTally{ctx, ctx->io_e.p}.end(n_off_curve, first_off_curve);
 }
 keaki_status keaki_hip_srs_g1_check(keaki_hip_ctx* ctx, const keaki_hip_srs_g1* srs, uint64_t* n_off_curve, uint64_t* first_off_curve) {
   CTX_GUARD(ctx);
@@ -3328,26 +2197,12 @@ keaki_status keaki_hip_g2_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, 
 // Rejected items are counted on the device: io_e = {count, first index}, added to by every launch of a call (the host forms run in chunks and
 // pass each chunk's first index). Host forms go through the stager of the KEM host batches (pipelined_regions); from PIPE_CHUNK items on that is
 // a pipeline of two halves, then of PIPE_CHUNK-item chunks.
-extern "C++" {
 namespace {
 struct CodecGroup { bool g2; size_t aff, wire; const char* name; };
 constexpr CodecGroup CODEC_G1 = {false, G1_AFF_BYTES, 32, "g1"}, CODEC_G2 = {true, G2_AFF_BYTES, 64, "g2"};
 size_t codec_chunk_items(const keaki_hip_ctx* ctx, size_t n) {
   if (!ctx->tune.pipe_chunks || n < PIPE_CHUNK) return n;
   return n >= 2 * PIPE_CHUNK ? PIPE_CHUNK : (((n + 1) / 2 + 63) & ~(size_t)63);
-}
-keaki_status codec_counter_begin(keaki_hip_ctx* ctx) {
-  ST_TRY(reserve(ctx, ctx->io_e, 16));
-  const uint64_t init[2] = {0, ~0ull};
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->io_e.p, init, 16, hipMemcpyHostToDevice, ctx->stream));
-  return KEAKI_OK;
-}
-keaki_status codec_counter_end(keaki_hip_ctx* ctx, uint64_t* n_bad, uint64_t* first_bad) {
-  uint64_t res[2];
-  ST_TRY(download(ctx, res, ctx->io_e.p, 16));
-  *n_bad = res[0];
-  if (first_bad) *first_bad = res[1];
-  return KEAKI_OK;
 }
 keaki_status codec_n_check(keaki_hip_ctx* ctx, const char* what, size_t n) {
   if (n >= (1ull << 31)) return fail(ctx, KEAKI_ERR_BAD_ARG, "%s: n must be < 2^31 per call", what);
@@ -3385,25 +2240,24 @@ keaki_status decompress_dev(const CodecGroup& g, keaki_hip_ctx* ctx, const void*
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.point_decompress");
   ST_TRY(decompress_args(g, ctx, d_bytes, n, check_subgroup, d_out, n_bad));
-  ST_TRY(codec_counter_begin(ctx));
+  ST_TRY(io_e_tally_begin(ctx));
   ST_TRY(decompress_run(g, ctx, d_bytes, 0, n, check_subgroup != 0, d_out, d_status));
-  return codec_counter_end(ctx, n_bad, first_bad);
+  return BadTally{ctx, ctx->io_e.p}.end(n_bad, first_bad);
 }
 keaki_status decompress_host(const CodecGroup& g, keaki_hip_ctx* ctx, const uint8_t* bytes, size_t n, int32_t check_subgroup, uint64_t* out, uint8_t* status,
                              uint64_t* n_bad, uint64_t* first_bad) {
   CTX_GUARD(ctx);                 // one lock from staging to the last download: io_a and io_e belong to this call until it returns
   TRACE_SCOPE("keaki.point_decompress");
   ST_TRY(decompress_args(g, ctx, bytes, n, check_subgroup, out, n_bad));
-  ST_TRY(codec_counter_begin(ctx));
+  ST_TRY(io_e_tally_begin(ctx));
   if (n)                          // the status bytes come last: every other region is a multiple of 16 B per item, so all of them stay aligned
                                   // status == NULL: a region with neither `in` nor `out` is device scratch of the stager, so the kernels still get a valid
                                   // d_status (they write it, nothing downloads it) -- never a null pointer, never a copy to NULL
     ST_TRY(pipelined_regions(ctx, n, codec_chunk_items(ctx, n), {}, {{bytes, nullptr, g.wire}, {nullptr, out, g.aff}, {nullptr, status, 1}},
       [&](size_t lo, size_t m, char* const*, char* const* d) { return decompress_run(g, ctx, d[0], lo, m, check_subgroup != 0, d[1], d[2]); }));
-  return codec_counter_end(ctx, n_bad, first_bad);
+  return BadTally{ctx, ctx->io_e.p}.end(n_bad, first_bad);
 }
 }  // namespace
-}  // extern "C++"
 
 keaki_status keaki_hip_g1_compress(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint8_t* bytes_out) { return compress_host(CODEC_G1, ctx, points_aff, n, bytes_out); }
 keaki_status keaki_hip_g2_compress(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint8_t* bytes_out) { return compress_host(CODEC_G2, ctx, points_aff, n, bytes_out); }
@@ -3428,20 +2282,20 @@ keaki_status keaki_hip_g2_subgroup_check_dev(keaki_hip_ctx* ctx, const void* d_p
   TRACE_SCOPE("keaki.g2_subgroup_check");
   if (!n_outside || (n && !d_points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_subgroup_check: null pointer");
   ST_TRY(codec_n_check(ctx, "g2_subgroup_check", n));
-  ST_TRY(codec_counter_begin(ctx));
+  ST_TRY(io_e_tally_begin(ctx));
   ST_TRY(g2_subgroup_run(ctx, const_cast<void*>(d_points_aff), n, 0, nullptr, false, ctx->io_e.p));     // clear = false: the points are only read
-  return codec_counter_end(ctx, n_outside, first_outside);
+  return BadTally{ctx, ctx->io_e.p}.end(n_outside, first_outside);
 }
 keaki_status keaki_hip_g2_subgroup_check(keaki_hip_ctx* ctx, const uint64_t* points_aff, size_t n, uint64_t* n_outside, uint64_t* first_outside) {
   CTX_GUARD(ctx);
   TRACE_SCOPE("keaki.g2_subgroup_check");
   if (!n_outside || (n && !points_aff)) return fail(ctx, KEAKI_ERR_BAD_ARG, "g2_subgroup_check: null pointer");
   ST_TRY(codec_n_check(ctx, "g2_subgroup_check", n));
-  ST_TRY(codec_counter_begin(ctx));
+  ST_TRY(io_e_tally_begin(ctx));
   if (n)
     ST_TRY(pipelined_regions(ctx, n, codec_chunk_items(ctx, n), {}, {{points_aff, nullptr, G2_AFF_BYTES}},
       [&](size_t lo, size_t m, char* const*, char* const* d) { return g2_subgroup_run(ctx, d[0], m, lo, nullptr, false, ctx->io_e.p); }));
-  return codec_counter_end(ctx, n_outside, first_outside);
+  return BadTally{ctx, ctx->io_e.p}.end(n_outside, first_outside);
 }
 
 // ---- self-test --------------------------------------------------------------------------------------------
@@ -3495,5 +2349,3 @@ keaki_status keaki_hip_selftest_point_ops(keaki_hip_ctx* ctx, uint32_t op, const
   ST_TRY(point_probe_run(ctx, op, ctx->io_a.p, n, ctx->io_b.p, tab ? ctx->fk_tab.p : nullptr));
   return download(feed, out, ctx->io_b.p, n * orec);
 }
-
-}  // extern "C"

@@ -1,4 +1,4 @@
-// How the host-array MSM and kzg_open cut their input into chunks: integer work on the tuning and the length alone. No HIP call and no
+// How the host-array MSM and kzg_open cut their input into chunks, and how a refused reservation shrinks: integer work alone. No HIP call and no
 // HIP header, so keaki_amd/host/host_plan_main.cpp checks the invariants on a CPU (tests/test_host_plan_cpu.py). `T` is Tuning
 // (internal.h) in the library; the functions read its members msm_pipe_chunks, pipe_chunks, msm_pipe_min and msm_pipe_growth only, and
 // the plan program passes a struct of those four.
@@ -58,6 +58,20 @@ OpenPlan open_plan(const T& t, size_t n) {
   if (p.chunks.size() <= 1) { p.chunks.clear(); return p; }
   for (const auto& c : p.chunks) p.ranges.push_back({c.first ? c.first - 1 : 0, c.second - 1 - (c.first ? c.first - 1 : 0)});
   return p;
+}
+
+// A reservation for `ch` items that shrinks until it fits (the launch chunks of the KZG verdict calls, api_kzg.hip): try_reserve(ch) is called
+// until it gives something other than `refused`, which is returned at once -- success with `ch` the count that fits; `refused` itself is
+// returned when ch is at the floor. In between the recorded error is cleared and ch = shrink(ch), the site's own rule (strictly smaller, not below the floor).
+// The status type is what try_reserve returns; `refused` is compared with it.
+template <class Refused, class Shrink, class TryReserve, class ClearError>
+auto reserve_shrinking(Refused refused, size_t& ch, size_t floor, Shrink shrink, TryReserve try_reserve, ClearError clear_error) {
+  for (;;) {
+    const auto st = try_reserve(ch);
+    if (st != refused || ch <= floor) return st;
+    clear_error();
+    ch = shrink(ch);
+  }
 }
 
 }  // namespace keaki_internal

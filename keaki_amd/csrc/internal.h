@@ -93,7 +93,7 @@ struct KeyedTable {
   void invalidate() { valid = false; }
   void publish(const uint64_t* k, uint32_t bits) { memcpy(key, k, sizeof(key)); wb = bits; valid = true; }
 };
-// The cache of encapsulate and kzg verify (api.hip: the KEM composites, keaki_hip_kzg_verify). A table built once per context stands beside its
+// The cache of encapsulate and kzg verify (api.hip: the KEM composites; api_kzg.hip: keaki_hip_kzg_verify). A table built once per context stands beside its
 // ready bit, which is set only after EVERY step of the build succeeded; the tables of one point are KeyedTables.
 struct KemState {
   // 16-bit window tables for batches of >= 256 items: of the generators (with room for the 13-bit table that the per-item-pairing path rebuilds for
@@ -144,7 +144,7 @@ inline void lane_destroy(hipStream_t& s, std::initializer_list<hipEvent_t*> evs)
   for (hipEvent_t* e : evs) if (*e) (void)hipEventDestroy(*e);
   if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
 }
-// host-pointer calls in chunks (api.hip: CopyFeed, pipelined): uploads and downloads of the neighbouring chunks on a stream of their own.
+// host-pointer calls in chunks (api_host.h: CopyFeed; api.hip: pipelined): uploads and downloads of the neighbouring chunks on a stream of their own.
 // [in: chunk staged | done: chunk computed], one pair per buffer half
 struct HostPipe {
   hipStream_t copy_stream = nullptr;
@@ -185,9 +185,9 @@ struct keaki_hip_ctx {
   keaki_internal::DevBuf ve_io, ve_pts, ve_out;     // kzg verify_each: the small in/out block (counters, commitment, [tau]_2, omega) | L and -proof of a launch chunk (128 B per item) | host form: the status bytes and L of the whole call
   keaki_internal::DevBuf vu_io, vu_work, vu_pass;   // vec_update: host form: indices, deltas, commitment and proofs of the call | the 2d Jacobian points of a table build, the terms of the commitment | header and window tables of a pass
   keaki_internal::DevBuf ks_io, ks_q;               // KZG set openings: points, values, Z, weights, I and the small results of a call | the quotient and the work of its passes (kzg_multi.hip)
-  keaki_internal::DevBuf vc_io, vc_work;            // kzg verify_cosets: the small in/out block (VcLayout, api.hip) | s, 1 / h, -J, g and the partial rows of a call (kzg_cosets.hip: verify_cosets_layout)
+  keaki_internal::DevBuf vc_io, vc_work;            // kzg verify_cosets: the small in/out block (VcLayout, api_kzg.hip) | s, 1 / h, -J, g and the partial rows of a call (kzg_cosets.hip: verify_cosets_layout)
   keaki_internal::DevBuf cp_work, cp_pairs, cp_in;  // kzg coset_pairs: 1 / h (n Fr), then the rows, the XYZZ sums and (route 2) the Jacobian sums of a launch chunk | verify_cosets_each: A, c and the zero values of the call; host forms: + the outputs | host forms: the values
-  keaki_internal::DevBuf vs_io, vs_work;            // kzg verify_sets: the small in/out block (VsLayout, api.hip) | the scalar rows, the weights, -J, g, the partial rows and (point_mode 1) the derived points of a call (kzg_sets.hip: verify_sets_layout)
+  keaki_internal::DevBuf vs_io, vs_work;            // kzg verify_sets: the small in/out block (VsLayout, api_kzg.hip) | the scalar rows, the weights, -J, g, the partial rows and (point_mode 1) the derived points of a call (kzg_sets.hip: verify_sets_layout)
   keaki_internal::DevBuf sp_work, sp_pairs, sp_in;  // kzg set_pairs: weights, derived points, the two scalar rows, the XYZZ sums and (G1 route 2) the Jacobian sums of a launch chunk | verify_sets_each: A, Z2 and the pairing side's blocks of a launch chunk; host forms: + the outputs | host forms: points and values
   keaki_internal::DevBuf gp_work;                   // pairing_product: the Miller-loop outputs of a call (384 B per pair), the partial products and the product
   keaki_internal::DevBuf fc_work;                   // FK23 coset openings (fk_coset.hip): twiddles, hat_a, the partial sums and the two transforms of a call; host forms: + coefficients and proofs

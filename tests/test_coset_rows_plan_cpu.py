@@ -80,5 +80,5 @@ def test_the_options_are_declared_and_the_library_shares_the_plan():
     assert m["coset_rows_min_lanes"] == (0, False) and m["coset_rows_route"] == (0, False) and m["coset_rows_wb"] == (0, False)
     names = [n for n, _ in V.table_options()]
     assert names.count("coset_rows_min_lanes") == 1 and names.count("coset_rows_route") == 1
-    api = V._src("api.hip")
+    api = V._src("api_kzg.hip")
     assert '#include "coset_rows_plan.h"' in api and "cr_wb(" in api and "cr_slices(" in api and "cr_chunk_items(" in api and "cr_route(" in api

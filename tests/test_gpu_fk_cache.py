@@ -1,4 +1,4 @@
-"""The cached FK23 transform of a G1 SRS handle (keaki_amd/csrc/api.hip: SrsCache, srs_cache_ensure) and the handle code that G1 and G2 share
+"""The cached FK23 transform of a G1 SRS handle (keaki_amd/csrc/api_host.h: SrsCache, srs_cache_ensure) and the handle code that G1 and G2 share
 (srs_upload / srs_wrap / srs_precompute / srs_free): one handle whose d changes, the four entries that share one transform, a rebuild
 that keaki_hip_debug_set_alloc_limit refuses, and both groups through upload, wrap, precompute, MSM and free. `tables` below is
 keaki_hip_ctx_memory's first word minus its value before the handles were made: a transform for d counts 2d Jacobian points of 96 B."""

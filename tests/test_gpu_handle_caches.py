@@ -1,4 +1,4 @@
-"""The three derived tables of a G1 SRS handle (keaki_amd/csrc/api.hip: SrsCache fk / upd / fkc, all kept by srs_cache_ensure) under the rules that
+"""The three derived tables of a G1 SRS handle (keaki_amd/csrc/api_host.h: SrsCache fk / upd / fkc, all kept by srs_cache_ensure) under the rules that
 one function now owns: a REPLACE that keaki_hip_debug_set_alloc_limit refuses leaves that cache empty, its bytes off the count, the caller's
 array as it was and the handle's other two caches alone; the next call builds it; and a handle freed through another context gives every
 cache's bytes back to the context that built them. fk is reached through open_fk_poly, upd through vec_update, fkc through open_fk_cosets_poly.

@@ -425,7 +425,7 @@ def test_a_chunked_call_that_fails_leaves_the_context_usable(oc, rand_fr):
 
 
 def test_a_plain_call_that_fails_behind_its_uploads_leaves_the_context_usable(oc, hip, rand_fr):
-    """the failure rule of the host-array calls holds for the plain forms too (api.hip: CopyFeed): pairing_batch of 1,024 pairs on a fresh
+    """the failure rule of the host-array calls holds for the plain forms too (api_host.h: CopyFeed): pairing_batch of 1,024 pairs on a fresh
     context whose allocation limit admits the two input buffers (requests of 73,984 and 147,712 bytes, both uploads enqueued) and refuses
     the output buffer (442,624 bytes) returns KEAKI_ERR_OOM with its stream drained, and the same call on the same context is right once
     the limit is lifted"""

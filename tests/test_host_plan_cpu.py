@@ -2,7 +2,11 @@
 and the length alone. keaki_amd/host/host_plan_main.cpp includes that header and nothing of HIP and checks, under AddressSanitizer + UBSan:
 for growth 50 .. 1000 percent, 2 .. 1000 forced chunks and every n in 0 .. 399 and around 2^16, 2^20, 2^21, 2^22, 2^24 -- the bounds run
 from 0 to n, strictly increasing, in at most 64 pieces, whole pages from 65,536 scalars on; the coefficient chunks of open partition [0, n)
-top first and their MSM ranges are non-empty and partition [0, n - 1); and the automatic bounds at 2^20, 2^21, 2^22 and 2^24. The program
+top first and their MSM ranges are non-empty and partition [0, n - 1); and the automatic bounds at 2^20, 2^21, 2^22 and 2^24. It also drives
+reserve_shrinking, the shrinking reservation of the KZG verdict calls (api_kzg.hip), with each of its four shrink rules against a reservation that
+refuses above a byte limit, from 1, floor, floor + 1, 33, 64, 65, 70 and 4,096 items with a limit for every count from the floor to the start: the
+counts tried decrease strictly and stay at or above the floor, the first that fits is accepted and is the last try, another failure returns after
+one try with the error not cleared, and a refusal at the floor comes back as a refusal. The program
 restates the defaults of the four chunking options (struct Tuning lives in internal.h, which needs HIP) and prints them; they are held
 against the struct here."""
 import os

@@ -107,5 +107,5 @@ def test_the_options_are_declared_and_the_library_shares_the_plan():
     assert m["set_rows_wb"] == (0, False) and m["set_rows_min_lanes"] == (0, False) and m["set_each_route"] == (0, False)
     names = [n for n, _ in V.table_options()]
     assert names.count("set_rows_wb") == 1 and names.count("set_rows_min_lanes") == 1 and names.count("set_each_route") == 1
-    api = V._src("api.hip")
+    api = V._src("api_kzg.hip")
     assert '#include "set_rows_plan.h"' in api and "sr_wb(" in api and "sr_slices(" in api and "sr_chunk_items(" in api and "se_chunk_items(" in api and "se_route(" in api
