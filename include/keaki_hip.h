@@ -144,6 +144,12 @@ keaki_status keaki_hip_ctx_set_option(keaki_hip_ctx* ctx, const char* name, int6
 /* Test hook: every single device allocation of this ctx above `bytes` fails with KEAKI_ERR_OOM (0 = no limit). This is how the tests
  * exercise the optional-memory fallbacks (SRS window tables, the wide GT table); nothing in the library sets it. */
 keaki_status keaki_hip_debug_set_alloc_limit(keaki_hip_ctx* ctx, size_t bytes);
+/* Test hook: waits for the context's streams (as keaki_hip_ctx_trim does), then sets every byte of the full capacity of every scratch workspace of
+ * the context to `byte` (its low 8 bits). Nothing is freed and no capacity changes. The cached tables of encapsulate and kzg verify (guarded by their
+ * ready / valid bits) and the tables of SRS handles are left alone. also_new != 0: every device allocation this context makes from now on is filled with
+ * the byte as well (a grown workspace, a table before its build); also_new = 0 switches that off. A call must return the same bytes whatever the
+ * workspaces held before it: this is how the tests find a read of a word the call did not write itself. ctx NULL -> KEAKI_ERR_BAD_ARG. */
+keaki_status keaki_hip_debug_poison_workspaces(keaki_hip_ctx* ctx, uint32_t byte, int32_t also_new);
 /* Device memory this ctx holds right now, bytes: out4[0] = window tables + FK23 transforms + coset transforms + vec_update tables of SRS handles built through this ctx (the
  * points themselves belong to the caller's upload), [1] = grow-only workspaces, [2] = fixed-base / GT tables of encapsulate, [3] = total. */
 keaki_status keaki_hip_ctx_memory(keaki_hip_ctx* ctx, size_t* out4);

@@ -64,6 +64,15 @@ keaki_status dev_alloc(keaki_hip_ctx* ctx, void** p, size_t bytes) {
     (void)hipGetLastError();
     return fail(ctx, e == hipErrorOutOfMemory ? KEAKI_ERR_OOM : KEAKI_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
   }
+  if (ctx && ctx->poison_new >= 0 && bytes) {          // keaki_hip_debug_poison_workspaces: complete before any stream of the call can touch the memory
+    hipError_t f = hipMemsetAsync(*p, ctx->poison_new, bytes, ctx->stream);
+    if (f == hipSuccess) f = hipStreamSynchronize(ctx->stream);
+    if (f != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(*p); *p = nullptr;
+      return fail(ctx, KEAKI_ERR_HIP, "poison fill of %zu bytes failed: %s", bytes, hipGetErrorString(f));
+    }
+  }
   return KEAKI_OK;
 }
 
@@ -720,6 +729,22 @@ keaki_status keaki_hip_debug_set_alloc_limit(keaki_hip_ctx* ctx, size_t bytes) {
   if (!ctx) return KEAKI_ERR_BAD_ARG;
   std::lock_guard<std::recursive_mutex> lock_(ctx->mu);
   ctx->tune.alloc_limit = bytes;
+  return KEAKI_OK;
+}
+// Test hook: every byte of every scratch workspace (keaki_hip_ctx::for_each_scratch) becomes `byte`, the full capacity, behind everything the context's
+// three streams hold; with also_new the allocation gate fills what it hands out from then on. The caches of KemState and the tables of SRS handles stay.
+keaki_status keaki_hip_debug_poison_workspaces(keaki_hip_ctx* ctx, uint32_t byte, int32_t also_new) {
+  CTX_GUARD(ctx);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->aux.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux.stream));
+  if (ctx->pipe.copy_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe.copy_stream));
+  hipError_t e = hipSuccess;
+  ctx->for_each_scratch([&](DevBuf* b, int) {
+    if (b->p && b->cap && e == hipSuccess) e = hipMemsetAsync(b->p, (int)(byte & 0xff), b->cap, ctx->stream);
+  });
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->poison_new = also_new ? (int)(byte & 0xff) : -1;
   return KEAKI_OK;
 }
 // Releases every grow-only workspace and encapsulate table of the context (they come back on the next call that needs them; a table's

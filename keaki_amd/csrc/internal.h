@@ -194,13 +194,19 @@ struct keaki_hip_ctx {
   // every DevBuf above with its memory class, kem's included (KemState::for_each_buf): what keaki_hip_ctx_destroy and _trim free and
   // keaki_hip_ctx_memory counts. A new workspace is added HERE.
   template <class F> void for_each_buf(F&& f) {
+    for_each_scratch(f);
+    kem.for_each_buf(f);
+  }
+  // the DevBufs declared directly above: scratch, every word a call reads was written by a kernel or copy of the SAME call, so
+  // keaki_hip_debug_poison_workspaces may overwrite all of them between calls. kem's buffers are caches behind ready / valid bits and are not in this list.
+  template <class F> void for_each_scratch(F&& f) {
     f(&fb_bases, 2);
     for (keaki_internal::DevBuf* b : {&digits, &hist, &offsets, &cursor, &sorted, &buckets, &acc29, &partials, &wsums, &tmp_a, &tmp_b, &tmp_c, &io_a, &io_b, &io_c,
                                       &io_d, &io_e, &perm, &heavy, &pair_ws, &fk_tab, &mb_canon, &mb_wsums, &mb_q, &fkb_pts, &fkb_fr, &em_offsets, &vb_io, &vb_s,
                                       &ve_io, &ve_pts, &ve_out, &vu_io, &vu_work, &vu_pass, &ks_io, &ks_q, &fc_work, &vc_io, &vc_work, &cp_work, &cp_pairs, &cp_in, &vs_io, &vs_work, &sp_work, &sp_pairs, &sp_in, &gp_work})
       f(b, 1);
-    kem.for_each_buf(f);
   }
+  int poison_new = -1;           // keaki_hip_debug_poison_workspaces(.., also_new = 1): dev_alloc fills every new allocation with this byte; -1 = off
   // instrumentation
   bool timing = false;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -29,7 +29,7 @@ EXPORTS = [
     "keaki_hip_group_encrypt_batch", "keaki_hip_group_decrypt_batch",
     "keaki_hip_encap_multi", "keaki_hip_encap_multi_dev", "keaki_hip_encrypt_multi", "keaki_hip_encrypt_multi_dev",
     "keaki_hip_selftest_field", "keaki_hip_selftest_field_ops", "keaki_hip_selftest_tower_ops", "keaki_hip_selftest_point_ops", "keaki_hip_open_fk", "keaki_hip_open_fk_poly", "keaki_hip_srs_g1_precompute_fk", "keaki_hip_fk_shard_create", "keaki_hip_fk_shard_free", "keaki_hip_fk_shard_sizes", "keaki_hip_fk_shard_setup", "keaki_hip_fk_shard_open", "keaki_hip_fr_fft", "keaki_hip_srs_g1_check", "keaki_hip_g2_check", "keaki_hip_g1_compress", "keaki_hip_g2_compress", "keaki_hip_g1_compress_dev", "keaki_hip_g2_compress_dev", "keaki_hip_g1_decompress", "keaki_hip_g2_decompress", "keaki_hip_g1_decompress_dev", "keaki_hip_g2_decompress_dev", "keaki_hip_g2_subgroup_check", "keaki_hip_g2_subgroup_check_dev", "keaki_hip_kzg_open", "keaki_hip_kzg_verify", "keaki_hip_kzg_verify_batch", "keaki_hip_kzg_verify_batch_dev", "keaki_hip_kzg_verify_each", "keaki_hip_kzg_verify_each_dev", "keaki_hip_final_exp_batch", "keaki_hip_miller_loop_batch", "keaki_hip_g2_prepare", "keaki_hip_set_timing", "keaki_hip_last_msm_bucket_ms", "keaki_hip_last_msm_total_ms", "keaki_hip_last_msm_window_bits",
-    "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
+    "keaki_hip_last_fk_ms", "keaki_hip_ctx_stream", "keaki_hip_ctx_device", "keaki_hip_ctx_set_option", "keaki_hip_debug_set_alloc_limit", "keaki_hip_debug_poison_workspaces", "keaki_hip_ctx_memory", "keaki_hip_ctx_trim", "keaki_hip_kzg_quotient", "keaki_hip_vec_commit", "keaki_hip_encap_prepare",
     "keaki_hip_srs_g1_precompute_update", "keaki_hip_vec_update", "keaki_hip_vec_update_dev",
     "keaki_hip_kzg_set_polys", "keaki_hip_kzg_set_polys_dev", "keaki_hip_kzg_open_multi", "keaki_hip_kzg_open_multi_dev",
     "keaki_hip_kzg_aggregate", "keaki_hip_kzg_aggregate_dev", "keaki_hip_kzg_verify_multi",
@@ -202,6 +202,7 @@ def load_library():
         lib.keaki_hip_last_fk_ms.argtypes = [vp, C.POINTER(C.c_float)]
         lib.keaki_hip_ctx_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
         lib.keaki_hip_debug_set_alloc_limit.argtypes = [vp, sz]
+        lib.keaki_hip_debug_poison_workspaces.argtypes = [vp, C.c_uint32, i32]
         lib.keaki_hip_ctx_memory.argtypes = [vp, C.POINTER(C.c_size_t)]
         lib.keaki_hip_ctx_trim.argtypes = [vp]
         lib.keaki_hip_ctx_stream.argtypes = [vp]
@@ -370,6 +371,10 @@ class KeakiHip:
     def debug_set_alloc_limit(self, nbytes: int):
         """test hook: single allocations of this context above nbytes fail with KEAKI_ERR_OOM (0 = no limit)"""
         self._ck(self.lib.keaki_hip_debug_set_alloc_limit(self.ctx, int(nbytes)))
+
+    def debug_poison_workspaces(self, byte: int, also_new: bool = True):
+        """test hook: fill every scratch workspace of this context with `byte`; also_new: and every allocation it makes from now on"""
+        self._ck(self.lib.keaki_hip_debug_poison_workspaces(self.ctx, int(byte) & 0xFF, 1 if also_new else 0))
 
     def memory(self) -> dict:
         out = (C.c_size_t * 4)()

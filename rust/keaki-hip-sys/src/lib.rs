@@ -66,6 +66,7 @@ extern "C" {
     pub fn keaki_hip_version() -> *const c_char;
     pub fn keaki_hip_ctx_set_option(ctx: *mut keaki_hip_ctx, name: *const c_char, value: i64) -> keaki_status;
     pub fn keaki_hip_debug_set_alloc_limit(ctx: *mut keaki_hip_ctx, bytes: usize) -> keaki_status;
+    pub fn keaki_hip_debug_poison_workspaces(ctx: *mut keaki_hip_ctx, byte: u32, also_new: i32) -> keaki_status;
     pub fn keaki_hip_ctx_memory(ctx: *mut keaki_hip_ctx, out4: *mut usize) -> keaki_status;
     pub fn keaki_hip_ctx_trim(ctx: *mut keaki_hip_ctx) -> keaki_status;
 
